@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - Mrays/s of the ray-tracing hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--scaling strong|weak] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Workload (config C3 of BASELINE.json): BOS render, 2e4 light-field sources x
@@ -17,10 +17,21 @@ node has fewer than N devices.
                               BASELINE metric "1e7-ray 256^3 BOS render @1/2/4/8 GPU"
   --scaling weak              every rank renders its own 1e7-ray scene (N x 1e7 rays per step)
 
-Prints ONE JSON line on rank 0 (contract in the task description) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value (Mrays/s over the K timed steps), unit, higher_is_better, dtype,
+ms_per_step (one timed step), and
   roofline      the march kernel against the pipe that bounds it (LDS reads), its
-                algorithmic bytes, f32 VALU fraction and the measured HBM traffic
+                algorithmic bytes, f32 VALU fraction -- from the timed steps' own statistics
+
+A plain run does only that: set up, warm up, time the K steps, print.  `--full` adds everything that takes runs of its own:
+  roofline      + the measured HBM traffic and instruction counts (child rocprofv3 --pmc passes), the wave-timing
+                pass (march_profile) and the float4 copy rate
   cpu_baseline  the CPU oracle (scalar C++ restatement, OpenMP) timed on a bounded sample
+  gpu_other_configs, abi_call, abi_call_devices8_same_gpu   the other BASELINE configurations and the host-image entry point
+  check         (N > 1) the parity check every multi-GPU line carries (`--check` asks for it in any run)
+
+`--dump-outputs DIR` writes what the timed path computed in its last step -- the sensor image rank 0 holds after the
+reduce, what a caller of the path receives -- as DIR/image.npy (float32, H x W).  The inputs are synthetic and seeded:
+the same arguments give the same inputs in every run.
 """
 from __future__ import annotations
 
@@ -52,10 +63,17 @@ VALU_PRACTICAL_CYCLES_PER_INST = 2.17
 SIMDS = 4 * 256
 
 
+def _positive_int(s: str) -> int:
+    v = int(s)
+    if v < 1:
+        raise argparse.ArgumentTypeError(f"must be >= 1, got {v}")
+    return v
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=_positive_int, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--scaling", choices=["strong", "weak"], default="strong")
     ap.add_argument("--interp", choices=["cubic", "linear"], default="cubic")
@@ -77,6 +95,11 @@ def parse_args(argv=None):
     ap.add_argument("--rehearse", action="store_true",
                     help="N ranks SHARING device 0, gloo reduce of host copies: exercises the N > 1 logic of this script on a "
                          "one-GPU box (RCCL cannot put two ranks on one GPU); the line is marked as a rehearsal, not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="also the side measurements that take runs of their own: CPU baseline, counter passes, wave-timing pass, copy rate, "
+                         "other configurations, the host-image entry point and (N > 1) the parity check; the --no-* switches trim them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's sensor image as DIR/image.npy (float32)")
     return ap.parse_args(argv)
 
 
@@ -501,7 +524,7 @@ def main():
     if world != args.gpus:
         print(f"bench.py: --gpus {args.gpus} but the launcher started WORLD_SIZE={world} ranks", file=sys.stderr, flush=True)
         sys.exit(2)
-    import numpy as np  # noqa: F401
+    import numpy as np
     import torch
     import torch.distributed as dist
 
@@ -628,8 +651,12 @@ def main():
         clock_mhz = float(st.shader_clock_mhz)
         wave_ms = float(st.march_wave_ms)
     rays_rank = (src_end - src_begin) * args.rays_per_source
+    if args.dump_outputs and rank == 0:
+        # the last timed step's image (after the reduce onto rank 0), before any side pass runs
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "image.npy"), image.cpu().numpy().astype(np.float32).reshape(H, W))
 
-    # ---- side passes AFTER the timed region (never part of `value`) -------------------------------------------------
+    # ---- side passes AFTER the timed region (never part of `value`; --full) ------------------------------------------
     # wave timing of the march launch: start-up ramp and drain (photon_scene_set_march_profile), over a few more steps
     side_image = torch.zeros_like(image) if rank == 0 else None
 
@@ -638,7 +665,7 @@ def main():
         scene.trace(side_image.data_ptr(), volume, args.algorithm, src_begin, src_end, stream=stream, want_stats=False)
 
     march_profile = None
-    if rank == 0 and windowed and lib.has_march_profile and not args.no_profile and not os.environ.get("PHOTON_BENCH_CHILD"):
+    if rank == 0 and windowed and lib.has_march_profile and args.full and not args.no_profile and not os.environ.get("PHOTON_BENCH_CHILD"):
         scene.set_march_profile(True)
         scene.stats_begin(stream)
         for _ in range(min(args.steps, 10)):
@@ -740,13 +767,14 @@ def main():
                         "really pass the LDS pipe; HBM sees the ray state and the touched texels only (hbm.traffic, measured)"}
     out = None
     if rank == 0:
-        roofline["hbm"]["copy_measured_gbs"] = round(lib.measure_copy_gbs(), 1)       # float4 streaming copy, read + write
+        if args.full:
+            roofline["hbm"]["copy_measured_gbs"] = round(lib.measure_copy_gbs(), 1)       # float4 streaming copy, read + write
         cpu = None
-        if args.cpu_sample_rays > 0 and world == 1:      # the CPU baseline is reported at N=1 only
+        if args.full and args.cpu_sample_rays > 0 and world == 1:      # the CPU baseline is reported at N=1 only
             cpu = cpu_baseline(lambda n_sources: make_call(seed=1, n_sources=n_sources), vol_path, interp,
                                args.cpu_sample_rays, args.rays_per_source)
         child = bool(os.environ.get("PHOTON_BENCH_CHILD"))
-        if world == 1 and not args.no_traffic and not child:
+        if world == 1 and args.full and not args.no_traffic and not child:
             traffic, insts, detail = measure_counters(args, "march_kernel")
             roofline["traffic"] = traffic
             roofline["hbm"].update(detail)
@@ -786,7 +814,7 @@ def main():
             roofline.update({"bound": "valu_f32 (algorithmic flops; instruction counts not measured in this run)", "achieved": t["achieved"],
                              "peak": t["peak"], "unit": "TFLOP/s", "frac": t["frac"]})
         others = None
-        if world == 1 and not child and not args.no_other_configs:
+        if world == 1 and args.full and not child and not args.no_other_configs:
             is_c3 = args.dots == 200 and args.volume == 256 and interp == 2 and args.algorithm == 2 and args.rays_per_source == 500
             others = gpu_other_configs(lib, torch, workdir, not args.no_c4, (elapsed / args.steps * 1e3, march_ms_avg) if is_c3 else None)
         desc = (f"C3: BOS, {total_rays} rays ({job_sources} sources x {args.rays_per_source}"
@@ -813,12 +841,12 @@ def main():
             "rays_marched": marched_total,
         }
         out["library"] = lib.version()
-        if world == 1 and not os.environ.get("PHOTON_BENCH_CHILD"):
+        if world == 1 and args.full and not os.environ.get("PHOTON_BENCH_CHILD"):
             out["abi_call"] = time_abi_call(lib, call, interp)
             if not args.no_other_configs:
                 out["abi_call_devices8_same_gpu"] = time_abi_call(lib, call, interp, devices=",".join(["%d" % local_rank] * 8))
                 out["abi_call_devices8_same_gpu"]["over_single_call"] = round(out["abi_call_devices8_same_gpu"]["ms"] / out["abi_call"]["ms"], 4)
-        do_check = args.check or (world > 1 and not child)      # every multi-GPU line carries its own parity check
+        do_check = args.check or (world > 1 and args.full and not child)      # every multi-GPU --full line carries its own parity check
         if args.rehearse:
             out["rehearsal"] = (f"{world} ranks SHARING one GPU, gloo reduce of host copies: exercises this script's N > 1 logic; "
                                 "NOT a multi-GPU measurement")

@@ -10,6 +10,14 @@ for p in (ROOT, os.path.dirname(os.path.abspath(__file__))):
 
 GOLDEN = os.path.join(ROOT, "tests", "golden")
 
+# torch before any test maps the library (test_abi.py dlopens it directly): one HIP runtime per process, torch's
+# (photon_amd/library.py, _one_hip_runtime_per_process) -- otherwise the whole suite in one process leaves the GPU tests
+# with a second runtime that finds no device
+try:
+    import torch  # noqa: F401
+except Exception:       # noqa: BLE001  -- the CPU tests run without a usable torch too
+    pass
+
 
 def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (runs through the HIP library)")

@@ -7,13 +7,16 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _bench(*extra):
+def _bench(*extra, bench_dir=None):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "PHOTON_DEVICES", "PHOTON_INTERP")}
+    if bench_dir:
+        env["PHOTON_BENCH_DIR"] = bench_dir
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--dots", "6",
                         "--volume", "48", *extra], stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=600)
     assert r.returncode == 0, r.stderr.decode("utf-8", "replace")[-2000:]
@@ -23,8 +26,33 @@ def _bench(*extra):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_dumps_its_image(photon, tmp_path, monkeypatch):
+    """A plain run (no --full) prints the headline line without any side measurement, and --dump-outputs writes the image
+    of the last timed step: the seeded job rendered through start_ray_tracing gives the same image, and so does a second run."""
+    from photon_amd import scenes
+    d = _bench("--dump-outputs", str(tmp_path / "a"), bench_dir=str(tmp_path))
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in d, key
+    assert d["unit"] == "Mrays/s" and d["higher_is_better"] is True and d["dtype"] == "f32" and d["steps"] == 2
+    assert d["value"] == pytest.approx(d["config"]["rays_total"] / d["ms_per_step"] * 1e-3, rel=1e-2)
+    assert d["cpu_baseline"] is None and d["gpu_other_configs"] is None and "abi_call" not in d and "check" not in d
+    r = d["roofline"]
+    assert r["march_profile"] is None and r["traffic"] is None and "copy_measured_gbs" not in r["hbm"] and r["kernel_ms"] > 0
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and a.shape == (1024, 1024) and a.sum() > 0
+    call = scenes.bos_scene(n_dots=6, points_per_dot=100, rays_per_source=500, density_grad_filename=str(tmp_path / "bos_48.nrrd"),
+                            seed=1, ray_tracing_algorithm=2)
+    monkeypatch.setenv("PHOTON_INTERP", "cubic")
+    ref = photon.render(call).astype(np.float64)
+    assert np.linalg.norm(a - ref) / np.linalg.norm(ref) <= 1e-5          # the parity tests' image tolerance
+    _bench("--dump-outputs", str(tmp_path / "b"), bench_dir=str(tmp_path))
+    b = np.load(tmp_path / "b" / "image.npy")
+    assert np.linalg.norm(a.astype(np.float64) - b) / np.linalg.norm(b.astype(np.float64)) <= 1e-6
+
+
+@pytest.mark.gpu
 def test_bench_line_contract(photon):
-    d = _bench("--cpu-sample-rays", "20000", "--check")
+    d = _bench("--full", "--cpu-sample-rays", "20000", "--check")
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
@@ -83,7 +111,7 @@ def test_bench_line_contract(photon):
 
 @pytest.mark.gpu
 def test_bench_weak_mode_and_trilinear(photon):
-    d = _bench("--cpu-sample-rays", "0", "--no-traffic", "--no-other-configs", "--scaling", "weak", "--interp", "linear")
+    d = _bench("--full", "--cpu-sample-rays", "0", "--no-traffic", "--no-other-configs", "--scaling", "weak", "--interp", "linear")
     assert d["scaling"] == "weak" and d["roofline"]["traffic"] is None and d["cpu_baseline"] is None
     assert "linear sampler" in d["config"]["workload"] and 0 < d["roofline"]["frac"] <= 1.0
     assert d["roofline"]["bound"].startswith("valu_f32") and d["roofline"]["unit"] == "TFLOP/s"
@@ -95,7 +123,7 @@ def test_bench_rehearsal_three_ranks_on_one_gpu(photon):
     """`bench.py --gpus 3 --rehearse`: the script starts its own three ranks, each traces its shard_range of the ONE
     job on the shared GPU, the images are sum-reduced onto rank 0 -- the N > 1 logic of the bench (sharding, counters,
     JSON) end to end; the reduced image must be the oracle's image of the whole job."""
-    d = _bench("--gpus", "3", "--rehearse", "--cpu-sample-rays", "0", "--no-traffic", "--check")
+    d = _bench("--full", "--gpus", "3", "--rehearse", "--cpu-sample-rays", "0", "--no-traffic", "--check")
     assert d["n_gpus"] == 3 and d["scaling"] == "strong" and "rehearsal" in d
     assert d["config"]["rays_total"] == 6 * 100 * 500 == d["rays_marched"]      # every source traced exactly once
     assert d["roofline"]["algorithmic_texel_rate"]["rays_per_launch"] == 2 * 100 * 500      # rank 0's third of the sources
@@ -105,6 +133,6 @@ def test_bench_rehearsal_three_ranks_on_one_gpu(photon):
     pr = d["per_rank"]                                   # every rank's clock / kernel time / step time: the slowest sets the step
     assert [r["rank"] for r in pr] == [0, 1, 2] and all(r["clock_mhz"] > 500 and r["kernel_ms"] > 0 and r["ms_per_step"] > 0 for r in pr)
     assert sum(r["rays"] for r in pr) == 6 * 100 * 500
-    w = _bench("--gpus", "2", "--rehearse", "--scaling", "weak", "--cpu-sample-rays", "0", "--no-traffic")
+    w = _bench("--full", "--gpus", "2", "--rehearse", "--scaling", "weak", "--cpu-sample-rays", "0", "--no-traffic")
     assert w["n_gpus"] == 2 and w["scaling"] == "weak" and w["config"]["rays_total"] == 2 * 6 * 100 * 500
     assert w["check"]["sharded_vs_single_gpu_rel_l2"] <= 1e-6                    # two different scenes, summed

@@ -11,6 +11,6 @@ for n in "$@"; do
   i=$((i + 1))
   log=gpurun_out/ab_${i}_${n}.log
   if [ "$n" = default ]; then unset PHOTON_LIBRARY; else export PHOTON_LIBRARY=$ROOT/build/variants/lib_$n.so; fi
-  timeout -k 10 180 python bench.py --steps 5 --warmup 2 --cpu-sample-rays 0 --no-traffic $args > "$log" 2>&1 || { echo "$n FAILED"; tail -5 "$log"; exit 1; }
+  timeout -k 10 180 python bench.py --full --steps 5 --warmup 2 --cpu-sample-rays 0 --no-traffic $args > "$log" 2>&1 || { echo "$n FAILED"; tail -5 "$log"; exit 1; }
   echo -n "[$args] $n: "; python tools/bench_line.py "$log"
 done

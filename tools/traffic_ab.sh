@@ -4,10 +4,13 @@
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd "$ROOT" || exit 1
 args=$1; shift
+log_dir=${LOG_DIR:-$ROOT/build/logs}
+mkdir -p "$log_dir"
 for v in "$@"; do
   if [ "$v" = default ]; then unset PHOTON_LIBRARY; else export PHOTON_LIBRARY=$ROOT/build/variants/lib_$v.so; fi
-  timeout -k 10 300 python bench.py --steps 5 --cpu-sample-rays 0 $args > gpurun_out/traffic_$v.log 2>&1 || { echo "$v FAILED"; tail -3 gpurun_out/traffic_$v.log; continue; }
-  python - gpurun_out/traffic_$v.log "$v" <<'PY'
+  log=$log_dir/traffic_$v.log
+  timeout -k 10 300 python bench.py --full --steps 5 --cpu-sample-rays 0 $args > "$log" 2>&1 || { echo "$v FAILED"; tail -3 "$log"; continue; }
+  python - "$log" "$v" <<'PY'
 import json, sys
 d = json.loads([l for l in open(sys.argv[1]) if l.startswith("{")][-1])
 r = d["roofline"]
