@@ -14,45 +14,42 @@ using namespace photon;
 
 namespace {
 
-int interpolation_from_env() {
-    const char *e = getenv("PHOTON_INTERP");
-    if (e && (strcmp(e, "cubic") == 0 || strcmp(e, "2") == 0)) return 2;
-    return 1;                       // the reference hard-codes interpolation_scheme = 1 (.cu:3330)
-}
+using Clock = std::chrono::steady_clock;
+double ms(Clock::time_point from, Clock::time_point to) { return std::chrono::duration<double, std::milli>(to - from).count(); }
 
-// PHOTON_ELEMENT_TRAIN=sequential: the working multi-element train instead of the reference's
-// "element 0 for every single-member group, nothing for the others" (.cu:1331-1333, 1049-1272)
-int element_train_from_env() {
-    const char *e = getenv("PHOTON_ELEMENT_TRAIN");
-    return e && (strcmp(e, "sequential") == 0 || strcmp(e, "1") == 0) ? 1 : 0;
-}
+// The arguments of one start_ray_tracing call but the image (include/parallel_ray_tracing.h).
+struct CallArgs {
+    float lens_pitch, image_distance;
+    scattering_data_t *sdp; char *scattering_type_str; lightfield_source_t *lsp;
+    int rays_per_source; float beam_wavelength, f_number; int num_elements;
+    double (*element_center)[3]; element_data_t *edp; double (*element_planes)[4]; int *sys_index;
+    camera_design_t *cam; bool density; char *density_path;
+    bool save_lightrays; char *pos_path, *dir_path; int num_lightrays_save; int algorithm;
+    bool add_pos_noise; float pos_noise_std; bool add_ngrad_noise; float ngrad_noise_std; float ratio;
+    bool save_intermediate; int num_intermediate_save;
+    bool dumping() const { return save_lightrays && num_lightrays_save > 0; }
+};
 
-// PHOTON_SKIP_DOOMED=0 marches every ray like the reference does (photon_scene_set_skip_doomed)
-int skip_doomed_from_env() {
-    const char *e = getenv("PHOTON_SKIP_DOOMED");
-    return !(e && strcmp(e, "0") == 0);
-}
-
-// PHOTON_RAY_ORDER=source|lens|auto (photon_scene_set_ray_order)
-int ray_order_from_env() {
-    const char *e = getenv("PHOTON_RAY_ORDER");
-    if (e && strcmp(e, "source") == 0) return 0;
-    if (e && strcmp(e, "lens") == 0) return 1;
-    return 2;
-}
-
-// PHOTON_TEX_WEIGHTS=fixed8|exact: trilinear weights as the reference's texture unit holds them (8 fractional bits:
-// the documented arithmetic of the tex3D() the reference calls; default) or as exact f32
-int weight_bits_from_env() {
-    const char *e = getenv("PHOTON_TEX_WEIGHTS");
-    return e && (strcmp(e, "exact") == 0 || strcmp(e, "0") == 0) ? 0 : 8;
-}
+// The environment knobs of one call (the ABI has no room for them: include/parallel_ray_tracing.h), read once at its start.
+// PHOTON_VERBOSE is the library's, not the call's (verbose()).
+struct CallSettings {
+    int interpolation;          // PHOTON_INTERP=cubic: 2; else 1, which the reference hard-codes (interpolation_scheme = 1, .cu:3330)
+    int element_train;          // PHOTON_ELEMENT_TRAIN=sequential: the working multi-element train instead of the reference's
+                                // "element 0 for every single-member group, nothing for the others" (.cu:1331-1333, 1049-1272)
+    int ray_order;              // PHOTON_RAY_ORDER=source|lens|auto (photon_scene_set_ray_order)
+    int skip_doomed;            // PHOTON_SKIP_DOOMED=0 marches every ray like the reference does (photon_scene_set_skip_doomed)
+    int weight_bits;            // PHOTON_TEX_WEIGHTS=fixed8|exact: trilinear weights as the reference's texture unit holds them (8
+                                // fractional bits: the documented arithmetic of the tex3D() the reference calls; default) or as exact f32
+    uint64_t noise_seed;        // PHOTON_NOISE_SEED: the noise hooks' seed, instead of the reference's time(NULL)
+    bool peer_reads;            // PHOTON_PEER_READS=0: never dereference another device's memory, always stage (for a node whose
+                                // peer mappings misbehave)
+    std::vector<int> devices;   // PHOTON_DEVICES (parse_devices)
+};
 
 // PHOTON_DEVICES: "all", or a comma-separated list of device ordinals (repeats allowed: "0,0" renders two
 // shards side by side on device 0).  Empty = the calling thread's current device only.
-std::vector<int> devices_from_env() {
+std::vector<int> parse_devices(const char *e) {
     std::vector<int> out;
-    const char *e = getenv("PHOTON_DEVICES");
     if (!e || !*e) return out;
     int count = 0;
     if (hipGetDeviceCount(&count) != hipSuccess || count < 1) return out;
@@ -75,6 +72,54 @@ std::vector<int> devices_from_env() {
         if (*end && *end != ',') break;
     }
     return out;
+}
+
+CallSettings settings_from_env() {
+    auto is = [](const char *e, const char *a, const char *b = nullptr) { return e && (strcmp(e, a) == 0 || (b && strcmp(e, b) == 0)); };
+    CallSettings s;
+    s.interpolation = is(getenv("PHOTON_INTERP"), "cubic", "2") ? 2 : 1;
+    s.element_train = is(getenv("PHOTON_ELEMENT_TRAIN"), "sequential", "1") ? 1 : 0;
+    const char *order = getenv("PHOTON_RAY_ORDER");
+    s.ray_order = is(order, "source") ? 0 : is(order, "lens") ? 1 : 2;
+    s.skip_doomed = !is(getenv("PHOTON_SKIP_DOOMED"), "0");
+    s.weight_bits = is(getenv("PHOTON_TEX_WEIGHTS"), "exact", "0") ? 0 : 8;
+    const char *seed = getenv("PHOTON_NOISE_SEED");
+    s.noise_seed = seed ? strtoull(seed, nullptr, 0) : 0x5eedULL;
+    s.peer_reads = !is(getenv("PHOTON_PEER_READS"), "0");
+    s.devices = parse_devices(getenv("PHOTON_DEVICES"));
+    return s;
+}
+
+// The scene of the call's sources [begin, end) on the current device, set up as the call and its settings say, and the call's
+// volume (cached on the device; with `shared`, the NRRD is parsed once for all devices of the call).  Returns 2 when the scene
+// upload fails (*scene stays null), else what cached_volume returns; *scene_ready is when the scene was set up.
+int setup_scene(const CallArgs &a, const CallSettings &cs, long long begin, long long end, SharedDensity *shared,
+                photon_scene **scene, photon_volume **vol, Clock::time_point *scene_ready = nullptr) {
+    lightfield_source_t block = *a.lsp;                                 // [begin, end) of the caller's arrays
+    block.x += begin; block.y += begin; block.z += begin; block.radiance += begin; block.diameter_index += begin;
+    block.num_particles = (int)(end - begin);
+    if (photon_scene_create(a.lens_pitch, a.image_distance, a.sdp, a.scattering_type_str, &block, a.rays_per_source,
+                            a.beam_wavelength, a.f_number, a.num_elements, a.element_center, a.edp, a.element_planes,
+                            a.sys_index, a.cam, a.ratio, scene)) return 2;
+    photon_scene *sc = *scene;
+    photon_scene_set_source_base(sc, begin);
+    // the reference's noise switches; gradient noise only exists inside the volume march (Euler, .h:853-863)
+    photon_scene_set_noise(sc, a.add_pos_noise, a.pos_noise_std, a.density && a.add_ngrad_noise, a.ngrad_noise_std, cs.noise_seed);
+    photon_scene_set_element_train(sc, cs.element_train);
+    photon_scene_set_ray_order(sc, cs.ray_order);
+    photon_scene_set_skip_doomed(sc, cs.skip_doomed);
+    if (scene_ready) *scene_ready = Clock::now();
+    if (!a.density) return 0;
+    const int rc = cached_volume(a.density_path, cs.interpolation, vol, shared);
+    if (!rc) photon_volume_set_weight_bits(*vol, cs.weight_bits);
+    return rc;
+}
+
+// A HIP error that ends the call: said on stderr as the call's one "image left untouched" line.
+bool hip_failed(hipError_t err, int line) {
+    if (err == hipSuccess) return false;
+    fprintf(stderr, "photon: HIP error %d (%s) at %s:%d; image left untouched\n", (int)err, hipGetErrorString(err), __FILE__, line);
+    return true;
 }
 
 bool write_dump(const char *dir, const char *prefix, int k, const std::vector<float> &v) {
@@ -132,16 +177,6 @@ hipStream_t worker_stream(int device, int slot) {
     return s;
 }
 
-// Arguments of one start_ray_tracing call, as the multi-device path hands them to its workers.
-struct CallArgs {
-    float lens_pitch, image_distance;
-    scattering_data_t *sdp; char *scattering_type_str; lightfield_source_t *lsp;
-    int rays_per_source; float beam_wavelength, f_number; int num_elements;
-    double (*element_center)[3]; element_data_t *edp; double (*element_planes)[4]; int *sys_index;
-    camera_design_t *cam; bool density; char *density_path; int algorithm;
-    bool add_pos_noise; float pos_noise_std; bool add_ngrad_noise; float ngrad_noise_std; float ratio;
-};
-
 // PHOTON_DEVICES (SURVEY 8e inside ONE call, for photon's single Python process).  What is distributed is the reference's
 // chunk loop over light-field sources (parallel_ray_tracing.cu:3505-3558): the sources are cut into contiguous,
 // count-balanced blocks, one per listed device; each device's host thread uploads ONLY its block (plus the replicated
@@ -152,9 +187,8 @@ struct CallArgs {
 // first one cannot map (no xGMI / PCIe peer path) has its accumulator copied into a block of the cache first
 // (hipMemcpyPeerAsync, all such copies in flight together) -- said on stderr when the pair is first seen, and per call
 // under PHOTON_VERBOSE.
-int render_on_devices(const std::vector<int> &devices, const CallArgs &a, float *image_array) {
-    const char *e = getenv("PHOTON_NOISE_SEED");
-    const uint64_t seed = e ? strtoull(e, nullptr, 0) : 0x5eedULL;
+int render_on_devices(const CallArgs &a, const CallSettings &cs, float *image_array) {
+    const std::vector<int> &devices = cs.devices;
     const long long n_src = a.lsp->num_particles;
     const size_t npix = (size_t)a.cam->x_pixel_number * a.cam->y_pixel_number;
     const size_t K = devices.size();
@@ -164,14 +198,11 @@ int render_on_devices(const std::vector<int> &devices, const CallArgs &a, float 
         for (size_t j = 0; j < k; j++) slot[k] += devices[j] == devices[k];
     SharedDensity shared;
     std::vector<std::thread> workers;
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = Clock::now();
     // peer access from the first device to the others, BEFORE any worker allocates its accumulator: what the sum's kernel
     // dereferences must have been allocated under the mapping (photon_pool.hpp); once per pair and process, then a table look-up
-    // PHOTON_PEER_READS=0: never dereference another device's memory, always stage (for a node whose peer mappings misbehave)
-    const char *pr = getenv("PHOTON_PEER_READS");
-    const bool allow_direct = !(pr && strcmp(pr, "0") == 0);
     std::vector<char> direct(K, 1);
-    for (size_t k = 1; k < K; k++) direct[k] = devices[k] == devices[0] || (allow_direct && peer_access(devices[0], devices[k])) ? 1 : 0;
+    for (size_t k = 1; k < K; k++) direct[k] = devices[k] == devices[0] || (cs.peer_reads && peer_access(devices[0], devices[k])) ? 1 : 0;
     // Two phases with a rendezvous between them: every worker first builds its scene (uploads) and gets its volume, THEN all
     // start tracing.  With distinct devices the rendezvous costs the spread of eight equal uploads; with a device listed more
     // than once (rehearsals, tests: all eight on one) it keeps one shard's uploads -- blit kernels -- from queueing behind
@@ -200,34 +231,18 @@ int render_on_devices(const std::vector<int> &devices, const CallArgs &a, float 
             const int rc_setup = guarded("start_ray_tracing (device worker, setup)", [&]() -> int {
                 if (hipSetDevice(devices[k]) != hipSuccess) return 1;
                 stream = worker_stream(devices[k], slot[k]);
-                lightfield_source_t shard = *a.lsp;                     // this device's block of the caller's arrays
-                shard.x += b; shard.y += b; shard.z += b; shard.radiance += b; shard.diameter_index += b;
-                shard.num_particles = (int)(e2 - b);
-                photon_scene *sc = nullptr;
-                if (photon_scene_create(a.lens_pitch, a.image_distance, a.sdp, a.scattering_type_str, &shard, a.rays_per_source,
-                                        a.beam_wavelength, a.f_number, a.num_elements, a.element_center, a.edp, a.element_planes,
-                                        a.sys_index, a.cam, a.ratio, &sc)) return 2;
-                scenes[k] = sc;
-                sc->dev.source_base = b;
-                photon_scene_set_noise(sc, a.add_pos_noise, a.pos_noise_std, a.density && a.add_ngrad_noise, a.ngrad_noise_std, seed);
-                photon_scene_set_element_train(sc, element_train_from_env());
-                photon_scene_set_ray_order(sc, ray_order_from_env());
-                photon_scene_set_skip_doomed(sc, skip_doomed_from_env());
-                int rc = 0;
-                if (a.density) rc = cached_volume(a.density_path, interpolation_from_env(), &volumes[k], &shared);
-                if (!rc && volumes[k]) photon_volume_set_weight_bits(volumes[k], weight_bits_from_env());
-                return rc;
+                return setup_scene(a, cs, b, e2, &shared, &scenes[k], &volumes[k]);
             });
             rendezvous.arrive_and_wait();                               // on every path: a worker that failed still arrives
             if (rc_setup) { rcs[k] = rc_setup; return; }
             rcs[k] = guarded("start_ray_tracing (device worker)", [&]() -> int {
-                const auto tw = std::chrono::steady_clock::now();
+                const auto tw = Clock::now();
                 int rc = trace_accumulate(scenes[k], volumes[k], a.algorithm, 0, e2 - b, stream, 0, nullptr);
                 if (!rc && hipStreamSynchronize(stream) != hipSuccess) rc = 4;
                 if (!rc) rc = march_error_check(scenes[k]);
                 if (!rc && verbose())
                     fprintf(stderr, "photon: device %d: sources [%lld, %lld) traced in %.3f ms\n", devices[k], b, e2,
-                            std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tw).count());
+                            ms(tw, Clock::now()));
                 return rc;
             });
         });
@@ -240,17 +255,14 @@ int render_on_devices(const std::vector<int> &devices, const CallArgs &a, float 
     // meanwhile, on the calling thread: the caller's image onto the first device
     int rc = all_started ? 0 : 1;
     auto check = [&](hipError_t err, int line) {
-        if (err != hipSuccess && !rc) {
-            fprintf(stderr, "photon: HIP error %d (%s) at %s:%d; image left untouched\n", (int)err, hipGetErrorString(err), __FILE__, line);
-            rc = (int)err;
-        }
+        if (!rc && hip_failed(err, line)) rc = (int)err;
         return rc == 0;
     };
     PoolBuffer<float> d_img;
     if (check(hipSetDevice(devices[0]), __LINE__) && check(d_img.alloc(npix), __LINE__))
         check(hipMemcpy(d_img.p, image_array, npix * sizeof(float), hipMemcpyHostToDevice), __LINE__);      // .cu:3309
     for (auto &w : workers) w.join();
-    const auto t_traced = std::chrono::steady_clock::now();
+    const auto t_traced = Clock::now();
     for (size_t k = 0; k < K && !rc; k++)
         if (rcs[k]) { fprintf(stderr, "photon: device %d failed (%d); image left untouched\n", devices[k], rcs[k]); rc = rcs[k]; }
     // ---- the sum, on the first device ----
@@ -280,10 +292,10 @@ int render_on_devices(const std::vector<int> &devices, const CallArgs &a, float 
         if (!rc) check(hipMemcpy(image_array, d_img.p, npix * sizeof(float), hipMemcpyDeviceToHost), __LINE__);      // .cu:3675 (waits for the kernel)
     }
     if (verbose()) {
-        const auto t_end = std::chrono::steady_clock::now();
+        const auto t_end = Clock::now();
         fprintf(stderr, "photon: %zu devices: shards traced in %.3f ms (uploads included); sum of %zu accumulators on device %d (%zu by direct peer reads, "
-                        "%zu staged) + fold + image out: %.3f ms\n", K, std::chrono::duration<double, std::milli>(t_traced - t_start).count(), K, devices[0],
-                K - 1 - n_staged, n_staged, std::chrono::duration<double, std::milli>(t_end - t_traced).count());
+                        "%zu staged) + fold + image out: %.3f ms\n", K, ms(t_start, t_traced), K, devices[0],
+                K - 1 - n_staged, n_staged, ms(t_traced, t_end));
     }
     for (size_t k = 0; k < K; k++)
         if (scenes[k]) { (void)hipSetDevice(devices[k]); photon_scene_free(scenes[k]); }       // waits for the device first
@@ -293,182 +305,141 @@ int render_on_devices(const std::vector<int> &devices, const CallArgs &a, float 
     return rc;
 }
 
-}  // namespace
+// Device blocks of the ray dumps (save_lightrays, save_intermediate_ray_data).
+struct DumpBuffers { PoolBuffer<float> pos, dir, inter_pos, inter_dir; };
 
-static void start_ray_tracing_impl(float lens_pitch, float image_distance, scattering_data_t *scattering_data_p,
-                                  char *scattering_type_str, lightfield_source_t *lightfield_source_p,
-                                  int lightray_number_per_particle, float beam_wavelength, float aperture_f_number,
-                                  int num_elements, double (*element_center)[3], element_data_t *element_data_p,
-                                  double (*element_plane_parameters)[4], int *element_system_index,
-                                  camera_design_t *camera_design_p, float *image_array,
-                                  bool simulate_density_gradients, char *density_grad_filename, bool save_lightrays,
-                                  char *lightray_position_save_path, char *lightray_direction_save_path,
-                                  int num_lightrays_save, int ray_tracing_algorithm, bool add_pos_noise,
-                                  float pos_noise_std, bool add_ngrad_noise, float ngrad_noise_std,
-                                  float ray_cone_pitch_ratio, bool save_intermediate_ray_data,
-                                  int num_intermediate_positions_save) {
-    const auto t0 = std::chrono::steady_clock::now();
-    if (!image_array || !camera_design_p || !lightfield_source_p) {
-        fprintf(stderr, "photon: start_ray_tracing: null argument; image left untouched\n");
-        return;
+// The trace of a call that dumps its rays, folded into d_image.  The reference's chunking decides which rays land in which
+// pos_/dir_ file (.cu:3366-3372, 3515-3611): chunks of source_point_number sources, one file pair per chunk; intermediate
+// dumps ride on the same chunking (.cu:3484-3492, 3535-3546, 3613-3670).
+int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume *vol, float *d_image, DumpBuffers &d) {
+    const long long num_particles = a.lsp->num_particles;
+    long long chunk = a.lsp->source_point_number;
+    if (num_particles < chunk) chunk = num_particles;
+    if (chunk < 1) chunk = 1;
+    if ((unsigned long long)(chunk * a.rays_per_source) > kMaxRaysPerLaunch) {
+        fprintf(stderr, "photon: source_point_number*rays exceeds %u rays per launch\n", kMaxRaysPerLaunch);
+        return 1;
     }
-    const bool dumping = save_lightrays && num_lightrays_save > 0;
-    int caller_device = 0;                                              // the caller's current device is restored on every path
-    const bool have_caller_device = hipGetDevice(&caller_device) == hipSuccess;
-    struct RestoreDevice { bool on; int dev; ~RestoreDevice() { if (on) (void)hipSetDevice(dev); } } restore{have_caller_device, caller_device};
-    {   // PHOTON_DEVICES: shard the sources of one call over several GPUs.  Ray dumps keep the
-        // reference's chunk -> file mapping and stay on one device.
-        const std::vector<int> devices = devices_from_env();
-        if (devices.size() > 1 && !dumping) {
-            const CallArgs a{lens_pitch, image_distance, scattering_data_p, scattering_type_str, lightfield_source_p,
-                             lightray_number_per_particle, beam_wavelength, aperture_f_number, num_elements, element_center,
-                             element_data_p, element_plane_parameters, element_system_index, camera_design_p,
-                             simulate_density_gradients, density_grad_filename, ray_tracing_algorithm, add_pos_noise,
-                             pos_noise_std, add_ngrad_noise, ngrad_noise_std, ray_cone_pitch_ratio};
-            const int rc = render_on_devices(devices, a, image_array);
-            if (!rc && verbose()) {
-                const double sec = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-                const long long n_src = lightfield_source_p->num_particles;
-                printf("photon: %lld sources x %d rays on %zu devices in %.3f s (%.2f Mrays/s incl. transfers)\n", n_src,
-                       lightray_number_per_particle, devices.size(), sec, n_src * (double)lightray_number_per_particle / sec * 1e-6);
-            }
-            return;
-        }
-        if (!devices.empty() && hipSetDevice(devices[0]) != hipSuccess) {
-            fprintf(stderr, "photon: cannot select device %d; image left untouched\n", devices[0]);
-            return;
-        }
+    const size_t nsave = (size_t)a.num_lightrays_save * 3;
+    const bool inter = a.density && a.save_intermediate && a.num_intermediate_save > 0;
+    const size_t ninter = inter ? nsave * (size_t)a.num_intermediate_save : 0;
+    PH_CHECK(d.pos.alloc(nsave));
+    PH_CHECK(d.dir.alloc(nsave));
+    if (inter) {
+        PH_CHECK(d.inter_pos.alloc(ninter));
+        PH_CHECK(d.inter_dir.alloc(ninter));
     }
-    photon_scene *scene = nullptr;
-    float *d_image = nullptr, *d_fpos = nullptr, *d_fdir = nullptr, *d_ipos = nullptr, *d_idir = nullptr;
-    // PHOTON_VERBOSE: where a call's time goes beside the trace itself (scene upload, volume, image in / out, frees)
-    auto t_prev = t0;
-    double t_scene = 0, t_volume = 0, t_image_in = 0, t_trace = 0, t_image_out = 0;
-    auto lap = [&](double &acc) { const auto now = std::chrono::steady_clock::now(); acc += std::chrono::duration<double, std::milli>(now - t_prev).count(); t_prev = now; };
-    auto cleanup = [&]() {
-        if (scene) photon_scene_free(scene);
-        pool_free(d_image);
-        pool_free(d_fpos);
-        pool_free(d_fdir);
-        pool_free(d_ipos);
-        pool_free(d_idir);
-    };
-#define PH_VOID(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { fprintf(stderr, "photon: HIP error %d (%s) at %s:%d; image left untouched\n", (int)_e, hipGetErrorString(_e), __FILE__, __LINE__); cleanup(); return; } } while (0)
-    if (photon_scene_create(lens_pitch, image_distance, scattering_data_p, scattering_type_str, lightfield_source_p,
-                            lightray_number_per_particle, beam_wavelength, aperture_f_number, num_elements,
-                            element_center, element_data_p, element_plane_parameters, element_system_index,
-                            camera_design_p, ray_cone_pitch_ratio, &scene)) {
-        fprintf(stderr, "photon: scene upload failed; image left untouched\n");
-        return;
-    }
-    lap(t_scene);
-    {   // noise hooks: same switches as the reference; seed from the environment instead of time(NULL)
-        const char *e = getenv("PHOTON_NOISE_SEED");
-        const uint64_t seed = e ? strtoull(e, nullptr, 0) : 0x5eedULL;
-        // gradient noise only exists inside the volume march (Euler, .h:853-863)
-        photon_scene_set_noise(scene, add_pos_noise, pos_noise_std, simulate_density_gradients && add_ngrad_noise,
-                               ngrad_noise_std, seed);
-        photon_scene_set_element_train(scene, element_train_from_env());
-        photon_scene_set_ray_order(scene, ray_order_from_env());
-        photon_scene_set_skip_doomed(scene, skip_doomed_from_env());
-    }
-    photon_volume *vol = nullptr;
-    if (simulate_density_gradients) {
-        if (cached_volume(density_grad_filename, interpolation_from_env(), &vol)) { cleanup(); return; }
-        photon_volume_set_weight_bits(vol, weight_bits_from_env());
-    }
-    lap(t_volume);
-    const int W = camera_design_p->x_pixel_number, H = camera_design_p->y_pixel_number;
-    const size_t npix = (size_t)W * H;
-    PH_VOID(pool_malloc((void **)&d_image, npix * sizeof(float)));
-    PH_VOID(hipMemcpy(d_image, image_array, npix * sizeof(float), hipMemcpyHostToDevice));     // .cu:3309
-    lap(t_image_in);
-
-    const long long num_particles = lightfield_source_p->num_particles;
-    const long long rps = lightray_number_per_particle;
-    int rc = 0;
-    if (dumping) {
-        // the reference's chunking decides which rays land in which pos_/dir_ file (.cu:3366-3372,
-        // 3515-3611): chunks of source_point_number sources, one file pair per chunk
-        long long chunk = lightfield_source_p->source_point_number;
-        if (num_particles < chunk) chunk = num_particles;
-        if (chunk < 1) chunk = 1;
-        if ((unsigned long long)(chunk * rps) > kMaxRaysPerLaunch) {
-            fprintf(stderr, "photon: source_point_number*rays exceeds %u rays per launch; image left untouched\n", kMaxRaysPerLaunch);
-            cleanup();
-            return;
-        }
-        const size_t nsave = (size_t)num_lightrays_save * 3;
-        PH_VOID(pool_malloc((void **)&d_fpos, nsave * sizeof(float)));
-        PH_VOID(pool_malloc((void **)&d_fdir, nsave * sizeof(float)));
-        std::vector<float> host(nsave);
-        // intermediate dumps ride on the same chunking (.cu:3484-3492, 3535-3546, 3613-3670)
-        const bool inter = simulate_density_gradients && save_intermediate_ray_data && num_intermediate_positions_save > 0;
-        const size_t ninter = inter ? nsave * (size_t)num_intermediate_positions_save : 0;
-        std::vector<float> host_inter(ninter);
+    std::vector<float> host(nsave), host_inter(ninter);
+    const DumpDev dump{d.pos.p, d.dir.p, a.num_lightrays_save, d.inter_pos.p, d.inter_dir.p, inter ? a.num_intermediate_save : 0};
+    const long long kmax = (num_particles + chunk - 1) / chunk;
+    { const int rc = begin_accumulate(scene, nullptr); if (rc) return rc; }
+    for (long long k = 0; k < kmax; k++) {
+        PH_CHECK(hipMemsetAsync(d.pos.p, 0xFF, nsave * sizeof(float), nullptr));     // all-ones = NaN (.cu:3527-3533); the null stream, like the chunk's launches
+        PH_CHECK(hipMemsetAsync(d.dir.p, 0xFF, nsave * sizeof(float), nullptr));
         if (inter) {
-            PH_VOID(pool_malloc((void **)&d_ipos, ninter * sizeof(float)));
-            PH_VOID(pool_malloc((void **)&d_idir, ninter * sizeof(float)));
+            PH_CHECK(hipMemsetAsync(d.inter_pos.p, 0xFF, ninter * sizeof(float), nullptr));
+            PH_CHECK(hipMemsetAsync(d.inter_dir.p, 0xFF, ninter * sizeof(float), nullptr));
         }
-        const long long kmax = (num_particles + chunk - 1) / chunk;
-        rc = begin_accumulate(scene, nullptr);
-        for (long long k = 0; k < kmax && rc == 0; k++) {
-            PH_VOID(hipMemsetAsync(d_fpos, 0xFF, nsave * sizeof(float), nullptr));    // all-ones = NaN (.cu:3527-3533); the null stream, like the chunk's launches
-            PH_VOID(hipMemsetAsync(d_fdir, 0xFF, nsave * sizeof(float), nullptr));
-            if (inter) {
-                PH_VOID(hipMemsetAsync(d_ipos, 0xFF, ninter * sizeof(float), nullptr));
-                PH_VOID(hipMemsetAsync(d_idir, 0xFF, ninter * sizeof(float), nullptr));
-            }
-            const DumpDev dump{d_fpos, d_fdir, num_lightrays_save, d_ipos, d_idir, inter ? num_intermediate_positions_save : 0};
-            rc = launch_chunk(scene, vol, ray_tracing_algorithm, k * chunk, std::min(num_particles, (k + 1) * chunk),
-                              dump, nullptr, nullptr, nullptr);
-            if (rc) break;
-            bool wrote = true;                                          // a dump that cannot be written fails the call
-            PH_VOID(hipMemcpy(host.data(), d_fpos, nsave * sizeof(float), hipMemcpyDeviceToHost));
-            wrote = write_dump(lightray_position_save_path, "pos_", (int)k, host) && wrote;
-            PH_VOID(hipMemcpy(host.data(), d_fdir, nsave * sizeof(float), hipMemcpyDeviceToHost));
-            wrote = write_dump(lightray_direction_save_path, "dir_", (int)k, host) && wrote;
-            if (inter) {
-                PH_VOID(hipMemcpy(host_inter.data(), d_ipos, ninter * sizeof(float), hipMemcpyDeviceToHost));
-                wrote = write_dump(lightray_position_save_path, "intermediate_pos_", (int)k, host_inter) && wrote;
-                PH_VOID(hipMemcpy(host_inter.data(), d_idir, ninter * sizeof(float), hipMemcpyDeviceToHost));
-                wrote = write_dump(lightray_direction_save_path, "intermediate_dir_", (int)k, host_inter) && wrote;
-            }
-            if (!wrote) rc = 5;
+        const int rc = launch_chunk(scene, vol, a.algorithm, k * chunk, std::min(num_particles, (k + 1) * chunk), dump, nullptr, nullptr, nullptr);
+        if (rc) return rc;
+        bool wrote = true;                                              // a dump that cannot be written fails the call
+        PH_CHECK(hipMemcpy(host.data(), d.pos.p, nsave * sizeof(float), hipMemcpyDeviceToHost));
+        wrote = write_dump(a.pos_path, "pos_", (int)k, host) && wrote;
+        PH_CHECK(hipMemcpy(host.data(), d.dir.p, nsave * sizeof(float), hipMemcpyDeviceToHost));
+        wrote = write_dump(a.dir_path, "dir_", (int)k, host) && wrote;
+        if (inter) {
+            PH_CHECK(hipMemcpy(host_inter.data(), d.inter_pos.p, ninter * sizeof(float), hipMemcpyDeviceToHost));
+            wrote = write_dump(a.pos_path, "intermediate_pos_", (int)k, host_inter) && wrote;
+            PH_CHECK(hipMemcpy(host_inter.data(), d.inter_dir.p, ninter * sizeof(float), hipMemcpyDeviceToHost));
+            wrote = write_dump(a.dir_path, "intermediate_dir_", (int)k, host_inter) && wrote;
         }
-        if (rc == 0) rc = launch_finalize(scene, d_image, nullptr);
+        if (!wrote) return 5;
+    }
+    return launch_finalize(scene, d_image, nullptr);
+}
+
+// When the phases of a one-device call ended (PHOTON_VERBOSE: where a call's time goes beside the trace itself).
+struct Phases { Clock::time_point start, scene, volume, image_in, trace, image_out; };
+
+// The call on the current device: 0, or non-zero once stderr has said why.  The device blocks are declared before the
+// scene, so the scene is freed first: photon_scene_free waits for the device, and no block may go back to the cache while
+// a kernel of the call can still use it.
+int render_on_one_device(const CallArgs &a, const CallSettings &cs, float *image_array, Phases &t) {
+    PoolBuffer<float> d_image;
+    DumpBuffers dumps;
+    struct SceneOwner { photon_scene *p = nullptr; ~SceneOwner() { photon_scene_free(p); } } scene;
+    photon_volume *vol = nullptr;                                       // the device's cached volume: not the call's to free
+    const long long num_particles = a.lsp->num_particles;
+    if (const int rc = setup_scene(a, cs, 0, num_particles, nullptr, &scene.p, &vol, &t.scene)) {
+        if (!scene.p) fprintf(stderr, "photon: scene upload failed; image left untouched\n");     // (a volume says why itself)
+        return rc;
+    }
+    t.volume = Clock::now();
+    const size_t npix = (size_t)a.cam->x_pixel_number * a.cam->y_pixel_number;
+    if (hip_failed(d_image.alloc(npix), __LINE__) ||
+        hip_failed(hipMemcpy(d_image.p, image_array, npix * sizeof(float), hipMemcpyHostToDevice), __LINE__)) return 1;  // .cu:3309
+    t.image_in = Clock::now();
+    int rc;
+    if (a.dumping()) {
+        rc = trace_with_dumps(a, scene.p, vol, d_image.p, dumps);
     } else {
-        if (simulate_density_gradients && save_intermediate_ray_data)
+        if (a.density && a.save_intermediate)
             fprintf(stderr, "photon: warning: save_intermediate_ray_data needs save_lightrays with num_lightrays_save > 0 "
                             "(the reference sizes the intermediate buffers by it, .cu:3488); nothing recorded\n");
-        rc = photon_trace(scene, vol, ray_tracing_algorithm, 0, num_particles, d_image, nullptr, nullptr);
+        rc = photon_trace(scene.p, vol, a.algorithm, 0, num_particles, d_image.p, nullptr, nullptr);
     }
     if (rc) {
         fprintf(stderr, "photon: trace failed (%d); image left untouched\n", rc);
-        cleanup();
-        return;
+        return rc;
     }
-    PH_VOID(hipDeviceSynchronize());
-    lap(t_trace);
-    if (march_error_check(scene)) {
+    if (hip_failed(hipDeviceSynchronize(), __LINE__)) return 1;
+    t.trace = Clock::now();
+    if (march_error_check(scene.p)) {
         fprintf(stderr, "photon: trace failed; image left untouched\n");
-        cleanup();
+        return 1;
+    }
+    if (hip_failed(hipMemcpy(image_array, d_image.p, npix * sizeof(float), hipMemcpyDeviceToHost), __LINE__)) return 1;  // .cu:3675
+    t.image_out = Clock::now();
+    return 0;
+}
+
+void start_ray_tracing_impl(const CallArgs &a, float *image_array) {
+    const auto t0 = Clock::now();
+    if (!image_array || !a.cam || !a.lsp) {
+        fprintf(stderr, "photon: start_ray_tracing: null argument; image left untouched\n");
         return;
     }
-    PH_VOID(hipMemcpy(image_array, d_image, npix * sizeof(float), hipMemcpyDeviceToHost));     // .cu:3675
-    lap(t_image_out);
-#undef PH_VOID
-    cleanup();
-    if (verbose()) {
-        double t_free = 0;
-        lap(t_free);
-        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-        printf("photon: %lld sources x %lld rays in %.3f s (%.2f Mrays/s incl. transfers)\n", num_particles, rps, s,
-               num_particles * rps / s * 1e-6);
-        printf("photon:   scene upload %.2f ms, volume %.2f, image in %.2f, trace (launches + wait) %.2f, image out %.2f, frees %.2f\n",
-               t_scene, t_volume, t_image_in, t_trace, t_image_out, t_free);
+    const CallSettings cs = settings_from_env();
+    int caller_device = 0;                                              // the caller's current device is restored on every path
+    const bool have_caller_device = hipGetDevice(&caller_device) == hipSuccess;
+    struct RestoreDevice { bool on; int dev; ~RestoreDevice() { if (on) (void)hipSetDevice(dev); } } restore{have_caller_device, caller_device};
+    const long long n_src = a.lsp->num_particles, rps = a.rays_per_source;
+    // PHOTON_DEVICES: shard the sources of one call over several GPUs.  Ray dumps keep the
+    // reference's chunk -> file mapping and stay on one device.
+    if (cs.devices.size() > 1 && !a.dumping()) {
+        const int rc = render_on_devices(a, cs, image_array);
+        if (!rc && verbose()) {
+            const double sec = ms(t0, Clock::now()) * 1e-3;
+            printf("photon: %lld sources x %d rays on %zu devices in %.3f s (%.2f Mrays/s incl. transfers)\n", n_src,
+                   a.rays_per_source, cs.devices.size(), sec, n_src * (double)rps / sec * 1e-6);
+        }
+        return;
     }
+    if (!cs.devices.empty() && hipSetDevice(cs.devices[0]) != hipSuccess) {
+        fprintf(stderr, "photon: cannot select device %d; image left untouched\n", cs.devices[0]);
+        return;
+    }
+    Phases t{t0};
+    if (render_on_one_device(a, cs, image_array, t) || !verbose()) return;
+    const auto t_end = Clock::now();                                    // the call's blocks and scene are freed
+    const double s = ms(t0, t_end) * 1e-3;
+    printf("photon: %lld sources x %lld rays in %.3f s (%.2f Mrays/s incl. transfers)\n", n_src, rps, s, n_src * rps / s * 1e-6);
+    printf("photon:   scene upload %.2f ms, volume %.2f, image in %.2f, trace (launches + wait) %.2f, image out %.2f, frees %.2f\n",
+           ms(t.start, t.scene), ms(t.scene, t.volume), ms(t.volume, t.image_in), ms(t.image_in, t.trace), ms(t.trace, t.image_out),
+           ms(t.image_out, t_end));
 }
+
+}  // namespace
 
 // The exported symbol: no C++ exception crosses the C boundary.
 extern "C" void start_ray_tracing(float lens_pitch, float image_distance, scattering_data_t *scattering_data_p,
@@ -484,13 +455,14 @@ extern "C" void start_ray_tracing(float lens_pitch, float image_distance, scatte
                                   float ray_cone_pitch_ratio, bool save_intermediate_ray_data,
                                   int num_intermediate_positions_save) {
     (void)guarded("start_ray_tracing", [&]() -> int {
-        start_ray_tracing_impl(lens_pitch, image_distance, scattering_data_p, scattering_type_str, lightfield_source_p,
-                               lightray_number_per_particle, beam_wavelength, aperture_f_number, num_elements, element_center,
-                               element_data_p, element_plane_parameters, element_system_index, camera_design_p, image_array,
-                               simulate_density_gradients, density_grad_filename, save_lightrays, lightray_position_save_path,
-                               lightray_direction_save_path, num_lightrays_save, ray_tracing_algorithm, add_pos_noise,
-                               pos_noise_std, add_ngrad_noise, ngrad_noise_std, ray_cone_pitch_ratio,
-                               save_intermediate_ray_data, num_intermediate_positions_save);
+        const CallArgs a{lens_pitch, image_distance, scattering_data_p, scattering_type_str, lightfield_source_p,
+                         lightray_number_per_particle, beam_wavelength, aperture_f_number, num_elements, element_center,
+                         element_data_p, element_plane_parameters, element_system_index, camera_design_p,
+                         simulate_density_gradients, density_grad_filename, save_lightrays, lightray_position_save_path,
+                         lightray_direction_save_path, num_lightrays_save, ray_tracing_algorithm, add_pos_noise, pos_noise_std,
+                         add_ngrad_noise, ngrad_noise_std, ray_cone_pitch_ratio, save_intermediate_ray_data,
+                         num_intermediate_positions_save};
+        start_ray_tracing_impl(a, image_array);
         return 0;
     });
 }

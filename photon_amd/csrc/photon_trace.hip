@@ -128,12 +128,6 @@ static bool launches_live_sources_only(photon_scene *s, const photon_volume *vol
     return s->live_sources_known;
 }
 
-// PHOTON_RAYGEN=kernel|fold (read once): where the rays of a launch through a volume are generated
-static bool raygen_folded() {
-    static const bool fold = [] { const char *e = getenv("PHOTON_RAYGEN"); return !(e && strcmp(e, "kernel") == 0); }();
-    return fold;
-}
-
 int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long long src_begin,
                         long long src_end, DumpDev dump, hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end) {
     const bool live_only = launches_live_samples_only(s, vol, dump);
@@ -170,8 +164,8 @@ int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long 
         int rc = ensure_workspace(s, n);
         if (rc) return rc;
         s->launched = true;                                     // from here on kernels of this scene may be in flight (scene_quiesce)
-        // ray generation: a kernel of its own (PHOTON_RAYGEN=kernel), or the prologue of the march's first piece (fold)
-        const bool fold = raygen_folded() && (algorithm == 1 || algorithm == 2);
+        // ray generation: the prologue of the march's first piece for Euler and RK4, a kernel of its own for the others
+        const bool fold = algorithm == 1 || algorithm == 2;
         if (!fold) {
             rc = launch_raygen(s, src_begin, n, stream);
             if (rc) return rc;
