@@ -371,6 +371,53 @@ int photon_trace(photon_scene_t *scene, const photon_volume_t *vol, int ray_trac
                  int64_t src_begin, int64_t src_end, float *d_image, void *stream,
                  photon_trace_stats_t *stats);
 
+/* Per-source sensor moments: photon_trace plus one RECORD of 8 doubles per traced source -- the ground truth of a synthetic
+ * BOS / PIV pair (how far each dot moved, by what angle its rays were bent) without ray dumps.
+ *   record[0]    n         rays of the source that reached the sensor: whose final position (all three components) is a
+ *                          number -- exactly the rays whose pos_ dump entry is one (an off-sensor hit is NaN)
+ *   record[1..3] sum x, y, z        final sensor-plane position, camera frame, microns (what pos_ dumps hold)
+ *   record[4..6] sum acos(dx, dy, dz)  of the direction dir_ dumps hold (radians: the angles the reference's reader
+ *                          works in, light_ray_processing.py:120-140)
+ *   record[7]    sum x^2 + y^2     second radial moment (rms spot radius of the dot's image)
+ * Records are additive (merge consecutive sources into a dot, concatenate shards and launches); a source with no arriving
+ * ray has an all-zero record.  Fixed summation order: every f32 is widened to f64 (exact); lane l of 64 adds the values of
+ * the rays j = l (mod 64), j < rays_per_source, in increasing j, from +0.0 -- j is the ray's OWN lens-sample index, never its
+ * slot in a launch; a ray that did not arrive adds nothing -- and the 64 partials are folded by halves (off = 32, 16, .., 1:
+ * p[l] += p[l + off] for l < off); the record is p[0].  So a record has the same bits whatever the ray order, the doomed-ray,
+ * lens-sample and live-source culls (they only drop rays that provably never reach the sensor), march segments, launch
+ * boundaries, [src_begin, src_end) splits or PHOTON_DEVICES sharding; photon_amd/deflections.py (moments_from_dumps)
+ * reproduces it on the host bit for bit, up to an ulp of f64 acos in fields 4-6.
+ * Cost: per launch a moments block of 24 B per (launched source x rays_per_source) -- at most kMaxRaysPerLaunch (2^26)
+ * entries, 1.5 GiB: with moments a launch takes at most 2^26 / rays_per_source sources even where the volume-free path
+ * launches only the live lens samples -- written by the sensor stage, read once by a reduction kernel.
+ *
+ * photon_trace_moments: photon_trace (same image up to f64 summation order, asynchronous, same rules for sharing a scene,
+ * no stats) that also writes the records of sources [src_begin, src_end) to d_records[source][8] (device memory, indexed by
+ * the source's place in the scene's list, num_sources records) and leaves every other record untouched.  A null d_records
+ * or a bad range: non-zero return, nothing written. */
+int photon_trace_moments(photon_scene_t *scene, const photon_volume_t *vol, int ray_tracing_algorithm,
+                         int64_t src_begin, int64_t src_end, float *d_image, double *d_records, void *stream);
+
+/* photon_start_ray_tracing_moments: start_ray_tracing (same 29 arguments, same PHOTON_* settings, the same image) plus the
+ * records of every source in source_moments, a HOST f64[num_particles][8].  With save_lightrays it also writes the dumps
+ * (records from the dump chunks); with PHOTON_DEVICES naming several devices each shard's records land in their own slice.
+ * Returns 0, or non-zero with the reason on stderr (then image and records are not to be used). */
+int photon_start_ray_tracing_moments(float lens_pitch, float image_distance,
+                                     scattering_data_t *scattering_data_p, char *scattering_type_str,
+                                     lightfield_source_t *lightfield_source_p,
+                                     int lightray_number_per_particle, float beam_wavelength,
+                                     float aperture_f_number, int num_elements,
+                                     double (*element_center)[3], element_data_t *element_data_p,
+                                     double (*element_plane_parameters)[4], int *element_system_index,
+                                     camera_design_t *camera_design_p, float *image_array,
+                                     bool simulate_density_gradients, char *density_grad_filename,
+                                     bool save_lightrays, char *lightray_position_save_path,
+                                     char *lightray_direction_save_path, int num_lightrays_save,
+                                     int ray_tracing_algorithm, bool add_pos_noise, float pos_noise_std,
+                                     bool add_ngrad_noise, float ngrad_noise_std,
+                                     float ray_cone_pitch_ratio, bool save_intermediate_ray_data,
+                                     int num_intermediate_positions_save, double *source_moments);
+
 /* Statistics over a WINDOW of photon_trace calls with no host synchronisation inside it (a timed loop): _begin zeroes
  * the counters on the stream; every photon_trace(..., stats = NULL) of this scene up to _end records its HIP events on
  * its stream and lets the counters run; _end waits for the stream and returns the SUMS over the window's traces

@@ -30,6 +30,13 @@ struct DumpDev {                    // ray dumps (save_lightrays), indexed by ch
     int inter_slots;
 };
 
+struct MomentsDev {                 // per-launch block of the per-source moments (photon_moments.hip), or all nullptr
+    // [place][rays_per_source] planes: place = the source's place in the launch, then its own lens sample (never the slot).
+    // x is prefilled with NaN: a ray that did not reach the sensor leaves its entry NaN and the other planes unwritten.
+    float *x, *y, *z;               // final sensor-plane position, camera frame (what pos_ dumps hold)
+    float *dx, *dy, *dz;            // the ray's direction as dir_ dumps hold it
+};
+
 enum { CNT_ON_SENSOR = 0, CNT_ITER = 1, CNT_SAMPLES = 2, CNT_TAPS = 3, CNT_MARCHED = 4, CNT_CLK = 5, CNT_REAL = 6, CNT_N = 7 };
 // Statistics counters are kept in kCounterSlots copies (one 64-byte line each) and summed on the host: with one
 // copy every wave of a launch ends on an atomic to the SAME address, and 1.6e5 same-address device-scope atomics

@@ -187,7 +187,9 @@ hipStream_t worker_stream(int device, int slot) {
 // first one cannot map (no xGMI / PCIe peer path) has its accumulator copied into a block of the cache first
 // (hipMemcpyPeerAsync, all such copies in flight together) -- said on stderr when the pair is first seen, and per call
 // under PHOTON_VERBOSE.
-int render_on_devices(const CallArgs &a, const CallSettings &cs, float *image_array) {
+// moments (photon_start_ray_tracing_moments): each worker also reduces its shard's per-source moments on its device and copies
+// them into its own slice of the caller's f64[num_particles][8].
+int render_on_devices(const CallArgs &a, const CallSettings &cs, float *image_array, double *moments) {
     const std::vector<int> &devices = cs.devices;
     const long long n_src = a.lsp->num_particles;
     const size_t npix = (size_t)a.cam->x_pixel_number * a.cam->y_pixel_number;
@@ -237,9 +239,14 @@ int render_on_devices(const CallArgs &a, const CallSettings &cs, float *image_ar
             if (rc_setup) { rcs[k] = rc_setup; return; }
             rcs[k] = guarded("start_ray_tracing (device worker)", [&]() -> int {
                 const auto tw = Clock::now();
-                int rc = trace_accumulate(scenes[k], volumes[k], a.algorithm, 0, e2 - b, stream, 0, nullptr);
+                PoolBuffer<double> d_records;                           // this shard's records (moments only)
+                if (moments && d_records.alloc((size_t)(e2 - b) * kMomentFields) != hipSuccess) return 2;
+                int rc = trace_accumulate(scenes[k], volumes[k], a.algorithm, 0, e2 - b, stream, 0, nullptr, d_records.p);
+                if (rc) (void)hipStreamSynchronize(stream);             // launches may be in flight: d_records goes back to the cache
                 if (!rc && hipStreamSynchronize(stream) != hipSuccess) rc = 4;
                 if (!rc) rc = march_error_check(scenes[k]);
+                if (!rc && moments && hipMemcpy(moments + (size_t)b * kMomentFields, d_records.p, (size_t)(e2 - b) * kMomentFields * sizeof(double),
+                                                hipMemcpyDeviceToHost) != hipSuccess) rc = 4;
                 if (!rc && verbose())
                     fprintf(stderr, "photon: device %d: sources [%lld, %lld) traced in %.3f ms\n", devices[k], b, e2,
                             ms(tw, Clock::now()));
@@ -311,7 +318,8 @@ struct DumpBuffers { PoolBuffer<float> pos, dir, inter_pos, inter_dir; };
 // The trace of a call that dumps its rays, folded into d_image.  The reference's chunking decides which rays land in which
 // pos_/dir_ file (.cu:3366-3372, 3515-3611): chunks of source_point_number sources, one file pair per chunk; intermediate
 // dumps ride on the same chunking (.cu:3484-3492, 3535-3546, 3613-3670).
-int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume *vol, float *d_image, DumpBuffers &d) {
+// d_records: also the per-source moments of every chunk (photon_start_ray_tracing_moments).
+int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume *vol, float *d_image, DumpBuffers &d, double *d_records) {
     const long long num_particles = a.lsp->num_particles;
     long long chunk = a.lsp->source_point_number;
     if (num_particles < chunk) chunk = num_particles;
@@ -333,6 +341,7 @@ int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume
     const DumpDev dump{d.pos.p, d.dir.p, a.num_lightrays_save, d.inter_pos.p, d.inter_dir.p, inter ? a.num_intermediate_save : 0};
     const long long kmax = (num_particles + chunk - 1) / chunk;
     { const int rc = begin_accumulate(scene, nullptr); if (rc) return rc; }
+    if (d_records) { const int rc = clear_records(d_records, 0, num_particles, nullptr); if (rc) return rc; }
     for (long long k = 0; k < kmax; k++) {
         PH_CHECK(hipMemsetAsync(d.pos.p, 0xFF, nsave * sizeof(float), nullptr));     // all-ones = NaN (.cu:3527-3533); the null stream, like the chunk's launches
         PH_CHECK(hipMemsetAsync(d.dir.p, 0xFF, nsave * sizeof(float), nullptr));
@@ -340,7 +349,8 @@ int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume
             PH_CHECK(hipMemsetAsync(d.inter_pos.p, 0xFF, ninter * sizeof(float), nullptr));
             PH_CHECK(hipMemsetAsync(d.inter_dir.p, 0xFF, ninter * sizeof(float), nullptr));
         }
-        const int rc = launch_chunk(scene, vol, a.algorithm, k * chunk, std::min(num_particles, (k + 1) * chunk), dump, nullptr, nullptr, nullptr);
+        const int rc = launch_chunk(scene, vol, a.algorithm, k * chunk, std::min(num_particles, (k + 1) * chunk), dump, nullptr, nullptr, nullptr,
+                                    d_records);
         if (rc) return rc;
         bool wrote = true;                                              // a dump that cannot be written fails the call
         PH_CHECK(hipMemcpy(host.data(), d.pos.p, nsave * sizeof(float), hipMemcpyDeviceToHost));
@@ -364,8 +374,10 @@ struct Phases { Clock::time_point start, scene, volume, image_in, trace, image_o
 // The call on the current device: 0, or non-zero once stderr has said why.  The device blocks are declared before the
 // scene, so the scene is freed first: photon_scene_free waits for the device, and no block may go back to the cache while
 // a kernel of the call can still use it.
-int render_on_one_device(const CallArgs &a, const CallSettings &cs, float *image_array, Phases &t) {
+// moments: also the per-source moments, into the caller's f64[num_particles][8] (photon_start_ray_tracing_moments).
+int render_on_one_device(const CallArgs &a, const CallSettings &cs, float *image_array, Phases &t, double *moments) {
     PoolBuffer<float> d_image;
+    PoolBuffer<double> d_records;
     DumpBuffers dumps;
     struct SceneOwner { photon_scene *p = nullptr; ~SceneOwner() { photon_scene_free(p); } } scene;
     photon_volume *vol = nullptr;                                       // the device's cached volume: not the call's to free
@@ -378,15 +390,17 @@ int render_on_one_device(const CallArgs &a, const CallSettings &cs, float *image
     const size_t npix = (size_t)a.cam->x_pixel_number * a.cam->y_pixel_number;
     if (hip_failed(d_image.alloc(npix), __LINE__) ||
         hip_failed(hipMemcpy(d_image.p, image_array, npix * sizeof(float), hipMemcpyHostToDevice), __LINE__)) return 1;  // .cu:3309
+    if (moments && hip_failed(d_records.alloc((size_t)num_particles * kMomentFields), __LINE__)) return 1;
     t.image_in = Clock::now();
     int rc;
     if (a.dumping()) {
-        rc = trace_with_dumps(a, scene.p, vol, d_image.p, dumps);
+        rc = trace_with_dumps(a, scene.p, vol, d_image.p, dumps, d_records.p);
     } else {
         if (a.density && a.save_intermediate)
             fprintf(stderr, "photon: warning: save_intermediate_ray_data needs save_lightrays with num_lightrays_save > 0 "
                             "(the reference sizes the intermediate buffers by it, .cu:3488); nothing recorded\n");
-        rc = photon_trace(scene.p, vol, a.algorithm, 0, num_particles, d_image.p, nullptr, nullptr);
+        rc = moments ? photon_trace_moments(scene.p, vol, a.algorithm, 0, num_particles, d_image.p, d_records.p, nullptr)
+                     : photon_trace(scene.p, vol, a.algorithm, 0, num_particles, d_image.p, nullptr, nullptr);
     }
     if (rc) {
         fprintf(stderr, "photon: trace failed (%d); image left untouched\n", rc);
@@ -399,15 +413,18 @@ int render_on_one_device(const CallArgs &a, const CallSettings &cs, float *image
         return 1;
     }
     if (hip_failed(hipMemcpy(image_array, d_image.p, npix * sizeof(float), hipMemcpyDeviceToHost), __LINE__)) return 1;  // .cu:3675
+    if (moments && hip_failed(hipMemcpy(moments, d_records.p, (size_t)num_particles * kMomentFields * sizeof(double), hipMemcpyDeviceToHost),
+                              __LINE__)) return 1;
     t.image_out = Clock::now();
     return 0;
 }
 
-void start_ray_tracing_impl(const CallArgs &a, float *image_array) {
+// 0, or non-zero once stderr has said why.  moments: also the per-source moments (photon_start_ray_tracing_moments).
+int start_ray_tracing_impl(const CallArgs &a, float *image_array, double *moments = nullptr) {
     const auto t0 = Clock::now();
     if (!image_array || !a.cam || !a.lsp) {
         fprintf(stderr, "photon: start_ray_tracing: null argument; image left untouched\n");
-        return;
+        return 1;
     }
     const CallSettings cs = settings_from_env();
     int caller_device = 0;                                              // the caller's current device is restored on every path
@@ -417,26 +434,28 @@ void start_ray_tracing_impl(const CallArgs &a, float *image_array) {
     // PHOTON_DEVICES: shard the sources of one call over several GPUs.  Ray dumps keep the
     // reference's chunk -> file mapping and stay on one device.
     if (cs.devices.size() > 1 && !a.dumping()) {
-        const int rc = render_on_devices(a, cs, image_array);
+        const int rc = render_on_devices(a, cs, image_array, moments);
         if (!rc && verbose()) {
             const double sec = ms(t0, Clock::now()) * 1e-3;
             printf("photon: %lld sources x %d rays on %zu devices in %.3f s (%.2f Mrays/s incl. transfers)\n", n_src,
                    a.rays_per_source, cs.devices.size(), sec, n_src * (double)rps / sec * 1e-6);
         }
-        return;
+        return rc;
     }
     if (!cs.devices.empty() && hipSetDevice(cs.devices[0]) != hipSuccess) {
         fprintf(stderr, "photon: cannot select device %d; image left untouched\n", cs.devices[0]);
-        return;
+        return 1;
     }
     Phases t{t0};
-    if (render_on_one_device(a, cs, image_array, t) || !verbose()) return;
+    if (const int rc = render_on_one_device(a, cs, image_array, t, moments)) return rc;
+    if (!verbose()) return 0;
     const auto t_end = Clock::now();                                    // the call's blocks and scene are freed
     const double s = ms(t0, t_end) * 1e-3;
     printf("photon: %lld sources x %lld rays in %.3f s (%.2f Mrays/s incl. transfers)\n", n_src, rps, s, n_src * rps / s * 1e-6);
     printf("photon:   scene upload %.2f ms, volume %.2f, image in %.2f, trace (launches + wait) %.2f, image out %.2f, frees %.2f\n",
            ms(t.start, t.scene), ms(t.scene, t.volume), ms(t.volume, t.image_in), ms(t.image_in, t.trace), ms(t.trace, t.image_out),
            ms(t.image_out, t_end));
+    return 0;
 }
 
 }  // namespace
@@ -464,5 +483,35 @@ extern "C" void start_ray_tracing(float lens_pitch, float image_distance, scatte
                          num_intermediate_positions_save};
         start_ray_tracing_impl(a, image_array);
         return 0;
+    });
+}
+
+// start_ray_tracing plus the per-source sensor moments (include/parallel_ray_tracing.h): the same call setup, settings and
+// launch plans, and source_moments = host f64[num_particles][8].
+extern "C" int photon_start_ray_tracing_moments(float lens_pitch, float image_distance, scattering_data_t *scattering_data_p,
+                                                char *scattering_type_str, lightfield_source_t *lightfield_source_p,
+                                                int lightray_number_per_particle, float beam_wavelength, float aperture_f_number,
+                                                int num_elements, double (*element_center)[3], element_data_t *element_data_p,
+                                                double (*element_plane_parameters)[4], int *element_system_index,
+                                                camera_design_t *camera_design_p, float *image_array,
+                                                bool simulate_density_gradients, char *density_grad_filename, bool save_lightrays,
+                                                char *lightray_position_save_path, char *lightray_direction_save_path,
+                                                int num_lightrays_save, int ray_tracing_algorithm, bool add_pos_noise,
+                                                float pos_noise_std, bool add_ngrad_noise, float ngrad_noise_std,
+                                                float ray_cone_pitch_ratio, bool save_intermediate_ray_data,
+                                                int num_intermediate_positions_save, double *source_moments) {
+    if (!source_moments) {
+        fprintf(stderr, "photon: photon_start_ray_tracing_moments: null source_moments; image left untouched\n");
+        return 1;
+    }
+    return guarded("photon_start_ray_tracing_moments", [&]() -> int {
+        const CallArgs a{lens_pitch, image_distance, scattering_data_p, scattering_type_str, lightfield_source_p,
+                         lightray_number_per_particle, beam_wavelength, aperture_f_number, num_elements, element_center,
+                         element_data_p, element_plane_parameters, element_system_index, camera_design_p,
+                         simulate_density_gradients, density_grad_filename, save_lightrays, lightray_position_save_path,
+                         lightray_direction_save_path, num_lightrays_save, ray_tracing_algorithm, add_pos_noise, pos_noise_std,
+                         add_ngrad_noise, ngrad_noise_std, ray_cone_pitch_ratio, save_intermediate_ray_data,
+                         num_intermediate_positions_save};
+        return start_ray_tracing_impl(a, image_array, source_moments);
     });
 }

@@ -11,6 +11,7 @@
 //   photon_post.hip          sensor post-processing, the streaming-copy yardstick
 //   photon_abi.hip           start_ray_tracing, PHOTON_DEVICES (several devices inside one call)
 //   photon_sort.hip          Morton order of a range of sources
+//   photon_moments.hip       per-source sensor moments: the reduction of a launch's moments block into records
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -143,6 +144,8 @@ struct photon_scene {
     bool live_sources_known = false;    // false: nothing could be ruled out (or the geometry is not covered): every source is launched
     bool live_sources_tried = false;    // the device pass has run (ensure_live_sources: with the scene's first volume-free launch)
     photon::LensCull source_cull;       // set at creation (host arithmetic only)
+    float *d_mom = nullptr;             // moments block of the launches that record per-source moments (6 planes), grown on demand
+    size_t mom_rays = 0;                // entries per plane
     PermEntry perms[4];                 // spatial (Morton) orders of the lens-major launch ranges seen last
     unsigned long long perm_clock = 0;
     photon_sort_scratch sort_scratch;   // keys / indices / radix-sort temporaries, grown on demand (photon_sort.hip)
@@ -213,18 +216,31 @@ int march_rays_launch_extra(int algorithm, const VolumeDev &vol, int n, float *p
 
 // ---- photon_sensor.hip ----
 int launch_raygen(photon_scene *s, long long src_begin, unsigned n, hipStream_t stream);
-// the sensor stage of a launch of n rays: from the marched state (from_state) or generating its rays in place
-int launch_sensor(photon_scene *s, bool from_state, long long src_begin, unsigned n, const DumpDev &dump, hipStream_t stream);
+// the sensor stage of a launch of n rays: from the marched state (from_state) or generating its rays in place; with mom, every
+// arriving ray also lands in the launch's moments block
+int launch_sensor(photon_scene *s, bool from_state, long long src_begin, unsigned n, const DumpDev &dump, hipStream_t stream,
+                  const MomentsDev *mom = nullptr);
+
+// ---- photon_moments.hip ----
+constexpr int kMomentFields = 8;        // n, sum x, y, z, sum acos dx, dy, dz, sum x^2 + y^2 (include/parallel_ray_tracing.h)
+// The records of the `places` sources of a launch from its moments block: place p is source src_list[p] (src_list) or
+// src_begin + p; record of source i at records + kMomentFields * i
+int launch_moments(const MomentsDev &mom, unsigned places, unsigned rays_per_source, long long src_begin, const int *src_list,
+                   double *records, hipStream_t stream);
 // image = (float)(image + accumulator): image_array is read-modify-write (parallel_ray_tracing.cu:3309, 3675)
 int launch_finalize(photon_scene *s, float *d_image, hipStream_t stream);
 
 // ---- photon_trace.hip ----
 int begin_accumulate(photon_scene *s, hipStream_t stream);
+// d_records: also the per-source moments of the launched sources (records of the scene's source list, photon_trace_moments)
 int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long long src_begin, long long src_end, DumpDev dump,
-                 hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end);
+                 hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end, double *d_records = nullptr);
 // The launch loop for sources [src_begin, src_end) into the scene's private f64 accumulator (zeroed first); timed: 0 no
-// events, 1 immediate (host waits per launch), 2 deferred (events of the open statistics window)
+// events, 1 immediate (host waits per launch), 2 deferred (events of the open statistics window).  d_records: the records of
+// [src_begin, src_end) are zeroed on the stream, then every launch writes those of the sources it traced.
 int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_tracing_algorithm, long long src_begin,
-                     long long src_end, hipStream_t stream, int timed, float *march_ms_out);
+                     long long src_end, hipStream_t stream, int timed, float *march_ms_out, double *d_records = nullptr);
+// zero the records of sources [src_begin, src_end) on the stream (their sources may all be culled)
+int clear_records(double *d_records, long long src_begin, long long src_end, hipStream_t stream);
 
 }  // namespace photon

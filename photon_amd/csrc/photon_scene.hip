@@ -175,6 +175,7 @@ void photon_scene_free(photon_scene_t *s) {
     free_resume_state(s);
     pool_free(s->d_profile);                                    // (d_counters and d_queue live in the upload block: allocs)
     pool_free(s->d_acc);
+    pool_free(s->d_mom);
     for (auto &p : s->perms) pool_free(p.d_perm);
     photon_sort_scratch_free(&s->sort_scratch);
     for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);

@@ -128,8 +128,31 @@ static bool launches_live_sources_only(photon_scene *s, const photon_volume *vol
     return s->live_sources_known;
 }
 
+// The moments block of a launch of `places` sources: six planes of places x rays_per_source floats (grown on demand), the x
+// plane prefilled with NaN on the launch's stream.  places x rays_per_source <= kMaxRaysPerLaunch (trace_accumulate caps the
+// sources of a launch by it), so the block stays below 24 B x kMaxRaysPerLaunch = 1.5 GiB.
+static int moments_block(photon_scene *s, unsigned places, hipStream_t stream, MomentsDev *out) {
+    const size_t rays = (size_t)places * (unsigned)s->dev.rays_per_source;
+    if (rays > kMaxRaysPerLaunch) {
+        fprintf(stderr, "photon: a moments block of %zu rays exceeds the %u-ray limit per launch\n", rays, kMaxRaysPerLaunch);
+        return 1;
+    }
+    if (s->mom_rays < rays) {
+        if (s->d_mom) { scene_quiesce(s); pool_free(s->d_mom); s->d_mom = nullptr; }     // an earlier launch may still use it
+        s->mom_rays = 0;
+        PH_CHECK(pool_malloc((void **)&s->d_mom, rays * 6 * sizeof(float)));
+        s->mom_rays = rays;
+    }
+    float *f = s->d_mom;
+    const size_t stride = s->mom_rays;
+    *out = MomentsDev{f, f + stride, f + 2 * stride, f + 3 * stride, f + 4 * stride, f + 5 * stride};
+    PH_CHECK(hipMemsetAsync(out->x, 0xFF, rays * sizeof(float), stream));      // all-ones = NaN: "did not arrive"
+    return 0;
+}
+
 int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long long src_begin,
-                        long long src_end, DumpDev dump, hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end) {
+                        long long src_end, DumpDev dump, hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end,
+                        double *d_records) {
     const bool live_only = launches_live_samples_only(s, vol, dump);
     s->dev.slot_rays = live_only ? s->live_count : s->dev.rays_per_source;
     s->dev.slot_map = live_only ? s->d_live : nullptr;
@@ -149,6 +172,13 @@ int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long 
         return 1;
     }
     const unsigned n = (unsigned)n64;
+    MomentsDev mom{};
+    if (d_records) {
+        s->launched = true;                                     // the prefill
+        const int rc = moments_block(s, (unsigned)n_sources, stream, &mom);
+        if (rc) return rc;
+    }
+    const MomentsDev *mom_p = d_records ? &mom : nullptr;
     s->dev.doom_margin = doom_margin(s, vol, algorithm, dump);
     s->dev.ray_order = 0;
     s->dev.src_perm = nullptr;
@@ -177,10 +207,15 @@ int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long 
         rc = launch_march(s, vol, algorithm, n, ray_base, idump, save, stream, ev_march_begin, fold ? src_begin : -1);
         if (rc) return rc;
         if (ev_march_end) PH_CHECK(hipEventRecord(ev_march_end, stream));
-        return launch_sensor(s, true, src_begin, n, dump, stream);
+        rc = launch_sensor(s, true, src_begin, n, dump, stream, mom_p);
+        if (rc) return rc;
+    } else {
+        s->launched = true;
+        const int rc = launch_sensor(s, false, src_begin, n, dump, stream, mom_p);
+        if (rc) return rc;
     }
-    s->launched = true;
-    return launch_sensor(s, false, src_begin, n, dump, stream);
+    if (!d_records) return 0;
+    return launch_moments(mom, (unsigned)n_sources, (unsigned)s->dev.rays_per_source, src_begin, s->dev.src_list, d_records, stream);
 }
 
 }  // namespace photon
@@ -205,7 +240,7 @@ namespace photon {
 // accumulators first.  timed: 0 no events; 1 immediate (the march of every launch is timed with ev[1], ev[2] and the host
 // waits for it: photon_trace with a stats pointer); 2 deferred (events of the open statistics window, no host wait).
 int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_tracing_algorithm, long long src_begin,
-                            long long src_end, hipStream_t stream, int timed, float *march_ms_out) {
+                            long long src_end, hipStream_t stream, int timed, float *march_ms_out, double *d_records) {
     const unsigned rps = (unsigned)scene->dev.rays_per_source;
     if (rps > kMaxRaysPerLaunch) { fprintf(stderr, "photon: too many rays per source\n"); return 1; }
     float march_ms = 0.f;
@@ -213,9 +248,11 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
     // a launch holds at most kMaxRaysPerLaunch rays: of those it really launches (the volume-free path leaves out dead lens samples
     // and sources that miss the sensor -- the sample PIV frame's 5e8 rays go in two launches, not eight)
     const unsigned slot_rays = launches_live_samples_only(scene, vol, no_dump) ? (unsigned)scene->live_count : rps;
-    const long long max_sources = std::max<long long>(1, kMaxRaysPerLaunch / slot_rays);
+    // with moments, also a moments block of at most kMaxRaysPerLaunch entries: it is indexed by lens sample, not by slot
+    const long long max_sources = std::max<long long>(1, kMaxRaysPerLaunch / (d_records ? rps : slot_rays));
     const bool listed = launches_live_sources_only(scene, vol, no_dump);
     { const int rc = begin_accumulate(scene, stream); if (rc) return rc; }
+    if (d_records) { const int rc = clear_records(d_records, src_begin, src_end, stream); if (rc) return rc; }
     for (long long b = src_begin, e = src_begin; b < src_end; b = e) {
         e = std::min<long long>(src_end, b + max_sources);
         if (listed) {                                           // up to max_sources LISTED sources: the range ends before the next one
@@ -233,7 +270,7 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
             { const int rc = window_event(scene, &i1); if (rc) return rc; }
             e0 = scene->win_events[i0]; e1 = scene->win_events[i1];
         }
-        const int rc = launch_chunk(scene, vol, ray_tracing_algorithm, b, e, no_dump, stream, e0, e1);
+        const int rc = launch_chunk(scene, vol, ray_tracing_algorithm, b, e, no_dump, stream, e0, e1, d_records);
         if (rc) return rc;
         if (timed == 2 && vol) scene->win_march.emplace_back(i0, i1);      // only pairs whose events were recorded
         if (timed == 1 && vol) {
@@ -269,14 +306,9 @@ static int read_counters(photon_scene *scene, bool have_volume, photon_trace_sta
     return 0;
 }
 
-extern "C" int photon_trace(photon_scene_t *scene, const photon_volume_t *vol, int ray_tracing_algorithm,
-                            int64_t src_begin, int64_t src_end, float *d_image, void *stream_p,
-                            photon_trace_stats_t *stats) {
-    if (!scene || !d_image || src_begin < 0 || src_end < src_begin || src_end > scene->dev.num_sources) {
-        fprintf(stderr, "photon: photon_trace: bad arguments (sources [%lld,%lld) of %d)\n", (long long)src_begin,
-                (long long)src_end, scene ? scene->dev.num_sources : -1);
-        return 1;
-    }
+// photon_trace and photon_trace_moments (d_records != nullptr)
+static int trace_call(photon_scene_t *scene, const photon_volume_t *vol, int ray_tracing_algorithm, int64_t src_begin, int64_t src_end,
+                      float *d_image, void *stream_p, photon_trace_stats_t *stats, double *d_records) {
     if (stats && scene->win_open) {
         fprintf(stderr, "photon: photon_trace: per-call stats inside an open statistics window (photon_scene_stats_begin); "
                         "pass stats = NULL and read them with photon_scene_stats_end\n");
@@ -290,7 +322,7 @@ extern "C" int photon_trace(photon_scene_t *scene, const photon_volume_t *vol, i
         fprintf(stderr, "photon: photon_trace: more than %u traces in one statistics window; close it with photon_scene_stats_end\n", kWindowMaxTraces);
         return 1;
     }
-    return guarded("photon_trace", [&]() -> int {
+    return guarded(d_records ? "photon_trace_moments" : "photon_trace", [&]() -> int {
         photon::DeviceScope on_scene_device(scene->device);
         hipStream_t stream = (hipStream_t)stream_p;
         const unsigned rps = (unsigned)scene->dev.rays_per_source;
@@ -306,7 +338,7 @@ extern "C" int photon_trace(photon_scene_t *scene, const photon_volume_t *vol, i
         }
         float march_ms = 0.f;
         const int timed = stats ? 1 : (scene->win_open ? 2 : 0);
-        { const int rc = trace_accumulate(scene, vol, ray_tracing_algorithm, src_begin, src_end, stream, timed, &march_ms); if (rc) return rc; }
+        { const int rc = trace_accumulate(scene, vol, ray_tracing_algorithm, src_begin, src_end, stream, timed, &march_ms, d_records); if (rc) return rc; }
         { const int rc = launch_finalize(scene, d_image, stream); if (rc) return rc; }
         if (stats) {
             PH_CHECK(hipEventRecord(scene->ev[3], stream));
@@ -326,6 +358,27 @@ extern "C" int photon_trace(photon_scene_t *scene, const photon_volume_t *vol, i
         }
         return 0;
     });
+}
+
+extern "C" int photon_trace(photon_scene_t *scene, const photon_volume_t *vol, int ray_tracing_algorithm,
+                            int64_t src_begin, int64_t src_end, float *d_image, void *stream_p,
+                            photon_trace_stats_t *stats) {
+    if (!scene || !d_image || src_begin < 0 || src_end < src_begin || src_end > scene->dev.num_sources) {
+        fprintf(stderr, "photon: photon_trace: bad arguments (sources [%lld,%lld) of %d)\n", (long long)src_begin,
+                (long long)src_end, scene ? scene->dev.num_sources : -1);
+        return 1;
+    }
+    return trace_call(scene, vol, ray_tracing_algorithm, src_begin, src_end, d_image, stream_p, stats, nullptr);
+}
+
+extern "C" int photon_trace_moments(photon_scene_t *scene, const photon_volume_t *vol, int ray_tracing_algorithm, int64_t src_begin,
+                                    int64_t src_end, float *d_image, double *d_records, void *stream_p) {
+    if (!scene || !d_image || !d_records || src_begin < 0 || src_end < src_begin || src_end > scene->dev.num_sources) {
+        fprintf(stderr, "photon: photon_trace_moments: bad arguments (sources [%lld,%lld) of %d, records %p)\n", (long long)src_begin,
+                (long long)src_end, scene ? scene->dev.num_sources : -1, (void *)d_records);
+        return 1;
+    }
+    return trace_call(scene, vol, ray_tracing_algorithm, src_begin, src_end, d_image, stream_p, nullptr, d_records);
 }
 
 // Statistics over a WINDOW of photon_trace calls without a host synchronisation inside it: _begin zeroes the counters (on

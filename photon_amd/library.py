@@ -21,7 +21,7 @@ DECLARED_SYMBOLS = (
     "start_ray_tracing", "photon_set_device", "photon_device_pci_bus_id", "photon_rand_table", "photon_volume_load_nrrd",
     "photon_volume_from_density", "photon_volume_info", "photon_volume_set_weight_bits", "photon_volume_download", "photon_volume_sample",
     "photon_volume_free", "photon_scene_create", "photon_scene_free", "photon_scene_set_noise", "photon_scene_set_element_train", "photon_scene_set_ray_order", "photon_scene_set_skip_doomed", "photon_scene_live_rays", "photon_scene_live_samples", "photon_scene_live_sources", "photon_sources_missing_sensor", "photon_scene_set_source_base", "photon_march_queue_group", "photon_march_queue_count", "photon_march_queue_chunk", "photon_march_queue_size",
-    "photon_scene_set_march_segments", "photon_march_segments_plan", "photon_trim_caches", "photon_trace",
+    "photon_scene_set_march_segments", "photon_march_segments_plan", "photon_trim_caches", "photon_trace", "photon_trace_moments", "photon_start_ray_tracing_moments",
     "photon_scene_stats_begin", "photon_scene_stats_end", "photon_scene_check", "photon_scene_set_march_profile", "photon_scene_march_profile", "photon_scene_march_profile_raw",
     "photon_trace_volume_rays", "photon_trace_volume_rays_queued", "photon_version",
     # section 3: scene generation on the device
@@ -125,6 +125,9 @@ class PhotonLibrary:
                   file=sys.stderr)
         L = self.lib
         self.start_ray_tracing = bind_start_ray_tracing(L)
+        # start_ray_tracing's 29 arguments + double *source_moments (host f64[num_particles][8]); returns 0 or non-zero
+        self.start_ray_tracing_moments = bind_start_ray_tracing(L, "photon_start_ray_tracing_moments", [ctypes.c_void_p])
+        self.start_ray_tracing_moments.restype = ctypes.c_int
         L.photon_version.restype = ctypes.c_char_p
         L.photon_set_device.argtypes = [ctypes.c_int]
         L.photon_rand_table.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
@@ -154,6 +157,8 @@ class PhotonLibrary:
             L.photon_scene_set_source_base.argtypes = [ctypes.c_void_p, ctypes.c_int64]
         L.photon_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(photon_trace_stats_t)]
+        L.photon_trace_moments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
+                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         self.has_stats_window = hasattr(L, "photon_scene_stats_begin")     # absent from libraries built before round 3 (A/B runs)
         if self.has_stats_window:
             L.photon_scene_stats_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
@@ -242,6 +247,17 @@ class PhotonLibrary:
             image = call.new_image()
         call.invoke(self.start_ray_tracing, image)
         return image
+
+    def render_moments(self, call: RayTracingCall, image: Optional[np.ndarray] = None):
+        """start_ray_tracing plus the per-source sensor moments (photon_start_ray_tracing_moments): returns (image, records),
+        records f64[num_sources][8] in the layout of photon_amd.deflections.RECORD_FIELDS."""
+        if image is None:
+            image = call.new_image()
+        records = np.zeros((call.num_sources, 8), np.float64)
+        status = []
+        call.invoke(lambda *args: status.append(self.start_ray_tracing_moments(*args)), image, extra=(_ptr(records),))
+        self._check(status[0], "photon_start_ray_tracing_moments")
+        return image, records
 
     def pci_bus_id(self) -> str:
         """PCI bus id of the current device, lower case as sysfs spells it ('0000:c1:00.0'); '' if unavailable."""
@@ -458,6 +474,18 @@ class Scene:
                                         ctypes.byref(stats) if stats is not None else None)
         self._lib._check(rc, "photon_trace")
         return stats
+
+    def trace_moments(self, d_image_ptr: int, d_records_ptr: int, volume: Optional[Volume] = None, algorithm: int = 0,
+                      src_begin: int = 0, src_end: Optional[int] = None, stream: int = 0):
+        """trace() plus the per-source sensor moments (photon_trace_moments): the records of sources [src_begin, src_end) go
+        to the DEVICE array f64[num_sources][8] at d_records_ptr; every other record is left as it is."""
+        if src_end is None:
+            src_end = self.num_sources
+        rc = self._lib.lib.photon_trace_moments(self.handle, volume.handle if volume is not None else None, int(algorithm),
+                                                int(src_begin), int(src_end), ctypes.c_void_p(int(d_image_ptr)),
+                                                ctypes.c_void_p(int(d_records_ptr)) if d_records_ptr else None,
+                                                ctypes.c_void_p(int(stream)) if stream else None)
+        self._lib._check(rc, "photon_trace_moments")
 
     @property
     def has_stats_window(self) -> bool:
