@@ -497,6 +497,44 @@ int photon_sources_bos(const double *dot_x, const double *dot_y, int n_dots, con
 int photon_sources_piv(uint64_t seed, long long n, const double box_min[3], const double box_max[3],
                        double z_object, double beam_fwhm, double irradiance_constant,
                        const double *diameter_cdf, int n_diameters, photon_sources_t **out);
+
+/* PIV frame pairs (time series): the particles of photon_sources_piv moved by a steady velocity field.
+ *
+ * photon_flow_t: u, v, w are host f32 [nz][ny][nx] (x fastest, like the density volume), velocity in microns per unit
+ * of t, on the nodes origin + (i, j, k) * spacing of the WORLD frame of photon_sources_piv (X, Y, Z, before the z_object
+ * shift).  Each axis needs n >= 2; spacing finite and > 0, origin finite.  Stored in HBM as one float4 {u, v, w, 0} per
+ * node, on the current device.
+ *
+ * Operation order (all f64, no fused multiply-add; photon_amd/piv_pairs.py follows it bit for bit):
+ *   sample V(p), per axis a:  f = (p_a - origin_a) / spacing_a;  c = floor(f);  c = c >= 0 ? c : 0;
+ *                             c = c <= n_a - 2 ? c : n_a - 2;  t_a = f - c;  t_a = t_a > 0 ? t_a : 0;  t_a = t_a < 1 ? t_a : 1
+ *                             (outside the grid: the boundary value; a NaN coordinate takes cell 0 and weight 0)
+ *     with lerp(a, b, t) = a + t * (b - a) on the node values widened to f64, per component:
+ *       V = lerp(lerp(lerp(v000, v100, tx), lerp(v010, v110, tx), ty), lerp(lerp(v001, v101, tx), lerp(v011, v111, tx), ty), tz)
+ *       (v_ijk: the node at cell + (i, j, k))
+ *   one RK4 step of h = t / steps:  k1 = V(p);  k2 = V(p + (0.5 h) k1);  k3 = V(p + (0.5 h) k2);  k4 = V(p + h k3);
+ *                                   p = p + (h / 6) * (((k1 + 2 k2) + 2 k3) + k4)      (per component, left to right)
+ *
+ * photon_sources_piv_advected: the frame at time t of the photon_sources_piv field with the same (seed, n, box, z_object,
+ * beam_fwhm, irradiance_constant, diameter_cdf).  Particle i starts at the f64 (X, Y, Z) photon_sources_piv draws for
+ * it, moves through `flow` by `steps` RK4 steps, and is stored as photon_sources_piv stores it: x = (float)X,
+ * y = (float)Y, z = (float)(Z + z_object), radiance = the laser-sheet profile at the NEW Z, diameter index unchanged (the
+ * same Philox word).  flow == NULL or t == 0: bit-identical to photon_sources_piv.  Every frame is counter-based: a time
+ * series is t = k dt with one seed, and any particle of any frame can be regenerated alone.
+ * world_xyz (host f64 [n][3], may be NULL): the particles' (X, Y, Z) at time t, before the cast -- the ground truth.
+ * The static skip of dead lens samples trusts a generated field's extent: it is taken from the positions stored (a device
+ * reduction), not from the box, which advected particles may have left.
+ * Refused (1, one stderr line, *out untouched): the arguments photon_sources_piv refuses, steps < 1, a non-finite t,
+ * t != 0 with flow == NULL. */
+typedef struct photon_flow photon_flow_t;
+int photon_flow_from_grid(const float *u, const float *v, const float *w, int nx, int ny, int nz,
+                          const double spacing[3], const double origin[3], photon_flow_t **out);
+void photon_flow_free(photon_flow_t *flow);
+int photon_sources_piv_advected(uint64_t seed, long long n, const double box_min[3], const double box_max[3],
+                                double z_object, double beam_fwhm, double irradiance_constant,
+                                const double *diameter_cdf, int n_diameters, const photon_flow_t *flow,
+                                double t, int steps, double *world_xyz, photon_sources_t **out);
+
 long long photon_sources_count(const photon_sources_t *sources);
 /* Copy back to host arrays (any of them may be NULL). */
 int photon_sources_download(const photon_sources_t *sources, float *x, float *y, float *z, double *radiance,

@@ -12,6 +12,7 @@
 //   photon_abi.hip           start_ray_tracing, PHOTON_DEVICES (several devices inside one call)
 //   photon_sort.hip          Morton order of a range of sources
 //   photon_moments.hip       per-source sensor moments: the reduction of a launch's moments block into records
+//   photon_flow.hip          velocity fields on a grid, the PIV field advected through one
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -242,5 +243,9 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
                      long long src_end, hipStream_t stream, int timed, float *march_ms_out, double *d_records = nullptr);
 // zero the records of sources [src_begin, src_end) on the stream (their sources may all be culled)
 int clear_records(double *d_records, long long src_begin, long long src_end, hipStream_t stream);
+
+// photon_scene.hip: a source handle with device arrays for n sources; the extent of generated sources (live_lens_samples)
+int sources_alloc(long long n, photon_sources **out);
+void sources_set_extent(photon_sources *src, double ax, double ay, double z0, double z1);
 
 }  // namespace photon

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "photon_internal.hpp"
+#include "piv_field.hpp"
 
 using namespace photon;
 
@@ -27,36 +28,16 @@ __global__ __launch_bounds__(256) void sources_bos_kernel(const double *__restri
     sdia[i] = 1;                                                        // run_simulation_02.py:1544
 }
 
-// PIV particle field (run_simulation_02.py:774-996): X, Y, Z uniform in the box, radiance = the laser
-// sheet's Gaussian profile in Z, Z shifted to the object plane.  The reference draws from numpy's unseeded
-// generator; here particle i takes the four words of Philox(seed, i) -- any particle can be regenerated.
-struct PivFieldDev {
-    double lo[3], hi[3];
-    double z_object, coef, two_sigma2;      // coef = irradiance_constant / (sigma sqrt(2 pi))
-    int n_diameters;                        // 0: diameter_index = 1 (run_simulation_02.py:992)
-};
+// PIV particle field (run_simulation_02.py:774-996): the draw and the store live in piv_field.hpp, shared with the
+// advected field of photon_flow.hip.
 __global__ __launch_bounds__(256) void sources_piv_kernel(unsigned long long seed, long long n, PivFieldDev f,
                                                           const double *__restrict__ diameter_cdf, float *sx, float *sy,
                                                           float *sz, double *srad, int *sdia) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const photon_u32x4 r = photon_philox4x32_10(seed, (unsigned long long)i, 0u, PHOTON_STREAM_SCENE);
-    const double ux = ((double)r.x + 0.5) * (1.0 / 4294967296.0), uy = ((double)r.y + 0.5) * (1.0 / 4294967296.0);
-    const double uz = ((double)r.z + 0.5) * (1.0 / 4294967296.0), ud = ((double)r.w + 0.5) * (1.0 / 4294967296.0);
-    const double X = (f.hi[0] - f.lo[0]) * ux + f.lo[0];
-    const double Y = (f.hi[1] - f.lo[1]) * uy + f.lo[1];
-    const double Z = (f.hi[2] - f.lo[2]) * uz + f.lo[2];
-    sx[i] = (float)X;
-    sy[i] = (float)Y;
-    sz[i] = (float)(Z + f.z_object);
-    srad[i] = f.coef * photon_det_exp(-1.0 * (Z * Z / f.two_sigma2));
-    int dia = 1;
-    if (f.n_diameters > 0) {
-        dia = f.n_diameters - 1;
-        for (int d = 0; d < f.n_diameters; d++)
-            if (ud < diameter_cdf[d]) { dia = d; break; }
-    }
-    sdia[i] = dia;
+    double X, Y, Z, ud;
+    piv_draw(seed, i, f, X, Y, Z, ud);
+    piv_store(i, f, X, Y, Z, ud, diameter_cdf, sx, sy, sz, srad, sdia);
 }
 
 // A scene's small host arrays (tables, optics, a shard's sources) travel in ONE block and one host-to-device copy: a scene
@@ -196,7 +177,9 @@ void photon_sources_free(photon_sources_t *src) {
     delete src;
 }
 
-static int sources_alloc(long long n, photon_sources **out) {
+}  // extern "C"
+
+int photon::sources_alloc(long long n, photon_sources **out) {
     photon_sources *src = new photon_sources();
     src->n = n;
     const size_t m = (size_t)std::max<long long>(n, 1);
@@ -211,6 +194,17 @@ static int sources_alloc(long long n, photon_sources **out) {
     *out = src;
     return 0;
 }
+
+// The extent live_lens_samples trusts for generated sources: the largest |x|, |y| and the z range of the particles, a rounding
+// to float wider.  A NaN anywhere leaves the extent unset (every lens sample is then launched).
+void photon::sources_set_extent(photon_sources *src, double ax, double ay, double z0, double z1) {
+    src->rmax = sqrt(ax * ax + ay * ay) * (1 + 1e-6);
+    src->zmin = z0 - 1e-6 * fabs(z0) - 1e-3;
+    src->zmax = z1 + 1e-6 * fabs(z1) + 1e-3;
+    src->have_extent = src->rmax == src->rmax && src->zmin == src->zmin && src->zmax == src->zmax;
+}
+
+extern "C" {
 
 int photon_sources_bos(const double *dot_x, const double *dot_y, int n_dots, const double *tmpl_x, const double *tmpl_y,
                        int n_tmpl, double z, double radiance, photon_sources_t **out) {
@@ -253,13 +247,7 @@ int photon_sources_piv(uint64_t seed, long long n, const double box_min[3], cons
     photon_sources *src = nullptr;
     int rc = sources_alloc(n, &src);
     if (rc) return rc;
-    PivFieldDev f;
-    for (int a = 0; a < 3; a++) { f.lo[a] = box_min[a]; f.hi[a] = box_max[a]; }
-    const double sigma = beam_fwhm / (2.0 * sqrt(2.0 * log(2.0)));     // run_simulation_02.py:961
-    f.z_object = z_object;
-    f.coef = irradiance_constant * (1.0 / (sigma * sqrt(2.0 * PHOTON_PI)));
-    f.two_sigma2 = 2.0 * (sigma * sigma);
-    f.n_diameters = n_diameters;
+    const PivFieldDev f = piv_field_setup(box_min, box_max, z_object, beam_fwhm, irradiance_constant, n_diameters);
     double *d_cdf = nullptr;
     auto fail = [&](int code) { if (d_cdf) (void)hipFree(d_cdf); photon_sources_free(src); return code; };
     if (n_diameters > 0) {
@@ -272,13 +260,9 @@ int photon_sources_piv(uint64_t seed, long long n, const double box_min[3], cons
         if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(4);
     }
     if (d_cdf) (void)hipFree(d_cdf);
-    {   // the box the particles were drawn from (sources_piv_kernel: X, Y uniform in the box, z = Z + z_object), a rounding to float wider
+    {   // the box the particles were drawn from (sources_piv_kernel: X, Y uniform in the box, z = Z + z_object)
         const double ax = std::max(fabs(box_min[0]), fabs(box_max[0])), ay = std::max(fabs(box_min[1]), fabs(box_max[1]));
-        const double z0 = std::min(box_min[2], box_max[2]) + z_object, z1 = std::max(box_min[2], box_max[2]) + z_object;
-        src->rmax = sqrt(ax * ax + ay * ay) * (1 + 1e-6);
-        src->zmin = z0 - 1e-6 * fabs(z0) - 1e-3;
-        src->zmax = z1 + 1e-6 * fabs(z1) + 1e-3;
-        src->have_extent = src->rmax == src->rmax && src->zmin == src->zmin && src->zmax == src->zmax;
+        sources_set_extent(src, ax, ay, std::min(box_min[2], box_max[2]) + z_object, std::max(box_min[2], box_max[2]) + z_object);
     }
     *out = src;
     return 0;

@@ -25,7 +25,8 @@ DECLARED_SYMBOLS = (
     "photon_scene_stats_begin", "photon_scene_stats_end", "photon_scene_check", "photon_scene_set_march_profile", "photon_scene_march_profile", "photon_scene_march_profile_raw",
     "photon_trace_volume_rays", "photon_trace_volume_rays_queued", "photon_version",
     # section 3: scene generation on the device
-    "photon_sources_bos", "photon_sources_piv", "photon_sources_count", "photon_sources_download", "photon_sources_free",
+    "photon_sources_bos", "photon_sources_piv", "photon_flow_from_grid", "photon_flow_free", "photon_sources_piv_advected",
+    "photon_sources_count", "photon_sources_download", "photon_sources_free",
     "photon_scene_create_from_sources", "photon_volume_gaussian", "photon_density_gaussian_write_nrrd",
     # section 4: sensor post-processing on the device
     "photon_postprocess_u16", "photon_measure_copy_gbs", "photon_selftest_normal_range_math", "photon_selftest_morton_order",
@@ -176,6 +177,13 @@ class PhotonLibrary:
         L.photon_sources_piv.argtypes = [ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
                                          ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
                                          ctypes.POINTER(ctypes.c_void_p)]
+        L.photon_flow_from_grid.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p,
+                                                                                     ctypes.POINTER(ctypes.c_void_p)]
+        L.photon_flow_free.argtypes = [ctypes.c_void_p]
+        L.photon_flow_free.restype = None
+        L.photon_sources_piv_advected.argtypes = (L.photon_sources_piv.argtypes[:-1] +
+                                                  [ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
+                                                   ctypes.POINTER(ctypes.c_void_p)])
         L.photon_sources_count.argtypes = [ctypes.c_void_p]
         L.photon_sources_count.restype = ctypes.c_longlong
         L.photon_sources_download.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 5
@@ -354,6 +362,38 @@ class PhotonLibrary:
                     "photon_sources_piv")
         return Sources(self, h)
 
+    def flow_from_grid(self, u, v, w, spacing, origin) -> "Flow":
+        """A steady velocity field (microns per unit of t) on the nodes origin + (i, j, k) * spacing of the PIV field's world
+        frame; u, v, w: [nz][ny][nx] (x fastest), stored as f32 (photon_flow_from_grid)."""
+        comps = [np.ascontiguousarray(a, dtype=np.float32) for a in (u, v, w)]
+        if comps[0].ndim != 3 or any(c.shape != comps[0].shape for c in comps):
+            raise ValueError("u, v, w must be three arrays of one shape [nz][ny][nx]")
+        nz, ny, nx = comps[0].shape
+        sp = np.ascontiguousarray(spacing, dtype=np.float64)
+        og = np.ascontiguousarray(origin, dtype=np.float64)
+        h = ctypes.c_void_p()
+        self._check(self.lib.photon_flow_from_grid(_ptr(comps[0]), _ptr(comps[1]), _ptr(comps[2]), nx, ny, nz, _ptr(sp), _ptr(og),
+                                                   ctypes.byref(h)), "photon_flow_from_grid")
+        return Flow(self, h)
+
+    def sources_piv_advected(self, seed: int, n: int, box_min, box_max, z_object: float, beam_fwhm: float,
+                             irradiance_constant: float, diameter_cdf=None, flow: Optional["Flow"] = None, t: float = 0.0,
+                             steps: int = 16, return_world: bool = False):
+        """The sources_piv field at time t: every particle moved through `flow` by `steps` RK4 steps
+        (photon_sources_piv_advected).  Returns Sources, or (Sources, world_xyz f64 [n][3]) with return_world."""
+        lo = np.ascontiguousarray(box_min, dtype=np.float64)
+        hi = np.ascontiguousarray(box_max, dtype=np.float64)
+        cdf = None if diameter_cdf is None else np.ascontiguousarray(diameter_cdf, dtype=np.float64)
+        world = np.empty((max(int(n), 0), 3), np.float64) if return_world else None
+        h = ctypes.c_void_p()
+        self._check(self.lib.photon_sources_piv_advected(int(seed), int(n), _ptr(lo), _ptr(hi), float(z_object), float(beam_fwhm),
+                                                         float(irradiance_constant), _ptr(cdf) if cdf is not None else None,
+                                                         0 if cdf is None else int(cdf.size),
+                                                         flow.handle if flow is not None else None, float(t), int(steps),
+                                                         _ptr(world) if world is not None else None, ctypes.byref(h)),
+                    "photon_sources_piv_advected")
+        return (Sources(self, h), world) if return_world else Sources(self, h)
+
     # ---- scenes -------------------------------------------------------------------------------
     def scene_create_from_sources(self, call: RayTracingCall, sources: "Sources") -> "Scene":
         """Like scene_create, with the light-field sources already in HBM (call's own source arrays unused)."""
@@ -454,6 +494,18 @@ class Sources:
     def free(self):
         if self.handle:
             self._lib.lib.photon_sources_free(self.handle)
+            self.handle = None
+
+
+class Flow:
+    """A velocity field on a grid in HBM (photon_flow_t)."""
+
+    def __init__(self, lib: PhotonLibrary, handle):
+        self._lib, self.handle = lib, handle
+
+    def free(self):
+        if self.handle:
+            self._lib.lib.photon_flow_free(self.handle)
             self.handle = None
 
 
