@@ -1,12 +1,12 @@
-// device_volume.hpp - refractive-index-gradient volume: samplers and ray integrators (device).
+// device_volume.hpp - refractive-index-gradient volume: per-lane samplers and volume geometry (device).
 //
 // Replaces, for gfx950, the CUDA texture path of the reference:
 //   tex3D(tex_data, ...) trilinear fetch      trace_rays_through_density_gradients.h:77,1052,1612-1646
 //   cubicTex3D(coeffs3D, ...) tricubic fetch  CubicInterpolationCUDA/code/internal/cubicTex3D_kernel.cu:48-81
 //   IntersectWithVolume / lookup / bounds     trace_rays_through_density_gradients.h:100-277
-//   euler / rk4                               trace_rays_through_density_gradients.h:743-1291
 // There is no texture unit on the path: texels are float4 in HBM (x fastest), addressed and
-// filtered in software with a fixed operation order.
+// filtered in software with a fixed operation order.  The integrators live in device_volume_coop.hpp
+// (RK4 / Euler: the wave-cooperative hot loop) and device_volume_extra.hpp (rk45 / Adams-Bashforth).
 #pragma once
 #include <float.h>
 #include "device_vec.hpp"
@@ -190,156 +190,10 @@ __device__ __forceinline__ void record_intermediate(const InterDump &d, int loop
 constexpr int kLoopMax = 10000000;      // loop_ctr_max (.h:765,981)
 constexpr int kSpinMax = 1 << 20;       // bound on the reference's uncounted `continue` spins
 
-// linear-branch fetch with the reference's "n-1 below data_min" repair (.h:1052-1065)
-__device__ __forceinline__ f4 fetch_linear(const VolumeDev &v, f3 l, const f4 &prev, float ambient,
-                                           MarchCount &mc) {
-    f4 val = tex3d_linear(v, l.x, l.y, l.z);
-    mc.samples++;
-    if (val.w < v.data_min) {
-        if (prev.w == 0) {
-            const f4 t = tex3d_linear(v, l.x, l.y, l.z - 1);
-            mc.samples++;
-            val = f4{t.x, t.y, t.z, ambient - 1};
-        } else {
-            val = prev;
-        }
-    }
-    return val;
-}
-
-// Sharma-Kumar-Ghatak RK4 of the ray equation (.h:952-1291).  INTERP is a compile-time branch.
-template <int INTERP>
-__device__ __forceinline__ void rk4(f3 &rpos, f3 &rdir, const VolumeDev &v, f3 scale, MarchCount &mc) {
-    const float ambient = 1.000277;
-    int loop_ctr = 0, spins = 0;
-    f3 pos, lookup, R_n, T_n, A, B, C, D;
-    f4 val, val_prev = f4{0, 0, 0, 0};
-    float delta_t, current_n;
-    while (true) {
-        if (loop_ctr > kLoopMax) break;
-        pos = rpos;
-        lookup = lookup_index(pos, v, scale);
-        if (!inside_box(pos, v, lookup) && loop_ctr != 0) break;
-        if (!can_access(v, lookup)) {
-            pos = pos + v.step_size / (1 + v.data_min) * rdir;
-            rpos = pos;
-            if (++spins > kSpinMax) break;
-            continue;
-        }
-        if (INTERP == 1) {
-            val = fetch_linear(v, lookup, val_prev, ambient, mc);
-        } else {
-            val = tex3d_cubic(v, lookup.x, lookup.y, lookup.z);
-            mc.samples++;
-            if (val.w < v.data_min) {
-                pos = pos + v.step_size / (1 + v.data_min) * rdir;
-                rpos = pos;
-                if (++spins > kSpinMax) break;
-                continue;
-            }
-        }
-        loop_ctr += 1;
-        val.w += 1;
-        current_n = val.w;
-        R_n = pos;
-        delta_t = v.step_size / val.w;
-        T_n = val.w * rdir;
-        D = mk3(val.w * val.x, val.w * val.y, val.w * val.z);
-        A = delta_t * D;
-        // reference: delta_t/2.0 and 1/8.0*delta_t in double, narrowed to float (.h:1088) --
-        // exact powers of two, so the f32 products below are the same values
-        pos = R_n + (0.5f * delta_t) * T_n + (0.125f * delta_t) * A;
-        lookup = lookup_index(pos, v, scale);
-        if (!inside_box(pos, v, lookup)) break;
-        if (INTERP == 1) {
-            val_prev = val; val_prev.w -= 1;
-            val = fetch_linear(v, lookup, val_prev, ambient, mc);
-        } else {
-            val = tex3d_cubic(v, lookup.x, lookup.y, lookup.z);
-            mc.samples++;
-        }
-        val.w += 1;
-        D = mk3(val.w * val.x, val.w * val.y, val.w * val.z);
-        B = delta_t * D;
-        pos = R_n + delta_t * T_n + (0.5f * delta_t) * B;                  // .h:1131
-        lookup = lookup_index(pos, v, scale);
-        if (!inside_box(pos, v, lookup)) break;
-        if (INTERP == 1) {
-            val_prev = val; val_prev.w -= 1;
-            val = fetch_linear(v, lookup, val_prev, ambient, mc);
-        } else {
-            val = tex3d_cubic(v, lookup.x, lookup.y, lookup.z);
-            mc.samples++;
-        }
-        val.w += 1;
-        D = mk3(val.w * val.x, val.w * val.y, val.w * val.z);
-        C = delta_t * D;
-        R_n = R_n + delta_t * (T_n + (float)(1 / 6.0) * (A + 2.0f * B));
-        T_n = T_n + (float)(1 / 6.0) * (A + 4.0f * B + C);
-        if (INTERP == 1) { val_prev = val; val_prev.w -= 1; }
-        rpos = R_n;
-        // linear branch divides by the first sample's n (.h:1178), cubic by the last (.h:1276)
-        rdir = normalize(T_n / (INTERP == 1 ? current_n : val.w));
-        mc.iterations++;
-    }
-}
-
-// Euler integrator (.h:743-950), noise hook not built.
-template <int INTERP>
-__device__ __forceinline__ void euler(f3 &rpos, f3 &rdir, const VolumeDev &v, f3 scale, MarchCount &mc) {
-    const float ambient = 1.000277;
-    int loop_ctr = 0, spins = 0;
-    f3 pos, dir, lookup, normal;
-    f4 val, val_prev = f4{0, 0, 0, 0};
-    while (true) {
-        if (loop_ctr > kLoopMax) break;
-        pos = rpos; dir = rdir;
-        lookup = lookup_index(pos, v, scale);
-        if (!inside_box(pos, v, lookup) && loop_ctr != 0) break;
-        if (INTERP == 1) {
-            if (!can_access(v, lookup)) {
-                pos = pos + v.step_size / (1 + v.data_min) * dir;
-                rpos = pos;
-                if (++spins > kSpinMax) break;
-                continue;
-            }
-            val = fetch_linear(v, lookup, val_prev, ambient, mc);
-            const float current_n = 1 + val.w;
-            normal = mk3(val.x, val.y, val.z);
-            dir = dir + v.step_size * normal;
-            pos = pos + v.step_size / current_n * dir;
-            rpos = pos; rdir = dir;
-            val_prev = val;
-            loop_ctr += 1;
-        } else {
-            val = tex3d_cubic(v, lookup.x, lookup.y, lookup.z);
-            mc.samples++;
-            if (val.w < v.data_min) {
-                pos = pos + v.step_size / (1 + v.data_min) * dir;
-                rpos = pos;
-                if (++spins > kSpinMax) break;
-                continue;
-            }
-            loop_ctr += 1;
-            normal = mk3(val.x, val.y, val.z);
-            dir = dir + v.step_size * normal;
-            dir = normalize(dir);
-            const float n = 1 + val.w;
-            pos = pos + dir * v.step_size / n;
-            rpos = pos; rdir = dir;
-        }
-        mc.iterations++;
-    }
-}
-
 // =============================================================================================
 // Per-lane building blocks shared with the wave-cooperative samplers (device_volume_coop.hpp).
 // =============================================================================================
 
-// The 64-tap separable sum with per-lane, clamped addressing (stragglers of incoherent waves).  Deliberately
-// NOT inlined: it is the rare path, and inlined at three call sites it would set the register budget (and so
-// the occupancy) of the whole march kernel.  It recomputes the B-spline weights from the coordinate -- same
-// operations, same values -- so a call site only has to pass three floats.
 // One of the four B-spline weights of bspline_weights(f, ...), selected at run time (same operations, same
 // values): lets the rolled loops below keep a single weight in registers instead of three arrays.
 __device__ __forceinline__ float bspline_weight_at(float f, int idx) {
@@ -348,6 +202,10 @@ __device__ __forceinline__ float bspline_weight_at(float f, int idx) {
     return idx == 0 ? w0 : idx == 1 ? w1 : idx == 2 ? w2 : w3;
 }
 
+// The 64-tap separable sum with per-lane, clamped addressing (stragglers of incoherent waves).  Deliberately
+// NOT inlined: it is the rare path, and inlined at three call sites it would set the register budget (and so
+// the occupancy) of the whole march kernel.  It recomputes the B-spline weights from the coordinate -- same
+// operations, same values -- so a call site only has to pass three floats.
 // Written for the SMALLEST register footprint, not for speed: every loop rolled, one texel in flight, weights
 // recomputed where they are used.  Under the AMDGPU calling convention a kernel's values that live across a
 // call sit above the callee's registers, so this function's count adds to the caller's: at 81 VGPRs (the first
@@ -380,38 +238,6 @@ __device__ __attribute__((noinline)) f4 cubic_gather_fn(const f4 *__restrict__ t
         else acc = f4{fmaf(wzc, s.x, acc.x), fmaf(wzc, s.y, acc.y), fmaf(wzc, s.z, acc.z), fmaf(wzc, s.w, acc.w)};
     }
     return acc;
-}
-
-template <bool CLAMP>
-__device__ __forceinline__ f4 linear_taps(const f4 *__restrict__ t, int nx, int ny, int nz, int i, int j, int k,
-                                          float a, float b, float c) {
-    const int i0 = CLAMP ? clampi(i, 0, nx - 1) : i, i1 = CLAMP ? clampi(i + 1, 0, nx - 1) : i + 1;
-    const int j0 = CLAMP ? clampi(j, 0, ny - 1) : j, j1 = CLAMP ? clampi(j + 1, 0, ny - 1) : j + 1;
-    const int k0 = CLAMP ? clampi(k, 0, nz - 1) : k, k1 = CLAMP ? clampi(k + 1, 0, nz - 1) : k + 1;
-    const size_t W = nx, WH = (size_t)nx * ny;
-    const f4 v000 = ldtexel(t + k0 * WH + j0 * W + i0), v100 = ldtexel(t + k0 * WH + j0 * W + i1);
-    const f4 v010 = ldtexel(t + k0 * WH + j1 * W + i0), v110 = ldtexel(t + k0 * WH + j1 * W + i1);
-    const f4 v001 = ldtexel(t + k1 * WH + j0 * W + i0), v101 = ldtexel(t + k1 * WH + j0 * W + i1);
-    const f4 v011 = ldtexel(t + k1 * WH + j1 * W + i0), v111 = ldtexel(t + k1 * WH + j1 * W + i1);
-    const f4 c00 = lerp4(v000, v100, a), c10 = lerp4(v010, v110, a);
-    const f4 c01 = lerp4(v001, v101, a), c11 = lerp4(v011, v111, a);
-    const f4 c0 = lerp4(c00, c10, b), c1 = lerp4(c01, c11, b);
-    return lerp4(c0, c1, c);
-}
-
-// trace_rays_through_density_gradients (.h:1455-1544): entry test + integrator dispatch.
-template <int ALGO, int INTERP>
-__device__ __forceinline__ void trace_volume(f3 &pos_io, f3 &dir_io, const VolumeDev &v, MarchCount &mc) {
-    const f3 mn = v.min_bound, mx = v.max_bound;
-    const f3 scale = mk3(1.0f / (mx.x - mn.x), 1.0f / (mx.y - mn.y), 1.0f / (mx.z - mn.z));
-    f3 pos = pos_io;
-    const f3 dir = dir_io;
-    if (pos.x <= mn.x || pos.y <= mn.y || pos.z <= mn.z || pos.x >= mx.x || pos.y >= mx.y || pos.z >= mx.z) {
-        if (!intersect_with_volume(pos, dir, mn, mx)) return;       // miss: ray left unchanged
-    }
-    pos_io = pos;
-    if (ALGO == 1) euler<INTERP>(pos_io, dir_io, v, scale, mc);
-    else rk4<INTERP>(pos_io, dir_io, v, scale, mc);
 }
 
 }  // namespace photon

@@ -866,7 +866,7 @@ __device__ __forceinline__ MarchResume resume_fresh() { return MarchResume{0, 0,
 // a cooperative sampler call each.  A lane whose ray leaves the box drops out of `active` (the
 // reference's `break`); a lane that has to step forward without sampling (the reference's
 // `continue`) sits out the rest of the trip and retries on the next one.  The per-ray operation
-// order is that of rk4<> in device_volume.hpp.
+// order is the reference's (.h:952-1291) as the CPU oracle's rk4 (photon_oracle.cpp) spells it.
 //
 // Shape of the code (round 3): the stage algebra runs UNPREDICATED on every lane -- a lane that does not take part
 // computes garbage nobody reads -- and the predicates (active, go, spin, first) are wave masks; only the commit of a
@@ -965,7 +965,7 @@ __device__ __forceinline__ unsigned long long rk4_coop(bool active_lane, f3 &rpo
 }
 
 // Wave-synchronous Euler integrator (reference: .h:743-950): one cooperative sample per trip.  Per-ray operation
-// order is that of euler<> in device_volume.hpp.
+// order is the reference's as the CPU oracle's euler (photon_oracle.cpp) spells it.
 // Gradient noise of the Euler integrator (.h:853-863): N(0,1)*sigma added to dn/dx, dn/dy.  NOISE is a template
 // parameter: with the Philox generator behind a run-time flag the default instantiation spilled 38 VGPRs into its loop.
 struct GradNoise { int on; float std; unsigned long long seed, ray_id; };

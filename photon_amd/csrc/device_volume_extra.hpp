@@ -207,7 +207,8 @@ __device__ __noinline__ void adams_bashforth(f3 &rpos, f3 &rdir, const VolumeDev
     }
 }
 
-// Entry test + dispatch for algorithms 3, 4 and the no-op default (the prologue of trace_volume, .h:1455-1544).
+// Entry test + dispatch for algorithms 3, 4 and the no-op default (the prologue of trace_rays_through_density_gradients,
+// .h:1455-1544).
 template <int ALGO>
 __device__ __forceinline__ void trace_volume_extra(f3 &pos_io, f3 &dir_io, const VolumeDev &v, MarchCount &mc) {
     const f3 mn = v.min_bound, mx = v.max_bound;

@@ -1,5 +1,5 @@
 // photon_moments.hip - per-source sensor moments (photon_trace_moments, photon_start_ray_tracing_moments): the reduction of a
-// launch's moments block (written by sensor_moments_kernel, photon_sensor.hip) into one record of kMomentFields doubles per source.
+// launch's moments block (written by sensor_kernel<..., MOM = true>, photon_sensor.hip) into one record of kMomentFields doubles per source.
 //
 // The summation order is part of the contract (include/parallel_ray_tracing.h): lane l of 64 adds, in increasing j, the values
 // of the source's rays j = l (mod 64) that arrived, starting from +0.0; the 64 partials are then folded by halves

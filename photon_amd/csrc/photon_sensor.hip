@@ -38,83 +38,12 @@ __global__ __launch_bounds__(256) void raygen_kernel(SceneDev sc, long long src_
 #endif
 template <int SPLAT> struct SplatArea { typedef SplatLds type; };
 template <> struct SplatArea<2> { typedef TapLds type; };
-template <bool FROM_STATE, bool TRAIN, int SPLAT>
+// MOM: also write every arriving ray's final position and its direction as the dumps hold it to the launch's moments block
+// (photon_moments.hip reduces it per source).  A template flag with `if constexpr`, not a run-time test or a shared inline
+// function, so that the MOM = false instantiations stay instruction for instruction what they were without the moments;
+// they only carry the unused `mom` argument in their kernarg segment.
+template <bool FROM_STATE, bool TRAIN, int SPLAT, bool MOM>
 __global__ __launch_bounds__(256, (SPLAT == 2 ? PHOTON_SENSOR_WAVES_TAPS : PHOTON_SENSOR_WAVES)) void sensor_kernel(SceneDev sc, long long src_begin, unsigned n_rays, RayStateDev st,
-                                                     double *image, DumpDev dump, unsigned long long *counters) {
-    __shared__ typename SplatArea<SPLAT>::type splat_lds[4];            // per wave: the parked rays of the cooperative splats
-    const unsigned r = blockIdx.x * blockDim.x + threadIdx.x;
-    int taps = 0;
-    unsigned on_sensor = 0;
-    SplatReq req;                                                       // erf splat, done wave-cooperatively below
-    req.valid = false;
-    req.X = req.Y = req.D = req.rfD = 0.f; req.scale = 0.0; req.c0 = req.c1 = req.r0 = req.r1 = 0;
-    TapReq tap;                                                         // 4-pixel splat, likewise
-    tap.valid = false;
-    tap.ii_ul = tap.jj_ul = 0; tap.inc[0] = tap.inc[1] = tap.inc[2] = tap.inc[3] = 0.f;
-    if (r < n_rays) {
-        Ray ray;
-        bool alive = true;
-        int source, local_ray;
-        slot_to_ray(sc, src_begin, n_rays, r, source, local_ray);
-        if (FROM_STATE) {                                              // back to the camera frame (.cu:2100-2122)
-            f3 p = mk3(st.px[r], st.py[r], st.pz[r]);
-            f3 d = mk3(st.dx[r], st.dy[r], st.dz[r]);
-            p = matvec(sc.cam.rotation_matrix, p);
-            d = normalize(matvec(sc.cam.rotation_matrix, d));
-            p.z = (float)(p.z + (sc.z_offset + 750e3));                 // .cu:2119
-            ray.pos = p;
-            ray.dir = d;
-            ray.radiance = st.radiance[r];
-            ray.wavelength = sc.beam_wavelength;
-            alive = !(isnan3(ray.dir) || isnan3(ray.pos));              // .cu:2125-2129
-        } else {
-            ray = generate_ray(sc, source, local_ray);
-        }
-        const bool dumping = dump.final_pos != nullptr && r < (unsigned)dump.num_save;
-        // the ray's identity for the noise generator: independent of the launch order
-        const unsigned long long ray_id = (unsigned long long)(sc.source_base + source) * (unsigned)sc.rays_per_source + (unsigned)local_ray;
-        f3 fin = nan3();
-        bool have_fin = false;
-        if (alive) {
-            if (dumping) {                                              // .cu:2136-2141
-                dump.final_dir[3 * r] = ray.dir.x; dump.final_dir[3 * r + 1] = ray.dir.y;
-                dump.final_dir[3 * r + 2] = ray.dir.z;
-            }
-            if (SPLAT != 2 && sc.elems[0].element_type == 'n') {        // .cu:2143-2158
-                const float z_obj = sc.object_distance + sc.z_offset;
-                fin = apparent_image(ray, sc.cam, z_obj, sc.z_offset, sc.elems[0], req, sc.noise, ray_id);
-                have_fin = true;
-                on_sensor = !isnan(fin.x);
-            } else {
-                ray = optical_system<TRAIN>(sc, ray);
-                if (!(isnan3(ray.dir) || isnan3(ray.pos))) {            // .cu:2172-2176
-                    if (SPLAT != 2 && sc.cam.implement_diffraction) {
-                        fin = sensor_diffraction(ray, sc.cam, req, sc.noise, ray_id);
-                        have_fin = true;
-                        on_sensor = !isnan(fin.x);
-                    } else {
-                        fin = sensor_bilinear(ray, sc.cam, tap, sc.noise, ray_id);
-                        have_fin = !(isnan(fin.x) || isnan(fin.y));     // .cu:2196
-                        on_sensor = have_fin;
-                    }
-                }
-            }
-        }
-        if (dumping && have_fin) {
-            dump.final_pos[3 * r] = fin.x; dump.final_pos[3 * r + 1] = fin.y; dump.final_pos[3 * r + 2] = fin.z;
-        }
-    }
-    if constexpr (SPLAT != 2) taps += erf_splat_wave(image, sc.cam.x_pixel_number, sc.cam.y_pixel_number, req, splat_lds[threadIdx.x >> 6]);      // all 64 lanes
-    taps += bilinear_splat_wave(image, sc.cam.x_pixel_number, sc.cam.y_pixel_number, tap, splat_lds[threadIdx.x >> 6]);     // all 64 lanes
-    wave_add(&counter_slot(counters)[CNT_TAPS], (unsigned long long)taps);
-    wave_add(&counter_slot(counters)[CNT_ON_SENSOR], (unsigned long long)on_sensor);
-}
-
-// sensor_kernel plus the per-source moments (photon_moments.hip): every arriving ray's final position and its direction as the
-// dumps hold it go to the launch's moments block.  A copy of sensor_kernel's body with those lines added, not a shared inline
-// function: moving the body into one gives the existing instantiations other register allocations (82 -> 84 VGPRs).
-template <bool FROM_STATE, bool TRAIN, int SPLAT>
-__global__ __launch_bounds__(256, (SPLAT == 2 ? PHOTON_SENSOR_WAVES_TAPS : PHOTON_SENSOR_WAVES)) void sensor_moments_kernel(SceneDev sc, long long src_begin, unsigned n_rays, RayStateDev st,
                                                      double *image, DumpDev dump, unsigned long long *counters, MomentsDev mom) {
     __shared__ typename SplatArea<SPLAT>::type splat_lds[4];            // per wave: the parked rays of the cooperative splats
     const unsigned r = blockIdx.x * blockDim.x + threadIdx.x;
@@ -150,9 +79,9 @@ __global__ __launch_bounds__(256, (SPLAT == 2 ? PHOTON_SENSOR_WAVES_TAPS : PHOTO
         const unsigned long long ray_id = (unsigned long long)(sc.source_base + source) * (unsigned)sc.rays_per_source + (unsigned)local_ray;
         f3 fin = nan3();
         bool have_fin = false;
-        f3 dir0 = nan3();                                               // the direction the dumps hold
+        f3 dir0 = nan3();                                               // MOM: the direction the dumps hold
         if (alive) {
-            dir0 = ray.dir;
+            if constexpr (MOM) dir0 = ray.dir;
             if (dumping) {                                              // .cu:2136-2141
                 dump.final_dir[3 * r] = ray.dir.x; dump.final_dir[3 * r + 1] = ray.dir.y;
                 dump.final_dir[3 * r + 2] = ray.dir.z;
@@ -180,12 +109,14 @@ __global__ __launch_bounds__(256, (SPLAT == 2 ? PHOTON_SENSOR_WAVES_TAPS : PHOTO
         if (dumping && have_fin) {
             dump.final_pos[3 * r] = fin.x; dump.final_pos[3 * r + 1] = fin.y; dump.final_pos[3 * r + 2] = fin.z;
         }
-        if (have_fin && !isnan(fin.x) && !isnan(fin.y) && !isnan(fin.z)) {    // arrived: the dump's position entry would be a number
-            // indexed by (the source's place in the launch, its own lens sample): independent of the slot the ray had
-            const unsigned place = sc.src_list ? r / (unsigned)sc.slot_rays : (unsigned)(source - src_begin);
-            const size_t k = (size_t)place * (unsigned)sc.rays_per_source + (unsigned)local_ray;
-            mom.x[k] = fin.x; mom.y[k] = fin.y; mom.z[k] = fin.z;
-            mom.dx[k] = dir0.x; mom.dy[k] = dir0.y; mom.dz[k] = dir0.z;
+        if constexpr (MOM) {
+            if (have_fin && !isnan(fin.x) && !isnan(fin.y) && !isnan(fin.z)) {    // arrived: the dump's position entry would be a number
+                // indexed by (the source's place in the launch, its own lens sample): independent of the slot the ray had
+                const unsigned place = sc.src_list ? r / (unsigned)sc.slot_rays : (unsigned)(source - src_begin);
+                const size_t k = (size_t)place * (unsigned)sc.rays_per_source + (unsigned)local_ray;
+                mom.x[k] = fin.x; mom.y[k] = fin.y; mom.z[k] = fin.z;
+                mom.dx[k] = dir0.x; mom.dy[k] = dir0.y; mom.dz[k] = dir0.z;
+            }
         }
     }
     if constexpr (SPLAT != 2) taps += erf_splat_wave(image, sc.cam.x_pixel_number, sc.cam.y_pixel_number, req, splat_lds[threadIdx.x >> 6]);      // all 64 lanes
@@ -213,32 +144,33 @@ int launch_raygen(photon_scene *s, long long src_begin, unsigned n, hipStream_t 
     return 0;
 }
 
-// The instantiation of KERNEL (sensor_kernel or sensor_moments_kernel) that the scene's camera and the launch's ray source call for.
-#define PH_SENSOR_LAUNCH(KERNEL, ...)                                                                                         \
-    do {                                                                                                                      \
-        if (taps_only && !from_state) hipLaunchKernelGGL((KERNEL<false, false, 2>), grid, block, 0, stream, __VA_ARGS__);      \
-        else if (taps_only) hipLaunchKernelGGL((KERNEL<true, false, 2>), grid, block, 0, stream, __VA_ARGS__);                 \
-        else if (from_state) {                                                                                                \
-            if (s->dev.train_mode) hipLaunchKernelGGL((KERNEL<true, true, 0>), grid, block, 0, stream, __VA_ARGS__);           \
-            else hipLaunchKernelGGL((KERNEL<true, false, 0>), grid, block, 0, stream, __VA_ARGS__);                            \
-        } else {                                                                                                              \
-            if (s->dev.train_mode) hipLaunchKernelGGL((KERNEL<false, true, 0>), grid, block, 0, stream, __VA_ARGS__);          \
-            else hipLaunchKernelGGL((KERNEL<false, false, 0>), grid, block, 0, stream, __VA_ARGS__);                           \
-        }                                                                                                                     \
-    } while (0)
+// The instantiation of sensor_kernel that the scene's camera, the launch's ray source and the moments block call for.
+template <bool MOM>
+static void launch_sensor_kernel(photon_scene *s, bool from_state, bool taps_only, long long src_begin, unsigned n, const DumpDev &dump,
+                                 hipStream_t stream, const MomentsDev &mom) {
+    const dim3 block(256), grid((n + 255) / 256);
+#define PH_SENSOR_ARGS grid, block, 0, stream, s->dev, src_begin, n, s->ws, s->d_acc, dump, s->d_counters, mom
+    if (taps_only && !from_state) hipLaunchKernelGGL((sensor_kernel<false, false, 2, MOM>), PH_SENSOR_ARGS);
+    else if (taps_only) hipLaunchKernelGGL((sensor_kernel<true, false, 2, MOM>), PH_SENSOR_ARGS);
+    else if (from_state) {
+        if (s->dev.train_mode) hipLaunchKernelGGL((sensor_kernel<true, true, 0, MOM>), PH_SENSOR_ARGS);
+        else hipLaunchKernelGGL((sensor_kernel<true, false, 0, MOM>), PH_SENSOR_ARGS);
+    } else {
+        if (s->dev.train_mode) hipLaunchKernelGGL((sensor_kernel<false, true, 0, MOM>), PH_SENSOR_ARGS);
+        else hipLaunchKernelGGL((sensor_kernel<false, false, 0, MOM>), PH_SENSOR_ARGS);
+    }
+#undef PH_SENSOR_ARGS
+}
 
 int launch_sensor(photon_scene *s, bool from_state, long long src_begin, unsigned n, const DumpDev &dump, hipStream_t stream,
                   const MomentsDev *mom) {
-    const dim3 block(256), grid((n + 255) / 256);
-    double *d_image = s->d_acc;
     // a camera without diffraction behind a real first element: the 4-pixel-only instantiations (the default element path; after a march: C5)
     const bool taps_only = !s->dev.train_mode && !s->dev.cam.implement_diffraction && s->dev.elems[0].element_type != 'n';
-    if (mom) PH_SENSOR_LAUNCH(sensor_moments_kernel, s->dev, src_begin, n, s->ws, d_image, dump, s->d_counters, *mom);
-    else PH_SENSOR_LAUNCH(sensor_kernel, s->dev, src_begin, n, s->ws, d_image, dump, s->d_counters);
+    if (mom) launch_sensor_kernel<true>(s, from_state, taps_only, src_begin, n, dump, stream, *mom);
+    else launch_sensor_kernel<false>(s, from_state, taps_only, src_begin, n, dump, stream, MomentsDev{});
     PH_CHECK(hipGetLastError());
     return 0;
 }
-#undef PH_SENSOR_LAUNCH
 
 int launch_finalize(photon_scene *s, float *d_image, hipStream_t stream) {
     const size_t npix = (size_t)s->dev.cam.x_pixel_number * s->dev.cam.y_pixel_number;

@@ -25,7 +25,7 @@ for w in "${wl[@]}"; do
     tail) cmd="$BT --steps 100"; pcmd="$BT --steps 20" ;;
     c4) cmd="$B --volume 512 --dots 2000"; pmc=0 ;;
     c5) cmd="$ROOT/tools/c5_full.py 0.25" ;;
-    piv) cmd="$ROOT/tools/sample_full.py piv_full" ;;          # the reference's sample PIV frame (5e8 requested rays, no volume): sensor_kernel<false,false>
+    piv) cmd="$ROOT/tools/sample_full.py piv_full" ;;          # the reference's sample PIV frame (5e8 requested rays, no volume): sensor_kernel<false,false,2,false>
     *) echo "unknown workload $w"; exit 1 ;;
   esac
   d="$out/$w"; mkdir -p "$d"
