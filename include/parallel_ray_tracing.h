@@ -613,6 +613,39 @@ int photon_postprocess_u16(float *d_image, int width, int height, float pixel_ga
                            int intensity_rescaling, float image_noise, uint64_t noise_seed, int crop_rows, int crop_cols,
                            uint16_t *d_out, int *out_rows, int *out_cols, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 5: windowed direct cross-correlation of an image pair on the device (PIV / BOS displacement
+ * fields): the measurement a PIV or BOS user runs on the two images, on images already in HBM.  Host
+ * model: photon_amd/piv_correlation.py (correlate_model, f64).
+ *   d_im1, d_im2  device f32[height*width], row-major (the library's images)
+ *   win           16, 32 or 64 (square windows);  step >= 1;  radius R in [1, win/2]
+ *   window (i, j) rows [i step, i step + win), columns [j step, j step + win); n_rows = (height - win)/step + 1,
+ *             n_cols = (width - win)/step + 1 (integer division), window k = i n_cols + j; centre at
+ *             (i step + (win-1)/2, j step + (win-1)/2) (row, column)
+ *   d_offset  device int[n][2] (ox, oy) integer predictor per window, or NULL (0)
+ * For every shift s = (sx, sy) in [-R, R]^2, with a = im1 over the window, b(p) = im2(p + o):
+ *   C(s) = sum_p (a(p) - mean a)(b(p + s) - mean b) over the win^2 pixels of the window, mean b over the window at
+ *   zero shift (its in-image pixels); pixels of im2 outside the image read as mean b (contribute 0).  Every shift
+ *   sums the same win^2 products: direct correlation over an enlarged region, no wrap-around, no zero-padding bias.
+ *   Cn = C / sqrt(sum (a - mean a)^2 * sum (b - mean b)^2), the second sum at zero shift.
+ * Peak s* = argmax C, ties to the first shift in row-major order (sy, then sx).  Subpixel, per axis, from C-, C0, C+
+ * through s*, in f64: Gaussian delta = (ln C- - ln C+) / (2 (ln C- - 2 ln C0 + ln C+)); parabolic
+ * (C- - C+) / (2 (C- - 2 C0 + C+)) if any of the three is <= 0; 0 when the denominator is 0; 0 and flag 1 when s*
+ * lies on the edge of the search square in that axis.
+ *   d_vectors device f32[n][4]: dx = ox + sx* + delta_x (columns), dy = oy + sy* + delta_y (rows) -- im2(p + d) ~ im1(p),
+ *             a pattern moving right / down gives positive values; peak = Cn(s*); ratio = C(s*) / max{C(s) :
+ *             |s - s*|_inf >= 2}, +inf when there is no such shift or that maximum is <= 0
+ *   d_flags   device int[n], bits: 1 peak on the search edge, 2 flat window (either energy 0: every output of the
+ *             window, its plane included, NaN), 4 a pixel the window needs lies outside im2
+ *   d_planes  device f32[n][(2R+1)^2] Cn, row-major (sy, then sx), or NULL
+ * d_vectors == NULL: only *n_rows / *n_cols are written (ask for the size first); nothing is launched.
+ * Refused (1, one stderr line, nothing written, no launch): win not 16 / 32 / 64, R out of range, step < 1, an
+ * image smaller than one window, a null image pointer, d_vectors without d_flags.  f32 sums in a fixed order: two
+ * calls on the same inputs return the same bits.  Asynchronous on `stream`. */
+int photon_piv_correlate(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int radius,
+                         const int *d_offset, float *d_vectors, int *d_flags, float *d_planes, int *n_rows, int *n_cols,
+                         void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,344 @@
+// photon_piv.hip - windowed direct cross-correlation of an image pair on the device (PIV / BOS displacement fields):
+// the measurement step of a synthetic-image error study, run on the two f32 images while they are still in HBM.
+// Definition: include/parallel_ray_tracing.h, section 5; host model: photon_amd/piv_correlation.py (correlate_model).
+//
+// One workgroup per window.  The mean-subtracted window of im1 (win^2) and of the search region of im2 ((win + 2R)^2,
+// b - mean(b), pixels outside the image 0) are staged in LDS.  The (2R+1)^2 shifts are cut into tiles of 4 (x) x 4 (y);
+// a lane owns one tile and one of K contiguous slices of the window's rows, walks its rows 4 columns at a time with
+// ds_read_b128, and keeps a sliding 8-value strip of each of its 4 im2 rows in registers: per 4 columns 1 + 4 LDS reads
+// for 64 FMAs.  The K partial planes are summed in a fixed order; every sum in the kernel has a fixed order, so two calls
+// on the same inputs return the same bits.  The plane stays in LDS for the argmax, the ratio and the subpixel fit.
+// f32 FMA on the VALU: gfx950's f32 MFMA runs at the VALU's f32 rate and the GEMM form of a correlation doubles the work.
+#include <algorithm>
+#include <cfloat>
+#include <climits>
+#include <cmath>
+
+#include "photon_internal.hpp"
+
+using namespace photon;
+
+namespace {
+
+constexpr int kTileX = 4;           // shifts per lane along x (one float4 of im2 per step)
+constexpr int kTileY = 4;           // shifts per lane along y
+constexpr int kMaxThreads = 512;
+constexpr int kRedWords = 64;       // block-reduction scratch: 16 floats x 2 + 16 ints (8 waves at most)
+
+typedef float v4f __attribute__((ext_vector_type(4)));
+
+// Fixed-order block sums: a butterfly inside each wave (every lane ends with the same bits), then the wave totals in wave
+// order.  blockDim.x is a multiple of 64.
+__device__ __forceinline__ void block_sum2(float &a, float &b, float *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+    }
+    const int nw = blockDim.x >> 6, w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        red[w] = a;
+        red[16 + w] = b;
+    }
+    __syncthreads();
+    a = 0.f;
+    b = 0.f;
+    for (int i = 0; i < nw; i++) {
+        a += red[i];
+        b += red[16 + i];
+    }
+}
+
+__device__ __forceinline__ float block_max(float v, float *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    const int nw = blockDim.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    v = red[0];
+    for (int i = 1; i < nw; i++) v = fmaxf(v, red[i]);
+    return v;
+}
+
+// argmax with the tie rule: the larger value, then the smaller index
+__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
+
+__device__ __forceinline__ void block_argmax(float &bv, int &bi, float *red, int *redi) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(bv, o, 64);
+        const int oi = __shfl_xor(bi, o, 64);
+        if (better(ov, oi, bv, bi)) {
+            bv = ov;
+            bi = oi;
+        }
+    }
+    const int nw = blockDim.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        red[threadIdx.x >> 6] = bv;
+        redi[threadIdx.x >> 6] = bi;
+    }
+    __syncthreads();
+    bv = red[0];
+    bi = redi[0];
+    for (int i = 1; i < nw; i++)
+        if (better(red[i], redi[i], bv, bi)) {
+            bv = red[i];
+            bi = redi[i];
+        }
+}
+
+// 3-point fit through (cm, c0, cp) in f64: Gaussian when all three are positive, parabolic otherwise; 0 for a flat triple
+__device__ __forceinline__ double subpixel(double cm, double c0, double cp) {
+    if (cm > 0.0 && c0 > 0.0 && cp > 0.0) {
+        const double lm = log(cm), l0 = log(c0), lp = log(cp);
+        const double den = 2.0 * (lm - 2.0 * l0 + lp);
+        return den != 0.0 ? (lm - lp) / den : 0.0;
+    }
+    const double den = 2.0 * (cm - 2.0 * c0 + cp);
+    return den != 0.0 ? (cm - cp) / den : 0.0;
+}
+
+// LDS layout (floats): a [WIN][WIN] | b [WIN + nSyp - 1][WIN + nSxp] | K partial planes [nSyp][nSxp] | reduction scratch.
+// nSxp, nSyp: 2R + 1 rounded up to the tile; the shifts past 2R read zero padding and are dropped.
+template <int WIN>
+__global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float *__restrict__ im1, const float *__restrict__ im2, int W, int H,
+                                                                    int step, int R, int n_cols, const int *__restrict__ offset, int K,
+                                                                    int nSxp, int nSyp, float *__restrict__ vectors,
+                                                                    int *__restrict__ flags, float *__restrict__ planes) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const int nS = 2 * R + 1, nS2 = nS * nS;
+    const int pitch = WIN + nSxp, rows = WIN + nSyp - 1, P = nSyp * nSxp;
+    float *sa = lds;
+    float *sb = sa + WIN * WIN;
+    float *sp = sb + rows * pitch;
+    float *red = sp + K * P;
+    int *redi = reinterpret_cast<int *>(red + 32);
+
+    const int win_id = blockIdx.x;
+    const int wy0 = (win_id / n_cols) * step, wx0 = (win_id % n_cols) * step;
+    const int ox = offset ? offset[2 * win_id] : 0, oy = offset ? offset[2 * win_id + 1] : 0;
+    const int tid = threadIdx.x, B = blockDim.x;
+
+    // ---- means: a over the window; b over the in-image pixels of the zero-shift window (outside pixels read as that mean)
+    float sum_a = 0.f, sum_b = 0.f, cnt_b = 0.f;
+    for (int i = tid; i < WIN * WIN; i += B) {
+        const int y = i / WIN, x = i % WIN;
+        const float v = im1[(size_t)(wy0 + y) * W + (wx0 + x)];
+        sa[i] = v;
+        sum_a += v;
+        const int gy = wy0 + oy + y, gx = wx0 + ox + x;
+        if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
+            sum_b += im2[(size_t)gy * W + gx];
+            cnt_b += 1.f;
+        }
+    }
+    block_sum2(sum_a, sum_b, red);
+    float cnt = cnt_b, dummy = 0.f;
+    block_sum2(cnt, dummy, red);
+    const float mean_a = sum_a / (float)(WIN * WIN);
+    const float mean_b = cnt > 0.f ? sum_b / cnt : 0.f;
+
+    // ---- mean-subtracted a in place; the b region with zero padding; the two energies (b at zero shift)
+    float ea = 0.f, eb = 0.f;
+    for (int i = tid; i < WIN * WIN; i += B) {
+        const float v = sa[i] - mean_a;
+        sa[i] = v;
+        ea = fmaf(v, v, ea);
+    }
+    const int span = WIN + 2 * R;
+    for (int i = tid; i < rows * pitch; i += B) {
+        const int ry = i / pitch, rx = i % pitch;
+        float v = 0.f;
+        if (ry < span && rx < span) {
+            const int gy = wy0 + oy - R + ry, gx = wx0 + ox - R + rx;
+            if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = im2[(size_t)gy * W + gx] - mean_b;
+            if (ry >= R && ry < R + WIN && rx >= R && rx < R + WIN) eb = fmaf(v, v, eb);
+        }
+        sb[i] = v;
+    }
+    block_sum2(ea, eb, red);           // (its barriers also publish sa and sb)
+
+    const bool outside = wy0 + oy - R < 0 || wx0 + ox - R < 0 || wy0 + oy + WIN - 1 + R >= H || wx0 + ox + WIN - 1 + R >= W;
+    if (!(ea > 0.f) || !(eb > 0.f)) {                           // flat window (block-uniform)
+        const float qnan = __builtin_nanf("");
+        if (tid == 0) {
+            vectors[4 * (size_t)win_id + 0] = qnan;
+            vectors[4 * (size_t)win_id + 1] = qnan;
+            vectors[4 * (size_t)win_id + 2] = qnan;
+            vectors[4 * (size_t)win_id + 3] = qnan;
+            flags[win_id] = 2 | (outside ? 4 : 0);
+        }
+        if (planes)
+            for (int i = tid; i < nS2; i += B) planes[(size_t)win_id * nS2 + i] = qnan;
+        return;
+    }
+
+    // ---- the correlation: item = (row slice k, shift tile ty, shift tile tx)
+    const int ntx = nSxp / kTileX, nty = nSyp / kTileY, units = ntx * nty;
+    for (int item = tid; item < units * K; item += B) {
+        const int k = item / units, unit = item % units;
+        const int sy0 = (unit / ntx) * kTileY, sx0 = (unit % ntx) * kTileX;
+        const int y0 = (k * WIN) / K, y1 = ((k + 1) * WIN) / K;
+        float acc[kTileY][kTileX];
+#pragma unroll
+        for (int u = 0; u < kTileY; u++)
+#pragma unroll
+            for (int t = 0; t < kTileX; t++) acc[u][t] = 0.f;
+        for (int y = y0; y < y1; y++) {
+            const float *arow = sa + y * WIN;
+            const float *brow = sb + (y + sy0) * pitch + sx0;
+            v4f prev[kTileY];
+#pragma unroll
+            for (int u = 0; u < kTileY; u++) prev[u] = *reinterpret_cast<const v4f *>(brow + u * pitch);
+#pragma unroll
+            for (int x = 0; x < WIN; x += 4) {
+                const v4f av = *reinterpret_cast<const v4f *>(arow + x);
+#pragma unroll
+                for (int u = 0; u < kTileY; u++) {
+                    const v4f nxt = *reinterpret_cast<const v4f *>(brow + u * pitch + x + 4);
+                    const float s[8] = {prev[u].x, prev[u].y, prev[u].z, prev[u].w, nxt.x, nxt.y, nxt.z, nxt.w};
+#pragma unroll
+                    for (int t = 0; t < kTileX; t++) {
+                        float c = acc[u][t];
+                        c = fmaf(av.x, s[t + 0], c);
+                        c = fmaf(av.y, s[t + 1], c);
+                        c = fmaf(av.z, s[t + 2], c);
+                        c = fmaf(av.w, s[t + 3], c);
+                        acc[u][t] = c;
+                    }
+                    prev[u] = nxt;
+                }
+            }
+        }
+        float *out = sp + k * P + sy0 * nSxp + sx0;
+#pragma unroll
+        for (int u = 0; u < kTileY; u++)
+            *reinterpret_cast<v4f *>(out + u * nSxp) = v4f{acc[u][0], acc[u][1], acc[u][2], acc[u][3]};
+    }
+    __syncthreads();
+
+    // ---- the plane (slices summed in order, into slice 0), its normalised copy, and the argmax
+    const double inv = 1.0 / sqrt((double)ea * (double)eb);
+    float bv = -INFINITY;
+    int bi = INT_MAX;
+    for (int i = tid; i < nS2; i += B) {
+        const int j = (i / nS) * nSxp + (i % nS);
+        float c = sp[j];
+        for (int k = 1; k < K; k++) c += sp[k * P + j];
+        sp[j] = c;
+        if (planes) planes[(size_t)win_id * nS2 + i] = (float)((double)c * inv);
+        if (better(c, i, bv, bi)) {
+            bv = c;
+            bi = i;
+        }
+    }
+    block_argmax(bv, bi, red, redi);            // (its barriers also publish the summed plane)
+    const int py = bi / nS, px = bi % nS;
+
+    // ---- the largest value at least 2 shifts away from the peak (Chebyshev distance)
+    float m2 = -INFINITY;
+    for (int i = tid; i < nS2; i += B) {
+        const int sy = i / nS, sx = i % nS;
+        if (max(abs(sy - py), abs(sx - px)) >= 2) m2 = fmaxf(m2, sp[sy * nSxp + sx]);
+    }
+    m2 = block_max(m2, red);
+
+    if (tid == 0) {
+        const float *row = sp + py * nSxp;
+        int f = outside ? 4 : 0;
+        double dx = 0.0, dy = 0.0;
+        if (px == 0 || px == nS - 1) f |= 1;
+        else dx = subpixel(row[px - 1], row[px], row[px + 1]);
+        if (py == 0 || py == nS - 1) f |= 1;
+        else dy = subpixel(row[px - nSxp], row[px], row[px + nSxp]);
+        vectors[4 * (size_t)win_id + 0] = (float)((double)(ox + px - R) + dx);
+        vectors[4 * (size_t)win_id + 1] = (float)((double)(oy + py - R) + dy);
+        vectors[4 * (size_t)win_id + 2] = (float)((double)bv * inv);
+        vectors[4 * (size_t)win_id + 3] = m2 > 0.f ? (float)((double)bv / (double)m2) : INFINITY;
+        flags[win_id] = f;
+    }
+}
+
+// How the shift tiles of one window are spread over a workgroup: K row slices and B threads (a multiple of 64), chosen
+// to waste the fewest lane-rows (the lanes past the last item of a round idle) within the LDS the device allows.
+struct Plan {
+    int K, threads, nSxp, nSyp;
+    size_t lds_bytes;
+};
+
+Plan plan_for(int win, int R, size_t lds_limit) {
+    Plan best{0, 0, 0, 0, 0};
+    const int nS = 2 * R + 1;
+    const int nSxp = (nS + kTileX - 1) / kTileX * kTileX, nSyp = (nS + kTileY - 1) / kTileY * kTileY;
+    const int units = (nSxp / kTileX) * (nSyp / kTileY);
+    const size_t fixed = (size_t)win * win + (size_t)(win + nSyp - 1) * (win + nSxp) + kRedWords;
+    long long best_cost = LLONG_MAX;
+    for (int K = 1; K <= 8 && K <= win / 4; K++) {
+        const size_t bytes = 4 * (fixed + (size_t)K * nSxp * nSyp);
+        if (bytes > lds_limit) break;
+        const int items = units * K;
+        const int threads = std::min(kMaxThreads, (items + 63) / 64 * 64);
+        const long long rounds = (items + threads - 1) / threads;
+        const long long cost = rounds * threads * ((win + K - 1) / K);
+        if (cost < best_cost) {
+            best_cost = cost;
+            best = Plan{K, threads, nSxp, nSyp, bytes};
+        }
+    }
+    return best;
+}
+
+template <int WIN>
+int launch(const float *im1, const float *im2, int W, int H, int step, int R, int n_rows, int n_cols, const int *offset,
+           float *vectors, int *flags, float *planes, hipStream_t stream) {
+    int dev = 0, lds_limit = 0;
+    PH_CHECK(hipGetDevice(&dev));
+    PH_CHECK(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    const Plan p = plan_for(WIN, R, (size_t)lds_limit);
+    if (p.K == 0) {
+        fprintf(stderr, "photon: photon_piv_correlate: win %d, radius %d needs more LDS than the device's %d bytes\n", WIN, R, lds_limit);
+        return 1;
+    }
+    if (p.lds_bytes > 65536)
+        PH_CHECK(hipFuncSetAttribute((const void *)piv_correlate_kernel<WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    hipLaunchKernelGGL(piv_correlate_kernel<WIN>, dim3((unsigned)(n_rows * n_cols)), dim3(p.threads), p.lds_bytes, stream, im1, im2, W, H,
+                       step, R, n_cols, offset, p.K, p.nSxp, p.nSyp, vectors, flags, planes);
+    PH_CHECK(hipGetLastError());
+    return 0;
+}
+
+}  // namespace
+
+extern "C" int photon_piv_correlate(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int radius,
+                                    const int *d_offset, float *d_vectors, int *d_flags, float *d_planes, int *n_rows, int *n_cols,
+                                    void *stream_p) {
+    const char *bad = nullptr;
+    if (win != 16 && win != 32 && win != 64) bad = "win must be 16, 32 or 64";
+    else if (radius < 1 || radius > win / 2) bad = "radius must lie in [1, win / 2]";
+    else if (step < 1) bad = "step must be >= 1";
+    else if (width < win || height < win) bad = "the image is smaller than one window";
+    else if (!d_im1 || !d_im2) bad = "null image pointer";
+    else if (d_vectors && !d_flags) bad = "d_vectors without d_flags";
+    if (bad) {
+        fprintf(stderr, "photon: photon_piv_correlate: %s (win %d, step %d, radius %d, %d x %d image)\n", bad, win, step, radius, width, height);
+        return 1;
+    }
+    const int rows = (height - win) / step + 1, cols = (width - win) / step + 1;
+    if ((long long)rows * cols > INT_MAX) {
+        fprintf(stderr, "photon: photon_piv_correlate: %d x %d windows are too many for one call\n", rows, cols);
+        return 1;
+    }
+    if (n_rows) *n_rows = rows;
+    if (n_cols) *n_cols = cols;
+    if (!d_vectors) return 0;                   // the size query
+    hipStream_t stream = (hipStream_t)stream_p;
+    switch (win) {
+    case 16: return launch<16>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, d_vectors, d_flags, d_planes, stream);
+    case 32: return launch<32>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, d_vectors, d_flags, d_planes, stream);
+    default: return launch<64>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, d_vectors, d_flags, d_planes, stream);
+    }
+}

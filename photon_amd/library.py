@@ -30,6 +30,8 @@ DECLARED_SYMBOLS = (
     "photon_scene_create_from_sources", "photon_volume_gaussian", "photon_density_gaussian_write_nrrd",
     # section 4: sensor post-processing on the device
     "photon_postprocess_u16", "photon_measure_copy_gbs", "photon_selftest_normal_range_math", "photon_selftest_morton_order",
+    # section 5: image-pair cross-correlation on the device
+    "photon_piv_correlate",
 )
 
 
@@ -198,6 +200,8 @@ class PhotonLibrary:
         L.photon_postprocess_u16.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int,
                                              ctypes.c_float, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
+        L.photon_piv_correlate.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [
+            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
 
     # ---- helpers --------------------------------------------------------------------------
     @staticmethod
@@ -294,6 +298,55 @@ class PhotonLibrary:
                                              ctypes.byref(r), ctypes.byref(c), ctypes.c_void_p(int(stream)) if stream else None)
         self._check(rc, "photon_postprocess_u16")
         return r.value, c.value
+
+    # ---- image-pair cross-correlation on the device (photon_piv_correlate) ------------------------------
+    def piv_correlate(self, d_im1_ptr: int, d_im2_ptr: int, width: int, height: int, win: int, step: int, radius: int,
+                      d_offset_ptr: int = 0, planes: bool = False, stream: int = 0):
+        """Correlate two device f32 images (raw pointers, row-major height x width) window by window; d_offset_ptr: device
+        int32 [n][2] integer offsets, or 0.  Returns torch device tensors (vectors [n_rows, n_cols, 4] = dx, dy, peak,
+        ratio; flags [n_rows, n_cols] int32; planes [n_rows, n_cols, 2R+1, 2R+1] or None), filled asynchronously on
+        `stream`.  The definition: include/parallel_ray_tracing.h, section 5 (photon_amd.piv_correlation: host model)."""
+        import torch
+        f = self.lib.photon_piv_correlate
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        args = (ctypes.c_void_p(int(d_im1_ptr)), ctypes.c_void_p(int(d_im2_ptr)), int(width), int(height), int(win), int(step),
+                int(radius))
+        self._check(f(*args, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None), "photon_piv_correlate")
+        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
+        dev = torch.device("cuda", torch.cuda.current_device())
+        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
+        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
+        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
+        rc = f(*args, ctypes.c_void_p(int(d_offset_ptr)) if d_offset_ptr else None, ctypes.c_void_p(vectors.data_ptr()),
+               ctypes.c_void_p(flags.data_ptr()), ctypes.c_void_p(pl.data_ptr()) if planes else None, None, None,
+               ctypes.c_void_p(int(stream)) if stream else None)
+        self._check(rc, "photon_piv_correlate")
+        return vectors, flags, pl
+
+    def correlate(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1):
+        """Displacement field of an image pair (torch tensors on the device or numpy arrays, [height, width]): returns numpy
+        (vectors [n_rows, n_cols, 4] = dx, dy, peak, ratio; flags [n_rows, n_cols]).  radius None = win // 2.  passes=2:
+        pass 1, the normalised median test and the predictor on the host (photon_amd.piv_correlation), then pass 2 with
+        the integer window offsets."""
+        import torch
+        from . import piv_correlation as pc
+        if int(passes) not in (1, 2):
+            raise ValueError(f"passes must be 1 or 2, not {passes}")
+        radius = int(win) // 2 if radius is None else int(radius)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
+        if a.dim() != 2 or a.shape != b.shape:
+            raise ValueError("im1 and im2 must be two 2-d images of one shape")
+        h, w = a.shape
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
+        vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
+        if int(passes) == 2:
+            offsets = pc.predictor(vectors, flags, pc.normalized_median_test(vectors))
+            d_off = torch.from_numpy(offsets).to(dev)
+            vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
+            vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
+        return vectors, flags
 
     # ---- volumes ------------------------------------------------------------------------------
     def volume_load_nrrd(self, path: str, interpolation: int = 1) -> "Volume":

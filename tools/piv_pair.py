@@ -6,9 +6,14 @@ each particle's centroid shift is held against the paraxial prediction -m(Z) (dX
 displacement.  Prints ms per frame, the advection's ms, the particles seen in both frames and the median / 99th percentile
 of |measured - predicted| in pixels, then one JSON line.  --tiff DIR writes both frames through the post-process
 (postprocess_image) and the TIFF writer; --bench-advect also times 1e6 particles x 16 steps through a 128^3 field.
-Run it on a GPU box under a time limit of its own:
+--correlate cross-correlates the pair on the device (photon_piv_correlate: 32 px windows, 16 px grid, R 16; one and two
+passes), prints the correlation's ms per pass and the median / 95th percentile over windows of |measured - truth| (truth:
+the mean image displacement of the particles whose frame-1 centroid lies in the window, counting those the laser sheet lights
+to >= 10 % of its peak, windows with >= 5 of them), and
+times 1024^2 pairs at win 32 / step 16 / R 16 and win 64 / step 32 / R 32 (multiply-adds per second, share of the f32
+FMA peak).  Run it on a GPU box under a time limit of its own:
 
-    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect]
+    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate]
 """
 import argparse
 import json
@@ -23,6 +28,8 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402  (first: one HIP runtime per process)
 from conftest import load_fixture_call  # noqa: E402
+from photon_amd import deflections  # noqa: E402
+from photon_amd import piv_correlation as pc  # noqa: E402
 from photon_amd import piv_pairs as pp  # noqa: E402
 from photon_amd.library import PhotonLibrary  # noqa: E402
 from photon_amd.ray_tracing import postprocess_image, write_tiff_u16  # noqa: E402
@@ -30,6 +37,61 @@ from photon_amd.ray_tracing import postprocess_image, write_tiff_u16  # noqa: E4
 # the sample frame's particle field (run_simulation_02.py:949-965 with the sample parameters): 1.5 x the field of view
 BOX_MIN, BOX_MAX = (-7.5e4, -7.5e4, -7.5e3), (7.5e4, 7.5e4, 7.5e3)
 BEAM_FWHM, IRRADIANCE = 730.0, 500.0
+FMA_PEAK = 157.3e12 / 2             # MI355X f32 vector peak, FMA per second
+
+
+def correlate_ms(lib, a, b, win, step, radius, offset=None, reps=20):
+    """Device time of one photon_piv_correlate call (events around `reps` back-to-back calls, after a warm-up)."""
+    h, w = a.shape
+    optr = offset.data_ptr() if offset is not None else 0
+    lib.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, optr)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        lib.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, optr)
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def correlate_pair(lib, images, records, cam, rays, lit, row):
+    """--correlate on the sample pair, then the 1024^2 timings; adds its figures to `row`.  lit: the particles the truth
+    counts (those inside the light sheet: the others image too faintly to take part in the correlation)."""
+    win, step, radius = 32, 16, 16
+    a, b = (torch.from_numpy(np.ascontiguousarray(im, np.float32)).cuda() for im in images)
+    m1 = deflections.dot_means(records[0], rays, 1, "arrived")
+    pos = pc.image_positions(deflections.to_pixels(m1["pos"], cam), cam)[lit]
+    d = pp.image_displacements(records[0], records[1], cam, rays)[lit]
+    truth, count = pc.window_truth(pos, d, images[0].shape, win, step, min_count=5)
+    ms1 = correlate_ms(lib, a, b, win, step, radius)
+    vec1, flags1 = lib.correlate(a, b, win, step, radius, passes=1)
+    offsets = torch.from_numpy(pc.predictor(vec1, flags1, pc.normalized_median_test(vec1))).cuda()
+    ms2 = correlate_ms(lib, a, b, win, step, radius, offsets)
+    vec2, flags2 = lib.correlate(a, b, win, step, radius, passes=2)
+    use = np.isfinite(truth).all(axis=-1)
+    for k, (vec, flags, ms) in enumerate(((vec1, flags1, ms1), (vec2, flags2, ms2)), 1):
+        ok = use & ((flags & pc.FLAG_FLAT) == 0)
+        err = np.hypot(*(pc.sensor_displacements(vec, cam)[ok] - truth[ok]).T)
+        print(f"correlation pass {k}: {ms:.3f} ms ({vec.shape[0]} x {vec.shape[1]} windows of {win} px, step {step}, R {radius}); "
+              f"|measured - truth| over {int(ok.sum())} windows with >= 5 particles: median {np.median(err):.4f} px, "
+              f"95th percentile {np.percentile(err, 95):.4f} px")
+        row[f"correlate_pass{k}_ms"] = round(ms, 4)
+        row[f"correlate_pass{k}_median_err_px"] = float(np.median(err))
+        row[f"correlate_pass{k}_p95_err_px"] = float(np.percentile(err, 95))
+    row["correlate_windows_with_truth"] = int(use.sum())
+    rng = np.random.default_rng(1)
+    n = 20_000
+    x, y = rng.uniform(-8, 1032, n), rng.uniform(-8, 1032, n)
+    big = [torch.from_numpy(pc.particle_image((1024, 1024), x + dx, y + dy).astype(np.float32)).cuda() for dx, dy in ((0, 0), (3.3, -2.6))]
+    for win, step, radius in ((32, 16, 16), (64, 32, 32)):
+        ms = correlate_ms(lib, big[0], big[1], win, step, radius)
+        n_rows, n_cols = pc.grid_shape((1024, 1024), win, step)
+        fma = n_rows * n_cols * (2 * radius + 1) ** 2 * win * win
+        rate = fma / (ms * 1e-3)
+        print(f"1024^2 pair, win {win} step {step} R {radius}: {ms:.3f} ms, {fma / 1e9:.2f} G multiply-adds, "
+              f"{rate / 1e12:.2f} T FMA/s = {100 * rate / FMA_PEAK:.1f} % of the f32 FMA peak")
+        row[f"correlate_1024_w{win}_ms"] = round(ms, 4)
+        row[f"correlate_1024_w{win}_fma_peak_frac"] = round(rate / FMA_PEAK, 4)
 
 
 def timed(fn, reps=3):
@@ -50,6 +112,7 @@ def main():
     ap.add_argument("--steps", type=int, default=16)
     ap.add_argument("--tiff", default=None)
     ap.add_argument("--bench-advect", action="store_true")
+    ap.add_argument("--correlate", action="store_true")
     args = ap.parse_args()
     lib = PhotonLibrary()
     lib.set_device(0)
@@ -129,6 +192,10 @@ def main():
         _, row["advect_1e6_16steps_128cubed_ms"] = timed(bench, 5)
         bflow.free()
         print(f"advection of 1e6 particles, 16 steps, 128^3 field: {row['advect_1e6_16steps_128cubed_ms']:.3f} ms")
+    if args.correlate:
+        sigma = BEAM_FWHM / (2.0 * math.sqrt(2.0 * math.log(2.0)))
+        lit = np.exp(-w1[:, 2] ** 2 / (2.0 * sigma * sigma)) >= 0.1       # within 2.15 sigma of the sheet's centre plane
+        correlate_pair(lib, images, records, cam, rays, lit, row)
     print(json.dumps(row), flush=True)
     if not math.isfinite(row["p99_err_px"]):
         sys.exit(1)
