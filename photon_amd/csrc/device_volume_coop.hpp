@@ -30,15 +30,78 @@
 
 namespace photon {
 
-// Debug build only (-DPHOTON_PATH_STATS=1, tools/path_stats.py): how often a wave's sample takes which sampler path.
+// SAMPLER-PATH COUNTERS.  Debug build only (-DPHOTON_PATH_STATS=1; photon_debug_path_stats, photon_amd/path_stats.py,
+// tools/path_stats.py, tests/test_sampler_paths_gpu.py): one slot per branch that changes which texels a lane blends or
+// which code computes its value.  C_ = tricubic sampler (photon_march_cubic.hip), L_ = trilinear (photon_march_linear.hip).
+// "wave": counted once per wave event, by the wave's first active lane; "lanes": the lanes of a ballot taken where control
+// flow is wave-uniform.  The default build compiles every path_stat() away: its device code does not depend on this list.
+// The Python mirror (photon_amd/path_stats.py) is checked against this enum by the suite: keep one name per line.
+enum PathSlot : int {
+    PS_C_COHERENT,              // wave: a sample served from the parked tile (the four rows below add up to it)
+    PS_C_HIT_CELL,              // wave:   every sampling lane in the parked cell: no leader, no fetch
+    PS_C_CELL_IN_TILE,          // wave:   one cell, another one of the parked tile: no fetch
+    PS_C_FETCH_UP,              // wave:   a tile fetched from the wave's cell upwards (k0 = ck)
+    PS_C_FETCH_DOWN,            // wave:   a tile fetched downwards (k0 = ck - (TL - 4))
+    PS_C_TILE_CLAMPED,          // wave: a tile fetch with a texel clamped at a volume face
+    PS_C_INCOHERENT,            // wave: a sample that goes to the bricks
+    PS_C_INCOHERENT_LANES,      // lanes: its sampling lanes
+    PS_C_BRICK_PASS,            // wave: a brick pass
+    PS_C_BRICK_FETCH,           // wave:   the pass fetches its brick
+    PS_C_BRICK_REUSED,          // wave:   the pass finds its brick parked
+    PS_C_BRICK_CLAMPED,         // wave: a brick fetch with a texel clamped at a volume face
+    PS_C_BRICK_LANES,           // lanes: served from a brick
+    PS_C_GATHER_LANES,          // lanes: left after PHOTON_BRICK_PASSES passes, per-lane cubic_gather_fn
+    PS_C_SPIN_OUTSIDE,          // lanes (march): first lookup not accessible, the reference's `continue` (RK4 only)
+    PS_C_SPIN_LOW,              // lanes (march): blend below the volume's minimum, `continue`
+    PS_C_SPIN_CAP,              // lanes (march): dropped at kSpinMax spins
+    PS_L_COHERENT,              // wave: a sample served from the parked tiles (A, or A and B)
+    PS_L_HIT_A,                 // wave:   every sampling lane in tile A, parked before
+    PS_L_HIT_B,                 // wave:   lanes in tiles A and B, parked before, only B's second test serves them
+    PS_L_TILE_B_LANES,          // lanes: served by a coherent sample from tile B
+    PS_L_FETCH,                 // wave: a tile fetch
+    PS_L_FETCH_TWO,             // wave:   a sample that fetches two new tiles
+    PS_L_FETCH_TO_B,            // wave:   a tile fetched into B
+    PS_L_FETCH_DOWN,            // wave:   the wave travels down: base TL - 2 below the leader
+    PS_L_BASE_AHEAD,            // wave:   ... and lanes of the column sit above the leader: base TL - 3 below it
+    PS_L_BASE_BEHIND,           // wave:   upwards, lanes of the column sit below the leader: base one below it
+    PS_L_TILE_CLAMPED,          // wave: a tile fetch with a texel clamped at a volume face
+    PS_L_NO_FREE_TILE,          // wave: more new columns than tiles that serve nobody: to the bricks
+    PS_L_OUT_OF_REACH,          // wave: every column parked, some lane's layer out of reach: to the bricks
+    PS_L_MARK_INCOHERENT,       // wave: a coherent wave goes to the bricks and marks itself incoherent
+    PS_L_TILES_SKIPPED,         // wave: an incoherent wave goes straight to the bricks (tick & PHOTON_TILE_RETRY_MASK != 0)
+    PS_L_RETRY,                 // wave: an incoherent wave tries its tiles again
+    PS_L_COHERENT_AGAIN,        // wave:   ... and they serve it: coherent again
+    PS_L_INCOHERENT,            // wave: a sample that goes to the bricks
+    PS_L_INCOHERENT_LANES,      // lanes: its sampling lanes
+    PS_L_BRICK_PASS,            // wave: a brick pass
+    PS_L_BRICK_FETCH,           // wave:   the pass fetches its brick
+    PS_L_BRICK_REUSED,          // wave:   the pass finds its brick parked
+    PS_L_BRICK_CLAMPED,         // wave: a brick fetch with a texel clamped at a volume face
+    PS_L_BRICK_LANES,           // lanes: served from a brick
+    PS_L_GATHER_LANES,          // lanes: left after PHOTON_BRICK_PASSES passes, per-lane linear_gather_fn
+    PS_L_SPIN_OUTSIDE,          // lanes (march): first lookup not accessible, the reference's `continue`
+    PS_L_SPIN_CAP,              // lanes (march): dropped at kSpinMax spins
+    PS_L_LOW,                   // wave (march): a blend below the volume's minimum
+    PS_L_REPAIR_LANES,          //   lanes: ... resampled one layer down through linear_gather_fn (val_prev == 0)
+    PS_L_KEEP_PREV_LANES,       //   lanes: ... that keep val_prev
+    PS_COUNT
+};
+constexpr int kPathSlots = PS_COUNT;
 #ifndef PHOTON_PATH_STATS
 #define PHOTON_PATH_STATS 0
 #endif
 #if PHOTON_PATH_STATS
-__device__ unsigned long long g_path_stats[8];      // 0 coherent samples, 1 tile fetches, 2 incoherent samples, 3 brick passes, 4 brick fetches, 5 gathered lanes, 6 lanes served per pass (sum)
-__device__ __forceinline__ void path_stat(int k, unsigned long long n = 1) { if ((threadIdx.x & 63) == 0) atomicAdd(&g_path_stats[k], n); }
-#else
-__device__ __forceinline__ void path_stat(int, unsigned long long = 1) {}
+__device__ unsigned long long g_path_stats[kPathSlots];
+// a wave event (call where control flow is wave-uniform): the first active lane counts it
+__device__ __forceinline__ void path_stat(PathSlot k, unsigned long long n = 1) {
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)ballot(true)) - 1) atomicAdd(&g_path_stats[k], n);
+}
+__device__ __forceinline__ void path_stat_if(PathSlot k, bool c) { if (c) path_stat(k); }   // c wave-uniform
+__device__ __forceinline__ void path_lanes(PathSlot k, unsigned long long mask) { if (mask != 0) path_stat(k, (unsigned long long)__popcll(mask)); }
+#else                                                           // arguments not even evaluated: the default build's code is as if they were not there
+#define path_stat(...) ((void)0)
+#define path_stat_if(...) ((void)0)
+#define path_lanes(...) ((void)0)
 #endif
 
 #ifndef PHOTON_BRICK_PASSES
@@ -410,6 +473,7 @@ __device__ __forceinline__ f4 tex3d_cubic_coop(const VolumeDev &v, const f4 *__r
         if (parked.ti != 0x7fffffff) {                          // wave-uniform
             asm volatile("");
             hit = ((ballot(__float_as_int(fi) == parked.ti) & ballot(__float_as_int(fj) == parked.tj) & ballot(__float_as_int(fk) == parked.tk)) & need) == need;
+            path_stat_if(PS_C_HIT_CELL, hit);
         }
         if (!hit) {
             const Lead c = lead_of(need, fi, fj, fk);
@@ -417,11 +481,12 @@ __device__ __forceinline__ f4 tex3d_cubic_coop(const VolumeDev &v, const f4 *__r
                 const int ck = (int)__int_as_float(c.k);
                 int dz = ck - parked.k0;
                 if (c.i != parked.ci || c.j != parked.cj || (unsigned)dz > (unsigned)(TL - 4)) {      // not in the parked tile
-                    path_stat(1);
                     const int ci = (int)__int_as_float(c.i), cj = (int)__int_as_float(c.j);
                     // the tile starts at the wave's cell when it travels upwards (or nothing tells), ends there when downwards
                     const bool down = c.i == parked.ci && c.j == parked.cj && dz < 0;
                     const int k0 = down ? ck - (TL - 4) : ck;
+                    path_stat(down ? PS_C_FETCH_DOWN : PS_C_FETCH_UP);
+                    path_stat_if(PS_C_TILE_CLAMPED, ci < 1 || ci + 2 > v.nx - 1 || cj < 1 || cj + 2 > v.ny - 1 || k0 < 1 || k0 + TL - 2 > v.nz - 1);
                     __builtin_amdgcn_wave_barrier();
                     int l = lane;
                     asm volatile("" : "+v"(l));                 // keep the tile's lane offsets out of the march loop's live registers
@@ -437,6 +502,8 @@ __device__ __forceinline__ f4 tex3d_cubic_coop(const VolumeDev &v, const f4 *__r
                     __builtin_amdgcn_wave_barrier();
                     parked.ci = c.i; parked.cj = c.j; parked.k0 = k0;
                     dz = ck - k0;
+                } else {
+                    path_stat(PS_C_CELL_IN_TILE);
                 }
                 parked.coff = dz * 16;
                 parked.reg = ldtexel(blk + parked.coff + (lane & 15));   // slab 0 of the cell, into every 16-lane row
@@ -447,7 +514,7 @@ __device__ __forceinline__ f4 tex3d_cubic_coop(const VolumeDev &v, const f4 *__r
             }
         }
         if (hit) {
-            path_stat(0);
+            path_stat(PS_C_COHERENT);
             const f4 *cell = blk + parked.coff;
             const f4 acc = cubic_taps_hybrid(cell, parked.reg, parked.more, wx, wy, wz);
             __builtin_amdgcn_wave_barrier();
@@ -464,7 +531,8 @@ __device__ __forceinline__ f4 tex3d_cubic_coop(const VolumeDev &v, const f4 *__r
     f4 acc = f4{0, 0, 0, 0};
     bool done = !lane_of(need);
     unsigned long long todo = need;
-    path_stat(2);
+    path_stat(PS_C_INCOHERENT);
+    path_lanes(PS_C_INCOHERENT_LANES, need);
 #pragma unroll 1
     for (int pass = 0; pass < PHOTON_BRICK_PASSES && todo != 0; pass++) {
         const int leader = __ffsll((long long)todo) - 1;
@@ -472,10 +540,11 @@ __device__ __forceinline__ f4 tex3d_cubic_coop(const VolumeDev &v, const f4 *__r
                   ck = __builtin_amdgcn_readlane(bk, leader);
         const int di = bi - ci + 2, dj = bj - cj + 2;
         const bool in_brick = !done && bk == ck && (unsigned)di <= 4u && (unsigned)dj <= 4u;
-        path_stat(3);
-        path_stat(6, (unsigned long long)__popcll(ballot(in_brick)));
+        path_stat(PS_C_BRICK_PASS);
+        path_lanes(PS_C_BRICK_LANES, ballot(in_brick));
+        path_stat(ci != parked.bi || cj != parked.bj || ck != parked.bk ? PS_C_BRICK_FETCH : PS_C_BRICK_REUSED);
         if (ci != parked.bi || cj != parked.bj || ck != parked.bk) {        // wave-uniform: the brick is not parked yet
-            path_stat(4);
+            path_stat_if(PS_C_BRICK_CLAMPED, ci < 3 || ci + 4 > v.nx - 1 || cj < 3 || cj + 4 > v.ny - 1 || ck < 1 || ck + 2 > v.nz - 1);
             __builtin_amdgcn_wave_barrier();
             int l = lane;
             asm volatile("" : "+v"(l));                         // keep the brick's lane offsets out of the march loop's live registers
@@ -504,7 +573,7 @@ __device__ __forceinline__ f4 tex3d_cubic_coop(const VolumeDev &v, const f4 *__r
         __builtin_amdgcn_wave_barrier();
         todo = ballot(!done);
     }
-    path_stat(5, (unsigned long long)__popcll(ballot(!done)));
+    path_lanes(PS_C_GATHER_LANES, ballot(!done));
     if (!done) acc = cubic_gather_fn(tex, v.nx, v.ny, v.nz, x, y, z);                       // stragglers
     return acc;
 }
@@ -610,15 +679,19 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
             dzq = (unsigned)(int)(fk - __int_as_float(parked.tk));
             ok_a = ballot(fib == parked.ti) & ballot(fjb == parked.tj) & ballot(dzq <= kDzMax);
             hit = (ok_a & need) == need;
+            path_stat_if(PS_L_HIT_A, hit);
             if (NT == 2 && !hit && parked.ui < kIncoherent) {   // wave-uniform
                 const unsigned dzu = (unsigned)(int)(fk - __int_as_float(parked.uk));
                 ok_b = ballot(fib == parked.ui) & ballot(fjb == parked.uj) & ballot(dzu <= kDzMax);
                 if (((ok_a | ok_b) & need) == need) {
                     hit = true;
+                    path_stat(PS_L_HIT_B);
                     dzq = lane_of(ok_a) ? dzq : dzu + TL;
                 }
             }
         }
+        path_stat_if(PS_L_TILES_SKIPPED, !hit && parked.ui == kIncoherent && (tick & (unsigned)PHOTON_TILE_RETRY_MASK) != 0);
+        path_stat_if(PS_L_RETRY, !hit && parked.ui == kIncoherent && (tick & (unsigned)PHOTON_TILE_RETRY_MASK) == 0);
         if (!hit && (parked.ui != kIncoherent || (tick & (unsigned)PHOTON_TILE_RETRY_MASK) == 0)) {      // wave-uniform: some sampling lanes have no tile
             // the columns of the lanes without a tile: at most as many as there are tiles that serve nobody
             const unsigned long long rest = need & ~(ok_a | ok_b);
@@ -633,10 +706,12 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
                 n_new = (rest2 & ~col2) != 0 ? 3 : 2;
             }
             const bool free_a = (ok_a & need) == 0, free_b = NT == 2 && (ok_b & need) == 0;
+            path_stat_if(PS_L_NO_FREE_TILE, n_new > (free_a ? 1 : 0) + (free_b ? 1 : 0));
             if (n_new <= (free_a ? 1 : 0) + (free_b ? 1 : 0)) {
+                path_stat_if(PS_L_FETCH_TWO, n_new == 2);
 #pragma unroll 1
                 for (int j = 0; j < n_new; j++) {
-                    path_stat(1);
+                    path_stat(PS_L_FETCH);
                     const bool to_a = j == 0 && free_a;         // the second new tile always goes to B
                     const Lead ld = j == 0 ? l1 : l2;
                     const unsigned long long lanes = j == 0 ? col1 : col2;
@@ -650,6 +725,11 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
                     const int ci = (int)__int_as_float(ld.i), cj = (int)__int_as_float(ld.j);
                     const int base = (int)klf - (down ? (ahead ? TL - 3 : TL - 2) : (behind ? 1 : 0));
                     f4 *const tile = blk + (to_a ? 0 : 4 * TL);
+                    path_stat_if(PS_L_FETCH_TO_B, !to_a);
+                    path_stat_if(PS_L_FETCH_DOWN, down);
+                    path_stat_if(PS_L_BASE_AHEAD, down && ahead);
+                    path_stat_if(PS_L_BASE_BEHIND, !down && behind);
+                    path_stat_if(PS_L_TILE_CLAMPED, ci < 0 || ci + 1 > v.nx - 1 || cj < 0 || cj + 1 > v.ny - 1 || base < 0 || base + TL - 1 > v.nz - 1);
                     __builtin_amdgcn_wave_barrier();
                     if (lane < 4 * TL) {
                         int l = lane;
@@ -678,11 +758,14 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
                     dzq = lane_of(ok_a) ? dzq : dzu + TL;
                 }
                 hit = ((ok_a | ok_b) & need) == need;
+                path_stat_if(PS_L_OUT_OF_REACH, !hit);
+                path_stat_if(PS_L_COHERENT_AGAIN, hit && parked.ui == kIncoherent);
                 if (hit && parked.ui == kIncoherent) parked.ui = 0x7fffffff;     // coherent again
             }
         }
         if (hit) {
-            path_stat(0);
+            path_stat(PS_L_COHERENT);
+            path_lanes(PS_L_TILE_B_LANES, need & ~ok_a);
             // q[tc*4 + tb*2 + {0: texel, 1: x-difference}], q = the lane's cell in its tile; same lerp tree as tex3d_linear
             const f4 *q = blk + ((dzq & (unsigned)(NT * TL - 1)) << 2);         // (the mask: lanes that do not sample stay inside the wave's LDS area)
 #if PHOTON_PRIO_BLEND != PHOTON_PRIO_BASE
@@ -698,6 +781,7 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
             __builtin_amdgcn_wave_barrier();
             return acc;
         }
+        path_stat_if(PS_L_MARK_INCOHERENT, parked.ui != kIncoherent);
         parked.ti = 0x7fffffff;                                 // to the bricks: the tiles are forgotten
         parked.ui = kIncoherent;
     }
@@ -707,7 +791,8 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
     f4 acc = f4{0, 0, 0, 0};
     bool done = !lane_of(need);
     unsigned long long todo = need;
-    path_stat(2);
+    path_stat(PS_L_INCOHERENT);
+    path_lanes(PS_L_INCOHERENT_LANES, need);
 #pragma unroll 1
     for (int pass = 0; pass < PHOTON_BRICK_PASSES && todo != 0; pass++) {
         const int leader = __ffsll((long long)todo) - 1;
@@ -715,10 +800,11 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
                   ck = __builtin_amdgcn_readlane(bk, leader);
         const int di = bi - ci + 3, dj = bj - cj + 3;
         const bool in_brick = !done && bk == ck && (unsigned)di <= 6u && (unsigned)dj <= 6u;
-        path_stat(3);
-        path_stat(6, (unsigned long long)__popcll(ballot(in_brick)));
+        path_stat(PS_L_BRICK_PASS);
+        path_lanes(PS_L_BRICK_LANES, ballot(in_brick));
+        path_stat(ci != parked.bi || cj != parked.bj || ck != parked.bk ? PS_L_BRICK_FETCH : PS_L_BRICK_REUSED);
         if (ci != parked.bi || cj != parked.bj || ck != parked.bk) {        // wave-uniform: the brick is not parked yet
-            path_stat(4);
+            path_stat_if(PS_L_BRICK_CLAMPED, ci < 3 || ci + 4 > v.nx - 1 || cj < 3 || cj + 4 > v.ny - 1 || ck < 0 || ck + 1 > v.nz - 1);
             __builtin_amdgcn_wave_barrier();
             int l = lane;
             asm volatile("" : "+v"(l));
@@ -752,7 +838,7 @@ __device__ __forceinline__ f4 tex3d_linear_coop(const VolumeDev &v, const f4 *__
         __builtin_amdgcn_wave_barrier();
         todo = ballot(!done);
     }
-    path_stat(5, (unsigned long long)__popcll(ballot(!done)));
+    path_lanes(PS_L_GATHER_LANES, ballot(!done));
     if (!done) acc = linear_gather_fn(tex, v.nx, v.ny, v.nz, x, y, z, v.weight_scale, v.weight_inv);
     return acc;
 }
@@ -832,6 +918,9 @@ __device__ __forceinline__ f4 sample_coop(const VolumeDev &v, const f4 *__restri
             const float ambient = 1.000277;
             const f4 val_prev = prev.get();                     // the lane's last sampled value
             const unsigned long long repair = low & ballot(val_prev.w == 0);
+            path_stat(PS_L_LOW);
+            path_lanes(PS_L_REPAIR_LANES, repair);
+            path_lanes(PS_L_KEEP_PREV_LANES, low & ~repair);
             if (repair != 0) {                                  // per lane, out of line: the same blend (the cooperative sampler's
                 count_samples(mc, repair);                      // own fallback), not a fourth copy of that sampler in the loop
                 if (lane_of(repair)) {
@@ -909,10 +998,12 @@ __device__ __forceinline__ unsigned long long rk4_coop(bool active_lane, f3 &rpo
             const unsigned long long access = access_mask(u, lookup);
             go = alive & access;
             spin = alive & ~access;                             // the reference's `continue`: step forward, retry next trip
+            path_lanes(INTERP == 1 ? PS_L_SPIN_OUTSIDE : PS_C_SPIN_OUTSIDE, spin);
         }
         f4 val = sample_coop<INTERP, QUANT, CNT, true>(v, tex, blk, go, lookup, prev, u.data_min, mc, parked, trips);
         if (INTERP == 2) {                                      // .h:1220-1227
             const unsigned long long low = go & ballot(val.w < u.data_min);
+            path_lanes(PS_C_SPIN_LOW, low);
             spin |= low;
             go &= ~low;
         }
@@ -923,6 +1014,7 @@ __device__ __forceinline__ unsigned long long rk4_coop(bool active_lane, f3 &rpo
                 rpos = rpos + u.spin_step * rdir;
                 if (kSpinLds) { spins = *spin_slot + 1; *spin_slot = spins; } else spins++;
             }
+            path_lanes(INTERP == 1 ? PS_L_SPIN_CAP : PS_C_SPIN_CAP, spin & ballot(spins > kSpinMax));
             active &= ~(spin & ballot(spins > kSpinMax));
         }
         if (kSpinLds) { if (lane_of(go)) atomicAdd(ctr_slot, 1); } else loop_ctr += lane_of(go) ? 1 : 0;
@@ -996,10 +1088,12 @@ __device__ __forceinline__ unsigned long long euler_coop(bool active_lane, f3 &r
             const unsigned long long access = access_mask(u, lookup);
             go = alive & access;
             spin = alive & ~access;
+            path_lanes(PS_L_SPIN_OUTSIDE, spin);
         }
         f4 val = sample_coop<INTERP, QUANT, CNT>(v, tex, blk, go, lookup, prev, u.data_min, mc, parked, trips);
         if (INTERP == 2) {                                      // .h:916-923
             const unsigned long long low = go & ballot(val.w < u.data_min);
+            path_lanes(PS_C_SPIN_LOW, low);
             spin |= low;
             go &= ~low;
         }
@@ -1010,6 +1104,7 @@ __device__ __forceinline__ unsigned long long euler_coop(bool active_lane, f3 &r
                 rpos = rpos + u.spin_step * rdir;
                 spins++;
             }
+            path_lanes(INTERP == 1 ? PS_L_SPIN_CAP : PS_C_SPIN_CAP, spin & ballot(spins > kSpinMax));
             active &= ~(spin & ballot(spins > kSpinMax));
         }
         if (INTERP == 1) {

@@ -11,13 +11,23 @@
 using namespace photon;
 
 #if PHOTON_PATH_STATS
-namespace photon { int march_path_stats_linear(unsigned long long out[8]); int march_path_stats_cubic(unsigned long long out[8]); }
-// debug builds only: read (and clear) the sampler-path counters of device_volume_coop.hpp, summed over the march units
-extern "C" int photon_debug_path_stats(unsigned long long out[8]) {
-    unsigned long long a[8] = {}, b[8] = {};
-    if (int rc = march_path_stats_linear(a)) return rc;
-    if (int rc = march_path_stats_cubic(b)) return rc;
-    for (int k = 0; k < 8; k++) out[k] = a[k] + b[k];
+namespace photon {
+int march_path_slots();
+int march_path_stats_linear(unsigned long long *out);
+int march_path_stats_cubic(unsigned long long *out);
+}
+// debug builds only: read (and clear) the sampler-path counters of device_volume_coop.hpp (enum PathSlot), summed over the
+// two march units; n_slots must be the enum's size (photon_amd/path_stats.py mirrors it)
+extern "C" int photon_debug_path_stats(unsigned long long *out, int n_slots) {
+    const int n = march_path_slots();
+    if (!out || n_slots != n) {
+        fprintf(stderr, "photon: photon_debug_path_stats: the library counts %d slots, the caller asked for %d\n", n, n_slots);
+        return 1;
+    }
+    std::vector<unsigned long long> a(n), b(n);
+    if (int rc = march_path_stats_linear(a.data())) return rc;
+    if (int rc = march_path_stats_cubic(b.data())) return rc;
+    for (int k = 0; k < n; k++) out[k] = a[k] + b[k];
     return 0;
 }
 #endif

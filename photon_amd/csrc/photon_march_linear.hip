@@ -29,10 +29,10 @@ int march_rays_launch_linear(int algorithm, const VolumeDev &vol, const f4 *tex,
 }
 
 #if PHOTON_PATH_STATS
-int march_path_stats_linear(unsigned long long out[8]) {   // debug builds only: read (and clear) this unit's sampler-path counters
+int march_path_stats_linear(unsigned long long *out) {    // debug builds only: read (and clear) this unit's sampler-path counters
     PH_CHECK(hipDeviceSynchronize());
-    PH_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(photon::g_path_stats), 8 * sizeof(unsigned long long)));
-    unsigned long long zero[8] = {};
+    PH_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(photon::g_path_stats), kPathSlots * sizeof(unsigned long long)));
+    unsigned long long zero[kPathSlots] = {};
     PH_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(photon::g_path_stats), zero, sizeof zero));
     return 0;
 }

@@ -1,7 +1,7 @@
 """Which sampler path the waves of a launch take (debug build of the library with -DPHOTON_PATH_STATS=1,
-build/variants/lib_pathstats.so): coherent tile / brick passes / per-lane gather, per wave-sample.
+build/variants/lib_pathstats.so): every slot of enum PathSlot (device_volume_coop.hpp) by name, and the summary ratios.
+    python tools/build_variant.py pathstats -DPHOTON_PATH_STATS=1
     PHOTON_LIBRARY=build/variants/lib_pathstats.so python tools/path_stats.py [c5 scale | c3] [--linear]"""
-import ctypes
 import json
 import os
 import sys
@@ -9,7 +9,7 @@ import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
-from photon_amd import scenes  # noqa: E402
+from photon_amd import path_stats, scenes  # noqa: E402
 from photon_amd.library import PhotonLibrary  # noqa: E402
 
 interp = 1 if "--linear" in sys.argv else 2
@@ -25,13 +25,18 @@ vol = lib.volume_load_nrrd(call.density_grad_filename, interp)
 H, W = call.image_shape
 img = torch.zeros(H * W, dtype=torch.float32, device="cuda")
 scene.trace(img.data_ptr(), vol, 2)
-out = (ctypes.c_ulonglong * 8)()
-lib.lib.photon_debug_path_stats(out)                      # clear after the warm-up
+path_stats.read(lib)                                     # clear after the warm-up
 st = scene.trace(img.data_ptr(), vol, 2, want_stats=True)
-lib.lib.photon_debug_path_stats(out)
-v = list(out)
-ws = v[0] + v[2]
+c = path_stats.read(lib)
+p = "L_" if interp == 1 else "C_"
+ws = c[p + "COHERENT"] + c[p + "INCOHERENT"]
+for k, v in c.items():
+    if k.startswith(p):
+        print(f"{k:22s} {v:14d}")
 print(json.dumps({"workload": what, "interp": interp, "rays_marched": st.rays_marched, "march_ms": round(st.march_ms, 2), "wave_samples": ws,
-                  "coherent_frac": round(v[0] / ws, 4), "tile_fetch_per_coherent": round(v[1] / max(v[0], 1), 3),
-                  "brick_passes_per_incoherent": round(v[3] / max(v[2], 1), 3), "brick_fetch_per_pass": round(v[4] / max(v[3], 1), 3),
-                  "lanes_per_pass": round(v[6] / max(v[3], 1), 1), "gathered_lanes_per_incoherent": round(v[5] / max(v[2], 1), 3)}))
+                  "coherent_frac": round(c[p + "COHERENT"] / max(ws, 1), 4),
+                  "tile_fetch_per_coherent": round((c["C_FETCH_UP"] + c["C_FETCH_DOWN"] if interp == 2 else c["L_FETCH"]) / max(c[p + "COHERENT"], 1), 3),
+                  "brick_passes_per_incoherent": round(c[p + "BRICK_PASS"] / max(c[p + "INCOHERENT"], 1), 3),
+                  "brick_fetch_per_pass": round(c[p + "BRICK_FETCH"] / max(c[p + "BRICK_PASS"], 1), 3),
+                  "lanes_per_pass": round(c[p + "BRICK_LANES"] / max(c[p + "BRICK_PASS"], 1), 1),
+                  "gathered_lanes_per_incoherent": round(c[p + "GATHER_LANES"] / max(c[p + "INCOHERENT"], 1), 3)}))
