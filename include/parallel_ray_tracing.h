@@ -646,6 +646,42 @@ int photon_piv_correlate(const float *d_im1, const float *d_im2, int width, int 
                          const int *d_offset, float *d_vectors, int *d_flags, float *d_planes, int *n_rows, int *n_cols,
                          void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 6: weighted least-squares integration of a gradient field on the device (BOS: displacements -> projected
+ * density).  Host model: photon_amd/bos_density.py (integrate_model, f64, the same iteration).
+ *   grid        ny x nx nodes, row-major: node k = i nx + j (row i, column j); hx between columns, hy between rows
+ *   d_gx, d_gy  device f64[ny*nx]: the gradient along +column and +row
+ *   d_w         device f64[ny*nx] weights, or NULL (1)
+ *   d_fixed     device u8[ny*nx] Dirichlet mask (nonzero = fixed), or NULL (the outer frame of the grid is fixed)
+ *   d_value     device f64[ny*nx] the values of the fixed nodes, or NULL (0)
+ * A node is valid when gx, gy and w are finite and w > 0.  Edge (i,j)->(i,j+1): weight w_e = min(w_k, w_k+1) when both
+ * ends are valid and neither is a fixed node with a value that is not finite, else 0; target t_e = hx (gx_k + gx_k+1) / 2.
+ * Edge (i,j)->(i+1,j): the same with hy and gy.  phi minimises E = sum_e w_e (phi_b - phi_a - t_e)^2 with the fixed
+ * nodes held at their values: the normal equations are the weighted graph Laplacian on the unknown nodes, SPD on every
+ * unknown node that reaches a fixed node through edges of positive weight (reachability: a BFS on the host).
+ *   d_phi       device f64[ny*nx] out: fixed nodes their value; reachable unknown nodes the solution; every other node
+ *               (no live edge, or an island without an anchor) NaN
+ * Solver: Jacobi-preconditioned CG from x0 = 0 in f64 (z = r / diag; alpha = 0 when p.q = 0, beta = 0 when the old r.z
+ * is 0).  ||r||_2 (the recursive, unpreconditioned residual; ||b|| over the reachable unknowns) is checked before the
+ * first iteration and then every PHOTON_INTEGRATE_CHECK_EVERY iterations; with tol > 0 the solver stops at the first
+ * check with ||r|| <= tol ||b||, else after exactly max_iter iterations (tol = 0: always max_iter).  ||b|| = 0: 0
+ * iterations, converged.  Every reduction has a fixed order: two calls on the same inputs return the same bits.
+ *   stats       iterations run; converged = final ||r|| <= tol ||b||; residual = final ||r|| / ||b|| (0 when ||b|| = 0);
+ *               unknowns = nodes solved for; unreachable = unknown nodes left NaN.  May be NULL.
+ * Refused (1, one stderr line, nothing written, no launch): nx or ny < 2, nx ny > INT_MAX, hx or hy not finite or not
+ * > 0, tol < 0 or NaN, max_iter < 0, a null d_gx, d_gy or d_phi.  Runs on `stream` and synchronises it before it
+ * returns. */
+#define PHOTON_INTEGRATE_CHECK_EVERY 8
+
+typedef struct photon_integrate_stats_t {
+    int iterations, converged, unknowns, unreachable;
+    double residual;
+} photon_integrate_stats_t;
+
+int photon_integrate_gradient(const double *d_gx, const double *d_gy, const double *d_w, const unsigned char *d_fixed,
+                              const double *d_value, int nx, int ny, double hx, double hy, double tol, int max_iter,
+                              double *d_phi, photon_integrate_stats_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,311 @@
+"""Projected density from a BOS displacement field: weighted least-squares integration of a gradient field (pure numpy:
+usable without a GPU).
+
+The device form is photon_integrate_gradient (include/parallel_ray_tracing.h, section 6; ``PhotonLibrary.integrate_gradient``
+on arrays, ``PhotonLibrary.integrate_gradient_ptr`` on raw device pointers).  This module holds
+
+* ``integrate_model``: its f64 host model -- the definition of section 6 and the same Jacobi-PCG iteration, check cadence,
+  NaN and anchor rules;
+* ``solve_direct``: a dense least-squares minimiser of the same energy for small grids, built from the edge list and not
+  from the normal equations: an independent reference;
+* ``weights_from_correlation``: 0 for median-test outliers, flat windows and vectors that are not finite, 1 otherwise;
+* the physics that turns a displacement field into the gradient of the projected density, and its truth:
+  ``displacement_factor``, ``node_geometry``, ``gradients_from_displacements``, ``chief_ray_projection``;
+* ``reconstruct``: correlate an image pair on the device, weigh, convert, integrate.
+
+Physics (the paraxial BOS relation photon states as epsilon = Delta pitch / (M Z_D), d(rho)/dx = epsilon n_0 / (K dz)).
+With P = int (rho - rho_0) ds (kg/m^3 um) along the chief ray and the gradient taken along world x, y in the volume's
+mid-plane, the dot shift in the axes of ``deflections.to_pixels`` is  d = F grad P,  F = (M Z_D / pitch) (K / n_0),
+n_0 = K rho_0 + 1, M = image_distance / object_distance, Z_D = object_distance - (origin_z + extent_z / 2): the distance
+from the target to the volume's mid-plane (the z convention of a volume that lies origin_z .. origin_z + extent_z in
+front of the lens).  Rays bend toward higher density; the dot seen through the volume moves along +F grad P on the
+sensor, which the lens has inverted.
+
+Grid geometry.  Node (i, j) is correlation window (i, j) at its centre (row, column index coordinates).  Its to_pixels
+position (x - 1, y - 1 for the 4-pixel splat; N - 2 - x, y for the erf splat: piv_correlation.image_positions inverted)
+gives the sensor point, the lens inverts it onto the target plane, X_t = -x_sensor / M, and the chief ray from X_t to the
+lens centre crosses the mid-plane at s X_t, s = (origin_z + extent_z / 2) / object_distance.  Node spacing:
+h = s step pitch / M.  Columns run along world -x for the 4-pixel splat and +x for the erf splat; rows along world -y.
+"""
+from __future__ import annotations
+
+import numpy as np
+
+CHECK_EVERY = 8                 # PHOTON_INTEGRATE_CHECK_EVERY: the residual is checked every this many iterations
+K_GLADSTONE_DALE = 0.225e-3     # m^3 / kg (air)
+RHO_0 = 1.225                   # kg / m^3
+
+
+def default_max_iter(nx: int, ny: int) -> int:
+    """The iteration cap when none is given: 20 max(nx, ny) (Jacobi-PCG needs about 3 n on a smooth field)."""
+    return 20 * max(int(nx), int(ny))
+
+
+def check_arguments(nx, ny, hx, hy, tol, max_iter):
+    """The arguments photon_integrate_gradient refuses, as a ValueError (null pointers aside)."""
+    nx, ny = int(nx), int(ny)
+    if nx < 2 or ny < 2:
+        raise ValueError(f"nx and ny must be >= 2, not {nx} x {ny}")
+    if nx * ny > 2 ** 31 - 1:
+        raise ValueError(f"{ny} x {nx} is more than INT_MAX nodes")
+    for name, h in (("hx", hx), ("hy", hy)):
+        if not (np.isfinite(h) and h > 0):
+            raise ValueError(f"{name} must be finite and > 0, not {h}")
+    if not tol >= 0:
+        raise ValueError(f"tol must be >= 0, not {tol}")
+    if int(max_iter) < 0:
+        raise ValueError(f"max_iter must be >= 0, not {max_iter}")
+
+
+def _inputs(gx, gy, w, fixed, value):
+    gx = np.asarray(gx, np.float64)
+    gy = np.asarray(gy, np.float64)
+    if gx.ndim != 2 or gx.shape != gy.shape:
+        raise ValueError("gx and gy must be two 2-d arrays of one shape")
+    ny, nx = gx.shape
+    w = np.ones_like(gx) if w is None else np.asarray(w, np.float64)
+    if fixed is None:
+        fixed = np.zeros((ny, nx), bool)
+        fixed[0, :] = fixed[-1, :] = fixed[:, 0] = fixed[:, -1] = True
+    else:
+        fixed = np.asarray(fixed) != 0
+    value = np.zeros_like(gx) if value is None else np.asarray(value, np.float64)
+    for name, a in (("w", w), ("fixed", fixed), ("value", value)):
+        if a.shape != gx.shape:
+            raise ValueError(f"{name} must have the shape of gx, {gx.shape}")
+    return gx, gy, w, fixed, value
+
+
+def edges(gx, gy, w=None, fixed=None, value=None, hx=1.0, hy=1.0):
+    """The edges of the definition: (wh, th) of (i,j)->(i,j+1), [ny, nx-1]; (wv, tv) of (i,j)->(i+1,j), [ny-1, nx]; and
+    the inputs (fixed mask, values) with the defaults applied."""
+    gx, gy, w, fixed, value = _inputs(gx, gy, w, fixed, value)
+    with np.errstate(invalid="ignore"):
+        valid = np.isfinite(gx) & np.isfinite(gy) & np.isfinite(w) & (w > 0)
+    live = valid & ~(fixed & ~np.isfinite(value))
+    with np.errstate(invalid="ignore"):
+        wh = np.where(live[:, :-1] & live[:, 1:], np.minimum(w[:, :-1], w[:, 1:]), 0.0)
+        wv = np.where(live[:-1, :] & live[1:, :], np.minimum(w[:-1, :], w[1:, :]), 0.0)
+        th = np.where(wh > 0, float(hx) * ((gx[:, :-1] + gx[:, 1:]) * 0.5), 0.0)
+        tv = np.where(wv > 0, float(hy) * ((gy[:-1, :] + gy[1:, :]) * 0.5), 0.0)
+    return wh, th, wv, tv, fixed, value
+
+
+def reachable(wh, wv, fixed):
+    """Unknown nodes that reach a fixed node through edges of positive weight: bool [ny, nx]."""
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components
+    ny, nx = fixed.shape
+    k = np.arange(ny * nx).reshape(ny, nx)
+    a = np.concatenate([k[:, :-1][wh > 0], k[:-1, :][wv > 0]])
+    b = np.concatenate([k[:, 1:][wh > 0], k[1:, :][wv > 0]])
+    g = coo_matrix((np.ones(a.size), (a, b)), shape=(ny * nx, ny * nx))
+    _, label = connected_components(g, directed=False)
+    anchored = np.zeros(label.max() + 1, bool)
+    anchored[label[fixed.ravel()]] = True
+    return (anchored[label] & ~fixed.ravel()).reshape(ny, nx)
+
+
+def _laplacian(wh, wv):
+    """A p on the whole grid (the caller keeps p = 0 off the solved nodes) and the diagonal, in the device's order."""
+    ny, nx = wh.shape[0], wv.shape[1]
+    wW = np.zeros((ny, nx)); wW[:, 1:] = wh
+    wE = np.zeros((ny, nx)); wE[:, :-1] = wh
+    wN = np.zeros((ny, nx)); wN[1:, :] = wv
+    wS = np.zeros((ny, nx)); wS[:-1, :] = wv
+    diag = ((wW + wE) + wN) + wS
+
+    def apply(p):
+        q = diag * p
+        q[:, 1:] -= wh * p[:, :-1]
+        q[:, :-1] -= wh * p[:, 1:]
+        q[1:, :] -= wv * p[:-1, :]
+        q[:-1, :] -= wv * p[1:, :]
+        return q
+    return apply, diag, (wW, wE, wN, wS)
+
+
+def integrate_model(gx, gy, w=None, fixed=None, value=None, hx=1.0, hy=1.0, tol=1e-8, max_iter=None):
+    """Host model of photon_integrate_gradient in f64.  Arrays [ny, nx] (gx along +column, gy along +row); w None = 1,
+    fixed None = the outer frame, value None = 0.  Returns (phi [ny, nx], stats dict: iterations, converged, unknowns,
+    unreachable, residual)."""
+    gx, gy, w, fixed, value = _inputs(gx, gy, w, fixed, value)
+    ny, nx = gx.shape
+    max_iter = default_max_iter(nx, ny) if max_iter is None else int(max_iter)
+    check_arguments(nx, ny, hx, hy, tol, max_iter)
+    wh, th, wv, tv, fixed, value = edges(gx, gy, w, fixed, value, hx, hy)
+    solve = reachable(wh, wv, fixed)
+    apply, diag, (wW, wE, wN, wS) = _laplacian(wh, wv)
+
+    # right-hand side in the device's order: W, E, N, S; a fixed neighbour adds w value
+    vfix = np.where(fixed & np.isfinite(value), value, 0.0)
+    b = np.zeros((ny, nx))
+    b[:, 1:] += wh * th + np.where(fixed[:, :-1], wh * vfix[:, :-1], 0.0)
+    b[:, :-1] += -(wh * th) + np.where(fixed[:, 1:], wh * vfix[:, 1:], 0.0)
+    b[1:, :] += wv * tv + np.where(fixed[:-1, :], wv * vfix[:-1, :], 0.0)
+    b[:-1, :] += -(wv * tv) + np.where(fixed[1:, :], wv * vfix[1:, :], 0.0)
+
+    x = np.zeros((ny, nx))
+    r = np.where(solve, b, 0.0)
+    safe = np.where(solve, diag, 1.0)
+    z = np.where(solve, r / safe, 0.0)
+    p = np.zeros((ny, nx))
+    rz = float(np.dot(r.ravel(), z.ravel()))
+    rr = float(np.dot(r.ravel(), r.ravel()))
+    bnorm = np.sqrt(rr)
+    it, rz_old = 0, 0.0
+    if bnorm > 0:
+        while True:
+            if it % CHECK_EVERY == 0 and tol > 0 and np.sqrt(rr) <= tol * bnorm:
+                break
+            if it == max_iter:
+                break
+            beta = 0.0 if it == 0 or rz_old == 0 else rz / rz_old
+            p = z + beta * p
+            q = np.where(solve, apply(p), 0.0)
+            pq = float(np.dot(p.ravel(), q.ravel()))
+            alpha = rz / pq if pq != 0 else 0.0
+            x = x + alpha * p
+            r = np.where(solve, r - alpha * q, 0.0)
+            z = np.where(solve, r / safe, 0.0)
+            rz_old, rz = rz, float(np.dot(r.ravel(), z.ravel()))
+            rr = float(np.dot(r.ravel(), r.ravel()))
+            it += 1
+    phi = np.where(fixed, value, np.where(solve, x, np.nan))
+    stats = dict(iterations=it, converged=int(bool(bnorm == 0 or np.sqrt(rr) <= tol * bnorm)),
+                 unknowns=int(solve.sum()), unreachable=int((~fixed & ~solve).sum()),
+                 residual=float(np.sqrt(rr) / bnorm) if bnorm > 0 else 0.0)
+    return phi, stats
+
+
+def solve_direct(gx, gy, w=None, fixed=None, value=None, hx=1.0, hy=1.0):
+    """The minimiser of E = sum_e w_e (phi_b - phi_a - t_e)^2 by a dense weighted least-squares solve over the edge list
+    (small grids: a few thousand unknowns at most).  Same output conventions as integrate_model."""
+    wh, th, wv, tv, fixed, value = edges(gx, gy, w, fixed, value, hx, hy)
+    ny, nx = fixed.shape
+    solve = reachable(wh, wv, fixed)
+    k = np.arange(ny * nx).reshape(ny, nx)
+    a = np.concatenate([k[:, :-1].ravel(), k[:-1, :].ravel()])
+    bb = np.concatenate([k[:, 1:].ravel(), k[1:, :].ravel()])
+    we = np.concatenate([wh.ravel(), wv.ravel()])
+    te = np.concatenate([th.ravel(), tv.ravel()])
+    s = solve.ravel()
+    use = (we > 0) & (s[a] | s[bb])
+    a, bb, we, te = a[use], bb[use], we[use], te[use]
+    col = -np.ones(ny * nx, np.int64)
+    col[s] = np.arange(int(s.sum()))
+    D = np.zeros((a.size, int(s.sum())))
+    rhs = te.copy()
+    vals = value.ravel()
+    for sign, node in ((1.0, bb), (-1.0, a)):
+        unk = s[node]
+        D[np.nonzero(unk)[0], col[node[unk]]] += sign
+        rhs[~unk] -= sign * vals[node[~unk]]
+    sq = np.sqrt(we)
+    sol = np.linalg.lstsq(D * sq[:, None], rhs * sq, rcond=None)[0] if D.shape[1] else np.zeros(0)
+    phi = np.where(fixed, value, np.nan).ravel()
+    phi[s] = sol
+    return phi.reshape(ny, nx)
+
+
+def weights_from_correlation(vectors, flags, outliers) -> np.ndarray:
+    """Integration weights from a correlation: 0 for median-test outliers, flat windows and vectors that are not finite,
+    1 otherwise.  vectors [n_rows, n_cols, >= 2], flags [n_rows, n_cols], outliers bool [n_rows, n_cols]."""
+    from .piv_correlation import FLAG_FLAT
+    v = np.asarray(vectors, np.float64)[..., :2]
+    bad = np.asarray(outliers, bool) | ((np.asarray(flags) & FLAG_FLAT) != 0) | ~np.isfinite(v).all(axis=-1)
+    return np.where(bad, 0.0, 1.0)
+
+
+# ---- physics ------------------------------------------------------------------------------------------------------------
+def _magnification(call) -> float:
+    return float(call.image_distance) / float(call.object_distance)
+
+
+def displacement_factor(call, origin_z: float, extent_z: float, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0) -> float:
+    """F of d = F grad P: pixels of dot shift per (kg/m^3 um of P per um), F = (M Z_D / pitch) (K / n_0)."""
+    Z_D = float(call.object_distance) - (float(origin_z) + 0.5 * float(extent_z))
+    n_0 = K * rho_0 + 1.0
+    return _magnification(call) * Z_D / float(call.camera["pixel_pitch"]) * (K / n_0)
+
+
+def axis_signs(camera) -> tuple:
+    """World direction of the grid's column and row axes: (-1, -1) for the 4-pixel splat, (+1, -1) for the erf splat."""
+    from . import deflections
+    return (1.0 if bool(deflections._camera(camera).get("implement_diffraction", False)) else -1.0), -1.0
+
+
+def node_geometry(shape, win: int, step: int, call, origin_z: float, extent_z: float):
+    """The integration grid of a correlation on an image of `shape`: (target-plane points (X_t, Y_t), mid-plane points
+    (X, Y), each [n_rows, n_cols] world microns, spacing h = s step pitch / M)."""
+    from . import piv_correlation as pc
+    cam = call.camera
+    rows, cols = pc.window_centres(shape, win, step)
+    pitch = float(cam["pixel_pitch"])
+    if bool(cam.get("implement_diffraction", False)):
+        x_tp, y_tp = int(cam["x_pixel_number"]) - 2 - cols, rows
+    else:
+        x_tp, y_tp = cols + 1.0, rows + 1.0
+    xs = x_tp * pitch - (int(cam["x_pixel_number"]) / 2 - 1) * pitch
+    ys = y_tp * pitch - (int(cam["y_pixel_number"]) / 2 - 1) * pitch
+    M = _magnification(call)
+    Xt, Yt = -xs / M, -ys / M
+    s = (float(origin_z) + 0.5 * float(extent_z)) / float(call.object_distance)
+    return (Xt, Yt), (s * Xt, s * Yt), s * step * pitch / M
+
+
+def gradients_from_displacements(disp_px, camera, factor: float):
+    """Dot shifts in the to_pixels axes [..., 2] -> (gx, gy): the gradient of P along the grid's columns and rows."""
+    d = np.asarray(disp_px, np.float64)
+    sx, sy = axis_signs(camera)
+    return sx * d[..., 0] / factor, sy * d[..., 1] / factor
+
+
+def chief_ray_projection(rho_fn, target_xy, object_distance: float, z_range, rho_0: float = RHO_0, samples: int = 2000):
+    """The truth: P = int (rho - rho_0) ds along each node's chief ray, from its target-plane point (X_t, Y_t) at distance
+    object_distance toward the lens centre, across z in z_range = (z0, z1) (midpoint rule, `samples` steps).
+    rho_fn(x, y, z) takes and returns arrays (world microns; z measured from the lens).  Returns [...] like X_t."""
+    Xt, Yt = (np.asarray(a, np.float64) for a in target_xy)
+    z0, z1 = (float(v) for v in z_range)
+    L = float(object_distance)
+    dz = (z1 - z0) / samples
+    zs = z0 + (np.arange(samples) + 0.5) * dz
+    out = np.empty(Xt.shape)
+    stretch = np.sqrt(1.0 + (Xt / L) ** 2 + (Yt / L) ** 2)
+    for idx in np.ndindex(Xt.shape):
+        x, y = Xt[idx] * zs / L, Yt[idx] * zs / L
+        out[idx] = (np.asarray(rho_fn(x, y, zs), np.float64) - rho_0).sum() * dz * stretch[idx]
+    return out
+
+
+def gaussian_projection(r2, amplitude: float, sigma: float):
+    """P of a Gaussian blob amplitude exp(-|r|^2 / 2 sigma^2) integrated along a straight line at squared distance r2."""
+    return amplitude * sigma * np.sqrt(2.0 * np.pi) * np.exp(-np.asarray(r2, np.float64) / (2.0 * sigma ** 2))
+
+
+def integrate_vectors(lib, vectors, flags, shape, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16,
+                      weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+    """Projected density from a correlation's vectors [n_rows, n_cols, >= 2] and flags on an image of `shape`: weights
+    (`weights`: "median" = weights_from_correlation after the normalised median test, "unit" = 1 wherever the vector is
+    finite), gradients, integration on the device with the frame fixed at P = 0 (the frame must lie where the density is
+    ambient).  Returns (phi [n_rows, n_cols] kg/m^3 um, mid-plane nodes (X, Y), stats dict)."""
+    from . import piv_correlation as pc
+    if weights == "median":
+        w = weights_from_correlation(vectors, flags, pc.normalized_median_test(vectors))
+    elif weights == "unit":
+        w = np.where(np.isfinite(np.asarray(vectors, np.float64)[..., :2]).all(axis=-1), 1.0, 0.0)
+    else:
+        raise ValueError(f"weights must be 'median' or 'unit', not {weights!r}")
+    gx, gy = gradients_from_displacements(pc.sensor_displacements(vectors, call.camera), call.camera,
+                                          displacement_factor(call, origin_z, extent_z, K, rho_0))
+    _, mid, h = node_geometry(shape, win, step, call, origin_z, extent_z)
+    phi, stats = lib.integrate_gradient(gx, gy, w, hx=h, hy=h, tol=tol)
+    return phi, mid, stats
+
+
+def reconstruct(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, passes: int = 2,
+                weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+    """Projected density from a BOS image pair (im1 without, im2 through the volume; torch device tensors or numpy):
+    ``PhotonLibrary.correlate`` (`passes`), then integrate_vectors.  Returns (phi, mid-plane nodes (X, Y), stats)."""
+    vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
+    return integrate_vectors(lib, vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step, weights, tol, K, rho_0)

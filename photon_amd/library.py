@@ -32,6 +32,8 @@ DECLARED_SYMBOLS = (
     "photon_postprocess_u16", "photon_measure_copy_gbs", "photon_selftest_normal_range_math", "photon_selftest_morton_order",
     # section 5: image-pair cross-correlation on the device
     "photon_piv_correlate",
+    # section 6: gradient-field integration on the device
+    "photon_integrate_gradient",
 )
 
 
@@ -48,6 +50,14 @@ class photon_trace_stats_t(ctypes.Structure):
                 ("sensor_taps", ctypes.c_uint64), ("march_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
                 ("rays_marched", ctypes.c_uint64), ("shader_clock_mhz", ctypes.c_float), ("traces", ctypes.c_uint32),
                 ("march_wave_ms", ctypes.c_float)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class photon_integrate_stats_t(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("converged", ctypes.c_int), ("unknowns", ctypes.c_int),
+                ("unreachable", ctypes.c_int), ("residual", ctypes.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -202,6 +212,9 @@ class PhotonLibrary:
                                              ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
         L.photon_piv_correlate.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [
             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
+        L.photon_integrate_gradient.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
+                                                                        ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
+                                                                        ctypes.POINTER(photon_integrate_stats_t), ctypes.c_void_p]
 
     # ---- helpers --------------------------------------------------------------------------
     @staticmethod
@@ -347,6 +360,54 @@ class PhotonLibrary:
             vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
             vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         return vectors, flags
+
+    # ---- gradient-field integration on the device (photon_integrate_gradient) ------------------------------------
+    def integrate_gradient_ptr(self, d_gx_ptr: int, d_gy_ptr: int, nx: int, ny: int, d_phi_ptr: int, d_w_ptr: int = 0,
+                               d_fixed_ptr: int = 0, d_value_ptr: int = 0, hx: float = 1.0, hy: float = 1.0, tol: float = 1e-8,
+                               max_iter: Optional[int] = None, stream: int = 0) -> dict:
+        """Integrate a device gradient field (raw pointers: f64 gx, gy, w, value and u8 fixed, row-major ny x nx; 0 = NULL)
+        into the device f64 array at d_phi_ptr.  Returns the stats as a dict; the call has synchronised `stream`.
+        max_iter None = 20 max(nx, ny).  The definition: include/parallel_ray_tracing.h, section 6
+        (photon_amd.bos_density: host model)."""
+        from .bos_density import default_max_iter
+        max_iter = default_max_iter(nx, ny) if max_iter is None else int(max_iter)
+        st = photon_integrate_stats_t()
+        vp = [ctypes.c_void_p(int(v)) if v else None for v in (d_gx_ptr, d_gy_ptr, d_w_ptr, d_fixed_ptr, d_value_ptr)]
+        rc = self.lib.photon_integrate_gradient(*vp, int(nx), int(ny), float(hx), float(hy), float(tol), max_iter,
+                                                ctypes.c_void_p(int(d_phi_ptr)) if d_phi_ptr else None, ctypes.byref(st),
+                                                ctypes.c_void_p(int(stream)) if stream else None)
+        self._check(rc, "photon_integrate_gradient")
+        return st.as_dict()
+
+    def integrate_gradient(self, gx, gy, w=None, fixed=None, value=None, hx: float = 1.0, hy: float = 1.0, tol: float = 1e-8,
+                           max_iter: Optional[int] = None):
+        """Weighted least-squares integration of a gradient field on the device (numpy arrays or torch device tensors,
+        [ny, nx]; gx along +column, gy along +row).  w: weights (None = 1); fixed: Dirichlet mask (None = the outer frame);
+        value: values at the fixed nodes (None = 0).  Returns (phi numpy f64 [ny, nx], stats dict); phi is NaN on the
+        unknown nodes that reach no fixed node.  max_iter None = 20 max(nx, ny)."""
+        import torch
+        from . import bos_density
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        def on_device(a, dtype):
+            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
+
+        tgx, tgy = on_device(gx, torch.float64), on_device(gy, torch.float64)
+        if tgx.dim() != 2 or tgx.shape != tgy.shape:
+            raise ValueError("gx and gy must be two 2-d arrays of one shape")
+        ny, nx = tgx.shape
+        tw, tv = on_device(w, torch.float64), on_device(value, torch.float64)
+        tf = None if fixed is None else on_device(torch.as_tensor(fixed) != 0, torch.uint8)
+        for name, t in (("w", tw), ("fixed", tf), ("value", tv)):
+            if t is not None and t.shape != tgx.shape:
+                raise ValueError(f"{name} must have the shape of gx, {tuple(tgx.shape)}")
+        bos_density.check_arguments(nx, ny, hx, hy, tol, bos_density.default_max_iter(nx, ny) if max_iter is None else max_iter)
+        phi = torch.empty((ny, nx), dtype=torch.float64, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        stats = self.integrate_gradient_ptr(tgx.data_ptr(), tgy.data_ptr(), nx, ny, phi.data_ptr(),
+                                            tw.data_ptr() if tw is not None else 0, tf.data_ptr() if tf is not None else 0,
+                                            tv.data_ptr() if tv is not None else 0, hx, hy, tol, max_iter, stream=stream)
+        return phi.cpu().numpy(), stats
 
     # ---- volumes ------------------------------------------------------------------------------
     def volume_load_nrrd(self, path: str, interpolation: int = 1) -> "Volume":
