@@ -682,6 +682,74 @@ int photon_integrate_gradient(const double *d_gx, const double *d_gy, const doub
                               const double *d_value, int nx, int ny, double hx, double hy, double tol, int max_iter,
                               double *d_phi, photon_integrate_stats_t *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 7: iterative image-deformation correlation (Scarano 2002; Astarita & Cardone 2005): the three device steps
+ * that, with section 5's correlation, measure a displacement that varies inside a window.  The vector field on the
+ * window grid is interpolated to every pixel, both images are warped half-way towards each other with a cubic
+ * B-spline, the warped pair is correlated for a small residual, and the residual is added, validated and smoothed.
+ * Host model: photon_amd/piv_deformation.py (f64); driver: PhotonLibrary.correlate_deform.  All three are asynchronous
+ * on `stream`, need no device scratch and return the same bits for the same inputs (every sum has a fixed order).
+ *
+ * Mirror.  An index i outside [0, n) reads the whole-sample mirror image ... c b | a b c ... y z | y x ... (period
+ * 2 (n - 1); n = 1: always 0), numpy.pad(mode="reflect"), scipy.ndimage mode="mirror".
+ *
+ * a. Coefficients.  d_coef (f32[height*width], not d_im) is the cubic B-spline coefficient image of d_im: the spline
+ *    S(y, x) = sum_kl c(k, l) B3(y - k) B3(x - l) over the mirrored coefficients equals the image at the pixel
+ *    centres.  c = h *_rows (h *_columns im) on the mirrored image, h[j] = sqrt(3) z^|j|, z = sqrt(3) - 2 (two-sided,
+ *    gain 1, sum |h| = 3).  The device truncates h at |j| <= 14 (|z|^15 = 2.6e-9) and sums in f32, along each row
+ *    first and then along each column, acc = sum_{j = 14 .. 1} h[j] (x[-j] + x[+j]), then + h[0] x[0], in that order.
+ *    Refused: width or height < 1, a null pointer, d_coef == d_im.
+ *
+ * b. Warp.  d_field: device f32, n_rows x n_cols vectors (dx, dy) `field_stride` floats apart (2, or 4: section 5's
+ *    d_vectors as they are); n_rows, n_cols must be section 5's grid for (height, width, win, step).  A vector with a
+ *    component that is not finite reads as (0, 0).  Dense displacement at pixel (row r, column q): bilinear in the
+ *    window-centre coordinates, fy = clamp((r - (win-1)/2) / step, 0, n_rows - 1), fx = clamp((q - (win-1)/2) / step, 0,
+ *    n_cols - 1): with i = min(floor(fy), n_rows - 2), wy = fy - i (i = 0, wy = 0 for one row; likewise j, wx),
+ *    D = T + wy (U - T), T = F(i, j) + wx (F(i, j+1) - F(i, j)), U the same on row i + 1: constant beyond the outermost
+ *    window centres.  The shift s = clamp(scale D, -2^24, 2^24) per component;
+ *    d_out(r, q) = S(r + s_y, q + s_x) = sum_{u=0..3} wy_u sum_{t=0..3} wx_t c(mirror(r + floor(s_y) - 1 + u),
+ *    mirror(q + floor(s_x) - 1 + t)), the weights from the fractions t = s - floor(s): ((1-t)^3, 4 - 3 t^2 (2 - t),
+ *    4 - 3 (1-t)^2 (1 + t), t^3) / 6.  scale = 0 returns the image the coefficients came from.  The driver warps frame 1
+ *    with scale -1/2 and frame 2 with +1/2: with the true field both outputs show the pattern half-way between the frames.
+ *    Refused: section 5's rules for win, step and the image size, a side of more than 2^22 pixels, a grid that is not
+ *    section 5's, field_stride not 2 or 4, a scale that is not finite, a null pointer, d_out == d_coef.
+ *
+ * c. Validate and update, per node k of the n_rows x n_cols grid, in f64, every step one IEEE operation in this order:
+ *    1. total t = ((pred + d) + 0) per component, pred = d_pred[k] (f32[n][2]; NULL: 0), d = (dx, dy) of d_vectors[k]
+ *       (f32[n][4]); both components NaN when d_flags[k] has bit 2 (flat) or either sum is not finite.  (+ 0: a total
+ *       of -0 reads as +0.)
+ *    2. the normalised median test (Westerweel & Scarano 2005; piv_correlation.normalized_median_test) over the 3 x 3
+ *       neighbourhood: the neighbours are the up to 8 nodes inside the grid whose total is not NaN, m of them.  Per
+ *       component: med = median of the neighbours' values, rm = median of |value - med|, r = |t - med| / (rm + eps).
+ *       The median of m sorted values is (v[(m-1)/2] + v[m/2]) / 2 (integer division).  The node is an outlier when
+ *       its total is NaN, or when m > 0 and r_x r_x + r_y r_y > threshold threshold (no square root; a NaN score, 0/0,
+ *       is no outlier).
+ *    3. an outlier takes, per component, the median of its neighbours that are not outliers themselves (and not NaN),
+ *       (0, 0) where there is none (piv_correlation.predictor without the rounding); every other node keeps t.
+ *    4. d_status int[n] = d_flags[k], bit 8 added on every outlier.
+ *    5. d_field f32[n][2] = the result of step 3, rounded to f32 (what a caller reports).  d_smooth f32[n][2], or
+ *       NULL: the 3 x 3 binomial filter of the f64 result of step 3, h(i, j) = ((v(i, j-1) + 2 v(i, j)) + v(i, j+1)) / 4
+ *       along each row, then ((h(i-1, j) + 2 h(i, j)) + h(i+1, j)) / 4 along each column, indices clamped to the grid
+ *       (edge values replicated), rounded once to f32: the predictor of the next iteration.
+ *    The device returns the model's status bit for bit, and its field and smooth values bit for bit.  d_pred must
+ *    not be one of the outputs (a node reads its neighbours' predictors).  Refused: n_rows or n_cols < 1, more than
+ *    INT_MAX nodes, eps < 0 or not finite, threshold <= 0 or not finite, a null d_vectors, d_flags, d_field or
+ *    d_status, d_pred == d_field or d_smooth.
+ * Every refusal: 1, one stderr line, nothing written, no launch.
+ *
+ * Driver (PhotonLibrary.correlate_deform; piv_deformation.correlate_deform_model): the coefficients of both frames
+ * once; pass 0 = photon_piv_correlate on the images with `radius`, validate with pred NULL -> F_1 = its d_smooth;
+ * iteration k = 1 .. iterations: warp frame 1 by -F_k / 2 and frame 2 by +F_k / 2, correlate the warped pair with
+ * residual_radius, validate with pred = F_k -> d_field the result of iteration k, d_smooth = F_k+1 (smooth off: d_field
+ * is passed on).  Known limits: the median test's one-sided neighbourhoods flag most border nodes of a strongly
+ * rotating field, which then take interior medians; a window whose warped footprint leaves the frame correlates
+ * mirrored particles, and section 5's bit 4 is not raised for that. */
+int photon_piv_bspline_coefficients(const float *d_im, int width, int height, float *d_coef, void *stream);
+int photon_piv_deform(const float *d_coef, int width, int height, const float *d_field, int field_stride, int n_rows,
+                      int n_cols, int win, int step, float scale, float *d_out, void *stream);
+int photon_piv_validate(const float *d_pred, const float *d_vectors, const int *d_flags, int n_rows, int n_cols, double eps,
+                        double threshold, float *d_field, float *d_smooth, int *d_status, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

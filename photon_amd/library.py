@@ -34,6 +34,8 @@ DECLARED_SYMBOLS = (
     "photon_piv_correlate",
     # section 6: gradient-field integration on the device
     "photon_integrate_gradient",
+    # section 7: iterative image-deformation correlation
+    "photon_piv_bspline_coefficients", "photon_piv_deform", "photon_piv_validate",
 )
 
 
@@ -215,6 +217,11 @@ class PhotonLibrary:
         L.photon_integrate_gradient.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
                                                                         ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
                                                                         ctypes.POINTER(photon_integrate_stats_t), ctypes.c_void_p]
+        L.photon_piv_bspline_coefficients.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+        L.photon_piv_deform.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 5 + [
+            ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
+        L.photon_piv_validate.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] + [
+            ctypes.c_void_p] * 4
 
     # ---- helpers --------------------------------------------------------------------------
     @staticmethod
@@ -360,6 +367,76 @@ class PhotonLibrary:
             vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
             vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         return vectors, flags
+
+    # ---- iterative image-deformation correlation on the device (section 7) ---------------------------------------------
+    @staticmethod
+    def _vp(ptr: int):
+        return ctypes.c_void_p(int(ptr)) if ptr else None
+
+    def bspline_coefficients(self, d_im_ptr: int, width: int, height: int, d_coef_ptr: int, stream: int = 0):
+        """photon_piv_bspline_coefficients on raw device pointers (f32 [height, width] in and out), asynchronous on `stream`."""
+        rc = self.lib.photon_piv_bspline_coefficients(self._vp(d_im_ptr), int(width), int(height), self._vp(d_coef_ptr), self._vp(stream))
+        self._check(rc, "photon_piv_bspline_coefficients")
+
+    def piv_deform(self, d_coef_ptr: int, width: int, height: int, d_field_ptr: int, field_stride: int, n_rows: int, n_cols: int,
+                   win: int, step: int, scale: float, d_out_ptr: int, stream: int = 0):
+        """photon_piv_deform on raw device pointers: the image of the coefficients warped by scale x the grid's field
+        (f32, `field_stride` 2 or 4 floats per vector), asynchronous on `stream`."""
+        rc = self.lib.photon_piv_deform(self._vp(d_coef_ptr), int(width), int(height), self._vp(d_field_ptr), int(field_stride),
+                                        int(n_rows), int(n_cols), int(win), int(step), float(scale), self._vp(d_out_ptr), self._vp(stream))
+        self._check(rc, "photon_piv_deform")
+
+    def piv_validate(self, d_pred_ptr: int, d_vectors_ptr: int, d_flags_ptr: int, n_rows: int, n_cols: int, d_field_ptr: int,
+                     d_smooth_ptr: int, d_status_ptr: int, eps: float = 0.1, threshold: float = 2.0, stream: int = 0):
+        """photon_piv_validate on raw device pointers (d_pred_ptr, d_smooth_ptr: 0 = NULL), asynchronous on `stream`."""
+        rc = self.lib.photon_piv_validate(self._vp(d_pred_ptr), self._vp(d_vectors_ptr), self._vp(d_flags_ptr), int(n_rows), int(n_cols),
+                                          float(eps), float(threshold), self._vp(d_field_ptr), self._vp(d_smooth_ptr),
+                                          self._vp(d_status_ptr), self._vp(stream))
+        self._check(rc, "photon_piv_validate")
+
+    def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
+                         residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0):
+        """Displacement field of an image pair by iterative image deformation (section 7; model:
+        photon_amd.piv_deformation.correlate_deform_model).  Pass 0 correlates the images with `radius` (None = win // 2);
+        every iteration warps both frames half-way by the validated, smoothed field, correlates the warped pair with
+        `residual_radius` and adds the residual.  Returns what ``correlate`` returns: numpy (vectors [n_rows, n_cols, 4] =
+        dx, dy of the last unsmoothed field, peak and ratio of the last correlation; status [n_rows, n_cols], section 5's
+        flags with bit 8 on replaced vectors).  Everything runs on the current stream; the host waits once, for the result."""
+        import torch
+        from . import piv_correlation as pc
+        if int(iterations) < 0:
+            raise ValueError(f"iterations must be >= 0, not {iterations}")
+        radius = int(win) // 2 if radius is None else int(radius)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
+        if a.dim() != 2 or a.shape != b.shape:
+            raise ValueError("im1 and im2 must be two 2-d images of one shape")
+        h, w = a.shape
+        pc.check_arguments((h, w), win, step, radius)
+        if int(iterations) > 0:
+            pc.check_arguments((h, w), win, step, residual_radius)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
+        r, c = flg.shape
+        field, smoothed = (torch.empty((2, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))     # ping-pong pairs
+        status = torch.empty((r, c), dtype=torch.int32, device=dev)
+        self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field[0].data_ptr(), smoothed[0].data_ptr(), status.data_ptr(),
+                          eps, threshold, stream)
+        cur = 0
+        if int(iterations) > 0:
+            coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=dev), torch.empty((2, h, w), dtype=torch.float32, device=dev)
+            self.bspline_coefficients(a.data_ptr(), w, h, coef[0].data_ptr(), stream)
+            self.bspline_coefficients(b.data_ptr(), w, h, coef[1].data_ptr(), stream)
+        for _ in range(int(iterations)):
+            pred = (smoothed if smooth else field)[cur]
+            self.piv_deform(coef[0].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, -0.5, warped[0].data_ptr(), stream)
+            self.piv_deform(coef[1].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, 0.5, warped[1].data_ptr(), stream)
+            vec, flg, _ = self.piv_correlate(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, residual_radius, stream=stream)
+            cur ^= 1
+            self.piv_validate(pred.data_ptr(), vec.data_ptr(), flg.data_ptr(), r, c, field[cur].data_ptr(), smoothed[cur].data_ptr(),
+                              status.data_ptr(), eps, threshold, stream)
+        out = torch.cat([field[cur], vec[..., 2:4]], dim=-1)
+        return out.cpu().numpy(), status.cpu().numpy()
 
     # ---- gradient-field integration on the device (photon_integrate_gradient) ------------------------------------
     def integrate_gradient_ptr(self, d_gx_ptr: int, d_gy_ptr: int, nx: int, ny: int, d_phi_ptr: int, d_w_ptr: int = 0,

@@ -7,7 +7,8 @@ section 6).  Prints JSON lines for two measurements:
 2. the end-to-end loop at a 1024^2 sensor: the off-centre blob of tests/bos_density_cases.py rendered without and through
    the volume (4-pixel splat), correlated in two passes (win 32, step 16), integrated, and held against the chief-ray
    projection: render, correlate and integrate ms, the relative L2 error over the nodes above 10 % of the peak and the
-   argmax offset in grid steps.
+   argmax offset in grid steps; then the same with PhotonLibrary.correlate_deform (3 iterations of image deformation,
+   header section 7) in place of the two-pass correlation.
 
 Kernel times come from a separate run under rocprofv3 --kernel-trace --stats.  Run it on a GPU box under a time limit:
 
@@ -75,7 +76,16 @@ def end_to_end(lib, n_pix: int = 1024) -> dict:
     t5 = time.perf_counter()
     P, mid, h = bc.truth(c2, n_pix)
     rel, off, holes = bc.errors(phi, P, mid, h)
-    return dict(measurement="end_to_end", sensor=f"{n_pix}x{n_pix}", rays_per_frame=c1.num_rays, nodes=f"{phi.shape[0]}x{phi.shape[1]}",
+    lib.correlate_deform(im1, im2, win=bc.WIN, step=bc.STEP, iterations=3)
+    t6 = time.perf_counter()
+    vectors_d, status_d = lib.correlate_deform(im1, im2, win=bc.WIN, step=bc.STEP, iterations=3)
+    t7 = time.perf_counter()
+    phi_d, _, st_d = bd.integrate_vectors(lib, vectors_d, status_d, (n_pix, n_pix), c2, bc.ORIGIN_Z, bc.EXTENT, bc.WIN, bc.STEP)
+    rel_d, off_d, holes_d = bc.errors(phi_d, P, mid, h)
+    deform = dict(correlate_ms_deform_3_iterations=round(1e3 * (t7 - t6), 2), deform_iterations_of_the_solver=st_d["iterations"],
+                  deform_rel_l2_error=round(rel_d, 4), deform_nan_share=round(holes_d, 4),
+                  deform_argmax_offset_steps=[round(off_d[0], 2), round(off_d[1], 2)], deform_replaced=int(((status_d & 8) != 0).sum()))
+    return dict(deform, measurement="end_to_end", sensor=f"{n_pix}x{n_pix}", rays_per_frame=c1.num_rays, nodes=f"{phi.shape[0]}x{phi.shape[1]}",
                 render_ms_without=round(1e3 * (t1 - t0), 1), render_ms_through=round(1e3 * (t2 - t1), 1),
                 correlate_ms_two_passes=round(1e3 * (t4 - t3), 2), integrate_ms_with_host_steps=round(1e3 * (t5 - t4), 2),
                 iterations=st["iterations"], rel_l2_error=round(rel, 4), nan_share=round(holes, 4), argmax_offset_steps=[round(off[0], 2), round(off[1], 2)])

@@ -11,9 +11,13 @@ passes), prints the correlation's ms per pass and the median / 95th percentile o
 the mean image displacement of the particles whose frame-1 centroid lies in the window, counting those the laser sheet lights
 to >= 10 % of its peak, windows with >= 5 of them), and
 times 1024^2 pairs at win 32 / step 16 / R 16 and win 64 / step 32 / R 32 (multiply-adds per second, share of the f32
-FMA peak).  Run it on a GPU box under a time limit of its own:
+FMA peak).  --deform adds iterative image deformation (PhotonLibrary.correlate_deform, header section 7): the same error
+figures after 1, 2 and 3 iterations against the same truth and windows (and against the truth that collects the particles
+by their position half-way between the frames, which is where a symmetric warp measures), and at 1024^2 the device-event
+times of the coefficients, one warp, one residual correlation at R 4 and one validate, and the wall time of the whole call
+beside correlate(passes=2).  Run it on a GPU box under a time limit of its own:
 
-    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate]
+    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate] [--deform]
 """
 import argparse
 import json
@@ -94,6 +98,77 @@ def correlate_pair(lib, images, records, cam, rays, lit, row):
         row[f"correlate_1024_w{win}_fma_peak_frac"] = round(rate / FMA_PEAK, 4)
 
 
+def event_ms(fn, reps=20):
+    """Device time of one call of fn (events around `reps` back-to-back calls, after a warm-up)."""
+    fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def wall_ms(fns, reps=12, warm=3):
+    """Median wall time of each of `fns` (name -> call that ends synchronised), alternating, after a warm-up."""
+    times = {k: [] for k in fns}
+    for rep in range(warm + reps):
+        for name, fn in fns.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            if rep >= warm:
+                times[name].append(1e3 * (time.perf_counter() - t0))
+    return {k: float(np.median(v)) for k, v in times.items()}
+
+
+def deform_pair(lib, images, records, cam, rays, lit, row):
+    """--deform on the sample pair, then the 1024^2 timings; adds its figures to `row`."""
+    win, step, radius = 32, 16, 16
+    a, b = (torch.from_numpy(np.ascontiguousarray(im, np.float32)).cuda() for im in images)
+    m1 = deflections.dot_means(records[0], rays, 1, "arrived")
+    pos = pc.image_positions(deflections.to_pixels(m1["pos"], cam), cam)[lit]
+    d = pp.image_displacements(records[0], records[1], cam, rays)[lit]
+    flip = -1.0 if bool(cam.get("implement_diffraction", False)) else 1.0
+    truths = {"frame1": pc.window_truth(pos, d, images[0].shape, win, step, min_count=5)[0],
+              "halfway": pc.window_truth(pos + 0.5 * d * np.array([flip, 1.0]), d, images[0].shape, win, step, min_count=5)[0]}
+    for it in (1, 2, 3):
+        vec, status = lib.correlate_deform(a, b, win, step, radius, iterations=it)
+        line = f"deformation, {it} iteration(s), {int(((status & 8) != 0).sum())} of {status.size} vectors replaced:"
+        for name, truth in truths.items():
+            ok = np.isfinite(truth).all(axis=-1) & ((status & pc.FLAG_FLAT) == 0)          # --correlate's window selection
+            err = np.hypot(*(pc.sensor_displacements(vec, cam)[ok] - truth[ok]).T)
+            line += f" {name} truth ({int(ok.sum())} windows) median {np.median(err):.4f} px, 95th percentile {np.percentile(err, 95):.4f} px;"
+            row[f"deform{it}_{name}_median_err_px"] = float(np.median(err))
+            row[f"deform{it}_{name}_p95_err_px"] = float(np.percentile(err, 95))
+        print(line)
+    rng = np.random.default_rng(1)
+    n = 20_000
+    x, y = rng.uniform(-8, 1032, n), rng.uniform(-8, 1032, n)
+    big = [torch.from_numpy(pc.particle_image((1024, 1024), x + dx, y + dy).astype(np.float32)).cuda() for dx, dy in ((0, 0), (3.3, -2.6))]
+    h = w = 1024
+    for win, step in ((32, 16), (64, 32)):
+        r, c = pc.grid_shape((h, w), win, step)
+        coef, out = torch.empty_like(big[0]), torch.empty_like(big[0])
+        vec, flg, _ = lib.piv_correlate(big[0].data_ptr(), big[1].data_ptr(), w, h, win, step, win // 2)
+        field, smooth = torch.empty((r, c, 2), device="cuda"), torch.empty((r, c, 2), device="cuda")
+        status = torch.empty((r, c), dtype=torch.int32, device="cuda")
+        lib.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smooth.data_ptr(), status.data_ptr())
+        ms = {"coefficients": event_ms(lambda: lib.bspline_coefficients(big[0].data_ptr(), w, h, coef.data_ptr())),
+              "warp": event_ms(lambda: lib.piv_deform(coef.data_ptr(), w, h, smooth.data_ptr(), 2, r, c, win, step, -0.5, out.data_ptr())),
+              "correlate_r4": event_ms(lambda: lib.piv_correlate(big[0].data_ptr(), big[1].data_ptr(), w, h, win, step, 4)),
+              "correlate_full": event_ms(lambda: lib.piv_correlate(big[0].data_ptr(), big[1].data_ptr(), w, h, win, step, win // 2)),
+              "validate": event_ms(lambda: lib.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smooth.data_ptr(),
+                                                            status.data_ptr()))}
+        ms.update(wall_ms({"correlate_deform_3_wall": lambda: lib.correlate_deform(big[0], big[1], win, step, iterations=3),
+                           "correlate_2_passes_wall": lambda: lib.correlate(big[0], big[1], win, step, passes=2)}))
+        print(f"1024^2, win {win} step {step} ({r} x {c} nodes): " + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items()))
+        for k, v in ms.items():
+            row[f"deform_1024_w{win}_{k}_ms"] = round(v, 4)
+
+
 def timed(fn, reps=3):
     out, best = None, 1e9
     for _ in range(reps):
@@ -113,6 +188,7 @@ def main():
     ap.add_argument("--tiff", default=None)
     ap.add_argument("--bench-advect", action="store_true")
     ap.add_argument("--correlate", action="store_true")
+    ap.add_argument("--deform", action="store_true")
     args = ap.parse_args()
     lib = PhotonLibrary()
     lib.set_device(0)
@@ -192,10 +268,13 @@ def main():
         _, row["advect_1e6_16steps_128cubed_ms"] = timed(bench, 5)
         bflow.free()
         print(f"advection of 1e6 particles, 16 steps, 128^3 field: {row['advect_1e6_16steps_128cubed_ms']:.3f} ms")
-    if args.correlate:
+    if args.correlate or args.deform:
         sigma = BEAM_FWHM / (2.0 * math.sqrt(2.0 * math.log(2.0)))
         lit = np.exp(-w1[:, 2] ** 2 / (2.0 * sigma * sigma)) >= 0.1       # within 2.15 sigma of the sheet's centre plane
+    if args.correlate:
         correlate_pair(lib, images, records, cam, rays, lit, row)
+    if args.deform:
+        deform_pair(lib, images, records, cam, rays, lit, row)
     print(json.dumps(row), flush=True)
     if not math.isfinite(row["p99_err_px"]):
         sys.exit(1)
