@@ -750,6 +750,103 @@ int photon_piv_deform(const float *d_coef, int width, int height, const float *d
 int photon_piv_validate(const float *d_pred, const float *d_vectors, const int *d_flags, int n_rows, int n_cols, double eps,
                         double threshold, float *d_field, float *d_smooth, int *d_status, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 8: dot tracking on an image pair (BOS dot patterns, particle tracking): find the dots of each image, locate
+ * each to a fraction of a pixel, pair the dots of the two frames and report one shift per dot -- the measurement that
+ * matches the per-dot truth of photon_trace_moments one to one, where sections 5 and 7 measure window averages.  Host
+ * model: photon_amd/dot_tracking.py (f64); driver: PhotonLibrary.track_dots.  Coordinates are index coordinates as in
+ * section 5: x = column, y = row, the centre of pixel (r, q) at (x, y) = (q, r).
+ * Every entry point is asynchronous on `stream`, takes the capacities of its arrays from the caller and reads the number
+ * of dots from device memory (a count below 0 reads as 0, one above the capacity as the capacity), so the chain
+ * detect -> fit -> match -> window means runs without a host wait in between.  Device scratch comes from the CALLER
+ * (d_scratch of at least photon_dots_*_scratch_bytes bytes, 16-byte aligned, not shared by calls that may overlap in
+ * time; its contents afterwards are unspecified); the entry points allocate nothing.  d_dots, d_shift and d_vectors
+ * (four floats per entry) must be 16-byte aligned.  Two calls on the same inputs
+ * return identical bytes: every output order and every summation order is fixed, and where atomics are used (integer
+ * counts, a maximum, the order of the cell lists inside the scratch) no output depends on the order in which they land.
+ * Every refusal: 1, one stderr line, nothing written, no launch.
+ *
+ * photon_dots_image_max: *d_max = the largest finite pixel, 0 when there is none above 0 (so that a threshold can be a
+ *    fraction of the maximum without a host wait).  Refused: width or height < 1, a null pointer.
+ *
+ * a. Detect.  The effective threshold is T = threshold * *d_scale, one f32 product (d_scale: a device f32, NULL = 1).
+ *    Pixel (r, q) with 1 <= r <= height - 2, 1 <= q <= width - 2 is a peak when its value v is finite, v > T, v > each of
+ *    the four neighbours that precede it in row-major order (NW, N, NE, W) and v >= each of the four that follow (E, SW,
+ *    S, SE); a comparison with a NaN neighbour counts as passed (a plateau yields its first pixel in row-major order
+ *    whose preceding neighbours are all lower).  d_peaks int[max_dots] receives the pixel indices r width + q in
+ *    increasing order; *d_count the total number found, which may exceed max_dots, in which case the first max_dots are
+ *    written.  Entries beyond the count are not written.  The device equals the model exactly.
+ *    Refused: an image smaller than 3 x 3, more than INT_MAX pixels, max_dots < 1, a threshold that is not finite, a null
+ *    d_im, d_peaks, d_count or d_scratch, a scratch smaller than photon_dots_detect_scratch_bytes(width, height).
+ *
+ * b. Locate.  Dot k < min(*d_count, max_dots) has its peak at pixel d_peaks[k] = r width + q.  With
+ *    I(p) = max(im(p) - background, 0) in f64, pixels outside the image and non-finite pixels reading 0:
+ *    1. start: per axis the 3-point fit of section 5 (Gaussian where all three of I-, I0, I+ are positive, parabolic
+ *       otherwise, 0 for a zero denominator) through the peak pixel, in f64: (x, y) = (q + delta_x, r + delta_y).
+ *    2. `iterations` rounds (0 .. 16) of the Gaussian-weighted centroid over the (2 box_radius + 1)^2 box centred on the
+ *       PEAK PIXEL (box_radius 1 .. 7): w(p) = I(p) exp(-(p_x - x)^2 / (2 sigma_w^2)) exp(-(p_y - y)^2 / (2 sigma_w^2)),
+ *       (x, y) <- sum w p / sum w, in f64.  The weight is separable: 2 (2 box_radius + 1) exponentials per round.  A round
+ *       whose sum w is not > 0 leaves (x, y) alone and sets status bit 4.
+ *    3. after the last round, with the final (x, y) and its weights: v = sum w ((p_x - x)^2 + (p_y - y)^2) / (2 sum w),
+ *       the weighted variance per axis; the dot's own variance s2 = v sigma_w^2 / (sigma_w^2 - v) - 1/12 (pixel
+ *       integration); diameter = 4 sqrt(s2) (the e^-2 diameter of piv_correlation.particle_image), NaN when iterations
+ *       = 0, when sum w is not > 0, or when s2 is not finite or not > 0.
+ *    d_dots f32[max_dots][4] = (x, y, I at the peak pixel, diameter), rounded once from f64; d_status int[max_dots] bits:
+ *    1 the box leaves the image; 2 the final position lies more than 1 px from the peak pixel's centre in either axis (the
+ *    position is reported as it is, the bit is a warning: a neighbour pulled the centroid); 4 as above; 8 d_peaks[k] is
+ *    no pixel index of the image (the dot is NaN).  Entries k >= the count are not written.  The device sums in f64 in
+ *    its own fixed order (each row of the box left to right, the rows folded pairwise): it agrees with the model to
+ *    rounding, not bit for bit.
+ *    Refused: width or height < 1, more than INT_MAX pixels, max_dots < 1, box_radius or iterations out of range,
+ *    sigma_w not finite or <= 0, background not finite, a null pointer.
+ *
+ * c. Pair.  Dots and status of frame 1 and frame 2 (section 8b's arrays; d_status1 / d_status2 may be NULL) with their
+ *    counts on the device.  A dot takes part when both coordinates are finite and (status & reject_mask) = 0.
+ *    Predictor: d_field (NULL = none), field_stride, n_rows, n_cols, win, step exactly as section 7b takes them (win any
+ *    size >= 1 here), evaluated at the dot's own continuous position (x, y) by 7b's bilinear rule in f32, one IEEE
+ *    operation per step: fy = clamp((y - (win-1)/2) / step, 0, n_rows - 1), i = min(floor(fy), max(n_rows - 2, 0)),
+ *    wy = fy - i, likewise fx, j, wx; T = F(i, j) + wx (F(i, j+1) - F(i, j)), U the same on row min(i + 1, n_rows - 1),
+ *    pred = T + wy (U - T); a vector with a component that is not finite reads as (0, 0).
+ *    Target of dot i of frame 1: t_i = p_i + pred(p_i) (f32; a target that is not finite takes no part).  For a target t
+ *    and a dot p of frame 2, d2 = (p_x - t_x)(p_x - t_x) + (p_y - t_y)(p_y - t_y) in f32 without contraction.
+ *    j*(i): the dot of frame 2 with the smallest d2 to t_i among those with d2 <= radius radius (one f32 product), ties
+ *    to the smallest j; i*(j): the target with the smallest d2 to p_j under the same rule, ties to the smallest i.  Dot
+ *    i is paired with j when j = j*(i) and i = i*(j).
+ *    d_pair int[max1] = j or -1; d_shift f32[max1][4] = (x_mid, y_mid, dx, dy) with d = p2_j - p1_i and mid = p1_i +
+ *    d / 2 (f32), NaN for an unpaired dot; *d_npaired the number of pairs.  Entries beyond the count of frame 1 are not
+ *    written.  The device equals the brute-force model exactly.  The search runs on a uniform grid of cells of
+ *    max(1.001 radius, 8, max(width, height) / 2048) pixels over the image (positions beyond it fall into the border
+ *    cells) and visits 3 x 3 cells.
+ *    Refused: width or height < 1, max1 or max2 < 1, radius not finite or <= 0, a null d_dots, d_count, d_pair, d_shift,
+ *    d_npaired or d_scratch, with a field: field_stride not 2 or 4, win or step < 1, an image smaller than one window,
+ *    a grid that is not section 5's; a scratch smaller than photon_dots_match_scratch_bytes(width, height, radius, max1, max2).
+ *
+ * d. Onto the window grid, so that tracked dots feed photon_piv_validate and photon_integrate_gradient unchanged.  For
+ *    section 5's grid of (height, width, win, step) (win any size >= 1): window (i, j) owns a paired dot (d_pair >= 0,
+ *    shift finite) when the pixel its anchor falls in, (floor(x + 1/2), floor(y + 1/2)) in f64, lies in the window
+ *    (piv_correlation.window_truth's rule); anchor 0 = the frame-1 position d_dots1 (what section 5 measures), 1 = the
+ *    midpoint of d_shift (what section 7 measures).  d_vectors f32[n][4] = (mean dx, mean dy, count, rms), in f64, the
+ *    sums in increasing dot index: mean = sum / count, rms = sqrt(sum ((dx - mean dx)^2 + (dy - mean dy)^2) / count),
+ *    each rounded once to f32; d_flags int[n] = 2 (section 5's "no data" bit; dx, dy and rms NaN, the count kept) when
+ *    count < min_count, else 0.  The device equals the model bit for bit.
+ *    Refused: win or step < 1, an image smaller than one window, max1 < 1, min_count < 1, anchor not 0 or 1, more than
+ *    INT_MAX windows, a null pointer. */
+size_t photon_dots_detect_scratch_bytes(int width, int height);                     /* 0 for arguments detect refuses */
+size_t photon_dots_match_scratch_bytes(int width, int height, float radius, int max1, int max2);
+int photon_dots_image_max(const float *d_im, int width, int height, float *d_max, void *stream);
+int photon_dots_detect(const float *d_im, int width, int height, float threshold, const float *d_scale, int max_dots,
+                       int *d_peaks, int *d_count, void *d_scratch, size_t scratch_bytes, void *stream);
+int photon_dots_fit(const float *d_im, int width, int height, const int *d_peaks, const int *d_count, int max_dots,
+                    int box_radius, double sigma_w, int iterations, double background, float *d_dots, int *d_status,
+                    void *stream);
+int photon_dots_match(const float *d_dots1, const int *d_status1, const int *d_count1, int max1, const float *d_dots2,
+                      const int *d_status2, const int *d_count2, int max2, int reject_mask, const float *d_field,
+                      int field_stride, int n_rows, int n_cols, int win, int step, float radius, int width, int height,
+                      int *d_pair, float *d_shift, int *d_npaired, void *d_scratch, size_t scratch_bytes, void *stream);
+int photon_dots_window_means(const float *d_dots1, const int *d_pair, const float *d_shift, const int *d_count1, int max1,
+                             int width, int height, int win, int step, int min_count, int anchor, float *d_vectors,
+                             int *d_flags, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

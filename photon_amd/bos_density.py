@@ -309,3 +309,20 @@ def reconstruct(lib, im1, im2, call, origin_z: float, extent_z: float, win: int 
     ``PhotonLibrary.correlate`` (`passes`), then integrate_vectors.  Returns (phi, mid-plane nodes (X, Y), stats)."""
     vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
     return integrate_vectors(lib, vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step, weights, tol, K, rho_0)
+
+
+def reconstruct_tracked(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, threshold: float = 0.25,
+                        relative: bool = True, min_count: int = 3, predict: bool = True, weights: str = "median", tol: float = 1e-8,
+                        K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, **track):
+    """Projected density from a BOS image pair by dot tracking: ``PhotonLibrary.track_dots`` (`threshold`, `relative` and
+    the keywords in `track`: box_radius, sigma_w, iterations, background, radius, max_dots) with the pairs averaged onto
+    the (win, step) grid at the frame-1 anchor, windows of fewer than `min_count` dots taking weight 0, then
+    integrate_vectors as ``reconstruct`` calls it.  predict: the pairing starts from one validated pass of window
+    correlation on the same grid (``PhotonLibrary.correlation_predictor``) -- without it a shift that approaches the
+    spacing of the dots pairs some of them with a neighbour, and those windows spoil the integral.  Returns (phi,
+    mid-plane nodes (X, Y), stats)."""
+    if predict and "predictor" not in track:
+        track["predictor"] = (lib.correlation_predictor(im1, im2, win, step), win, step)
+    res = lib.track_dots(im1, im2, threshold, relative=relative, grid=(win, step, min_count, 0), **track)
+    return integrate_vectors(lib, res["vectors"], res["flags"], tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step,
+                             weights, tol, K, rho_0)

@@ -36,6 +36,9 @@ DECLARED_SYMBOLS = (
     "photon_integrate_gradient",
     # section 7: iterative image-deformation correlation
     "photon_piv_bspline_coefficients", "photon_piv_deform", "photon_piv_validate",
+    # section 8: dot tracking
+    "photon_dots_detect_scratch_bytes", "photon_dots_match_scratch_bytes", "photon_dots_image_max", "photon_dots_detect", "photon_dots_fit",
+    "photon_dots_match", "photon_dots_window_means",
 )
 
 
@@ -222,6 +225,17 @@ class PhotonLibrary:
             ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
         L.photon_piv_validate.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] + [
             ctypes.c_void_p] * 4
+        vp, ci = ctypes.c_void_p, ctypes.c_int
+        L.photon_dots_detect_scratch_bytes.argtypes = [ci, ci]
+        L.photon_dots_detect_scratch_bytes.restype = ctypes.c_size_t
+        L.photon_dots_match_scratch_bytes.argtypes = [ci, ci, ctypes.c_float, ci, ci]
+        L.photon_dots_match_scratch_bytes.restype = ctypes.c_size_t
+        L.photon_dots_image_max.argtypes = [vp, ci, ci, vp, vp]
+        L.photon_dots_detect.argtypes = [vp, ci, ci, ctypes.c_float, vp, ci, vp, vp, vp, ctypes.c_size_t, vp]
+        L.photon_dots_fit.argtypes = [vp, ci, ci, vp, vp, ci, ci, ctypes.c_double, ci, ctypes.c_double, vp, vp, vp]
+        L.photon_dots_match.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ctypes.c_float, ci, ci, vp, vp, vp, vp,
+                                        ctypes.c_size_t, vp]
+        L.photon_dots_window_means.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
 
     # ---- helpers --------------------------------------------------------------------------
     @staticmethod
@@ -437,6 +451,150 @@ class PhotonLibrary:
                               status.data_ptr(), eps, threshold, stream)
         out = torch.cat([field[cur], vec[..., 2:4]], dim=-1)
         return out.cpu().numpy(), status.cpu().numpy()
+
+    # ---- dot tracking on the device (section 8) ---------------------------------------------------------------------------
+    def dots_scratch_bytes(self, width: int, height: int, radius: Optional[float] = None, max1: int = 0, max2: int = 0) -> int:
+        """Bytes of device scratch dots_detect needs for a width x height image, or with `radius` what dots_match needs for
+        that radius and the capacities max1, max2 (0: arguments the call would refuse)."""
+        if radius is None:
+            return int(self.lib.photon_dots_detect_scratch_bytes(int(width), int(height)))
+        return int(self.lib.photon_dots_match_scratch_bytes(int(width), int(height), float(radius), int(max1), int(max2)))
+
+    def dots_image_max(self, d_im_ptr: int, width: int, height: int, d_max_ptr: int, stream: int = 0):
+        """photon_dots_image_max on raw device pointers: the largest finite pixel into the device f32 at d_max_ptr."""
+        rc = self.lib.photon_dots_image_max(self._vp(d_im_ptr), int(width), int(height), self._vp(d_max_ptr), self._vp(stream))
+        self._check(rc, "photon_dots_image_max")
+
+    def dots_detect(self, d_im_ptr: int, width: int, height: int, threshold: float, d_scale_ptr: int, max_dots: int, d_peaks_ptr: int,
+                    d_count_ptr: int, d_scratch_ptr: int, scratch_bytes: int, stream: int = 0):
+        """photon_dots_detect on raw device pointers (d_scale_ptr: 0 = NULL), asynchronous on `stream`."""
+        rc = self.lib.photon_dots_detect(self._vp(d_im_ptr), int(width), int(height), float(threshold), self._vp(d_scale_ptr), int(max_dots),
+                                         self._vp(d_peaks_ptr), self._vp(d_count_ptr), self._vp(d_scratch_ptr), int(scratch_bytes),
+                                         self._vp(stream))
+        self._check(rc, "photon_dots_detect")
+
+    def dots_fit(self, d_im_ptr: int, width: int, height: int, d_peaks_ptr: int, d_count_ptr: int, max_dots: int, box_radius: int,
+                 sigma_w: float, iterations: int, background: float, d_dots_ptr: int, d_status_ptr: int, stream: int = 0):
+        """photon_dots_fit on raw device pointers, asynchronous on `stream`."""
+        rc = self.lib.photon_dots_fit(self._vp(d_im_ptr), int(width), int(height), self._vp(d_peaks_ptr), self._vp(d_count_ptr),
+                                      int(max_dots), int(box_radius), float(sigma_w), int(iterations), float(background),
+                                      self._vp(d_dots_ptr), self._vp(d_status_ptr), self._vp(stream))
+        self._check(rc, "photon_dots_fit")
+
+    def dots_match(self, d_dots1_ptr: int, d_status1_ptr: int, d_count1_ptr: int, max1: int, d_dots2_ptr: int, d_status2_ptr: int,
+                   d_count2_ptr: int, max2: int, radius: float, width: int, height: int, d_pair_ptr: int, d_shift_ptr: int,
+                   d_npaired_ptr: int, d_scratch_ptr: int, scratch_bytes: int, d_field_ptr: int = 0, field_stride: int = 2,
+                   n_rows: int = 0, n_cols: int = 0, win: int = 0, step: int = 0, reject_mask: int = 0, stream: int = 0):
+        """photon_dots_match on raw device pointers (d_field_ptr: 0 = no predictor), asynchronous on `stream`."""
+        rc = self.lib.photon_dots_match(self._vp(d_dots1_ptr), self._vp(d_status1_ptr), self._vp(d_count1_ptr), int(max1),
+                                        self._vp(d_dots2_ptr), self._vp(d_status2_ptr), self._vp(d_count2_ptr), int(max2), int(reject_mask),
+                                        self._vp(d_field_ptr), int(field_stride), int(n_rows), int(n_cols), int(win), int(step),
+                                        float(radius), int(width), int(height), self._vp(d_pair_ptr), self._vp(d_shift_ptr),
+                                        self._vp(d_npaired_ptr), self._vp(d_scratch_ptr), int(scratch_bytes), self._vp(stream))
+        self._check(rc, "photon_dots_match")
+
+    def dots_window_means(self, d_dots1_ptr: int, d_pair_ptr: int, d_shift_ptr: int, d_count1_ptr: int, max1: int, width: int,
+                          height: int, win: int, step: int, min_count: int, anchor: int, d_vectors_ptr: int, d_flags_ptr: int,
+                          stream: int = 0):
+        """photon_dots_window_means on raw device pointers, asynchronous on `stream`."""
+        rc = self.lib.photon_dots_window_means(self._vp(d_dots1_ptr), self._vp(d_pair_ptr), self._vp(d_shift_ptr), self._vp(d_count1_ptr),
+                                               int(max1), int(width), int(height), int(win), int(step), int(min_count), int(anchor),
+                                               self._vp(d_vectors_ptr), self._vp(d_flags_ptr), self._vp(stream))
+        self._check(rc, "photon_dots_window_means")
+
+    def correlation_predictor(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, eps: float = 0.1,
+                              threshold: float = 2.0):
+        """A predictor for track_dots from one pass of window correlation: photon_piv_correlate, then photon_piv_validate
+        (median test, replacement, 3 x 3 smoothing) -- pass 0 of correlate_deform.  Returns the smoothed field as a torch
+        device tensor [n_rows, n_cols, 2], queued on the current stream: hand it to track_dots as predictor=(field, win, step)
+        and a displacement larger than the spacing of the dots no longer pairs a dot with its neighbour."""
+        import torch
+        from . import piv_correlation as pc
+        radius = int(win) // 2 if radius is None else int(radius)
+        dev = torch.device("cuda", torch.cuda.current_device())
+        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
+        if a.dim() != 2 or a.shape != b.shape:
+            raise ValueError("im1 and im2 must be two 2-d images of one shape")
+        h, w = a.shape
+        pc.check_arguments((h, w), win, step, radius)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
+        r, c = flg.shape
+        field, smoothed = (torch.empty((r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))
+        status = torch.empty((r, c), dtype=torch.int32, device=dev)
+        self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smoothed.data_ptr(), status.data_ptr(), eps, threshold,
+                          stream)
+        return smoothed
+
+    def track_dots(self, im1, im2, threshold: float, box_radius: int = 3, sigma_w: float = 1.0, iterations: int = 4,
+                   background: float = 0.0, radius: float = 3.0, predictor=None, max_dots: Optional[int] = None, grid=None,
+                   relative: bool = False, reject_mask: int = 0) -> dict:
+        """Per-dot shifts of an image pair (section 8; model: photon_amd.dot_tracking.track_dots_model, the same keys):
+        detect and locate the dots of both frames, pair them within `radius` px of frame 1's position (plus the predictor:
+        None, or (field [n_rows, n_cols, 2 or 4], win, step) as correlate / correlate_deform return it), and with
+        grid = (win, step, min_count, anchor) average the pairs onto section 5's window grid.  relative: `threshold` is a
+        fraction of each image's maximum, taken on the device.  max_dots None = one dot per 32 pixels, at least 1024.
+        Returns numpy: dots1 / dots2 [n, 4] = x, y, peak, diameter; status1 / status2; count1 / count2 (what detect
+        found: above max_dots the first max_dots were kept); pair [n1]; shift [n1, 4] = x_mid, y_mid, dx, dy; npaired;
+        vectors [n_rows, n_cols, 4] = mean dx, mean dy, count, rms and flags with a grid.  Everything runs on the current
+        stream from torch-allocated buffers; the host waits once, for the result."""
+        import torch
+        from . import dot_tracking as dt
+        from . import piv_correlation as pc
+        dev = torch.device("cuda", torch.cuda.current_device())
+        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
+        if a.dim() != 2 or a.shape != b.shape:
+            raise ValueError("im1 and im2 must be two 2-d images of one shape")
+        h, w = a.shape
+        cap = dt.default_max_dots((h, w)) if max_dots is None else int(max_dots)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        det_bytes = self.dots_scratch_bytes(w, h)
+        mat_bytes = self.dots_scratch_bytes(w, h, radius, cap, cap) if cap >= 1 and radius > 0 else 0
+        scratch = torch.empty(max(det_bytes, mat_bytes, 16), dtype=torch.uint8, device=dev)   # the calls are ordered on one stream
+        ints = torch.empty((2, cap + 1), dtype=torch.int32, device=dev)        # per frame: peaks [cap], count
+        dots = torch.empty((2, cap, 4), dtype=torch.float32, device=dev)
+        status = torch.empty((2, cap), dtype=torch.int32, device=dev)
+        top = torch.empty(2, dtype=torch.float32, device=dev)
+        for f, im in enumerate((a, b)):
+            d_scale = 0
+            if relative:
+                d_scale = top[f].data_ptr()
+                self.dots_image_max(im.data_ptr(), w, h, d_scale, stream)
+            self.dots_detect(im.data_ptr(), w, h, threshold, d_scale, cap, ints[f].data_ptr(), ints[f, cap:].data_ptr(),
+                             scratch.data_ptr(), scratch.numel(), stream)
+            self.dots_fit(im.data_ptr(), w, h, ints[f].data_ptr(), ints[f, cap:].data_ptr(), cap, box_radius, sigma_w, iterations,
+                          background, dots[f].data_ptr(), status[f].data_ptr(), stream)
+        pair = torch.empty(cap + 1, dtype=torch.int32, device=dev)             # pair [cap], npaired
+        shift = torch.empty((cap, 4), dtype=torch.float32, device=dev)
+        field_args = {}
+        if predictor is not None:
+            field, pwin, pstep = predictor
+            fld = torch.as_tensor(field).to(device=dev, dtype=torch.float32).contiguous()
+            if fld.dim() != 3 or fld.shape[2] not in (2, 4):
+                raise ValueError("the predictor field must be [n_rows, n_cols, 2 or 4]")
+            field_args = dict(d_field_ptr=fld.data_ptr(), field_stride=int(fld.shape[2]), n_rows=int(fld.shape[0]), n_cols=int(fld.shape[1]),
+                              win=int(pwin), step=int(pstep))
+        self.dots_match(dots[0].data_ptr(), status[0].data_ptr(), ints[0, cap:].data_ptr(), cap, dots[1].data_ptr(), status[1].data_ptr(),
+                        ints[1, cap:].data_ptr(), cap, radius, w, h, pair.data_ptr(), shift.data_ptr(), pair[cap:].data_ptr(),
+                        scratch.data_ptr(), scratch.numel(), reject_mask=reject_mask, stream=stream, **field_args)
+        vectors = flags = None
+        if grid is not None:
+            win, step, min_count, anchor = grid
+            if int(win) < 1 or int(step) < 1 or h < int(win) or w < int(win):
+                raise ValueError(f"no window grid of win {win}, step {step} on a {h} x {w} image")
+            r, c = pc.grid_shape((h, w), win, step)
+            vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
+            flags = torch.empty((r, c), dtype=torch.int32, device=dev)
+            self.dots_window_means(dots[0].data_ptr(), pair.data_ptr(), shift.data_ptr(), ints[0, cap:].data_ptr(), cap, w, h, win, step,
+                                   min_count, anchor, vectors.data_ptr(), flags.data_ptr(), stream)
+        counts = ints[:, cap].cpu().numpy()                                     # the one host wait
+        n1, n2 = (min(int(c), cap) for c in counts)
+        out = {"dots1": dots[0, :n1].cpu().numpy(), "dots2": dots[1, :n2].cpu().numpy(), "status1": status[0, :n1].cpu().numpy(),
+               "status2": status[1, :n2].cpu().numpy(), "count1": int(counts[0]), "count2": int(counts[1]),
+               "pair": pair[:n1].cpu().numpy(), "shift": shift[:n1].cpu().numpy(), "npaired": int(pair[cap].item())}
+        if grid is not None:
+            out["vectors"], out["flags"] = vectors.cpu().numpy(), flags.cpu().numpy()
+        return out
 
     # ---- gradient-field integration on the device (photon_integrate_gradient) ------------------------------------
     def integrate_gradient_ptr(self, d_gx_ptr: int, d_gy_ptr: int, nx: int, ny: int, d_phi_ptr: int, d_w_ptr: int = 0,
