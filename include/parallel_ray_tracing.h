@@ -329,7 +329,7 @@ int photon_scene_set_ray_order(photon_scene_t *scene, int mode);
  * train.  start_ray_tracing reads PHOTON_SKIP_DOOMED=0|1.
  * WITHOUT a volume the same switch keeps the dead LENS SAMPLES from being launched at all: ray k of every source is aimed at
  * the same point of the lens plane (.cu:123-141), so which samples miss the aperture is decided once per scene, from the
- * caller's source arrays, with a bound that holds for every source (photon_scene.hip, live_lens_samples); the volume-free
+ * caller's source arrays, with a bound that holds for every source (photon_cull.hip, live_lens_samples); the volume-free
  * PIV frame of the reference's sample data (5e8 rays) 25.6 -> 15.5 ms, the image bit for bit.  rays_launched keeps counting
  * sources x rays_per_source.  photon_scene_live_rays: how many lens samples per source such a launch keeps (rays_per_source
  * when none can be ruled out: narrow cones, tilted or off-axis first element, BOS patterns generated on the device; PIV fields
@@ -339,7 +339,7 @@ int photon_scene_live_rays(const photon_scene_t *scene);
 /* the kept lens samples themselves, ascending (out: room for `capacity` >= photon_scene_live_rays entries); returns their number, -1 on a bad argument */
 int photon_scene_live_samples(const photon_scene_t *scene, int *out, int capacity);
 /* The same switch also leaves out, on the volume-free path, the SOURCES whose image cannot fall on the sensor (one biconvex
- * thick lens or one thin lens on the axis, no sensor-position noise, no dumps: photon_scene.hip, source_misses_sensor --
+ * thick lens or one thin lens on the axis, no sensor-position noise, no dumps: photon_cull.hip, source_misses_sensor --
  * an interval bound on where the lens can put the source's rays; photon's sample PIV frame draws particles over a field 1.5 x
  * wider than the camera sees, run_simulation_02.py:956-958).  The image is unchanged.  The list is made once per scene, by its
  * first volume-free photon_trace (or by the query below): one small kernel and two small copies on the null stream, for which

@@ -18,7 +18,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB_NAME = "libparallel_ray_tracing.so"
 LIB_PATH = os.path.join(HERE, LIB_NAME)
 
-UNITS = ("photon_pool", "photon_volume", "photon_scene", "photon_march", "photon_march_linear", "photon_march_cubic", "photon_march_extra",
+UNITS = ("photon_pool", "photon_volume", "photon_scene", "photon_cull", "photon_march", "photon_march_linear", "photon_march_cubic", "photon_march_extra",
          "photon_sensor", "photon_moments", "photon_trace", "photon_post", "photon_piv", "photon_piv_deform", "photon_dots", "photon_density", "photon_abi", "photon_sort", "photon_flow", "photon_version")
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 HEADERS = [os.path.join(CSRC, h) for h in ("device_vec.hpp", "device_volume.hpp", "device_volume_coop.hpp", "device_volume_extra.hpp", "device_optics.hpp",

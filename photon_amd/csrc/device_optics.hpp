@@ -65,7 +65,7 @@ struct SceneDev {
     // coherent when the cone is as wide as the aperture (PIV through a volume).
     int ray_order;
     // slots per source of THIS launch and what lens sample each stands for: rays_per_source and the identity (nullptr), or -- the
-    // volume-free path -- only the lens samples that can reach the first element's aperture from any source (photon_scene.hip)
+    // volume-free path -- only the lens samples that can reach the first element's aperture from any source (photon_cull.hip)
     int slot_rays;
     const int *slot_map;
     const int *src_perm;                // spatial order of THIS launch's sources (lens-major only); nullptr = identity
@@ -289,7 +289,7 @@ __device__ __forceinline__ float front_axis_distance(const element_data_t &e, f3
 
 // Stage 1a for one launch slot (parallel_ray_tracing.cu:2004-2082): generate the ray and move it into the volume's world frame;
 // a ray aimed so far outside the first element's aperture that no deflection the volume can produce brings it back
-// (SceneDev::doom_margin, launch_chunk) is marked dead (NaN position): the march skips it, the sensor stage drops it as it
+// (SceneDev::doom_margin, make_trace_plan) is marked dead (NaN position): the march skips it, the sensor stage drops it as it
 // would after the lens.  ONE body for raygen_kernel and for the march kernels' own prologue (march_kernel.hpp): same bits.
 struct RayPD { f3 p, d; };
 __device__ __forceinline__ RayPD generate_state(const SceneDev &sc, long long src_begin, unsigned n_rays, unsigned r, double &radiance) {

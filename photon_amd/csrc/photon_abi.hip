@@ -340,6 +340,7 @@ int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume
     std::vector<float> host(nsave), host_inter(ninter);
     const DumpDev dump{d.pos.p, d.dir.p, a.num_lightrays_save, d.inter_pos.p, d.inter_dir.p, inter ? a.num_intermediate_save : 0};
     const long long kmax = (num_particles + chunk - 1) / chunk;
+    const TracePlan plan = make_trace_plan(scene, vol, a.algorithm, dump.final_pos || dump.inter_pos, d_records != nullptr);
     { const int rc = begin_accumulate(scene, nullptr); if (rc) return rc; }
     if (d_records) { const int rc = clear_records(d_records, 0, num_particles, nullptr); if (rc) return rc; }
     for (long long k = 0; k < kmax; k++) {
@@ -349,8 +350,8 @@ int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume
             PH_CHECK(hipMemsetAsync(d.inter_pos.p, 0xFF, ninter * sizeof(float), nullptr));
             PH_CHECK(hipMemsetAsync(d.inter_dir.p, 0xFF, ninter * sizeof(float), nullptr));
         }
-        const int rc = launch_chunk(scene, vol, a.algorithm, k * chunk, std::min(num_particles, (k + 1) * chunk), dump, nullptr, nullptr, nullptr,
-                                    d_records);
+        const LaunchRange range = next_launch(scene, plan, k * chunk, std::min(num_particles, (k + 1) * chunk));     // the whole chunk
+        const int rc = launch_chunk(scene, vol, a.algorithm, plan, range, dump, nullptr, nullptr, nullptr, d_records);
         if (rc) return rc;
         bool wrote = true;                                              // a dump that cannot be written fails the call
         PH_CHECK(hipMemcpy(host.data(), d.pos.p, nsave * sizeof(float), hipMemcpyDeviceToHost));

@@ -4,11 +4,15 @@
 //   photon_pool.hip          block cache, allocation helper, peer-access record
 //   photon_volume.hip        NRRD parser, gradient-volume build + B-spline prefilter kernels, volume handle API, volume cache
 //   photon_scene.hip         scene / source handles, on-device scene generation, the glibc rand table
+//   photon_cull.hip          what a launch may leave out (dead lens samples, sources off the sensor, doomed rays), the plan of a trace
 //   photon_march.hip         host side of a march launch: segment planner, work queues, wave-timing profile
 //   photon_march_{linear,cubic,extra}.hip   the march kernels (march_kernel.hpp), one unit per sampler
 //   photon_sensor.hip        ray generation, sensor stage (lens / aperture / splats), finalize
 //   photon_trace.hip         launch loop of a trace, photon_trace, statistics
 //   photon_post.hip          sensor post-processing, the streaming-copy yardstick
+//   photon_piv.hip           cross-correlation of image pairs: PIV / BOS displacement fields
+//   photon_dots.hip          BOS dot tracking: per-dot shifts from an image pair
+//   photon_density.hip       BOS displacement fields integrated into projected density
 //   photon_abi.hip           start_ray_tracing, PHOTON_DEVICES (several devices inside one call)
 //   photon_sort.hip          Morton order of a range of sources
 //   photon_moments.hip       per-source sensor moments: the reduction of a launch's moments block into records
@@ -88,7 +92,7 @@ struct photon_sources {                 // light-field sources generated in HBM 
     double *radiance = nullptr;
     int *diameter_index = nullptr;
     // where the generator put them, when it can say (the PIV field's box): the largest distance from the z axis and the z range --
-    // what the static skip of dead lens samples needs to know about sources it cannot read (photon_scene.hip, live_lens_samples)
+    // what the static skip of dead lens samples needs to know about sources it cannot read (photon_cull.hip, live_lens_samples)
     bool have_extent = false;
     double rmax = 0, zmin = 0, zmax = 0;
 };
@@ -96,7 +100,7 @@ struct photon_sources {                 // light-field sources generated in HBM 
 struct PermEntry { long long begin = -1, end = -1; int *d_perm = nullptr; size_t capacity = 0; unsigned long long stamp = 0; };
 
 namespace photon {
-// What the source cull of the volume-free path needs beside a source's coordinates (photon_scene.hip, source_misses_sensor)
+// What the source cull of the volume-free path needs beside a source's coordinates (photon_cull.hip, source_misses_sensor)
 struct LensCull {
     bool ok = false;
     bool thin = false;                  // element 't': one refraction on the element's plane (.cu:416-503); focal = its focal length
@@ -141,10 +145,10 @@ struct photon_scene {
     const int *d_live = nullptr;        // the lens samples that can reach element 0's aperture from ANY source of this scene, ascending
     int live_count = 0;                 // (part of the upload block); == rays_per_source when none can be ruled out (or nothing is known)
     std::vector<int> live_host;         // the same list on the host (photon_scene_live_samples: tests hold the bound against exact geometry)
-    const int *d_live_sources = nullptr;    // the sources whose image can fall on the sensor (photon_scene.hip, source_misses_sensor), ascending;
+    const int *d_live_sources = nullptr;    // the sources whose image can fall on the sensor (photon_cull.hip, source_misses_sensor), ascending;
     std::vector<int> live_sources;      // part of the upload block, and the same list on the host; used by the volume-free path only
     bool live_sources_known = false;    // false: nothing could be ruled out (or the geometry is not covered): every source is launched
-    bool live_sources_tried = false;    // the device pass has run (ensure_live_sources: with the scene's first volume-free launch)
+    bool live_sources_tried = false;    // the device pass has run (ensure_live_sources: with the scene's first volume-free trace)
     photon::LensCull source_cull;       // set at creation (host arithmetic only)
     float *d_mom = nullptr;             // moments block of the launches that record per-source moments (6 planes), grown on demand
     size_t mom_rays = 0;                // entries per plane
@@ -193,14 +197,38 @@ int cached_volume(const char *path, int interpolation, photon_volume **out, Shar
 // Wait for the device before blocks of this scene go back to the cache (its kernels may still be using them); no-op for a
 // scene that never launched anything.
 void scene_quiesce(photon_scene *s);
-int ensure_live_sources(photon_scene *s);
 void free_resume_state(photon_scene *s);
 int ensure_workspace(photon_scene *s, size_t rays);
+
+// ---- photon_cull.hip ----
+// scene creation: the lens samples that can reach the first aperture from some source; the constants of the source cull
+std::vector<int> live_lens_samples(const std::vector<float> &lx, const std::vector<float> &ly, const lightfield_source_t *lsp,
+                                   const photon_sources *generated, size_t n_sources, float image_distance, int num_elements,
+                                   const element_data_t *edp, const double (*center)[3], const double (*plane)[4]);
+LensCull lens_cull_setup(const std::vector<float> &lx, const std::vector<float> &ly, float image_distance, float beam_wavelength,
+                         int num_elements, const element_data_t *edp, const double (*center)[3], const double (*plane)[4],
+                         const int *sys_index, const camera_design_t *cam);
+// the scene's list of sources that can reach the sensor, made on first use (a device pass on the null stream, host waits)
+int ensure_live_sources(photon_scene *s);
+// What the launches of one trace share.  Made per trace, never kept: the scene's setters take effect on the next trace.
+struct TracePlan {
+    bool live_samples_only;             // slot_rays = live_count, slot_map = d_live
+    bool listed_sources;                // launches take slices of scene->live_sources
+    bool lens_major;                    // lens-major order over Morton-sorted sources
+    float doom_margin;                  // rays further than this outside the first aperture are not marched; 0 = off
+    int slot_rays;                      // slots per source of every launch
+    long long max_sources;              // (listed) sources per launch
+};
+TracePlan make_trace_plan(photon_scene *s, const photon_volume *vol, int algorithm, bool dumping, bool with_moments);
+// one launch of a trace: sources [begin, end) in the caller's order, of which n_sources are launched -- src_list when they are listed
+struct LaunchRange { long long begin, end, n_sources; const int *src_list; };
+LaunchRange next_launch(const photon_scene *s, const TracePlan &plan, long long begin, long long limit);
 
 // ---- photon_march.hip ----
 // The march launch of n rays whose state sits in the scene's workspace (stage 1b): persistent grid, work queues, segments.
 // gen_src_begin >= 0: no raygen_kernel has run; the march generates the rays of sources [gen_src_begin, ...) itself (algorithms 1, 2)
-int launch_march(photon_scene *s, const photon_volume *vol, int algorithm, unsigned n, unsigned long long ray_base,
+// dev: the scene as this launch sees it (launch_chunk)
+int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol, int algorithm, unsigned n, unsigned long long ray_base,
                  const InterDump &idump, bool save, hipStream_t stream, hipEvent_t ev_march_begin, long long gen_src_begin = -1);
 // Did any march wave give a segment up?  Reads (and clears) the scene's error word; the caller has synchronised.
 int march_error_check(photon_scene *scene);
@@ -217,11 +245,11 @@ int march_rays_launch_cubic(int algorithm, const VolumeDev &vol, const f4 *tex, 
 int march_rays_launch_extra(int algorithm, const VolumeDev &vol, int n, float *pos, float *dir, int *steps);
 
 // ---- photon_sensor.hip ----
-int launch_raygen(photon_scene *s, long long src_begin, unsigned n, hipStream_t stream);
+int launch_raygen(photon_scene *s, const SceneDev &dev, long long src_begin, unsigned n, hipStream_t stream);
 // the sensor stage of a launch of n rays: from the marched state (from_state) or generating its rays in place; with mom, every
 // arriving ray also lands in the launch's moments block
-int launch_sensor(photon_scene *s, bool from_state, long long src_begin, unsigned n, const DumpDev &dump, hipStream_t stream,
-                  const MomentsDev *mom = nullptr);
+int launch_sensor(photon_scene *s, const SceneDev &dev, bool from_state, long long src_begin, unsigned n, const DumpDev &dump,
+                  hipStream_t stream, const MomentsDev *mom = nullptr);
 
 // ---- photon_moments.hip ----
 constexpr int kMomentFields = 8;        // n, sum x, y, z, sum acos dx, dy, dz, sum x^2 + y^2 (include/parallel_ray_tracing.h)
@@ -234,8 +262,9 @@ int launch_finalize(photon_scene *s, float *d_image, hipStream_t stream);
 
 // ---- photon_trace.hip ----
 int begin_accumulate(photon_scene *s, hipStream_t stream);
+// One launch of a trace: decides nothing (plan, range: photon_cull.hip).
 // d_records: also the per-source moments of the launched sources (records of the scene's source list, photon_trace_moments)
-int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long long src_begin, long long src_end, DumpDev dump,
+int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, const TracePlan &plan, const LaunchRange &range, DumpDev dump,
                  hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end, double *d_records = nullptr);
 // The launch loop for sources [src_begin, src_end) into the scene's private f64 accumulator (zeroed first); timed: 0 no
 // events, 1 immediate (host waits per launch), 2 deferred (events of the open statistics window).  d_records: the records of
@@ -245,7 +274,7 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
 // zero the records of sources [src_begin, src_end) on the stream (their sources may all be culled)
 int clear_records(double *d_records, long long src_begin, long long src_end, hipStream_t stream);
 
-// photon_scene.hip: a source handle with device arrays for n sources; the extent of generated sources (live_lens_samples)
+// photon_scene.hip: a source handle with device arrays for n sources; the extent of generated sources (photon_cull.hip, live_lens_samples)
 int sources_alloc(long long n, photon_sources **out);
 void sources_set_extent(photon_sources *src, double ax, double ay, double z0, double z1);
 

@@ -206,8 +206,8 @@ extern "C" int photon_march_segments_plan(unsigned n_rays, int depth, int ray_tr
 namespace photon {
 
 // The march launch of n rays whose state sits in the scene's workspace (stage 1b): persistent grid, work queues, segments.
-int launch_march(photon_scene *s, const photon_volume *vol, int algorithm, unsigned n, unsigned long long ray_base,
-                        const InterDump &idump, bool save, hipStream_t stream, hipEvent_t ev_march_begin, long long gen_src_begin) {
+int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol, int algorithm, unsigned n, unsigned long long ray_base,
+                 const InterDump &idump, bool save, hipStream_t stream, hipEvent_t ev_march_begin, long long gen_src_begin) {
     const dim3 block(256), grid((n + 255) / 256);
     const int interp = vol->dev.interpolation;
     const f4 *tex = interp == 2 ? vol->d_coeffs : vol->d_texels;
@@ -223,7 +223,7 @@ int launch_march(photon_scene *s, const photon_volume *vol, int algorithm, unsig
     // previous segment of its group long done) and nothing indexes a ray's iterations (dumps, gradient noise).
     unsigned segments = 1;
     MarchArgs margs{};
-    if ((algorithm == 1 || algorithm == 2) && !save && !s->dev.noise.add_ngrad) {
+    if ((algorithm == 1 || algorithm == 2) && !save && !dev.noise.add_ngrad) {
         const unsigned groups = (n + 63u) / 64u;
         // resident march waves: five or six per SIMD (the launch bounds of the march kernels)
         const unsigned slots = (unsigned)s->num_cus * 4u * march_waves_of(algorithm, interp);
@@ -235,19 +235,19 @@ int launch_march(photon_scene *s, const photon_volume *vol, int algorithm, unsig
             if (segments > 1) { const int rc = ensure_resume_state(s, interp == 1, stream); if (rc) return rc; }
         }
     }
-    margs.vol = vol->dev; margs.tex = tex; margs.n_rays = n; margs.st = s->ws; margs.counters = s->d_counters; margs.noise = s->dev.noise;
+    margs.vol = vol->dev; margs.tex = tex; margs.n_rays = n; margs.st = s->ws; margs.counters = s->d_counters; margs.noise = dev.noise;
     margs.ray_base = ray_base; margs.idump = idump; margs.queue = s->d_queue; margs.profile = profile; margs.segments = segments;
     margs.epoch = s->march_epoch; margs.error = scene_error_word(s);
-    if (gen_src_begin >= 0 && (algorithm == 1 || algorithm == 2)) { margs.gen = 1u; margs.src_begin = gen_src_begin; margs.scene = s->dev; }
+    if (gen_src_begin >= 0 && (algorithm == 1 || algorithm == 2)) { margs.gen = 1u; margs.src_begin = gen_src_begin; margs.scene = dev; }
     // queue chunks: small ones (tail balance) for the tricubic kernels where neighbouring groups are neighbouring SOURCES and
     // the volume is small enough for every L2 to hold what its waves touch; lens-major launches (neighbouring groups share
     // a lens tile, their rays fan out over the whole volume) and large volumes keep the L2-friendly 128 -- C5 at a
     // quarter: 11.0 GB of HBM traffic per launch with 16-group chunks against 3.8 GB with 128, 38.03 against 37.94 ms
-    margs.chunk_shift = interp == 2 && s->dev.ray_order == 0 && (size_t)vol->dev.nx * vol->dev.ny * vol->dev.nz <= ((size_t)1 << 24)
+    margs.chunk_shift = interp == 2 && dev.ray_order == 0 && (size_t)vol->dev.nx * vol->dev.ny * vol->dev.nz <= ((size_t)1 << 24)
                             ? kChunkShiftCubic : kChunkShiftLinear;
     int rc;
     if (algorithm != 1 && algorithm != 2) rc = march_launch_extra(algorithm, grid, block, stream, vol->dev, n, s->ws, s->d_counters);
-    else if (interp == 1) rc = march_launch_linear(algorithm, save, algorithm == 1 && s->dev.noise.add_ngrad != 0, segments > 1, mgrid, mblock, stream, margs);
+    else if (interp == 1) rc = march_launch_linear(algorithm, save, algorithm == 1 && dev.noise.add_ngrad != 0, segments > 1, mgrid, mblock, stream, margs);
     else rc = march_launch_cubic(algorithm, segments > 1, mgrid, mblock, stream, margs);
     if (rc) return rc;
     PH_CHECK(hipGetLastError());
@@ -308,7 +308,7 @@ extern "C" int photon_trace_volume_rays_queued(const photon_volume_t *vol, int r
         for (int c = 0; c < 6; c++) PH_CHECK(hipMemcpy(arrays[c], soa.data() + (size_t)c * n, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
         const InterDump no_dump{nullptr, nullptr, 0, 0, 0u};
         sc.launched = true;
-        { const int rc = launch_march(&sc, vol, ray_tracing_algorithm, (unsigned)n, 0ull, no_dump, false, nullptr, nullptr); if (rc) return rc; }
+        { const int rc = launch_march(&sc, sc.dev, vol, ray_tracing_algorithm, (unsigned)n, 0ull, no_dump, false, nullptr, nullptr); if (rc) return rc; }
         PH_CHECK(hipDeviceSynchronize());
         { const int rc = march_error_check(&sc); if (rc) return rc; }
         for (int c = 0; c < 6; c++) PH_CHECK(hipMemcpy(soa.data() + (size_t)c * n, arrays[c], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));

@@ -138,36 +138,36 @@ __global__ __launch_bounds__(256) void finalize_image_kernel(float *__restrict__
 
 namespace photon {
 
-int launch_raygen(photon_scene *s, long long src_begin, unsigned n, hipStream_t stream) {
-    hipLaunchKernelGGL(raygen_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, s->dev, src_begin, n, s->ws);
+int launch_raygen(photon_scene *s, const SceneDev &dev, long long src_begin, unsigned n, hipStream_t stream) {
+    hipLaunchKernelGGL(raygen_kernel, dim3((n + 255) / 256), dim3(256), 0, stream, dev, src_begin, n, s->ws);
     PH_CHECK(hipGetLastError());
     return 0;
 }
 
 // The instantiation of sensor_kernel that the scene's camera, the launch's ray source and the moments block call for.
 template <bool MOM>
-static void launch_sensor_kernel(photon_scene *s, bool from_state, bool taps_only, long long src_begin, unsigned n, const DumpDev &dump,
-                                 hipStream_t stream, const MomentsDev &mom) {
+static void launch_sensor_kernel(photon_scene *s, const SceneDev &dev, bool from_state, bool taps_only, long long src_begin, unsigned n,
+                                 const DumpDev &dump, hipStream_t stream, const MomentsDev &mom) {
     const dim3 block(256), grid((n + 255) / 256);
-#define PH_SENSOR_ARGS grid, block, 0, stream, s->dev, src_begin, n, s->ws, s->d_acc, dump, s->d_counters, mom
+#define PH_SENSOR_ARGS grid, block, 0, stream, dev, src_begin, n, s->ws, s->d_acc, dump, s->d_counters, mom
     if (taps_only && !from_state) hipLaunchKernelGGL((sensor_kernel<false, false, 2, MOM>), PH_SENSOR_ARGS);
     else if (taps_only) hipLaunchKernelGGL((sensor_kernel<true, false, 2, MOM>), PH_SENSOR_ARGS);
     else if (from_state) {
-        if (s->dev.train_mode) hipLaunchKernelGGL((sensor_kernel<true, true, 0, MOM>), PH_SENSOR_ARGS);
+        if (dev.train_mode) hipLaunchKernelGGL((sensor_kernel<true, true, 0, MOM>), PH_SENSOR_ARGS);
         else hipLaunchKernelGGL((sensor_kernel<true, false, 0, MOM>), PH_SENSOR_ARGS);
     } else {
-        if (s->dev.train_mode) hipLaunchKernelGGL((sensor_kernel<false, true, 0, MOM>), PH_SENSOR_ARGS);
+        if (dev.train_mode) hipLaunchKernelGGL((sensor_kernel<false, true, 0, MOM>), PH_SENSOR_ARGS);
         else hipLaunchKernelGGL((sensor_kernel<false, false, 0, MOM>), PH_SENSOR_ARGS);
     }
 #undef PH_SENSOR_ARGS
 }
 
-int launch_sensor(photon_scene *s, bool from_state, long long src_begin, unsigned n, const DumpDev &dump, hipStream_t stream,
-                  const MomentsDev *mom) {
+int launch_sensor(photon_scene *s, const SceneDev &dev, bool from_state, long long src_begin, unsigned n, const DumpDev &dump,
+                  hipStream_t stream, const MomentsDev *mom) {
     // a camera without diffraction behind a real first element: the 4-pixel-only instantiations (the default element path; after a march: C5)
-    const bool taps_only = !s->dev.train_mode && !s->dev.cam.implement_diffraction && s->dev.elems[0].element_type != 'n';
-    if (mom) launch_sensor_kernel<true>(s, from_state, taps_only, src_begin, n, dump, stream, *mom);
-    else launch_sensor_kernel<false>(s, from_state, taps_only, src_begin, n, dump, stream, MomentsDev{});
+    const bool taps_only = !dev.train_mode && !dev.cam.implement_diffraction && dev.elems[0].element_type != 'n';
+    if (mom) launch_sensor_kernel<true>(s, dev, from_state, taps_only, src_begin, n, dump, stream, *mom);
+    else launch_sensor_kernel<false>(s, dev, from_state, taps_only, src_begin, n, dump, stream, MomentsDev{});
     PH_CHECK(hipGetLastError());
     return 0;
 }

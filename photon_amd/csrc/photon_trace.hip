@@ -1,5 +1,5 @@
 // photon_trace.hip - the launch loop of a trace (the reference's chunk loop, parallel_ray_tracing.cu:3505-3558, on
-// inputs resident in HBM): ray order and doomed-ray rules per launch, raygen -> march -> sensor stage, photon_trace and
+// inputs resident in HBM): one launch as its plan says (photon_cull.hip), raygen -> march -> sensor stage, photon_trace and
 // the statistics window.  Host code only: every kernel is launched through the unit that defines it.
 #include <algorithm>
 #include <cmath>
@@ -19,12 +19,14 @@ using namespace photon;
 // The permutation of a launched range is kept (a few ranges: a job's chunks, a caller alternating shards), and the sort's
 // scratch lives in the scene: a lens-major launch of a range seen before costs nothing, a new range costs the sort's
 // kernels on the stream -- no allocation, no host wait, so photon_trace without stats stays asynchronous.
-static int ensure_source_order(photon_scene *s, long long src_begin, long long src_end, hipStream_t stream, const int **perm_out) {
+// The slot of the range, with room for it: its own when the range was seen before, else the least recently used one, marked
+// empty (begin < 0) until sort_sources has filled it.
+static int source_order_slot(photon_scene *s, long long src_begin, long long src_end, PermEntry **out) {
     const size_t n = (size_t)(src_end - src_begin);
     s->perm_clock++;
     PermEntry *slot = nullptr;
     for (auto &p : s->perms)
-        if (p.d_perm && p.begin == src_begin && p.end == src_end) { p.stamp = s->perm_clock; *perm_out = p.d_perm; return 0; }
+        if (p.d_perm && p.begin == src_begin && p.end == src_end) { p.stamp = s->perm_clock; *out = &p; return 0; }
     for (auto &p : s->perms)                                            // least recently used (an empty one first)
         if (!slot || (!p.d_perm && slot->d_perm) || (!!p.d_perm == !!slot->d_perm && p.stamp < slot->stamp)) slot = &p;
     slot->begin = slot->end = -1;
@@ -34,105 +36,20 @@ static int ensure_source_order(photon_scene *s, long long src_begin, long long s
         PH_CHECK(pool_malloc((void **)&slot->d_perm, std::max<size_t>(n, 1) * sizeof(int)));
         slot->capacity = n;
     }
-    const int rc = photon_morton_order(s->dev.sx, s->dev.sy, (int)src_begin, (long long)n, slot->d_perm, stream, &s->sort_scratch);
+    *out = slot;
+    return 0;
+}
+static int sort_sources(photon_scene *s, PermEntry *slot, long long src_begin, long long src_end, hipStream_t stream) {
+    const int rc = photon_morton_order(s->dev.sx, s->dev.sy, (int)src_begin, src_end - src_begin, slot->d_perm, stream, &s->sort_scratch);
     if (rc) return rc;
     slot->begin = src_begin; slot->end = src_end; slot->stamp = s->perm_clock;
-    *perm_out = slot->d_perm;
     return 0;
 }
 
-// Which order a launch uses.  Lens-major pays off when the ray cone of a source is wider than the volume's
-// texels where it crosses the volume (then the 64 rays of ONE source fan out over many texel blocks, while
-// 64 neighbouring sources aimed at one lens point stay together); source-major otherwise (BOS: the cone is a
-// micron wide) and whenever something indexes rays by the reference's launch order (ray dumps) or the march
-// needs per-ray ids (gradient noise).
-static bool use_lens_major(const photon_scene *s, const photon_volume *vol, const DumpDev &dump) {
-    if (!vol || dump.final_pos || dump.inter_pos || s->dev.noise.add_ngrad || s->dev.rays_per_source < 2) return false;
-    if (s->ray_order_mode != 2) return s->ray_order_mode == 1;
-    const double z_obj = (double)s->dev.object_distance + s->dev.z_offset;             // camera frame
-    const double z_face = (double)vol->dev.min_bound.z + s->dev.z_offset + 750e3;      // the volume's lens-side face
-    const double span = z_obj - s->lens_z;
-    if (!(span > 0)) return false;
-    double frac = (z_obj - z_face) / span;
-    frac = frac < 0 ? 0 : (frac > 1 ? 1 : frac);
-    const double cone = (double)s->dev.ratio * s->dev.lens_pitch * frac;               // cone diameter at that face
-    const photon_volume_info_t &i = vol->info;
-    const double texel = std::min((double)i.grid_spacing[0], std::min((double)i.grid_spacing[1], (double)i.grid_spacing[2]));
-    return cone > texel;
-}
-
-// Rays that cannot reach the sensor need not be marched.  The reference kills a ray whose intersection with the
-// first element's front surface lies more than pitch/2 from the axis (.cu:447, 560-566) -- for a full-aperture
-// cone that is half of all rays, because the lens-sample radius goes up to pitch, not pitch/2 (.cu:123-124).
-// The volume only bends a ray by a bounded angle: |d(n t)/ds| = |grad n| <= G, so after a path of length L inside
-// the volume its direction is off by at most G L / n_min, and its footprint on the lens by at most that angle times
-// the distance still to go (plus the walk-off inside the volume).  Returns that bound, times a safety factor
-// that also covers the tricubic sampler's overshoot and the integrator's error, plus a thousandth of the
-// aperture; 0 when the skip does not apply.
-// the reference's element path (optical_system without the working train) applies element 0 once per single-member group of
-// the sequence: is there one, and is element 0 a lens with an aperture test?
-static bool first_aperture_applies(const photon_scene *s) {
-    if (s->dev.train_mode != 0) return false;
-    const char type = s->dev.elems[0].element_type;
-    if (type != 'l' && type != 't') return false;
-    bool applied = false;
-    const int n = std::min(s->dev.num_elements, kMaxElements);
-    int seq = 0;
-    for (int k = 0; k < n; k++) seq = std::max(seq, s->dev.sys_index[k]);
-    for (int idx = 0; idx < seq && !applied; idx++) {
-        int count = 0;
-        for (int k = 0; k < n; k++) count += (seq - s->dev.sys_index[k] == idx);
-        applied = count == 1;
-    }
-    return applied;
-}
-
-static float doom_margin(const photon_scene *s, const photon_volume *vol, int algorithm, const DumpDev &dump) {
-    if (!s->skip_doomed || !vol || (algorithm != 1 && algorithm != 2) || dump.final_pos || dump.inter_pos) return 0.f;
-    if (s->dev.noise.add_ngrad || !first_aperture_applies(s)) return 0.f;
-    const VolumeDev &v = vol->dev;
-    const double ex = (double)v.max_bound.x - v.min_bound.x, ey = (double)v.max_bound.y - v.min_bound.y,
-                 ez = (double)v.max_bound.z - v.min_bound.z;
-    const double L = sqrt(ex * ex + ey * ey + ez * ez);
-    const double n_min = 1.0 + std::min(0.0, (double)v.data_min);
-    const double angle = (double)vol->grad_max * L / n_min;
-    const double z_obj = (double)s->dev.object_distance + s->dev.z_offset;
-    const double to_lens = fabs(z_obj - s->lens_z) + L;                 // generous: the whole object-lens distance
-    const double pitch = s->dev.elems[0].element_geometry.pitch;
-    const double margin = 8.0 * angle * (to_lens + L) + 1e-3 * pitch;
-    if (!(margin == margin) || !(pitch > 0)) return 0.f;
-    return (float)margin;
-}
-
-namespace photon {
-
-int begin_accumulate(photon_scene *s, hipStream_t stream) {
-    const size_t npix = (size_t)s->dev.cam.x_pixel_number * s->dev.cam.y_pixel_number;
-    s->launched = true;                                     // the fill and, later, the finalize kernel use d_acc even when no source is traced
-    if (!s->acc_clean) PH_CHECK(hipMemsetAsync(s->d_acc, 0, npix * sizeof(double), stream));      // else: left zeroed by the last finalize
-    s->acc_clean = false;
-    return 0;
-}
-
-// Without a volume only the lens samples that can reach the first aperture are launched (photon_scene.hip, live_lens_samples):
-// the dead ones would be generated, meet the element's front surface and be dropped -- half of a full-aperture PIV cone.
-static bool launches_live_samples_only(const photon_scene *s, const photon_volume *vol, const DumpDev &dump) {
-    return !vol && s->skip_doomed && s->d_live && s->live_count < s->dev.rays_per_source && !dump.final_pos && !dump.inter_pos &&
-           first_aperture_applies(s);
-}
-// ... and only the sources whose image can fall on the sensor (photon_scene.hip, source_misses_sensor): same conditions, no
-// sensor-position noise (unbounded), the scene's source list as it was created
-static bool launches_live_sources_only(photon_scene *s, const photon_volume *vol, const DumpDev &dump) {
-    if (vol || !s->skip_doomed || dump.final_pos || dump.inter_pos || s->dev.noise.add_pos || !first_aperture_applies(s)) return false;
-    if (ensure_live_sources(s)) return false;               // the scene's first volume-free launch decides the list (a failure: everything is launched)
-    return s->live_sources_known;
-}
-
-// The moments block of a launch of `places` sources: six planes of places x rays_per_source floats (grown on demand), the x
-// plane prefilled with NaN on the launch's stream.  places x rays_per_source <= kMaxRaysPerLaunch (trace_accumulate caps the
-// sources of a launch by it), so the block stays below 24 B x kMaxRaysPerLaunch = 1.5 GiB.
-static int moments_block(photon_scene *s, unsigned places, hipStream_t stream, MomentsDev *out) {
-    const size_t rays = (size_t)places * (unsigned)s->dev.rays_per_source;
+// Room for the moments block of a launch of `places` sources: six planes of places x rays_per_source floats (grown on demand).
+// places x rays_per_source <= kMaxRaysPerLaunch (make_trace_plan caps the sources of a launch by it), so the block stays below
+// 24 B x kMaxRaysPerLaunch = 1.5 GiB.
+static int moments_block(photon_scene *s, size_t rays, MomentsDev *out) {
     if (rays > kMaxRaysPerLaunch) {
         fprintf(stderr, "photon: a moments block of %zu rays exceeds the %u-ray limit per launch\n", rays, kMaxRaysPerLaunch);
         return 1;
@@ -146,76 +63,64 @@ static int moments_block(photon_scene *s, unsigned places, hipStream_t stream, M
     float *f = s->d_mom;
     const size_t stride = s->mom_rays;
     *out = MomentsDev{f, f + stride, f + 2 * stride, f + 3 * stride, f + 4 * stride, f + 5 * stride};
-    PH_CHECK(hipMemsetAsync(out->x, 0xFF, rays * sizeof(float), stream));      // all-ones = NaN: "did not arrive"
     return 0;
 }
 
-int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, long long src_begin,
-                        long long src_end, DumpDev dump, hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end,
-                        double *d_records) {
-    const bool live_only = launches_live_samples_only(s, vol, dump);
-    s->dev.slot_rays = live_only ? s->live_count : s->dev.rays_per_source;
-    s->dev.slot_map = live_only ? s->d_live : nullptr;
-    s->dev.src_list = nullptr;
-    long long n_sources = src_end - src_begin;
-    if (launches_live_sources_only(s, vol, dump)) {
-        const auto lo = std::lower_bound(s->live_sources.begin(), s->live_sources.end(), (int)src_begin);
-        const auto hi = std::lower_bound(lo, s->live_sources.end(), (int)src_end);
-        n_sources = hi - lo;
-        s->dev.src_list = s->d_live_sources + (lo - s->live_sources.begin());
-    }
-    const unsigned long long n64 = (unsigned long long)n_sources * (unsigned)s->dev.slot_rays;
+namespace photon {
+
+int begin_accumulate(photon_scene *s, hipStream_t stream) {
+    const size_t npix = (size_t)s->dev.cam.x_pixel_number * s->dev.cam.y_pixel_number;
+    s->launched = true;                                     // the fill and, later, the finalize kernel use d_acc even when no source is traced
+    if (!s->acc_clean) PH_CHECK(hipMemsetAsync(s->d_acc, 0, npix * sizeof(double), stream));      // else: left zeroed by the last finalize
+    s->acc_clean = false;
+    return 0;
+}
+
+int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, const TracePlan &plan, const LaunchRange &range, DumpDev dump,
+                 hipStream_t stream, hipEvent_t ev_march_begin, hipEvent_t ev_march_end, double *d_records) {
+    const long long src_begin = range.begin, src_end = range.end;
+    const unsigned long long n64 = (unsigned long long)range.n_sources * (unsigned)plan.slot_rays;
     if (n64 == 0) return 0;
     if (n64 > kMaxRaysPerLaunch) {
         fprintf(stderr, "photon: a launch of %llu rays (sources [%lld, %lld) x %d) exceeds the %u-ray limit per launch\n", n64,
                 src_begin, src_end, s->dev.rays_per_source, kMaxRaysPerLaunch);
         return 1;
     }
-    const unsigned n = (unsigned)n64;
+    const unsigned n = (unsigned)n64, places = (unsigned)range.n_sources;
+    // Room first: whatever has to grow waits for the scene's earlier launches (scene_quiesce, which clears `launched`) ...
+    const size_t mom_rays = (size_t)places * (unsigned)s->dev.rays_per_source;
     MomentsDev mom{};
-    if (d_records) {
-        s->launched = true;                                     // the prefill
-        const int rc = moments_block(s, (unsigned)n_sources, stream, &mom);
-        if (rc) return rc;
-    }
+    PermEntry *order = nullptr;
+    if (d_records) { const int rc = moments_block(s, mom_rays, &mom); if (rc) return rc; }
+    if (plan.lens_major) { const int rc = source_order_slot(s, src_begin, src_end, &order); if (rc) return rc; }
+    if (vol) { const int rc = ensure_workspace(s, n); if (rc) return rc; }
+    // ... then the launch: from here on kernels of this scene may be in flight
+    s->launched = true;
+    if (d_records) PH_CHECK(hipMemsetAsync(mom.x, 0xFF, mom_rays * sizeof(float), stream));       // all-ones = NaN: "did not arrive"
+    if (order && order->begin < 0) { const int rc = sort_sources(s, order, src_begin, src_end, stream); if (rc) return rc; }
+    SceneDev dev = s->dev;                                      // the scene as this launch sees it
+    dev.slot_rays = plan.slot_rays;
+    dev.slot_map = plan.live_samples_only ? s->d_live : nullptr;
+    dev.src_list = range.src_list;
+    dev.doom_margin = plan.doom_margin;
+    dev.ray_order = order ? 1 : 0;
+    dev.src_perm = order ? order->d_perm : nullptr;
     const MomentsDev *mom_p = d_records ? &mom : nullptr;
-    s->dev.doom_margin = doom_margin(s, vol, algorithm, dump);
-    s->dev.ray_order = 0;
-    s->dev.src_perm = nullptr;
-    if (use_lens_major(s, vol, dump)) {
-        const int *perm = nullptr;
-        const int rc = ensure_source_order(s, src_begin, src_end, stream, &perm);
-        if (rc) return rc;
-        s->launched = true;                                     // the sort's kernels
-        s->dev.ray_order = 1;
-        s->dev.src_perm = perm;
-    }
     if (vol) {
-        int rc = ensure_workspace(s, n);
-        if (rc) return rc;
-        s->launched = true;                                     // from here on kernels of this scene may be in flight (scene_quiesce)
         // ray generation: the prologue of the march's first piece for Euler and RK4, a kernel of its own for the others
         const bool fold = algorithm == 1 || algorithm == 2;
-        if (!fold) {
-            rc = launch_raygen(s, src_begin, n, stream);
-            if (rc) return rc;
-        }
+        if (!fold) { const int rc = launch_raygen(s, dev, src_begin, n, stream); if (rc) return rc; }
         const int interp = vol->dev.interpolation;
-        const unsigned long long ray_base = (unsigned long long)(s->dev.source_base + src_begin) * (unsigned)s->dev.rays_per_source;
+        const unsigned long long ray_base = (unsigned long long)(dev.source_base + src_begin) * (unsigned)dev.rays_per_source;
         const InterDump idump{dump.inter_pos, dump.inter_dir, dump.inter_slots, dump.num_save, 0u};
         const bool save = dump.inter_pos != nullptr && interp == 1;     // only the trilinear branches record
-        rc = launch_march(s, vol, algorithm, n, ray_base, idump, save, stream, ev_march_begin, fold ? src_begin : -1);
+        const int rc = launch_march(s, dev, vol, algorithm, n, ray_base, idump, save, stream, ev_march_begin, fold ? src_begin : -1);
         if (rc) return rc;
         if (ev_march_end) PH_CHECK(hipEventRecord(ev_march_end, stream));
-        rc = launch_sensor(s, true, src_begin, n, dump, stream, mom_p);
-        if (rc) return rc;
-    } else {
-        s->launched = true;
-        const int rc = launch_sensor(s, false, src_begin, n, dump, stream, mom_p);
-        if (rc) return rc;
     }
+    { const int rc = launch_sensor(s, dev, vol != nullptr, src_begin, n, dump, stream, mom_p); if (rc) return rc; }
     if (!d_records) return 0;
-    return launch_moments(mom, (unsigned)n_sources, (unsigned)s->dev.rays_per_source, src_begin, s->dev.src_list, d_records, stream);
+    return launch_moments(mom, places, (unsigned)dev.rays_per_source, src_begin, dev.src_list, d_records, stream);
 }
 
 }  // namespace photon
@@ -245,23 +150,12 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
     if (rps > kMaxRaysPerLaunch) { fprintf(stderr, "photon: too many rays per source\n"); return 1; }
     float march_ms = 0.f;
     const DumpDev no_dump{nullptr, nullptr, 0, nullptr, nullptr, 0};
-    // a launch holds at most kMaxRaysPerLaunch rays: of those it really launches (the volume-free path leaves out dead lens samples
-    // and sources that miss the sensor -- the sample PIV frame's 5e8 rays go in two launches, not eight)
-    const unsigned slot_rays = launches_live_samples_only(scene, vol, no_dump) ? (unsigned)scene->live_count : rps;
-    // with moments, also a moments block of at most kMaxRaysPerLaunch entries: it is indexed by lens sample, not by slot
-    const long long max_sources = std::max<long long>(1, kMaxRaysPerLaunch / (d_records ? rps : slot_rays));
-    const bool listed = launches_live_sources_only(scene, vol, no_dump);
+    const TracePlan plan = make_trace_plan(scene, vol, ray_tracing_algorithm, false, d_records != nullptr);
     { const int rc = begin_accumulate(scene, stream); if (rc) return rc; }
     if (d_records) { const int rc = clear_records(d_records, src_begin, src_end, stream); if (rc) return rc; }
-    for (long long b = src_begin, e = src_begin; b < src_end; b = e) {
-        e = std::min<long long>(src_end, b + max_sources);
-        if (listed) {                                           // up to max_sources LISTED sources: the range ends before the next one
-            const auto &ls = scene->live_sources;
-            const auto lo = std::lower_bound(ls.begin(), ls.end(), (int)b);
-            e = (ls.end() - lo) > max_sources ? (long long)lo[max_sources] : src_end;
-            e = std::min<long long>(e, src_end);
-            if (e <= b) e = src_end;                            // (cannot happen: lo[max_sources] > *lo >= b)
-        }
+    for (long long b = src_begin; b < src_end;) {
+        const LaunchRange r = next_launch(scene, plan, b, src_end);
+        b = r.end;
         hipEvent_t e0 = nullptr, e1 = nullptr;
         if (timed == 1 && vol) { e0 = scene->ev[1]; e1 = scene->ev[2]; }
         size_t i0 = 0, i1 = 0;
@@ -270,7 +164,7 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
             { const int rc = window_event(scene, &i1); if (rc) return rc; }
             e0 = scene->win_events[i0]; e1 = scene->win_events[i1];
         }
-        const int rc = launch_chunk(scene, vol, ray_tracing_algorithm, b, e, no_dump, stream, e0, e1, d_records);
+        const int rc = launch_chunk(scene, vol, ray_tracing_algorithm, plan, r, no_dump, stream, e0, e1, d_records);
         if (rc) return rc;
         if (timed == 2 && vol) scene->win_march.emplace_back(i0, i1);      // only pairs whose events were recorded
         if (timed == 1 && vol) {

@@ -77,7 +77,7 @@ __global__ __launch_bounds__(256) void build_volume_kernel(const float *__restri
         __syncthreads();
     }
     if (threadIdx.x == 0) block_min[blockIdx.x] = red[0];
-    // block maximum of |grad n| (bounds how far the volume can bend a ray: launch_chunk's doom margin)
+    // block maximum of |grad n| (bounds how far the volume can bend a ray: photon_cull.hip, doom_margin)
     __syncthreads();
     red[threadIdx.x] = gmag == gmag ? gmag : 0.f;
     __syncthreads();

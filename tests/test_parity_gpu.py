@@ -1394,7 +1394,7 @@ def _render_skip_pair(photon, call, monkeypatch):
 @pytest.mark.parametrize("variant", ["sample", "wide_field", "thin_lens", "ratio_0.7", "deep_sheet", "tilted_lens", "flipped_normal"])
 def test_dead_lens_samples_are_not_launched_and_nothing_changes(photon, oracle, monkeypatch, variant):
     """The volume-free path launches only the lens samples that can reach the first element's aperture from SOME source
-    (photon_scene.hip, live_lens_samples: a bound over all sources of the scene; the reference aims ray k of every source at
+    (photon_cull.hip, live_lens_samples: a bound over all sources of the scene; the reference aims ray k of every source at
     the same point of the lens plane, parallel_ray_tracing.cu:123-141, and kills what meets the front surface beyond pitch / 2,
     :447, 560-566).  A ray that is not launched adds nothing; so the image with the skip must equal the image without it BIT
     FOR BIT (the surviving rays' increments are the same f32 numbers, added in f64) -- with sources far off the axis, a sheet
@@ -1435,7 +1435,7 @@ def test_dead_lens_samples_are_not_launched_and_nothing_changes(photon, oracle, 
 
 @pytest.mark.parametrize("variant", ["sample", "off_centre", "deep_sheet", "chunks", "devices", "thin_lens"])
 def test_sources_that_miss_the_sensor_are_not_launched_and_nothing_changes(photon, oracle, monkeypatch, variant):
-    """The volume-free path also leaves out the SOURCES whose image cannot fall on the sensor (photon_scene.hip,
+    """The volume-free path also leaves out the SOURCES whose image cannot fall on the sensor (photon_cull.hip,
     source_misses_sensor: an interval bound on where one biconvex thick lens -- or one thin lens -- can put a source's rays; photon's sample PIV
     frame draws particles over a field 1.5 x wider than the camera sees, run_simulation_02.py:956-958).  The list the scene
     launches is the complement of the host bound (tests/test_source_cull.py holds that against exact ray tracing); the image

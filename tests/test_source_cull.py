@@ -1,4 +1,4 @@
-"""The bound behind the source cull of the volume-free path (photon_scene.hip, source_misses_sensor) on its own: host
+"""The bound behind the source cull of the volume-free path (photon_cull.hip, source_misses_sensor) on its own: host
 arithmetic of the product library, no GPU -- held against exact float64 ray tracing of EVERY ray of EVERY source it rules
 out, over hundreds of random thick-lens (and, one in five, thin-lens) cameras (focal length, f-number, both radii, thickness, index, object distance,
 field, cone) including ones the sample data never visits."""
