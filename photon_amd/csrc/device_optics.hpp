@@ -399,6 +399,62 @@ __device__ __forceinline__ Ray optical_system(const SceneDev &sc, Ray ray) {
     return ray;
 }
 
+// SPLAT-PATH COUNTERS.  Debug build only (-DPHOTON_PATH_STATS=1, the build that counts the sampler paths; read by
+// photon_debug_splat_stats, photon_amd/path_stats.py, tools/path_stats.py, tests/test_splat_paths_gpu.py): one slot per
+// branch of the sensor stage that changes which code computes a pixel.  E_ = erf splat, T_ = 4-pixel splat, K_ = the
+// sensor_kernel instantiation that ran.  "wave": counted once per wave, where control flow is wave-uniform; "lanes": one
+// per ray; "tiles" / "taps": one per tile / tap.  The counters live in the sensor unit alone (photon_sensor.hip defines
+// PHOTON_SENSOR_UNIT); everywhere else, and in the default build, every splat_stat() compiles away.
+// The Python mirror (photon_amd/path_stats.py) is checked against this enum by the suite: keep one name per line.
+enum SplatSlot : int {
+    SS_E_WAVES,                 // wave: erf_splat_wave called with a live ray (cooperative + fall-back)
+    SS_E_COOP,                  // wave:   the cooperative route
+    SS_E_FALLBACK,              // wave:   every live ray through erf_splat_lane, for one or more of the three reasons below
+    SS_E_FB_WIDE,               // wave:     a ray's window is wider or higher than kSplatSlots
+    SS_E_FB_TILES,              // wave:     the wave's window needs more than kSplatTiles tiles
+    SS_E_FB_RADIUS,             // wave:     the render radius is not wave-uniform, not in (0, 1e4), or r0 does not fit 19 bits
+    SS_E_SHARED_X_LANES,        // lanes (cooperative): column factors from shared edges (X >= 8)
+    SS_E_BOTH_X_LANES,          // lanes (cooperative): column factors with both edges evaluated per pixel (X < 8)
+    SS_E_SHARED_Y_LANES,        // lanes (cooperative): row factors from shared edges (Y >= 8)
+    SS_E_BOTH_Y_LANES,          // lanes (cooperative): row factors with both edges evaluated per pixel (Y < 8)
+    SS_E_CLIPPED_LANES,         // lanes (cooperative): the window reaches beyond the image: clipping bits of the pattern
+    SS_E_LANE_CLIPPED_LANES,    // lanes (fall-back): the window reaches beyond the image
+    SS_E_TILES,                 // tiles (cooperative): tiles with a contributing ray (the two rows below add up to it)
+    SS_E_TILES_SAME,            // tiles:   every contributing ray has the same window: the unrolled loop
+    SS_E_TILES_MIXED,           // tiles:   windows differ: offsets travel with the masks
+    SS_E_MULTI_TILE,            // wave (cooperative): the wave's window spans more than one tile
+    SS_T_WAVES,                 // wave: bilinear_splat_wave called with a live ray
+    SS_T_COOP,                  // wave:   the cooperative route
+    SS_T_LANE_ROUTE,            // wave:   more than kSplatTiles tiles: bilinear_splat_lane
+    SS_T_MULTI_TILE,            // wave (cooperative): more than one tile
+    SS_T_TAPS_LANDED,           // taps: added to the image (with the row below: 4 per ray on the sensor)
+    SS_T_TAPS_DROPPED,          // taps: pixel outside the sensor, or its index (ii-1)*W + jj-1 before the image (tap_lands)
+    SS_T_TAPS_WRAPPED,          // taps: landed from column 0 in the last column of the row before
+    SS_K_GEN_ERF,               // wave: sensor_kernel<false, false, 0>: rays generated in place, lens or apparent image, either splat
+    SS_K_STATE_ERF,             // wave: sensor_kernel<true, false, 0>: the same after a march
+    SS_K_GEN_TRAIN,             // wave: sensor_kernel<false, true, 0>: the element train
+    SS_K_STATE_TRAIN,           // wave: sensor_kernel<true, true, 0>: the element train after a march
+    SS_K_GEN_TAPS,              // wave: sensor_kernel<false, false, 2>: the 4-pixel-only kernel
+    SS_K_STATE_TAPS,            // wave: sensor_kernel<true, false, 2>: the 4-pixel-only kernel after a march
+    SS_COUNT
+};
+constexpr int kSplatStatSlots = SS_COUNT;
+#ifndef PHOTON_PATH_STATS
+#define PHOTON_PATH_STATS 0
+#endif
+#if PHOTON_PATH_STATS && defined(PHOTON_SENSOR_UNIT)
+__device__ unsigned long long g_splat_stats[kSplatStatSlots];
+__device__ __forceinline__ void splat_stat(SplatSlot k, unsigned long long n = 1) {         // a wave event: the first active lane counts it
+    if ((int)(threadIdx.x & 63) == __ffsll((long long)ballot(true)) - 1) atomicAdd(&g_splat_stats[k], n);
+}
+__device__ __forceinline__ void splat_stat_if(SplatSlot k, bool c) { if (c) splat_stat(k); }                   // c wave-uniform
+__device__ __forceinline__ void splat_lanes(SplatSlot k, bool c) { if (c) atomicAdd(&g_splat_stats[k], 1ull); }   // per lane
+#else                                                           // arguments not even evaluated: the default build's code is as if they were not there
+#define splat_stat(...) ((void)0)
+#define splat_stat_if(...) ((void)0)
+#define splat_lanes(...) ((void)0)
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // Gaussian-spot (erf) splat: I0*pi/32 * d_erf(col) * d_erf(row) over the pixels within
 // render_fraction*D of the centroid (.cu:1477-1540 / :1660-1730).
@@ -530,8 +586,18 @@ __device__ __forceinline__ int erf_splat_wave(double *image, int W, int H, const
     // the render radius is a camera constant (render_fraction * D): wave-uniform; r0 travels in 20 bits
     const float rfD = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(__shfl(q.rfD, __ffsll((long long)any) - 1, 64))));
     const bool fits = !q.valid || (nw <= kSplatSlots && nh <= kSplatSlots && q.rfD == rfD && q.r0 > -(1 << 18) && q.r0 < (1 << 18));
-    if (ballot(!fits) != 0 || tiles_x * tiles_y > kSplatTiles || !(rfD > 0.f && rfD < 1.0e4f))     // wave-uniform branch
+    splat_stat(SS_E_WAVES);
+    if (ballot(!fits) != 0 || tiles_x * tiles_y > kSplatTiles || !(rfD > 0.f && rfD < 1.0e4f)) {   // wave-uniform branch
+        splat_stat(SS_E_FALLBACK);
+        splat_stat_if(SS_E_FB_WIDE, ballot(q.valid && (nw > kSplatSlots || nh > kSplatSlots)) != 0);
+        splat_stat_if(SS_E_FB_TILES, tiles_x * tiles_y > kSplatTiles);
+        splat_stat_if(SS_E_FB_RADIUS, ballot(q.valid && !(q.rfD == rfD && q.r0 > -(1 << 18) && q.r0 < (1 << 18))) != 0 || !(rfD > 0.f && rfD < 1.0e4f));
+        splat_lanes(SS_E_LANE_CLIPPED_LANES, q.valid && (q.c0 < 0 || q.c1 > W - 1 || q.r0 < 0 || q.r1 > H - 1));
         return q.valid ? erf_splat_lane(image, W, H, q) : 0;
+    }
+    splat_stat(SS_E_COOP);
+    splat_stat_if(SS_E_MULTI_TILE, tiles_x * tiles_y > 1);
+    splat_lanes(SS_E_CLIPPED_LANES, q.valid && (q.c0 < 0 || q.c1 > W - 1 || q.r0 < 0 || q.r1 > H - 1));
     const float rad2_max = sqrt_threshold(rfD);
     const float sqrt8 = sqrtf(8.0f);
     // ---- park this ray's factors.  The reference evaluates erf at both edges of every pixel; neighbouring pixels share
@@ -540,6 +606,8 @@ __device__ __forceinline__ int erf_splat_wave(double *image, int W, int H, const
     // rows evaluate both edges like the reference does.
     if (q.valid) {
         const bool exact_x = q.X >= 8.0f, exact_y = q.Y >= 8.0f;
+        splat_lanes(exact_x ? SS_E_SHARED_X_LANES : SS_E_BOTH_X_LANES, true);
+        splat_lanes(exact_y ? SS_E_SHARED_Y_LANES : SS_E_BOTH_Y_LANES, true);
         double *fx = lds.f[lane], *fy = lds.f[lane] + kSplatSlots;
         // the reference's sqrt8 * (idx - X -+ 0.5) / D: the quotients through the reciprocal of D (photon_det_div_rcp: the same
         // correctly rounded values as the divisions, three operations each instead of eleven)
@@ -635,6 +703,8 @@ __device__ __forceinline__ int erf_splat_wave(double *image, int W, int H, const
             double sum = 0.0;
             const int first = __ffsll((long long)rays) - 1;
             const int dx0 = __builtin_amdgcn_readlane(dx, first), dy0 = __builtin_amdgcn_readlane(dy, first);
+            splat_stat(SS_E_TILES);
+            splat_stat(ballot(mine != 0 && (dx != dx0 || dy != dy0)) == 0 ? SS_E_TILES_SAME : SS_E_TILES_MIXED);
             if (ballot(mine != 0 && (dx != dx0 || dy != dy0)) == 0) {       // wave-uniform
                 // EVERY ray that renders here has the same window (one light source per wave: seven BOS waves in eight): the
                 // factors of ray r sit at a compile-time offset from one per-lane address -- the loop over r is unrolled, no
@@ -796,7 +866,22 @@ __device__ __forceinline__ int bilinear_splat_wave(double *image, int W, int H, 
     const int cmin = wave_min_i(q.valid ? q.jj_ul : big), cmax = wave_max_i(q.valid ? q.jj_ul + 1 : -big);
     const int rmin = wave_min_i(q.valid ? q.ii_ul : big), rmax = wave_max_i(q.valid ? q.ii_ul + 1 : -big);
     const int tiles_x = (cmax - cmin) / 8 + 1, tiles_y = (rmax - rmin) / 8 + 1;
-    if (tiles_x * tiles_y > kSplatTiles) return q.valid ? bilinear_splat_lane(image, W, H, q) : 0;  // wave-uniform
+    splat_stat(SS_T_WAVES);
+#if PHOTON_PATH_STATS && defined(PHOTON_SENSOR_UNIT)
+    if (q.valid)                                                        // what becomes of this ray's four taps, on either route
+        for (int k = 0; k < 4; k++) {
+            const int ii = q.ii_ul + (k >> 1), jj = q.jj_ul + (k & 1);
+            const bool lands = tap_lands(ii, jj, W, H);
+            splat_lanes(lands ? SS_T_TAPS_LANDED : SS_T_TAPS_DROPPED, true);
+            splat_lanes(SS_T_TAPS_WRAPPED, lands && jj == 0);
+        }
+#endif
+    if (tiles_x * tiles_y > kSplatTiles) {                              // wave-uniform
+        splat_stat(SS_T_LANE_ROUTE);
+        return q.valid ? bilinear_splat_lane(image, W, H, q) : 0;
+    }
+    splat_stat(SS_T_COOP);
+    splat_stat_if(SS_T_MULTI_TILE, tiles_x * tiles_y > 1);
     if (q.valid) {
         lds.head[lane] = make_float4(__int_as_float(q.ii_ul), __int_as_float(q.jj_ul), q.inc[0], q.inc[1]);
         lds.tail(lane) = make_float2(q.inc[2], q.inc[3]);

@@ -1,6 +1,7 @@
 // photon_sensor.hip - the kernels either side of the volume march: ray generation (stage 1a) and the sensor stage
 // (stage 2: lens / aperture / apparent image + erf or 4-pixel splat into the scene's private f64 accumulator, one kernel),
 // and the fold of that accumulator into the caller's image.
+#define PHOTON_SENSOR_UNIT 1            // the splat-path counters of a debug build live here (device_optics.hpp, enum SplatSlot)
 #include "photon_internal.hpp"
 
 using namespace photon;
@@ -47,6 +48,8 @@ __global__ __launch_bounds__(256, (SPLAT == 2 ? PHOTON_SENSOR_WAVES_TAPS : PHOTO
                                                      double *image, DumpDev dump, unsigned long long *counters, MomentsDev mom) {
     __shared__ typename SplatArea<SPLAT>::type splat_lds[4];            // per wave: the parked rays of the cooperative splats
     const unsigned r = blockIdx.x * blockDim.x + threadIdx.x;
+    splat_stat(SPLAT == 2 ? (FROM_STATE ? SS_K_STATE_TAPS : SS_K_GEN_TAPS)
+               : TRAIN ? (FROM_STATE ? SS_K_STATE_TRAIN : SS_K_GEN_TRAIN) : (FROM_STATE ? SS_K_STATE_ERF : SS_K_GEN_ERF));
     int taps = 0;
     unsigned on_sensor = 0;
     SplatReq req;                                                       // erf splat, done wave-cooperatively below
@@ -135,6 +138,22 @@ __global__ __launch_bounds__(256) void finalize_image_kernel(float *__restrict__
         acc[i] = 0.0;
     }
 }
+
+#if PHOTON_PATH_STATS
+// debug builds only: read (and clear) the splat-path counters of device_optics.hpp (enum SplatSlot); n_slots must be the
+// enum's size (photon_amd/path_stats.py mirrors it)
+extern "C" int photon_debug_splat_stats(unsigned long long *out, int n_slots) {
+    if (!out || n_slots != kSplatStatSlots) {
+        fprintf(stderr, "photon: photon_debug_splat_stats: the library counts %d slots, the caller asked for %d\n", kSplatStatSlots, n_slots);
+        return 1;
+    }
+    PH_CHECK(hipDeviceSynchronize());
+    PH_CHECK(hipMemcpyFromSymbol(out, HIP_SYMBOL(photon::g_splat_stats), kSplatStatSlots * sizeof(unsigned long long)));
+    const unsigned long long zero[kSplatStatSlots] = {};
+    PH_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(photon::g_splat_stats), zero, sizeof zero));
+    return 0;
+}
+#endif
 
 namespace photon {
 

@@ -4,7 +4,11 @@
     lib = PhotonLibrary(path=build_library(extra_flags=("-DPHOTON_PATH_STATS=1",), out_path=...))
     read(lib)           # {slot name: count} since the last read; reading clears the counters
 
-C_ slots count the tricubic sampler's march, L_ slots the trilinear one's (both weight modes)."""
+C_ slots count the tricubic sampler's march, L_ slots the trilinear one's (both weight modes).
+
+The same build counts the paths of the sensor stage: `enum SplatSlot` (photon_amd/csrc/device_optics.hpp), mirrored by
+SPLAT_SLOTS and read by read_splat().  E_ slots count the erf splat, T_ slots the 4-pixel splat, K_ slots the
+sensor_kernel instantiations."""
 from __future__ import annotations
 
 import ctypes
@@ -24,6 +28,16 @@ SLOTS = (
     "L_SPIN_CAP", "L_LOW", "L_REPAIR_LANES", "L_KEEP_PREV_LANES",
 )
 
+OPTICS_HEADER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "device_optics.hpp")
+
+SPLAT_SLOTS = (
+    "E_WAVES", "E_COOP", "E_FALLBACK", "E_FB_WIDE", "E_FB_TILES", "E_FB_RADIUS",
+    "E_SHARED_X_LANES", "E_BOTH_X_LANES", "E_SHARED_Y_LANES", "E_BOTH_Y_LANES", "E_CLIPPED_LANES", "E_LANE_CLIPPED_LANES",
+    "E_TILES", "E_TILES_SAME", "E_TILES_MIXED", "E_MULTI_TILE",
+    "T_WAVES", "T_COOP", "T_LANE_ROUTE", "T_MULTI_TILE", "T_TAPS_LANDED", "T_TAPS_DROPPED", "T_TAPS_WRAPPED",
+    "K_GEN_ERF", "K_STATE_ERF", "K_GEN_TRAIN", "K_STATE_TRAIN", "K_GEN_TAPS", "K_STATE_TAPS",
+)
+
 PATH_STATS_FLAGS = ("-DPHOTON_PATH_STATS=1",)
 
 
@@ -35,6 +49,28 @@ def header_slots(path: str = HEADER):
     names = re.findall(r"^\s*PS_(\w+)\s*,", body, re.M)
     assert names and names[-1] != "COUNT"
     return tuple(names)
+
+
+def header_splat_slots(path: str = OPTICS_HEADER):
+    """The slot names of `enum SplatSlot` as the header spells them (without the SS_ prefix), in order."""
+    with open(path) as f:
+        text = f.read()
+    body = re.search(r"enum SplatSlot\s*:\s*int\s*\{(.*?)\};", text, re.S).group(1)
+    names = re.findall(r"^\s*SS_(\w+)\s*,", body, re.M)
+    assert names and names[-1] != "COUNT"
+    return tuple(names)
+
+
+def read_splat(lib) -> dict:
+    """Counters of the sensor unit since the last read (which this one clears), by slot name."""
+    f = lib.lib.photon_debug_splat_stats
+    f.argtypes = [ctypes.c_void_p, ctypes.c_int]
+    f.restype = ctypes.c_int
+    out = (ctypes.c_ulonglong * len(SPLAT_SLOTS))()
+    rc = f(ctypes.cast(out, ctypes.c_void_p), len(SPLAT_SLOTS))
+    if rc != 0:
+        raise RuntimeError(f"photon_debug_splat_stats failed ({rc})")
+    return dict(zip(SPLAT_SLOTS, (int(v) for v in out)))
 
 
 def read(lib) -> dict:
