@@ -300,9 +300,28 @@ unsigned photon_march_queue_size(unsigned n_groups, unsigned xcd, unsigned sub, 
 int photon_scene_set_march_segments(photon_scene_t *scene, int segments);
 /* The library's own choice for a launch of n_rays through a volume whose longest axis has `depth` texels, on a device of
  * num_cus compute units: returns the number of pieces (1 = whole marches), *halving (may be NULL) = 1 when their lengths
- * halve (1/2, 1/4, ... of the depth) rather than being equal.  Pure host arithmetic (a cost model fitted to a sweep on C3:
- * DESIGN.md section 4.1); for tests and documentation. */
+ * halve (1/2, 1/4, ... of the depth) rather than being equal.  The planner every march launch goes through (a cost model
+ * fitted to a sweep on C3: DESIGN.md section 4.1), asked about a source-major launch without dumps or noise, with no scene
+ * setting and PHOTON_MARCH_SEGMENTS ignored; pure host arithmetic, 0 for integrators other than 1 and 2. */
 int photon_march_segments_plan(unsigned n_rays, int depth, int ray_tracing_algorithm, int interpolation, int num_cus, int *halving);
+/* Everything the library decides about one march launch before it enqueues it, from the same planner, as a trace would
+ * decide it (PHOTON_MARCH_SEGMENTS and PHOTON_MARCH_SEGMENT_SHAPE are read): n_rays through an nx x ny x nz volume on a
+ * device of num_cus compute units.  scene_segments: what photon_scene_set_march_segments holds (-1 = not set).  flags:
+ * bit 0 intermediate ray dumps are asked for, bit 1 gradient noise, bit 2 a lens-major launch.  Pure host arithmetic.
+ * The caller sets struct_size = sizeof(photon_march_plan_t); returns 0, or 1 for arguments no launch can have. */
+typedef struct photon_march_plan_t {
+    uint32_t struct_size;
+    int segments;               /* pieces per march; piece s covers the trips [seg_begin[s], seg_begin[s + 1]) */
+    int shape;                  /* 0 equal pieces, 1 halving, 2 tapered */
+    unsigned seg_begin[65];
+    unsigned groups_per_chunk;  /* consecutive 64-ray groups a work queue owns as one chunk */
+    unsigned grid_blocks, block_threads;
+    int persistent;             /* 1: a grid that fills the chip once and serves the work queues (integrators 1, 2); 0: one thread per ray */
+    int save, noise, segmented; /* the kernel variant: records intermediate dumps, draws gradient noise, marches in pieces */
+    int generates_rays;         /* 1: the march generates its rays itself, no ray-generation kernel runs before it */
+} photon_march_plan_t;
+int photon_march_launch_plan(unsigned n_rays, int nx, int ny, int nz, int ray_tracing_algorithm, int interpolation, int num_cus,
+                             int scene_segments, int flags, photon_march_plan_t *out);
 
 /* A scene that holds only a SLICE of a job's source list (one rank of a multi-GPU job uploads just its shard): the
  * index, in the job's list, of this scene's first source.  Only the noise hooks read it -- their generator is keyed by the

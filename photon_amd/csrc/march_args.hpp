@@ -81,15 +81,12 @@ __device__ __forceinline__ void wave_add(unsigned long long *dst, unsigned long 
 #ifndef PHOTON_MARCH_WAVES_NOISE
 #define PHOTON_MARCH_WAVES_NOISE 3      // the gradient-noise instantiations (Philox + Box-Muller in f64 inside the loop) need ~130 VGPRs: at five
 #endif                                  // waves per SIMD they spilled 46-70 of them into the loop (176-208 B of scratch per lane); three waves, no spill
-template <int ALGO, int INTERP, bool NOISE> constexpr int march_waves() {
-    return NOISE ? PHOTON_MARCH_WAVES_NOISE : INTERP == 1 ? (ALGO == 2 ? PHOTON_MARCH_WAVES_LINEAR : PHOTON_MARCH_WAVES_EULER_LINEAR) : PHOTON_MARCH_WAVES;
-}
-// resident march waves per SIMD of a launch (the segment planner's chip fill)
-inline unsigned march_waves_of(int algorithm, int interp) {
-    return interp == 1 ? (algorithm == 2 ? PHOTON_MARCH_WAVES_LINEAR : PHOTON_MARCH_WAVES_EULER_LINEAR) : PHOTON_MARCH_WAVES;
+// resident march waves per SIMD: the kernels' launch bound (march_kernel.hpp) and the segment planner's chip fill (plan_march)
+constexpr int march_waves(int algorithm, int interp, bool noise) {
+    return noise ? PHOTON_MARCH_WAVES_NOISE : interp == 1 ? (algorithm == 2 ? PHOTON_MARCH_WAVES_LINEAR : PHOTON_MARCH_WAVES_EULER_LINEAR) : PHOTON_MARCH_WAVES;
 }
 #ifndef PHOTON_MARCH_SEGMENTS
-#define PHOTON_MARCH_SEGMENTS 32        // most segments a ray's march is cut into in launches of several chip fills (launch_march picks)
+#define PHOTON_MARCH_SEGMENTS 32        // most segments a ray's march is cut into in launches of several chip fills (plan_march picks)
 #endif
 constexpr unsigned kQueueStride = 16;                           // u32 per queue counter: one 64-byte line each
 #ifndef PHOTON_SUBQUEUES
@@ -102,7 +99,7 @@ constexpr unsigned kQueueDoneSlot = 63;                         // the line that
 // in one L2; small ones balance the XCDs' queues at the end of a launch.  Measured on C3 with the segmented march (HBM
 // traffic does not care: 4.0-4.15 GB): tricubic RK4 march with chunks of 128 / 32 / 16 / 8 groups 57.70 / 57.59 / 57.53 /
 // 57.55 ms (one GPU's eighth 7.60 / 7.55 / 7.53 / 7.51), trilinear RK4 19.83 / 19.89 / 19.92: 16 for the tricubic kernels in
-// source-major launches through volumes of up to 256^3 texels, 128 otherwise (launch_march says why).
+// source-major launches through volumes of up to 256^3 texels, 128 otherwise (plan_march says why).
 #ifndef PHOTON_CHUNK_SHIFT_CUBIC
 #define PHOTON_CHUNK_SHIFT_CUBIC 4
 #endif
@@ -134,7 +131,7 @@ struct MarchArgs {
                                         // one runs until every ray has left): equal, halving or tapered pieces (plan_segments)
     unsigned epoch;                     // tag of this launch in RayStateDev::seg_flag
     unsigned *error;                    // waves that gave a segment up (zero unless the hand-off between segments is broken)
-    unsigned chunk_shift;               // log2 of the groups per queue chunk (launch_march)
+    unsigned chunk_shift;               // log2 of the groups per queue chunk (plan_march)
     // Ray generation folded into the march (round 6): gen != 0 = no raygen_kernel ran; the wave that takes the FIRST piece of a
     // group generates its rays itself (generate_state: the kernel's own body) from this copy of the scene description, read
     // through the argument segment where it is used, and writes only what the sensor stage needs beside the marched state:
@@ -144,6 +141,27 @@ struct MarchArgs {
     SceneDev scene;
 };
 typedef const __attribute__((address_space(4))) MarchArgs *MarchArgsPtr;
+
+// What a march launch is, decided before anything is enqueued (plan_march, photon_march.hip: pure host arithmetic).
+enum SegShape { SEG_UNIFORM = 0, SEG_HALVING = 1, SEG_TAPER = 2 };
+struct MarchKnobs {                     // read once per trace (march_knobs): the scene's setting, else PHOTON_MARCH_SEGMENTS; PHOTON_MARCH_SEGMENT_SHAPE
+    int want = PHOTON_MARCH_SEGMENTS;   // most pieces per march (1: whole marches)
+    bool forced = false;                // segment launches of any size, into `want` pieces (tests)
+    int shape = -1;                     // a SegShape, or -1: the planner's choice
+    unsigned taper = 0;                 // SEG_TAPER: how often the last piece is halved
+};
+struct MarchPlan {
+    unsigned n_rays;
+    int algorithm, interp;              // the kernel: march_kernel<algorithm, interp, save, noise, segmented> (march_launch), or
+    bool save, noise, segmented;        // the per-ray kernel of the other algorithms (persistent == false)
+    bool persistent, fold;              // persistent: a grid that fills the chip once and serves the work queues, else one thread per ray;
+                                        // fold: ray generation is the prologue of the march's first piece, no raygen kernel runs
+    unsigned grid, block, chunk_shift;  // chunk_shift: log2 of the groups per queue chunk
+    unsigned segments, seg_begin[kMaxSegments + 1];     // pieces per march; piece s covers the trips [seg_begin[s], seg_begin[s + 1])
+    int shape;                          // SegShape of the pieces (SEG_UNIFORM for whole marches)
+};
+// the plan's kernel, enqueued (march_kernel.hpp; instantiated per sampler in photon_march_linear.hip / _cubic.hip)
+template <int INTERP> int march_launch(const MarchPlan &plan, hipStream_t stream, const MarchArgs &a);
 
 // Groups of a launch of n_groups that belong to queue (xcd, sub): its items are k = 0 .. that many - 1 (march_queue_group).
 __host__ __device__ inline unsigned march_queue_size(unsigned n_groups, unsigned xcd, unsigned sub, unsigned shift) {

@@ -3,6 +3,9 @@
 // Included by the translation units that instantiate them (photon_march_linear.hip, photon_march_cubic.hip); the host
 // side of a launch (planner, queues, segments) is photon_march.hip.
 #pragma once
+#include <cstdio>
+#include <utility>
+
 #include "device_volume_coop.hpp"
 #include "march_args.hpp"
 
@@ -227,7 +230,7 @@ __device__ __forceinline__ void march_group(unsigned group, unsigned seg, unsign
 }
 
 template <int ALGO, int INTERP, bool SAVE, bool NOISE, bool SEG>
-__global__ __launch_bounds__(PHOTON_MARCH_BLOCK, (march_waves<ALGO, INTERP, NOISE>())) void march_kernel(MarchArgs) {
+__global__ __launch_bounds__(PHOTON_MARCH_BLOCK, march_waves(ALGO, INTERP, NOISE)) void march_kernel(MarchArgs) {
     __shared__ f4 tiles[PHOTON_MARCH_BLOCK / 64][wave_lds_texels<INTERP>()];           // per wave: tile + brick, rows padded (device_volume_coop.hpp)
     f4 *const tile = tiles[threadIdx.x >> 6];
     const unsigned lane = threadIdx.x & 63u;
@@ -302,6 +305,32 @@ __global__ __launch_bounds__(PHOTON_MARCH_BLOCK, (march_waves<ALGO, INTERP, NOIS
         }
     }
 }
+
+// The march kernels that exist.  Dumps are recorded and gradient noise is drawn by the trilinear branches only (the noise hook by
+// Euler's alone, .h:853-863), and both index a ray's iterations: no segmented march has either.
+constexpr bool march_kernel_exists(int algo, int interp, bool save, bool noise, bool seg) {
+    return (algo == 1 || algo == 2) && (interp == 1 || interp == 2) && !(seg && (save || noise)) && !(interp == 2 && (save || noise)) &&
+           !(noise && algo != 1);
+}
+// A plan's kernel, enqueued: the one place a MarchPlan becomes march_kernel<ALGO, INTERP, SAVE, NOISE, SEG>.  Each sampler's unit
+// instantiates its own march_launch (photon_march_linear.hip, photon_march_cubic.hip), and with it that sampler's kernels.
+template <int ALGO, int INTERP, bool SAVE, bool NOISE, bool SEG>
+bool march_launch_variant(const MarchPlan &p, hipStream_t stream, const MarchArgs &a) {
+    if constexpr (march_kernel_exists(ALGO, INTERP, SAVE, NOISE, SEG))
+        if (p.algorithm == ALGO && p.interp == INTERP && p.save == SAVE && p.noise == NOISE && p.segmented == SEG) {
+            hipLaunchKernelGGL((march_kernel<ALGO, INTERP, SAVE, NOISE, SEG>), dim3(p.grid), dim3(p.block), 0, stream, a);
+            return true;
+        }
+    return false;
+}
+template <int INTERP, int... V>         // V: bit 0 noise, bit 1 save, bit 2 segmented, bit 3 Euler rather than RK4
+int march_launch_any(const MarchPlan &p, hipStream_t stream, const MarchArgs &a, std::integer_sequence<int, V...>) {
+    if ((march_launch_variant<2 - (V >> 3), INTERP, (V >> 1 & 1) != 0, (V & 1) != 0, (V >> 2 & 1) != 0>(p, stream, a) || ...)) return 0;
+    fprintf(stderr, "photon: no march kernel for algorithm %d, sampler %d, save %d, noise %d, segmented %d\n", p.algorithm, p.interp, p.save, p.noise, p.segmented);
+    return 1;
+}
+template <int INTERP>
+int photon::march_launch(const MarchPlan &p, hipStream_t stream, const MarchArgs &a) { return march_launch_any<INTERP>(p, stream, a, std::make_integer_sequence<int, 16>()); }
 
 template <int ALGO, int INTERP>
 __global__ __launch_bounds__(256) void march_rays_kernel(VolumeDev v, const f4 *__restrict__ tex, int n,

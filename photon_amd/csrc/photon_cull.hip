@@ -389,6 +389,7 @@ TracePlan photon::make_trace_plan(photon_scene *s, const photon_volume *vol, int
     // not eight); with moments, also a moments block of at most as many entries, and that is indexed by lens sample, not by slot
     p.slot_rays = p.live_samples_only ? s->live_count : rps;
     p.max_sources = std::max<long long>(1, kMaxRaysPerLaunch / (unsigned)(with_moments ? rps : p.slot_rays));
+    p.march = march_knobs(s->march_segments);
     return p;
 }
 

@@ -5,8 +5,8 @@
 //   photon_volume.hip        NRRD parser, gradient-volume build + B-spline prefilter kernels, volume handle API, volume cache
 //   photon_scene.hip         scene / source handles, on-device scene generation, the glibc rand table
 //   photon_cull.hip          what a launch may leave out (dead lens samples, sources off the sensor, doomed rays), the plan of a trace
-//   photon_march.hip         host side of a march launch: segment planner, work queues, wave-timing profile
-//   photon_march_{linear,cubic,extra}.hip   the march kernels (march_kernel.hpp), one unit per sampler
+//   photon_march.hip         host side of a march launch: its plan (pieces, queue chunks, grid, kernel), the enqueue, wave-timing profile
+//   photon_march_{linear,cubic,extra}.hip   the march kernels and the one plan -> kernel dispatcher (march_kernel.hpp), one unit per sampler
 //   photon_sensor.hip        ray generation, sensor stage (lens / aperture / splats), finalize
 //   photon_trace.hip         launch loop of a trace, photon_trace, statistics
 //   photon_post.hip          sensor post-processing, the streaming-copy yardstick
@@ -199,6 +199,8 @@ int cached_volume(const char *path, int interpolation, photon_volume **out, Shar
 void scene_quiesce(photon_scene *s);
 void free_resume_state(photon_scene *s);
 int ensure_workspace(photon_scene *s, size_t rays);
+// room for what a segmented march keeps per ray between its pieces (after ensure_workspace, which drops it when it regrows)
+int ensure_resume_state(photon_scene *s, bool linear);
 
 // ---- photon_cull.hip ----
 // scene creation: the lens samples that can reach the first aperture from some source; the constants of the source cull
@@ -218,6 +220,7 @@ struct TracePlan {
     float doom_margin;                  // rays further than this outside the first aperture are not marched; 0 = off
     int slot_rays;                      // slots per source of every launch
     long long max_sources;              // (listed) sources per launch
+    MarchKnobs march;                   // how the marches may be cut into pieces (march_knobs)
 };
 TracePlan make_trace_plan(photon_scene *s, const photon_volume *vol, int algorithm, bool dumping, bool with_moments);
 // one launch of a trace: sources [begin, end) in the caller's order, of which n_sources are launched -- src_list when they are listed
@@ -225,18 +228,23 @@ struct LaunchRange { long long begin, end, n_sources; const int *src_list; };
 LaunchRange next_launch(const photon_scene *s, const TracePlan &plan, long long begin, long long limit);
 
 // ---- photon_march.hip ----
-// The march launch of n rays whose state sits in the scene's workspace (stage 1b): persistent grid, work queues, segments.
-// gen_src_begin >= 0: no raygen_kernel has run; the march generates the rays of sources [gen_src_begin, ...) itself (algorithms 1, 2)
-// dev: the scene as this launch sees it (launch_chunk)
-int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol, int algorithm, unsigned n, unsigned long long ray_base,
-                 const InterDump &idump, bool save, hipStream_t stream, hipEvent_t ev_march_begin, long long gen_src_begin = -1);
+// The scene's setting (photon_scene_set_march_segments: -1 none) or else PHOTON_MARCH_SEGMENTS, and PHOTON_MARCH_SEGMENT_SHAPE.
+MarchKnobs march_knobs(int scene_segments);
+// What the march launch of n rays is (stage 1b): kernel, grid, queue chunks, pieces.  Pure: no HIP call, no environment, no scene.
+// dumps: intermediate ray dumps are asked for; ray_order: SceneDev::ray_order of the launch; have_rays: the rays' state already
+// sits in the workspace (a raygen kernel ran, or the caller put it there)
+MarchPlan plan_march(unsigned n, int num_cus, const VolumeDev &vol, int algorithm, bool dumps, bool noise, int ray_order, bool have_rays,
+                     const MarchKnobs &knobs);
+// Enqueues the march the plan describes over the rays in the scene's workspace; decides nothing and allocates nothing (the
+// caller has made room: ensure_workspace, and ensure_resume_state for a plan of several pieces).  With plan.fold the march
+// generates the rays of sources [src_begin, ...) itself.  dev: the scene as this launch sees it (launch_chunk)
+int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol, const MarchPlan &plan, unsigned long long ray_base,
+                 const InterDump &idump, long long src_begin, hipStream_t stream, hipEvent_t ev_march_begin);
 // Did any march wave give a segment up?  Reads (and clears) the scene's error word; the caller has synchronised.
 int march_error_check(photon_scene *scene);
 int profile_reset(photon_scene *s, hipStream_t stream);
 
 // ---- the march kernels, one unit per sampler (photon_march_linear.hip / _cubic.hip / _extra.hip) ----
-int march_launch_linear(int algorithm, bool save, bool noise, bool segmented, dim3 grid, dim3 block, hipStream_t stream, const MarchArgs &a);
-int march_launch_cubic(int algorithm, bool segmented, dim3 grid, dim3 block, hipStream_t stream, const MarchArgs &a);
 int march_launch_extra(int algorithm, dim3 grid, dim3 block, hipStream_t stream, const VolumeDev &vol, unsigned n_rays, const RayStateDev &st,
                        unsigned long long *counters);
 // plain one-thread-per-ray grids over [n][3] position / direction arrays (photon_trace_volume_rays)

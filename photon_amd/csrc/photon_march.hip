@@ -1,7 +1,7 @@
-// photon_march.hip - host side of a march launch (stage 1b): how many pieces a launch's marches are cut into and how
-// long each is (plan_segments), the persistent grid and its work queues, the per-ray resume state, the wave-timing
-// profile, and the march-only entry points the parity tests drive.  The kernels themselves are instantiated in
-// photon_march_{linear,cubic,extra}.hip (march_kernel.hpp).
+// photon_march.hip - host side of a march launch (stage 1b).  plan_march decides what the launch is -- how many pieces its
+// marches are cut into and how long each is (plan_segments), the queue chunks, the grid, the kernel -- from numbers alone;
+// launch_march enqueues what a plan says.  Also the wave-timing profile and the march-only entry points the parity tests
+// drive.  The kernels themselves are instantiated in photon_march_{linear,cubic,extra}.hip (march_kernel.hpp).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -32,10 +32,18 @@ extern "C" int photon_debug_path_stats(unsigned long long *out, int n_slots) {
 }
 #endif
 
+// Queue chunks: small ones (tail balance) for the tricubic kernels where neighbouring groups are neighbouring SOURCES and
+// the volume is small enough for every L2 to hold what its waves touch; lens-major launches (neighbouring groups share
+// a lens tile, their rays fan out over the whole volume) and large volumes keep the L2-friendly 128 -- C5 at a
+// quarter: 11.0 GB of HBM traffic per launch with 16-group chunks against 3.8 GB with 128, 38.03 against 37.94 ms
+static unsigned march_chunk_shift(int interp, int ray_order, size_t texels) {
+    return interp == 2 && ray_order == 0 && texels <= ((size_t)1 << 24) ? kChunkShiftCubic : kChunkShiftLinear;
+}
+
 extern "C" {
 
 unsigned photon_march_queue_count(void) { return 8u * kSubQueues; }
-unsigned photon_march_queue_chunk(int interpolation) { return 1u << (interpolation == 2 ? kChunkShiftCubic : kChunkShiftLinear); }
+unsigned photon_march_queue_chunk(int interpolation) { return 1u << march_chunk_shift(interpolation, 0, 1); }     // source-major, a small volume
 static unsigned chunk_shift_of(unsigned groups_per_chunk) {    // log2 of a power of two in [1, 2^16]; 32 otherwise
     for (unsigned s = 0; s <= 16; s++) if (groups_per_chunk == (1u << s)) return s;
     return 32u;
@@ -80,33 +88,21 @@ int photon_trace_volume_rays(const photon_volume_t *vol, int ray_tracing_algorit
 
 }  // extern "C"
 
-// What a segmented march keeps per ray between segments (MarchResume) and the per-group flags; allocated with the first
-// segmented launch of a workspace size.  The flags carry the launch's epoch, so they are zeroed once, here (and when the
-// 24-bit epoch wraps), not per launch.
-static int ensure_resume_state(photon_scene *s, bool linear, hipStream_t stream) {
-    const size_t rays = s->ws_rays, groups = (rays + 63) / 64;
-    if (!s->ws.ctr) {
-        unsigned *u = nullptr;
-        PH_CHECK(pool_malloc((void **)&u, (2 * rays + groups) * sizeof(unsigned)));
-        s->ws.ctr = u; s->ws.spins = u + rays; s->ws.seg_flag = u + 2 * rays;
-        PH_CHECK(hipMemsetAsync(s->ws.seg_flag, 0, groups * sizeof(unsigned), stream));
-        s->march_epoch = 0;
-    }
-    if (linear && !s->ws.vprev) PH_CHECK(pool_malloc((void **)&s->ws.vprev, 4 * rays * sizeof(float)));
-    if (++s->march_epoch >= (1u << 24)) {
-        PH_CHECK(hipMemsetAsync(s->ws.seg_flag, 0, groups * sizeof(unsigned), stream));
-        s->march_epoch = 1;
-    }
-    return 0;
-}
-
-// Segments per march of a launch large enough to be segmented: PHOTON_MARCH_SEGMENTS=<n> (1 = whole marches), or
-// PHOTON_MARCH_SEGMENTS=force:<n> to segment launches of any size (tests of the hand-off between segments).
-static int march_segments_default(bool *forced) {
-    const char *e = getenv("PHOTON_MARCH_SEGMENTS");            // read per launch: tests switch it between calls
-    if (e && !strncmp(e, "force:", 6)) { *forced = true; e += 6; }
-    const int v = (e && atoi(e) > 0) ? atoi(e) : PHOTON_MARCH_SEGMENTS;
-    return v > 64 ? 64 : v;
+// Segments per march of a launch large enough to be segmented: the scene's setting (an explicit count above 1 segments
+// launches of any size: tests), else PHOTON_MARCH_SEGMENTS=<n> (1 = whole marches), or PHOTON_MARCH_SEGMENTS=force:<n> to
+// segment launches of any size (tests of the hand-off between segments).  PHOTON_MARCH_SEGMENT_SHAPE=uniform|halving|taper:<t>
+// overrides the planner's choice of shape (A/B runs, tests).  Read once per trace: tests switch them between calls.
+MarchKnobs photon::march_knobs(int scene_segments) {
+    MarchKnobs k;
+    k.forced = scene_segments > 1;
+    const char *n = scene_segments >= 0 ? nullptr : getenv("PHOTON_MARCH_SEGMENTS");       // the scene's setting beats the environment
+    if (n && !strncmp(n, "force:", 6)) { k.forced = true; n += 6; }
+    k.want = std::min(scene_segments >= 0 ? scene_segments : n && atoi(n) > 0 ? atoi(n) : k.want, 64);
+    const char *e = getenv("PHOTON_MARCH_SEGMENT_SHAPE");
+    if (e && !strcmp(e, "uniform")) k.shape = SEG_UNIFORM;
+    if (e && !strcmp(e, "halving")) k.shape = SEG_HALVING;
+    if (e && !strncmp(e, "taper:", 6)) { k.shape = SEG_TAPER; k.taper = (unsigned)std::max(1, std::min(atoi(e + 6), 8)); }
+    return k;
 }
 
 // Shape of the pieces of a segmented march.  Equal pieces; HALVING pieces (1/2, 1/4, ... of the depth, the last two equal):
@@ -115,14 +111,9 @@ static int march_segments_default(bool *forced) {
 // eighth of C3, 3.8 fills: 8.07-8.15 ms halving against 7.53-7.62 equal; the full job, 30.5 fills: 56.95 against 57.28; the
 // front stays clear while r / 2 <= R - 2 for every round r <= R of a pass: halving from 12 fills on); TAPERED pieces: equal
 // ones, the last of them halved t times (.., u, u/2, u/4, u/4 for t = 2) -- a short final pass without the long chain of
-// ever faster passes.  PHOTON_MARCH_SEGMENT_SHAPE=uniform|halving|taper:<t> overrides the choice (A/B runs, tests).
-enum SegShape { SEG_UNIFORM = 0, SEG_HALVING = 1, SEG_TAPER = 2 };
-static SegShape segment_shape(double fills, unsigned *taper) {
-    const char *e = getenv("PHOTON_MARCH_SEGMENT_SHAPE");
-    *taper = 0;
-    if (e && !strcmp(e, "uniform")) return SEG_UNIFORM;
-    if (e && !strcmp(e, "halving")) return SEG_HALVING;
-    if (e && !strncmp(e, "taper:", 6)) { *taper = (unsigned)std::max(1, std::min(atoi(e + 6), 8)); return SEG_TAPER; }
+// ever faster passes.  MarchKnobs::shape overrides the choice.
+static SegShape segment_shape(double fills, const MarchKnobs &knobs) {
+    if (knobs.shape >= 0) return (SegShape)knobs.shape;
     return fills >= 12.0 ? SEG_HALVING : SEG_UNIFORM;
 }
 
@@ -134,12 +125,12 @@ static SegShape segment_shape(double fills, unsigned *taper) {
 // texel of depth; x3 for RK4's three samples, x3 for the 64-tap sampler: RK4 tricubic through 256 texels = 2304 units =
 // 1.9 ms).  Only the last pass's pieces need to be short: R (S - 1) c + 0.75 (last piece), minimised over S for the shape
 // in use.  At most `cap` pieces; `forced` takes the cap itself (tests); the shortest piece is 4 trips.
-static unsigned plan_segments(unsigned groups, unsigned slots, unsigned depth, int algorithm, int interp, unsigned cap, bool forced,
+static unsigned plan_segments(unsigned groups, unsigned slots, unsigned depth, int algorithm, int interp, const MarchKnobs &knobs,
                               unsigned *begin, int *shape_out) {
     const double fills = (double)groups / (double)std::max(slots, 1u);
-    unsigned taper = 0;
-    const SegShape shape = segment_shape(fills, &taper);
-    cap = std::max(1u, std::min(cap, kMaxSegments));
+    const SegShape shape = segment_shape(fills, knobs);
+    const unsigned taper = knobs.taper, cap = std::max(1u, std::min((unsigned)knobs.want, kMaxSegments));
+    const bool forced = knobs.forced;
     // lengths (as fractions of the depth) of the S pieces of a shape
     auto lengths = [&](unsigned S) {
         std::vector<double> len;
@@ -191,65 +182,59 @@ static unsigned plan_segments(unsigned groups, unsigned slots, unsigned depth, i
     return S;
 }
 
-// The library's choice for a launch of n_rays through a volume of `depth` texels on a device of num_cus compute units
-// (host restatement for tests and documentation; PHOTON_MARCH_SEGMENT_SHAPE is honoured, PHOTON_MARCH_SEGMENTS is not).
-extern "C" int photon_march_segments_plan(unsigned n_rays, int depth, int ray_tracing_algorithm, int interpolation, int num_cus, int *halving) {
-    if (depth < 1 || num_cus < 1 || (ray_tracing_algorithm != 1 && ray_tracing_algorithm != 2)) return 0;
-    const unsigned groups = (n_rays + 63u) / 64u, slots = (unsigned)num_cus * 4u * march_waves_of(ray_tracing_algorithm, interpolation);
-    int shape = 0;
-    unsigned s = 1, begin[kMaxSegments + 1];
-    if (groups >= slots + slots / 4) s = plan_segments(groups, slots, (unsigned)depth, ray_tracing_algorithm, interpolation, PHOTON_MARCH_SEGMENTS, false, begin, &shape);
-    if (halving) *halving = shape == SEG_HALVING ? 1 : 0;
-    return (int)s;
-}
-
 namespace photon {
 
-// The march launch of n rays whose state sits in the scene's workspace (stage 1b): persistent grid, work queues, segments.
-int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol, int algorithm, unsigned n, unsigned long long ray_base,
-                 const InterDump &idump, bool save, hipStream_t stream, hipEvent_t ev_march_begin, long long gen_src_begin) {
-    const dim3 block(256), grid((n + 255) / 256);
-    const int interp = vol->dev.interpolation;
-    const f4 *tex = interp == 2 ? vol->d_coeffs : vol->d_texels;
+MarchPlan plan_march(unsigned n, int num_cus, const VolumeDev &vol, int algorithm, bool dumps, bool noise, int ray_order, bool have_rays,
+                     const MarchKnobs &knobs) {
+    MarchPlan p{};
+    const int interp = vol.interpolation;
+    const unsigned depth = (unsigned)std::max(vol.nx, std::max(vol.ny, vol.nz));
+    p.n_rays = n; p.algorithm = algorithm; p.interp = interp;
+    p.segments = 1; p.shape = SEG_UNIFORM; p.seg_begin[1] = depth;
+    p.chunk_shift = march_chunk_shift(interp, ray_order, (size_t)vol.nx * vol.ny * vol.nz);
+    p.persistent = algorithm == 1 || algorithm == 2;
+    if (!p.persistent) { p.block = 256; p.grid = (n + 255) / 256; return p; }      // rk45, adams_bashforth, no-op: one thread per ray, after a raygen kernel
+    p.save = dumps && interp == 1;                          // only the trilinear branches record
+    p.noise = noise && algorithm == 1 && interp == 1;       // the gradient-noise hook exists in that branch only (.h:853-863)
+    p.fold = !have_rays;                                    // ray generation: the prologue of the march's first piece
     // persistent waves: a grid that fills the chip once (more workgroups than fit only find empty queues and leave)
-    const unsigned all_blocks = (n + PHOTON_MARCH_BLOCK - 1) / PHOTON_MARCH_BLOCK;
-    const unsigned fill_blocks = (unsigned)s->num_cus * 8u * (256 / PHOTON_MARCH_BLOCK);
-    const dim3 mblock(PHOTON_MARCH_BLOCK), mgrid(std::min(all_blocks, fill_blocks));
-    if (ev_march_begin) PH_CHECK(hipEventRecord(ev_march_begin, stream));
-    unsigned long long *profile = nullptr;                  // wave timing of this launch, while there are free slots
-    if (s->d_profile && s->prof_next < kProfileLaunches && (algorithm == 1 || algorithm == 2))
-        profile = s->d_profile + (size_t)(s->prof_next++) * kProfileSub * PF_N;
+    p.block = PHOTON_MARCH_BLOCK;
+    p.grid = std::min((n + PHOTON_MARCH_BLOCK - 1) / PHOTON_MARCH_BLOCK, (unsigned)num_cus * 8u * (256 / PHOTON_MARCH_BLOCK));
     // Segments: only where the launch is several times what the chip holds at once (a segment's wave then finds the
     // previous segment of its group long done) and nothing indexes a ray's iterations (dumps, gradient noise).
-    unsigned segments = 1;
-    MarchArgs margs{};
-    if ((algorithm == 1 || algorithm == 2) && !save && !dev.noise.add_ngrad) {
+    if (!p.save && !noise && knobs.want > 1) {
         const unsigned groups = (n + 63u) / 64u;
-        // resident march waves: five or six per SIMD (the launch bounds of the march kernels)
-        const unsigned slots = (unsigned)s->num_cus * 4u * march_waves_of(algorithm, interp);
-        bool forced = s->march_segments > 1;                // an explicit count segments launches of any size (tests)
-        const int want = s->march_segments >= 0 ? s->march_segments : march_segments_default(&forced);
-        if (want > 1 && (forced || groups >= slots + slots / 4)) {
-            const unsigned depth = (unsigned)std::max(vol->dev.nx, std::max(vol->dev.ny, vol->dev.nz));
-            segments = plan_segments(groups, slots, depth, algorithm, interp, (unsigned)std::min(want, 64), forced, margs.seg_begin, nullptr);
-            if (segments > 1) { const int rc = ensure_resume_state(s, interp == 1, stream); if (rc) return rc; }
-        }
+        // resident march waves: five to seven per SIMD (the launch bounds of the march kernels)
+        const unsigned slots = (unsigned)num_cus * 4u * (unsigned)march_waves(algorithm, interp, false);
+        if (knobs.forced || groups >= slots + slots / 4) p.segments = plan_segments(groups, slots, depth, algorithm, interp, knobs, p.seg_begin, &p.shape);
     }
-    margs.vol = vol->dev; margs.tex = tex; margs.n_rays = n; margs.st = s->ws; margs.counters = s->d_counters; margs.noise = dev.noise;
-    margs.ray_base = ray_base; margs.idump = idump; margs.queue = s->d_queue; margs.profile = profile; margs.segments = segments;
-    margs.epoch = s->march_epoch; margs.error = scene_error_word(s);
-    if (gen_src_begin >= 0 && (algorithm == 1 || algorithm == 2)) { margs.gen = 1u; margs.src_begin = gen_src_begin; margs.scene = dev; }
-    // queue chunks: small ones (tail balance) for the tricubic kernels where neighbouring groups are neighbouring SOURCES and
-    // the volume is small enough for every L2 to hold what its waves touch; lens-major launches (neighbouring groups share
-    // a lens tile, their rays fan out over the whole volume) and large volumes keep the L2-friendly 128 -- C5 at a
-    // quarter: 11.0 GB of HBM traffic per launch with 16-group chunks against 3.8 GB with 128, 38.03 against 37.94 ms
-    margs.chunk_shift = interp == 2 && dev.ray_order == 0 && (size_t)vol->dev.nx * vol->dev.ny * vol->dev.nz <= ((size_t)1 << 24)
-                            ? kChunkShiftCubic : kChunkShiftLinear;
-    int rc;
-    if (algorithm != 1 && algorithm != 2) rc = march_launch_extra(algorithm, grid, block, stream, vol->dev, n, s->ws, s->d_counters);
-    else if (interp == 1) rc = march_launch_linear(algorithm, save, algorithm == 1 && dev.noise.add_ngrad != 0, segments > 1, mgrid, mblock, stream, margs);
-    else rc = march_launch_cubic(algorithm, segments > 1, mgrid, mblock, stream, margs);
-    if (rc) return rc;
+    p.segmented = p.segments > 1;
+    return p;
+}
+
+// The march launch of the plan's rays, whose state sits in the scene's workspace (stage 1b): enqueues, decides nothing.
+int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol, const MarchPlan &plan, unsigned long long ray_base,
+                 const InterDump &idump, long long src_begin, hipStream_t stream, hipEvent_t ev_march_begin) {
+    if (ev_march_begin) PH_CHECK(hipEventRecord(ev_march_begin, stream));
+    if (!plan.persistent) return march_launch_extra(plan.algorithm, dim3(plan.grid), dim3(plan.block), stream, vol->dev, plan.n_rays, s->ws, s->d_counters);
+    MarchArgs margs{};
+    if (s->d_profile && s->prof_next < kProfileLaunches)     // wave timing of this launch, while there are free slots
+        margs.profile = s->d_profile + (size_t)(s->prof_next++) * kProfileSub * PF_N;
+    if (plan.segmented) {
+        // the per-group flags carry the launch's epoch, so they are zeroed once (epoch 0: fresh from ensure_resume_state) and when
+        // the 24-bit epoch wraps, not per launch
+        if (s->march_epoch == 0 || s->march_epoch + 1 >= (1u << 24)) {
+            PH_CHECK(hipMemsetAsync(s->ws.seg_flag, 0, (s->ws_rays + 63) / 64 * sizeof(unsigned), stream));
+            s->march_epoch = 0;
+        }
+        s->march_epoch++;
+        memcpy(margs.seg_begin, plan.seg_begin, sizeof margs.seg_begin);
+    }
+    margs.vol = vol->dev; margs.tex = plan.interp == 2 ? vol->d_coeffs : vol->d_texels; margs.n_rays = plan.n_rays; margs.st = s->ws;
+    margs.counters = s->d_counters; margs.noise = dev.noise; margs.ray_base = ray_base; margs.idump = idump; margs.queue = s->d_queue;
+    margs.segments = plan.segments; margs.epoch = s->march_epoch; margs.error = scene_error_word(s); margs.chunk_shift = plan.chunk_shift;
+    if (plan.fold) { margs.gen = 1u; margs.src_begin = src_begin; margs.scene = dev; }
+    if (const int rc = plan.interp == 1 ? march_launch<1>(plan, stream, margs) : march_launch<2>(plan, stream, margs)) return rc;
     PH_CHECK(hipGetLastError());
     return 0;
 }
@@ -290,7 +275,6 @@ extern "C" int photon_trace_volume_rays_queued(const photon_volume_t *vol, int r
             pool_free(s->ws.px); pool_free(s->ws.radiance); free_resume_state(s);
             pool_free(s->d_counters); pool_free(s->d_queue);
         } } cleanup{&sc};
-        sc.march_segments = segments;
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess) {
             sc.device = dev;
@@ -307,8 +291,10 @@ extern "C" int photon_trace_volume_rays_queued(const photon_volume_t *vol, int r
         float *arrays[6] = {sc.ws.px, sc.ws.py, sc.ws.pz, sc.ws.dx, sc.ws.dy, sc.ws.dz};
         for (int c = 0; c < 6; c++) PH_CHECK(hipMemcpy(arrays[c], soa.data() + (size_t)c * n, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
         const InterDump no_dump{nullptr, nullptr, 0, 0, 0u};
+        const MarchPlan plan = plan_march((unsigned)n, sc.num_cus, vol->dev, ray_tracing_algorithm, false, false, 0, true, march_knobs(segments));
+        if (plan.segmented) { const int rc = ensure_resume_state(&sc, plan.interp == 1); if (rc) return rc; }
         sc.launched = true;
-        { const int rc = launch_march(&sc, sc.dev, vol, ray_tracing_algorithm, (unsigned)n, 0ull, no_dump, false, nullptr, nullptr); if (rc) return rc; }
+        { const int rc = launch_march(&sc, sc.dev, vol, plan, 0ull, no_dump, 0, nullptr, nullptr); if (rc) return rc; }
         PH_CHECK(hipDeviceSynchronize());
         { const int rc = march_error_check(&sc); if (rc) return rc; }
         for (int c = 0; c < 6; c++) PH_CHECK(hipMemcpy(soa.data() + (size_t)c * n, arrays[c], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
@@ -316,6 +302,41 @@ extern "C" int photon_trace_volume_rays_queued(const photon_volume_t *vol, int r
             for (int c = 0; c < 3; c++) { pos[3 * i + c] = soa[(size_t)c * n + i]; dir[3 * i + c] = soa[(size_t)(3 + c) * n + i]; }
         return 0;
     });
+}
+
+// The library's choice for a launch of n_rays through a volume of `depth` texels on a device of num_cus compute units: the plan
+// of a source-major launch with the default knobs (PHOTON_MARCH_SEGMENT_SHAPE is honoured, PHOTON_MARCH_SEGMENTS is not).
+extern "C" int photon_march_segments_plan(unsigned n_rays, int depth, int ray_tracing_algorithm, int interpolation, int num_cus, int *halving) {
+    if (depth < 1 || num_cus < 1 || (ray_tracing_algorithm != 1 && ray_tracing_algorithm != 2)) return 0;
+    VolumeDev v{};
+    v.nx = v.ny = v.nz = depth; v.interpolation = interpolation;
+    MarchKnobs knobs = march_knobs(1);                           // a scene setting keeps PHOTON_MARCH_SEGMENTS out: the shape override alone,
+    knobs.want = MarchKnobs().want;                             // then the default count
+    const MarchPlan p = plan_march(n_rays, num_cus, v, ray_tracing_algorithm, false, false, 0, false, knobs);
+    if (halving) *halving = p.shape == SEG_HALVING ? 1 : 0;
+    return (int)p.segments;
+}
+
+// The whole plan of a march launch as a trace would make it (both environment variables are read), for tests: host arithmetic only.
+extern "C" int photon_march_launch_plan(unsigned n_rays, int nx, int ny, int nz, int ray_tracing_algorithm, int interpolation, int num_cus,
+                                        int scene_segments, int flags, photon_march_plan_t *out) {
+    if (!out || out->struct_size < sizeof(photon_march_plan_t) || n_rays > kMaxRaysPerLaunch || nx < 1 || ny < 1 || nz < 1 || num_cus < 1 ||
+        (interpolation != 1 && interpolation != 2) || scene_segments < -1 || scene_segments == 0 || scene_segments > 64) {
+        fprintf(stderr, "photon: photon_march_launch_plan: bad arguments (set struct_size = sizeof(photon_march_plan_t))\n");
+        return 1;
+    }
+    VolumeDev v{};
+    v.nx = nx; v.ny = ny; v.nz = nz; v.interpolation = interpolation;
+    const MarchPlan p = plan_march(n_rays, num_cus, v, ray_tracing_algorithm, flags & 1, flags & 2, flags & 4 ? 1 : 0, false, march_knobs(scene_segments));
+    const uint32_t size = out->struct_size;
+    memset(out, 0, sizeof *out);
+    out->struct_size = size;
+    out->segments = (int)p.segments; out->shape = p.shape;
+    for (unsigned k = 0; k <= p.segments; k++) out->seg_begin[k] = p.seg_begin[k];
+    out->groups_per_chunk = 1u << p.chunk_shift;
+    out->grid_blocks = p.grid; out->block_threads = p.block; out->persistent = p.persistent;
+    out->save = p.save; out->noise = p.noise; out->segmented = p.segmented; out->generates_rays = p.fold;
+    return 0;
 }
 
 extern "C" int photon_scene_set_march_segments(photon_scene_t *scene, int segments) {

@@ -5,17 +5,7 @@
 
 namespace photon {
 
-int march_launch_cubic(int algorithm, bool segmented, dim3 grid, dim3 block, hipStream_t stream, const MarchArgs &a) {
-    if (algorithm == 1) {
-        if (segmented) hipLaunchKernelGGL((march_kernel<1, 2, false, false, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((march_kernel<1, 2, false, false, false>), grid, block, 0, stream, a);
-    } else {
-        if (segmented) hipLaunchKernelGGL((march_kernel<2, 2, false, false, true>), grid, block, 0, stream, a);
-        else hipLaunchKernelGGL((march_kernel<2, 2, false, false, false>), grid, block, 0, stream, a);
-    }
-    PH_CHECK(hipGetLastError());
-    return 0;
-}
+template int march_launch<2>(const MarchPlan &, hipStream_t, const MarchArgs &);     // and with it the tricubic march kernels
 
 int march_rays_launch_cubic(int algorithm, const VolumeDev &vol, const f4 *tex, int n, float *pos, float *dir, int *steps) {
     const dim3 grid((n + 255) / 256), block(256);

@@ -6,19 +6,7 @@
 
 namespace photon {
 
-#define PH_MARCH(A, S, N) do { if (!S && !N && segmented) hipLaunchKernelGGL((march_kernel<A, 1, false, false, true>), grid, block, 0, stream, a); \
-                              else hipLaunchKernelGGL((march_kernel<A, 1, S, N, false>), grid, block, 0, stream, a); } while (0)
-int march_launch_linear(int algorithm, bool save, bool noise, bool segmented, dim3 grid, dim3 block, hipStream_t stream, const MarchArgs &a) {
-    if (algorithm == 1) {                                   // the gradient-noise hook exists in this branch only (.h:853-863)
-        if (save) { if (noise) PH_MARCH(1, true, true); else PH_MARCH(1, true, false); }
-        else { if (noise) PH_MARCH(1, false, true); else PH_MARCH(1, false, false); }
-    } else {
-        if (save) PH_MARCH(2, true, false); else PH_MARCH(2, false, false);
-    }
-    PH_CHECK(hipGetLastError());
-    return 0;
-}
-#undef PH_MARCH
+template int march_launch<1>(const MarchPlan &, hipStream_t, const MarchArgs &);     // and with it the trilinear march kernels
 
 int march_rays_launch_linear(int algorithm, const VolumeDev &vol, const f4 *tex, int n, float *pos, float *dir, int *steps) {
     const dim3 grid((n + 255) / 256), block(256);

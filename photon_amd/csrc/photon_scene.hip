@@ -536,6 +536,21 @@ void free_resume_state(photon_scene *s) {
     s->ws.spins = nullptr; s->ws.seg_flag = nullptr;
 }
 
+// What a segmented march keeps per ray between segments (MarchResume) and the per-group flags; allocated with the first
+// segmented launch of a workspace size.  The flags carry the launch's epoch: epoch 0 = not zeroed yet (launch_march does it,
+// on the launch's stream).
+int ensure_resume_state(photon_scene *s, bool linear) {
+    const size_t rays = s->ws_rays, groups = (rays + 63) / 64;
+    if (!s->ws.ctr) {
+        unsigned *u = nullptr;
+        PH_CHECK(pool_malloc((void **)&u, (2 * rays + groups) * sizeof(unsigned)));
+        s->ws.ctr = u; s->ws.spins = u + rays; s->ws.seg_flag = u + 2 * rays;
+        s->march_epoch = 0;
+    }
+    if (linear && !s->ws.vprev) PH_CHECK(pool_malloc((void **)&s->ws.vprev, 4 * rays * sizeof(float)));
+    return 0;
+}
+
 int ensure_workspace(photon_scene *s, size_t rays) {
     if (s->ws_rays >= rays) return 0;
     scene_quiesce(s);                                           // a smaller launch of this scene may still be using the old blocks

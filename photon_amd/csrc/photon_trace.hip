@@ -93,7 +93,12 @@ int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, const
     PermEntry *order = nullptr;
     if (d_records) { const int rc = moments_block(s, mom_rays, &mom); if (rc) return rc; }
     if (plan.lens_major) { const int rc = source_order_slot(s, src_begin, src_end, &order); if (rc) return rc; }
-    if (vol) { const int rc = ensure_workspace(s, n); if (rc) return rc; }
+    MarchPlan march{};
+    if (vol) {
+        march = plan_march(n, s->num_cus, vol->dev, algorithm, dump.inter_pos != nullptr, s->dev.noise.add_ngrad != 0, order ? 1 : 0, false, plan.march);
+        { const int rc = ensure_workspace(s, n); if (rc) return rc; }
+        if (march.segmented) { const int rc = ensure_resume_state(s, march.interp == 1); if (rc) return rc; }
+    }
     // ... then the launch: from here on kernels of this scene may be in flight
     s->launched = true;
     if (d_records) PH_CHECK(hipMemsetAsync(mom.x, 0xFF, mom_rays * sizeof(float), stream));       // all-ones = NaN: "did not arrive"
@@ -108,13 +113,10 @@ int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, const
     const MomentsDev *mom_p = d_records ? &mom : nullptr;
     if (vol) {
         // ray generation: the prologue of the march's first piece for Euler and RK4, a kernel of its own for the others
-        const bool fold = algorithm == 1 || algorithm == 2;
-        if (!fold) { const int rc = launch_raygen(s, dev, src_begin, n, stream); if (rc) return rc; }
-        const int interp = vol->dev.interpolation;
+        if (!march.fold) { const int rc = launch_raygen(s, dev, src_begin, n, stream); if (rc) return rc; }
         const unsigned long long ray_base = (unsigned long long)(dev.source_base + src_begin) * (unsigned)dev.rays_per_source;
         const InterDump idump{dump.inter_pos, dump.inter_dir, dump.inter_slots, dump.num_save, 0u};
-        const bool save = dump.inter_pos != nullptr && interp == 1;     // only the trilinear branches record
-        const int rc = launch_march(s, dev, vol, algorithm, n, ray_base, idump, save, stream, ev_march_begin, fold ? src_begin : -1);
+        const int rc = launch_march(s, dev, vol, march, ray_base, idump, src_begin, stream, ev_march_begin);
         if (rc) return rc;
         if (ev_march_end) PH_CHECK(hipEventRecord(ev_march_end, stream));
     }

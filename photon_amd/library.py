@@ -21,7 +21,7 @@ DECLARED_SYMBOLS = (
     "start_ray_tracing", "photon_set_device", "photon_device_pci_bus_id", "photon_rand_table", "photon_volume_load_nrrd",
     "photon_volume_from_density", "photon_volume_info", "photon_volume_set_weight_bits", "photon_volume_download", "photon_volume_sample",
     "photon_volume_free", "photon_scene_create", "photon_scene_free", "photon_scene_set_noise", "photon_scene_set_element_train", "photon_scene_set_ray_order", "photon_scene_set_skip_doomed", "photon_scene_live_rays", "photon_scene_live_samples", "photon_scene_live_sources", "photon_sources_missing_sensor", "photon_scene_set_source_base", "photon_march_queue_group", "photon_march_queue_count", "photon_march_queue_chunk", "photon_march_queue_size",
-    "photon_scene_set_march_segments", "photon_march_segments_plan", "photon_trim_caches", "photon_trace", "photon_trace_moments", "photon_start_ray_tracing_moments",
+    "photon_scene_set_march_segments", "photon_march_segments_plan", "photon_march_launch_plan", "photon_trim_caches", "photon_trace", "photon_trace_moments", "photon_start_ray_tracing_moments",
     "photon_scene_stats_begin", "photon_scene_stats_end", "photon_scene_check", "photon_scene_set_march_profile", "photon_scene_march_profile", "photon_scene_march_profile_raw",
     "photon_trace_volume_rays", "photon_trace_volume_rays_queued", "photon_version",
     # section 3: scene generation on the device
@@ -77,6 +77,30 @@ class photon_march_profile_t(ctypes.Structure):
         d = {n: getattr(self, n) for n, _ in self._fields_ if n != "struct_size"}
         d["drain_ms"] = d["span_ms"] - d["end_mean_ms"]
         return {k: (round(v, 4) if isinstance(v, float) else v) for k, v in d.items()}
+
+
+class photon_march_plan_t(ctypes.Structure):
+    _fields_ = [("struct_size", ctypes.c_uint32), ("segments", ctypes.c_int), ("shape", ctypes.c_int),
+                ("seg_begin", ctypes.c_uint * 65), ("groups_per_chunk", ctypes.c_uint), ("grid_blocks", ctypes.c_uint),
+                ("block_threads", ctypes.c_uint), ("persistent", ctypes.c_int), ("save", ctypes.c_int), ("noise", ctypes.c_int),
+                ("segmented", ctypes.c_int), ("generates_rays", ctypes.c_int)]
+
+
+def bind_march_launch_plan(lib):
+    """photon_march_launch_plan of a loaded library (host arithmetic: needs no GPU), as
+    f(n_rays, dims, algorithm, interpolation, num_cus=256, scene_segments=-1, flags=0) -> photon_march_plan_t."""
+    f = lib.photon_march_launch_plan
+    f.argtypes = [ctypes.c_uint] + [ctypes.c_int] * 8 + [ctypes.POINTER(photon_march_plan_t)]
+
+    def plan(n_rays, dims, algorithm, interpolation, num_cus=256, scene_segments=-1, flags=0):
+        nx, ny, nz = (dims, dims, dims) if np.isscalar(dims) else dims
+        out = photon_march_plan_t(struct_size=ctypes.sizeof(photon_march_plan_t))
+        rc = f(int(n_rays), int(nx), int(ny), int(nz), int(algorithm), int(interpolation), int(num_cus), int(scene_segments),
+               int(flags), ctypes.byref(out))
+        if rc != 0:
+            raise PhotonError(f"photon_march_launch_plan failed with code {rc} (see stderr)")
+        return out
+    return plan
 
 
 class PhotonError(RuntimeError):
@@ -183,6 +207,8 @@ class PhotonLibrary:
             L.photon_scene_stats_end.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(photon_trace_stats_t)]
         if hasattr(L, "photon_scene_set_march_segments"):
             L.photon_scene_set_march_segments.argtypes = [ctypes.c_void_p, ctypes.c_int]
+        if hasattr(L, "photon_march_launch_plan"):                           # absent from older libraries (A/B runs)
+            self.march_launch_plan = bind_march_launch_plan(L)
         self.has_march_profile = hasattr(L, "photon_scene_march_profile")  # round 4
         if self.has_march_profile:
             L.photon_scene_set_march_profile.argtypes = [ctypes.c_void_p, ctypes.c_int]

@@ -167,3 +167,166 @@ def test_march_segments_plan():
     assert p(100_000_000 // 2, 512, 2, 2)[0] >= 2                # one launch of C4
     assert p(10_000_000, 8, 2, 2)[0] <= 2                        # the shortest piece is 4 trips
     assert plan(10_000_000, 256, 3, 2, 256, None) == 0           # integrators 3 / 4 are not segmented: refused
+
+
+# ---- the plan of a march launch (photon_march_launch_plan: the planner every launch goes through, host arithmetic) ----
+_SWEEP_RAYS = [64 * k for k in (1, 100, 5000, 6399, 6400, 6401, 7680, 20000, 156250, 1048576)]
+_SWEEP_DEPTHS = (4, 8, 16, 48, 128, 256, 512, 1024)
+DUMPS, NOISE, LENS_MAJOR = 1, 2, 4             # flags of photon_march_launch_plan
+UNIFORM, HALVING, TAPER = 0, 1, 2
+
+
+@pytest.fixture()
+def march_plan(monkeypatch):
+    """f(n_rays, dims, algorithm, interpolation, num_cus=256, scene_segments=-1, flags=0) -> photon_march_plan_t, with
+    the two environment variables of the planner unset."""
+    import ctypes
+    from photon_amd import build
+    from photon_amd.library import bind_march_launch_plan
+    monkeypatch.delenv("PHOTON_MARCH_SEGMENTS", raising=False)
+    monkeypatch.delenv("PHOTON_MARCH_SEGMENT_SHAPE", raising=False)
+    lib = ctypes.CDLL(build.build_library(verbose=False))
+    plan = bind_march_launch_plan(lib)
+    old = lib.photon_march_segments_plan
+    old.argtypes = [ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
+    old.restype = ctypes.c_int
+
+    def segments_plan(rays, depth, algo, interp, cus):
+        h = ctypes.c_int(-1)
+        return old(rays, depth, algo, interp, cus, ctypes.byref(h)), h.value
+    plan.segments_plan = segments_plan
+    return plan
+
+
+def _boundaries(p):
+    return [p.seg_begin[k] for k in range(p.segments + 1)]
+
+
+def _check_boundaries(p, depth, what):
+    b = _boundaries(p)
+    assert b[0] == 0 and b[-1] == depth, (what, b)
+    if p.segments > 1:
+        assert min(np.diff(b)) >= 4, (what, b)
+    assert p.segmented == (p.segments > 1), what
+
+
+def test_march_launch_plan_agrees_with_segments_plan(march_plan):
+    """With no scene setting and no environment, the launch plan's pieces are those photon_march_segments_plan reports, over
+    launches below, at and above 1.25 chip fills of every kernel's wave count (960 plans); and every plan's boundaries run from
+    0 to the depth in pieces of at least 4 trips."""
+    for rays in _SWEEP_RAYS:
+        for depth in _SWEEP_DEPTHS:
+            for algo in (1, 2):
+                for interp in (1, 2):
+                    for cus in (64, 256, 304):
+                        p = march_plan(rays, depth, algo, interp, cus)
+                        what = (rays, depth, algo, interp, cus)
+                        assert (p.segments, int(p.shape == HALVING)) == march_plan.segments_plan(*what), what
+                        _check_boundaries(p, depth, what)
+
+
+def test_march_launch_plan_forced_counts_keep_their_boundaries(march_plan, monkeypatch):
+    for forced in (2, 5, 64):
+        monkeypatch.setenv("PHOTON_MARCH_SEGMENTS", f"force:{forced}")
+        for rays in _SWEEP_RAYS:
+            for depth in _SWEEP_DEPTHS:
+                for algo, interp in ((1, 1), (2, 1), (1, 2), (2, 2)):
+                    p = march_plan(rays, depth, algo, interp)
+                    assert 1 <= p.segments <= forced
+                    _check_boundaries(p, depth, (forced, rays, depth, algo, interp))
+                    if depth >= 4 * forced and p.shape == UNIFORM:
+                        assert p.segments == forced, (forced, rays, depth, algo, interp)
+
+
+@pytest.mark.parametrize("rays, depth, algo, interp, segments, shape", [
+    (10_000_000, 256, 2, 2, 4, HALVING),
+    (10_000_000, 256, 2, 1, 1, UNIFORM),
+    (1_250_000, 256, 2, 2, 11, UNIFORM),
+    (1_250_000, 256, 2, 1, 4, UNIFORM),
+    (2_000_000, 128, 2, 2, 6, UNIFORM),
+    (50_000_000, 512, 2, 2, 3, HALVING),
+    (10_000_000, 256, 1, 2, 3, HALVING),
+    (5_000_000, 256, 2, 2, 5, HALVING),
+    (5_000_000, 256, 2, 1, 2, HALVING),
+    (12_032, 48, 2, 2, 1, UNIFORM),
+])
+def test_march_launch_plan_pins(march_plan, rays, depth, algo, interp, segments, shape):
+    """The plans the library made before the planner was one function (256 compute units, depth^3 texels)."""
+    p = march_plan(rays, depth, algo, interp)
+    assert (p.segments, p.shape) == (segments, shape)
+    assert p.segmented == (segments > 1) and p.save == 0 and p.noise == 0 and p.persistent == 1
+
+
+def test_march_launch_plan_piece_boundaries(march_plan, monkeypatch):
+    assert _boundaries(march_plan(10_000_000, 256, 2, 2)) == [0, 128, 192, 224, 256]       # halving, the last two equal
+    monkeypatch.setenv("PHOTON_MARCH_SEGMENTS", "force:3")
+    p = march_plan(12_032, 256, 2, 2)
+    assert _boundaries(p) == [0, 85, 171, 256] and p.shape == UNIFORM
+    monkeypatch.setenv("PHOTON_MARCH_SEGMENTS", "force:5")
+    assert _boundaries(march_plan(12_032, 8, 2, 2)) == [0, 4, 8]                             # no piece shorter than 4 trips
+
+
+def test_march_launch_plan_knobs(march_plan, monkeypatch):
+    """The scene's setting beats PHOTON_MARCH_SEGMENTS; force: and an explicit count segment launches of any size;
+    PHOTON_MARCH_SEGMENT_SHAPE overrides the shape."""
+    monkeypatch.setenv("PHOTON_MARCH_SEGMENTS", "1")
+    assert march_plan(10_000_000, 256, 2, 2).segments == 1
+    monkeypatch.setenv("PHOTON_MARCH_SEGMENTS", "force:5")
+    assert march_plan(12_032, 256, 2, 2).segments == 5
+    monkeypatch.setenv("PHOTON_MARCH_SEGMENTS", "force:7")
+    assert march_plan(12_032, 256, 2, 2, scene_segments=3).segments == 3
+    assert march_plan(12_032, 256, 2, 2, scene_segments=1).segments == 1
+    assert march_plan(10_000_000, 256, 2, 2, scene_segments=1).segments == 1
+    monkeypatch.delenv("PHOTON_MARCH_SEGMENTS")
+    monkeypatch.setenv("PHOTON_MARCH_SEGMENT_SHAPE", "uniform")
+    p = march_plan(10_000_000, 256, 2, 2)
+    assert p.shape == UNIFORM and p.segments > 1 and len(set(np.diff(_boundaries(p)))) <= 2     # equal up to rounding
+    monkeypatch.setenv("PHOTON_MARCH_SEGMENT_SHAPE", "taper:2")
+    p = march_plan(10_000_000, 256, 2, 2)
+    assert p.shape == TAPER and p.segments > 1
+    _check_boundaries(p, 256, "taper:2")
+
+
+def test_march_launch_plan_exclusions(march_plan):
+    """Dumps and gradient noise index a ray's iterations: such launches march whole, even when a count is forced.  (The
+    tricubic branches record no intermediate dumps: with them the flag changes nothing, save stays 0.)  The integrators
+    other than Euler and RK4 run one thread per ray after a ray-generation kernel."""
+    n = 12_032
+    for algo in (1, 2):
+        p = march_plan(n, 48, algo, 1, scene_segments=5, flags=DUMPS)
+        assert (p.segments, p.segmented, p.save, p.noise) == (1, 0, 1, 0)
+        for interp in (1, 2):
+            p = march_plan(n, 48, algo, interp, scene_segments=5, flags=NOISE)
+            assert (p.segments, p.segmented, p.save) == (1, 0, 0) and p.noise == int(algo == 1 and interp == 1)
+            p = march_plan(10_000_000, 256, algo, interp, flags=NOISE)
+            assert (p.segments, p.segmented) == (1, 0)
+            p = march_plan(n, 48, algo, interp, scene_segments=5, flags=DUMPS | NOISE)
+            assert (p.segments, p.segmented) == (1, 0)
+            assert march_plan(n, 48, algo, interp, scene_segments=5).segments == 5
+        p = march_plan(10_000_000, 256, algo, 1, flags=DUMPS)
+        assert (p.segments, p.segmented, p.save) == (1, 0, 1)
+        assert march_plan(n, 48, algo, 2, scene_segments=5, flags=DUMPS).save == 0
+    for algo in (0, 3, 4):
+        for interp in (1, 2):
+            for rays in (1, 255, 256, 257, n, 10_000_000):
+                p = march_plan(rays, 256, algo, interp, scene_segments=5)
+                assert (p.persistent, p.grid_blocks, p.block_threads) == (0, (rays + 255) // 256, 256)
+                assert (p.segments, p.segmented, p.generates_rays) == (1, 0, 0)
+
+
+def test_march_launch_plan_grid_and_chunks(march_plan):
+    for algo in (1, 2):
+        for interp in (1, 2):
+            for cus in (64, 256, 304):
+                for rays in (1, 256, 257, 12_032, 256 * 8 * cus - 1, 256 * 8 * cus, 256 * 8 * cus + 1, 10_000_000):
+                    p = march_plan(rays, 256, algo, interp, cus)
+                    assert p.grid_blocks == min((rays + 255) // 256, 8 * cus) and p.block_threads == 256
+                    assert p.persistent == 1 and p.generates_rays == 1
+        # queue chunks: 16 groups for the tricubic kernels in source-major launches through at most 2^24 texels, else 128
+        assert march_plan(10_000_000, 256, algo, 2).groups_per_chunk == 16
+        assert march_plan(10_000_000, (128, 256, 512), algo, 2).groups_per_chunk == 16
+        assert march_plan(10_000_000, (257, 256, 256), algo, 2).groups_per_chunk == 128
+        assert march_plan(10_000_000, 256, algo, 2, flags=LENS_MAJOR).groups_per_chunk == 128
+        for dims in (48, 256, (257, 256, 256)):
+            for flags in (0, LENS_MAJOR):
+                assert march_plan(10_000_000, dims, algo, 1, flags=flags).groups_per_chunk == 128

@@ -118,3 +118,38 @@ def test_large_launch_is_segmented_by_default(photon, workdir):
     assert whole["launches"] == 1 and seg["launches"] == 1 and seg["waves"] > 1000      # (the drain itself: test_zz_perf_bounds_gpu.py)
     scene.free()
     vol.free()
+
+
+def test_resume_state_room_is_made_before_the_launch(photon, volume_file):
+    """The room for what a segmented march keeps per ray is made with the workspace's, before anything of the launch is
+    enqueued.  One scene through every way that room comes and goes: whole marches first (none), the first segmented
+    launch (allocated), a larger launch (the workspace regrows and drops it), the trilinear sampler (its extra plane is
+    allocated late), then another piece count.  Every segmented trace counts what the whole marches of its range and
+    sampler count, and its image is theirs up to the order of the f64 sums."""
+    import torch
+    call = scenes.bos_scene(n_dots=6, points_per_dot=20, rays_per_source=100, density_grad_filename=volume_file)
+    scene = photon.scene_create(call)
+    vols = {interp: photon.volume_load_nrrd(volume_file, interp) for interp in (1, 2)}
+    H, W = call.image_shape
+    half, every = call.num_sources // 2, call.num_sources
+
+    def trace(segments, interp, src_end):
+        scene.set_march_segments(segments)
+        img = torch.zeros(H * W, dtype=torch.float32, device="cuda")
+        st = scene.trace(img.data_ptr(), vols[interp], 2, 0, src_end, want_stats=True)
+        return img.cpu().numpy().astype(np.float64), st
+
+    ref = {(2, half): trace(1, 2, half)}
+    got = [((2, half), trace(3, 2, half)), ((2, every), trace(3, 2, every)), ((1, every), trace(3, 1, every)),
+           ((2, every), trace(5, 2, every))]
+    ref[(2, every)] = trace(1, 2, every)
+    ref[(1, every)] = trace(1, 1, every)
+    assert ref[(2, half)][1].rk_iterations > 0 and 0 < ref[(2, half)][1].rays_marched < ref[(2, every)][1].rays_marched
+    for step, (key, (img, st)) in enumerate(got):
+        ref_img, ref_st = ref[key]
+        for f in ("rk_iterations", "volume_samples", "rays_marched", "rays_on_sensor", "sensor_taps"):
+            assert getattr(st, f) == getattr(ref_st, f), (step, key, f)
+        assert rel_l2(img, ref_img) <= 1e-12, (step, key)
+    scene.free()
+    for v in vols.values():
+        v.free()
