@@ -278,7 +278,7 @@ int render_on_devices(const CallArgs &a, const CallSettings &cs, float *image_ar
     if (!rc && check(hipSetDevice(devices[0]), __LINE__)) {
         std::vector<const double *> peers;
         for (size_t k = 1; k < K && !rc; k++) {
-            const double *other = scenes[k]->d_acc;
+            const double *other = scenes[k]->acc.p;
             if (!direct[k]) {                                           // no peer mapping: the runtime stages the copy through the host
                 if (!check(staged[k].alloc(npix), __LINE__)) break;
                 if (!check(hipMemcpyPeerAsync(staged[k].p, devices[0], other, devices[k], npix * sizeof(double), nullptr), __LINE__)) break;
@@ -293,7 +293,7 @@ int render_on_devices(const CallArgs &a, const CallSettings &cs, float *image_ar
             g.n = (int)std::min<size_t>(kGatherPeers, peers.size() - at);
             for (int j = 0; j < g.n; j++) g.peer[j] = peers[at + j];
             const bool last = at + g.n >= peers.size();
-            hipLaunchKernelGGL(gather_sum_kernel, grid, block, 0, nullptr, scenes[0]->d_acc, g, last ? d_img.p : nullptr, npix);
+            hipLaunchKernelGGL(gather_sum_kernel, grid, block, 0, nullptr, scenes[0]->acc.p, g, last ? d_img.p : nullptr, npix);
             if (!check(hipGetLastError(), __LINE__) || last) break;
         }
         if (!rc) check(hipMemcpy(image_array, d_img.p, npix * sizeof(float), hipMemcpyDeviceToHost), __LINE__);      // .cu:3675 (waits for the kernel)
@@ -341,8 +341,8 @@ int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume
     const DumpDev dump{d.pos.p, d.dir.p, a.num_lightrays_save, d.inter_pos.p, d.inter_dir.p, inter ? a.num_intermediate_save : 0};
     const long long kmax = (num_particles + chunk - 1) / chunk;
     const TracePlan plan = make_trace_plan(scene, vol, a.algorithm, dump.final_pos || dump.inter_pos, d_records != nullptr);
-    { const int rc = begin_accumulate(scene, nullptr); if (rc) return rc; }
-    if (d_records) { const int rc = clear_records(d_records, 0, num_particles, nullptr); if (rc) return rc; }
+    PH_TRY(begin_accumulate(scene, nullptr));
+    if (d_records) PH_TRY(clear_records(d_records, 0, num_particles, nullptr));
     for (long long k = 0; k < kmax; k++) {
         PH_CHECK(hipMemsetAsync(d.pos.p, 0xFF, nsave * sizeof(float), nullptr));     // all-ones = NaN (.cu:3527-3533); the null stream, like the chunk's launches
         PH_CHECK(hipMemsetAsync(d.dir.p, 0xFF, nsave * sizeof(float), nullptr));
@@ -351,8 +351,7 @@ int trace_with_dumps(const CallArgs &a, photon_scene *scene, const photon_volume
             PH_CHECK(hipMemsetAsync(d.inter_dir.p, 0xFF, ninter * sizeof(float), nullptr));
         }
         const LaunchRange range = next_launch(scene, plan, k * chunk, std::min(num_particles, (k + 1) * chunk));     // the whole chunk
-        const int rc = launch_chunk(scene, vol, a.algorithm, plan, range, dump, nullptr, nullptr, nullptr, d_records);
-        if (rc) return rc;
+        PH_TRY(launch_chunk(scene, vol, a.algorithm, plan, range, dump, nullptr, nullptr, nullptr, d_records));
         bool wrote = true;                                              // a dump that cannot be written fails the call
         PH_CHECK(hipMemcpy(host.data(), d.pos.p, nsave * sizeof(float), hipMemcpyDeviceToHost));
         wrote = write_dump(a.pos_path, "pos_", (int)k, host) && wrote;
@@ -448,7 +447,7 @@ int start_ray_tracing_impl(const CallArgs &a, float *image_array, double *moment
         return 1;
     }
     Phases t{t0};
-    if (const int rc = render_on_one_device(a, cs, image_array, t, moments)) return rc;
+    PH_TRY(render_on_one_device(a, cs, image_array, t, moments));
     if (!verbose()) return 0;
     const auto t_end = Clock::now();                                    // the call's blocks and scene are freed
     const double s = ms(t0, t_end) * 1e-3;

@@ -279,15 +279,14 @@ int photon::ensure_live_sources(photon_scene *s) {
     const size_t ns = (size_t)s->dev.num_sources;
     if (!s->source_cull.ok || ns == 0) return 0;
     DeviceScope on_scene_device(s->device);
-    unsigned char *d_off = nullptr;
-    PH_CHECK(pool_malloc((void **)&d_off, ns));
+    PoolBuffer<unsigned char> d_off;
+    PH_CHECK(d_off.alloc(ns));
     hipLaunchKernelGGL(source_cull_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, nullptr, s->source_cull, s->dev.sx, s->dev.sy, s->dev.sz,
-                       (long long)ns, d_off);
+                       (long long)ns, d_off.p);
     std::vector<unsigned char> off(ns);
-    hipError_t he = hipGetLastError();
-    if (he == hipSuccess) he = hipMemcpy(off.data(), d_off, ns, hipMemcpyDeviceToHost);
-    pool_free(d_off);
-    PH_CHECK(he);
+    PH_CHECK(hipGetLastError());
+    PH_CHECK(hipMemcpy(off.data(), d_off.p, ns, hipMemcpyDeviceToHost));
+    d_off.reset();                                                      // back to the cache before the list below asks it for a block
     std::vector<int> keep;
     keep.reserve(ns);
     for (size_t i = 0; i < ns; i++)
@@ -295,8 +294,7 @@ int photon::ensure_live_sources(photon_scene *s) {
     if (keep.size() == ns) return 0;
     if (keep.empty()) keep.push_back(0);                                // a launch of zero rays is nobody's friend
     int *d_keep = nullptr;
-    PH_CHECK(pool_malloc((void **)&d_keep, keep.size() * sizeof(int)));
-    s->allocs.push_back(d_keep);
+    PH_TRY(scene_block(s, keep.size() * sizeof(int), &d_keep));
     PH_CHECK(hipMemcpy(d_keep, keep.data(), keep.size() * sizeof(int), hipMemcpyHostToDevice));
     s->d_live_sources = d_keep;
     s->live_sources = std::move(keep);

@@ -17,7 +17,7 @@ using namespace photon;
 struct photon_flow {
     int n[3] = {0, 0, 0};               // nodes along x, y, z
     double spacing[3] = {0, 0, 0}, origin[3] = {0, 0, 0};
-    float4 *d_uvw = nullptr;            // [nz][ny][nx], x fastest
+    DeviceBuffer<float4> uvw;           // [nz][ny][nx], x fastest
 };
 
 struct FlowDev {
@@ -129,28 +129,20 @@ int photon_flow_from_grid(const float *u, const float *v, const float *w, int nx
         const size_t nodes = (size_t)nx * ny * nz;
         std::vector<float4> host(nodes);
         for (size_t q = 0; q < nodes; q++) host[q] = make_float4(u[q], v[q], w[q], 0.f);
-        photon_flow *flow = new photon_flow();
+        std::unique_ptr<photon_flow> flow(new photon_flow());
         flow->n[0] = nx; flow->n[1] = ny; flow->n[2] = nz;
         for (int a = 0; a < 3; a++) { flow->spacing[a] = spacing[a]; flow->origin[a] = origin[a]; }
-        if (device_malloc((void **)&flow->d_uvw, nodes * sizeof(float4)) != hipSuccess) {
+        if (flow->uvw.alloc(nodes) != hipSuccess) {
             fprintf(stderr, "photon: photon_flow_from_grid: device allocation failed\n");
-            delete flow;
             return 3;
         }
-        if (hipMemcpy(flow->d_uvw, host.data(), nodes * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) {
-            photon_flow_free(flow);
-            return 4;
-        }
-        *out = flow;
+        if (hipMemcpy(flow->uvw.p, host.data(), nodes * sizeof(float4), hipMemcpyHostToDevice) != hipSuccess) return 4;
+        *out = flow.release();
         return 0;
     });
 }
 
-void photon_flow_free(photon_flow_t *flow) {
-    if (!flow) return;
-    if (flow->d_uvw) (void)hipFree(flow->d_uvw);
-    delete flow;
-}
+void photon_flow_free(photon_flow_t *flow) { delete flow; }
 
 int photon_sources_piv_advected(uint64_t seed, long long n, const double box_min[3], const double box_max[3], double z_object,
                                 double beam_fwhm, double irradiance_constant, const double *diameter_cdf, int n_diameters,
@@ -161,54 +153,43 @@ int photon_sources_piv_advected(uint64_t seed, long long n, const double box_min
         return 1;
     }
     return guarded("photon_sources_piv_advected", [&]() -> int {
-        photon_sources *src = nullptr;
-        int rc = sources_alloc(n, &src);
-        if (rc) return rc;
+        std::unique_ptr<photon_sources> src;
+        PH_TRY(sources_alloc(n, &src));
         const PivFieldDev f = piv_field_setup(box_min, box_max, z_object, beam_fwhm, irradiance_constant, n_diameters);
         FlowDev g{};
         const bool moving = flow && t != 0;             // flow == NULL or t == 0: the frame of photon_sources_piv itself
         if (moving) {
-            g.uvw = flow->d_uvw;
+            g.uvw = flow->uvw.p;
             for (int a = 0; a < 3; a++) { g.n[a] = flow->n[a]; g.spacing[a] = flow->spacing[a]; g.origin[a] = flow->origin[a]; }
         }
         const double h = moving ? t / steps : 0.0;
         const int run_steps = moving ? steps : 0;
         const unsigned blocks = (unsigned)((n + kBlock - 1) / kBlock);
-        double *d_cdf = nullptr, *d_world = nullptr;
-        float4 *d_partial = nullptr;
-        auto fail = [&](int code) {
-            if (d_cdf) (void)hipFree(d_cdf);
-            if (d_world) (void)hipFree(d_world);
-            if (d_partial) (void)hipFree(d_partial);
-            photon_sources_free(src);
-            return code;
-        };
+        DeviceBuffer<double> d_cdf, d_world;
+        DeviceBuffer<float4> d_partial;
         if (n_diameters > 0) {
-            if (device_malloc((void **)&d_cdf, n_diameters * sizeof(double)) != hipSuccess) return fail(3);
-            if (hipMemcpy(d_cdf, diameter_cdf, n_diameters * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(4);
+            if (d_cdf.alloc((size_t)n_diameters) != hipSuccess) return 3;
+            if (hipMemcpy(d_cdf.p, diameter_cdf, n_diameters * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
         }
         std::vector<float4> partial(blocks);
         if (n) {
-            if (device_malloc((void **)&d_partial, blocks * sizeof(float4)) != hipSuccess) return fail(3);
-            if (world_xyz && device_malloc((void **)&d_world, (size_t)n * 3 * sizeof(double)) != hipSuccess) return fail(3);
-            hipLaunchKernelGGL(sources_piv_advected_kernel, dim3(blocks), dim3(kBlock), 0, 0, (unsigned long long)seed, n, f, d_cdf,
-                               g, h, run_steps, src->x, src->y, src->z, src->radiance, src->diameter_index, d_world, d_partial);
-            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(4);
-            if (hipMemcpy(partial.data(), d_partial, blocks * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return fail(4);
+            if (d_partial.alloc(blocks) != hipSuccess) return 3;
+            if (world_xyz && d_world.alloc((size_t)n * 3) != hipSuccess) return 3;
+            hipLaunchKernelGGL(sources_piv_advected_kernel, dim3(blocks), dim3(kBlock), 0, 0, (unsigned long long)seed, n, f, d_cdf.p,
+                               g, h, run_steps, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p, d_world.p, d_partial.p);
+            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;
+            if (hipMemcpy(partial.data(), d_partial.p, blocks * sizeof(float4), hipMemcpyDeviceToHost) != hipSuccess) return 4;
             if (world_xyz &&
-                hipMemcpy(world_xyz, d_world, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return fail(4);
+                hipMemcpy(world_xyz, d_world.p, (size_t)n * 3 * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return 4;
         }
-        if (d_cdf) (void)hipFree(d_cdf);
-        if (d_world) (void)hipFree(d_world);
-        if (d_partial) (void)hipFree(d_partial);
         // the extent of the particles as stored -- not the box they were drawn from, which they may have left
         if (n) {
             float4 e = partial[0];
             for (unsigned b = 1; b < blocks; b++)
                 e = make_float4(pmax(e.x, partial[b].x), pmax(e.y, partial[b].y), pmin(e.z, partial[b].z), pmax(e.w, partial[b].w));
-            sources_set_extent(src, e.x, e.y, e.z, e.w);
+            sources_set_extent(src.get(), e.x, e.y, e.z, e.w);
         }
-        *out = src;
+        *out = src.release();
         return 0;
     });
 }

@@ -1,9 +1,10 @@
 // photon_internal.hpp - what the translation units of libparallel_ray_tracing.so share on the host side: error
 // handling, the handle types behind include/parallel_ray_tracing.h, and the functions one unit calls in another.
 //
-//   photon_pool.hip          block cache, allocation helper, peer-access record
+//   photon_pool.hip / .hpp   block cache, allocation helper, the two owners of device memory (DeviceBuffer, PoolBuffer), peer-access record
 //   photon_volume.hip        NRRD parser, gradient-volume build + B-spline prefilter kernels, volume handle API, volume cache
-//   photon_scene.hip         scene / source handles, on-device scene generation, the glibc rand table
+//   photon_scene.hip         scene / source handles (their blocks are owner members: nothing is freed by hand), the workspace a scene
+//                            grows on demand, on-device scene generation, the glibc rand table
 //   photon_cull.hip          what a launch may leave out (dead lens samples, sources off the sensor, doomed rays), the plan of a trace
 //   photon_march.hip         host side of a march launch: its plan (pieces, queue chunks, grid, kernel), the enqueue, wave-timing profile
 //   photon_march_{linear,cubic,extra}.hip   the march kernels and the one plan -> kernel dispatcher (march_kernel.hpp), one unit per sampler
@@ -25,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <exception>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <utility>
@@ -50,6 +52,12 @@
             return (int)_e;                                                                     \
         }                                                                                       \
     } while (0)
+// the same for a call of the library's own that returns 0 or a code its caller hands on (it has said why on stderr)
+#define PH_TRY(expr)                                                                            \
+    do {                                                                                        \
+        const int _rc = (expr);                                                                 \
+        if (_rc) return _rc;                                                                    \
+    } while (0)
 
 namespace photon {
 
@@ -73,6 +81,16 @@ int guarded(const char *what, F &&body) {
     return 100;
 }
 
+// a HIP event that is destroyed with its owner
+struct Event {
+    hipEvent_t e = nullptr;
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    ~Event() { if (e) (void)hipEventDestroy(e); }
+    hipError_t create() { return hipEventCreate(&e); }
+    operator hipEvent_t() const { return e; }
+};
+
 }  // namespace photon
 
 // =============================================================================================
@@ -82,22 +100,21 @@ struct photon_volume {
     float grad_max = 0.f;               // largest |grad n| of the texels (per micron)
     photon::VolumeDev dev{};
     photon_volume_info_t info{};
-    photon::f4 *d_texels = nullptr;
-    photon::f4 *d_coeffs = nullptr;
+    photon::DeviceBuffer<photon::f4> texels, coeffs;     // dev.texels / dev.coeffs are views of them
 };
 
 struct photon_sources {                 // light-field sources generated in HBM (SoA, like lightfield_source_t)
     long long n = 0;
-    float *x = nullptr, *y = nullptr, *z = nullptr;
-    double *radiance = nullptr;
-    int *diameter_index = nullptr;
+    photon::DeviceBuffer<float> x, y, z;
+    photon::DeviceBuffer<double> radiance;
+    photon::DeviceBuffer<int> diameter_index;
     // where the generator put them, when it can say (the PIV field's box): the largest distance from the z axis and the z range --
     // what the static skip of dead lens samples needs to know about sources it cannot read (photon_cull.hip, live_lens_samples)
     bool have_extent = false;
     double rmax = 0, zmin = 0, zmax = 0;
 };
 
-struct PermEntry { long long begin = -1, end = -1; int *d_perm = nullptr; size_t capacity = 0; unsigned long long stamp = 0; };
+struct PermEntry { long long begin = -1, end = -1; photon::PoolBuffer<int> perm; unsigned long long stamp = 0; };
 
 namespace photon {
 // What the source cull of the volume-free path needs beside a source's coordinates (photon_cull.hip, source_misses_sensor)
@@ -109,11 +126,18 @@ struct LensCull {
 };
 }  // namespace photon
 
+// Every device block of a scene is a member that releases itself (photon_pool.hpp); the structs that kernels take (dev, ws)
+// are views, filled from the owners.  The destructor only waits for the scene's work (scene_quiesce); whoever deletes a
+// scene has its device current until the members are gone (photon_scene_free).
 struct photon_scene {
+    ~photon_scene();
     photon::SceneDev dev{};
-    std::vector<void *> allocs;         // device buffers owned by the scene
-    photon::RayStateDev ws{};           // march -> sensor state, grown on demand
+    std::vector<photon::PoolBuffer<char>> allocs;       // what was uploaded: the block of small arrays, large arrays, the source list
+    photon::RayStateDev ws{};           // march -> sensor state: views of the four blocks below, grown on demand (ensure_workspace)
     size_t ws_rays = 0;
+    photon::PoolBuffer<float> ray_state, vprev;         // px .. dz; the resume state's last sampled values
+    photon::PoolBuffer<double> radiance;
+    photon::PoolBuffer<unsigned> resume;                // ctr | spins | seg_flag
     unsigned long long *d_counters = nullptr;   // kCounterSlots x kCounterStride statistics words; the last word of slot 0 is the march's
                                         // hand-off error count (scene_error_word), so whatever zeroes the statistics zeroes it too
     unsigned *d_queue = nullptr;        // the march's work queues: room for 64 counters a cache line apart, 8 XCDs x kSubQueues (4) in use + the
@@ -123,16 +147,16 @@ struct photon_scene {
     int num_cus = 256;                  // compute units of the scene's device (size of the persistent march grid)
     unsigned march_epoch = 0;           // tag of the last segmented march launch in ws.seg_flag
     int march_segments = -1;            // photon_scene_set_march_segments: -1 the library's choice, 1 whole marches, n segments
-    unsigned long long *d_profile = nullptr;    // wave-timing slots of the march launches (photon_scene_set_march_profile), or nullptr
+    photon::PoolBuffer<unsigned long long> profile;     // wave-timing slots of the march launches (photon_scene_set_march_profile), or empty
     unsigned prof_next = 0;             // march launches since the slots were last zeroed
-    double *d_acc = nullptr;            // f64 sensor accumulator, W*H
+    photon::PoolBuffer<double> acc;     // f64 sensor accumulator, W*H
     bool acc_clean = false;             // the accumulator is all zeros (finalize_image_kernel leaves it so): the next trace needs no memset
     bool launched = false;              // kernels of this scene may be in flight: its blocks go back to the cache only after a device sync
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+    photon::Event ev[4];
     // statistics window (photon_scene_stats_begin / _end): traces inside it record their events and leave the counters
     // running instead of synchronising per call -- a timed loop then has no host sync and no D2H copy inside it
     bool win_open = false;
-    std::vector<hipEvent_t> win_events;        // created on demand, reused by the next window
+    std::vector<photon::Event> win_events;     // created on demand, reused by the next window
     size_t win_used = 0;
     std::vector<std::pair<size_t, size_t>> win_march, win_total;      // (begin, end) event indices
     uint64_t win_rays = 0;
@@ -150,8 +174,7 @@ struct photon_scene {
     bool live_sources_known = false;    // false: nothing could be ruled out (or the geometry is not covered): every source is launched
     bool live_sources_tried = false;    // the device pass has run (ensure_live_sources: with the scene's first volume-free trace)
     photon::LensCull source_cull;       // set at creation (host arithmetic only)
-    float *d_mom = nullptr;             // moments block of the launches that record per-source moments (6 planes), grown on demand
-    size_t mom_rays = 0;                // entries per plane
+    photon::PoolBuffer<float> mom;      // moments block of the launches that record per-source moments (6 planes), grown on demand
     PermEntry perms[4];                 // spatial (Morton) orders of the lens-major launch ranges seen last
     unsigned long long perm_clock = 0;
     photon_sort_scratch sort_scratch;   // keys / indices / radix-sort temporaries, grown on demand (photon_sort.hip)
@@ -197,7 +220,23 @@ int cached_volume(const char *path, int interpolation, photon_volume **out, Shar
 // Wait for the device before blocks of this scene go back to the cache (its kernels may still be using them); no-op for a
 // scene that never launched anything.
 void scene_quiesce(photon_scene *s);
-void free_resume_state(photon_scene *s);
+// The scene's regrow rule: a block that has to grow lets go of its old memory only after the scene's earlier launches are
+// done with it.  Everything of a scene that grows on demand grows through here.
+template <typename Buffer>
+int scene_reserve(photon_scene *s, Buffer &b, size_t n) {
+    if (b.p && b.n >= n) return 0;
+    if (b.p) scene_quiesce(s);
+    PH_CHECK(b.reserve(n));
+    return 0;
+}
+// a block of `bytes` that the scene owns from here on
+template <typename T>
+int scene_block(photon_scene *s, size_t bytes, T **out) {
+    s->allocs.emplace_back();
+    PH_CHECK(s->allocs.back().alloc(bytes));
+    *out = reinterpret_cast<T *>(s->allocs.back().p);
+    return 0;
+}
 int ensure_workspace(photon_scene *s, size_t rays);
 // room for what a segmented march keeps per ray between its pieces (after ensure_workspace, which drops it when it regrows)
 int ensure_resume_state(photon_scene *s, bool linear);
@@ -282,8 +321,8 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
 // zero the records of sources [src_begin, src_end) on the stream (their sources may all be culled)
 int clear_records(double *d_records, long long src_begin, long long src_end, hipStream_t stream);
 
-// photon_scene.hip: a source handle with device arrays for n sources; the extent of generated sources (photon_cull.hip, live_lens_samples)
-int sources_alloc(long long n, photon_sources **out);
+// photon_scene.hip: a source handle with device arrays for n sources, the caller's until it releases it; the extent of generated sources (photon_cull.hip, live_lens_samples)
+int sources_alloc(long long n, std::unique_ptr<photon_sources> *out);
 void sources_set_extent(photon_sources *src, double ax, double ay, double z0, double z1);
 
 }  // namespace photon

@@ -25,8 +25,8 @@ extern "C" int photon_debug_path_stats(unsigned long long *out, int n_slots) {
         return 1;
     }
     std::vector<unsigned long long> a(n), b(n);
-    if (int rc = march_path_stats_linear(a.data())) return rc;
-    if (int rc = march_path_stats_cubic(b.data())) return rc;
+    PH_TRY(march_path_stats_linear(a.data()));
+    PH_TRY(march_path_stats_cubic(b.data()));
     for (int k = 0; k < n; k++) out[k] = a[k] + b[k];
     return 0;
 }
@@ -73,7 +73,7 @@ int photon_trace_volume_rays(const photon_volume_t *vol, int ray_tracing_algorit
     PH_CHECK(hipMemcpy(d_p.p, pos, b3, hipMemcpyHostToDevice));
     PH_CHECK(hipMemcpy(d_d.p, dir, b3, hipMemcpyHostToDevice));
     const int interp = vol->dev.interpolation;
-    const f4 *tex = interp == 2 ? vol->d_coeffs : vol->d_texels;
+    const f4 *tex = interp == 2 ? vol->coeffs.p : vol->texels.p;
     int rc;
     if (ray_tracing_algorithm != 1 && ray_tracing_algorithm != 2) rc = march_rays_launch_extra(ray_tracing_algorithm, vol->dev, n, d_p.p, d_d.p, d_s.p);
     else if (interp == 1) rc = march_rays_launch_linear(ray_tracing_algorithm, vol->dev, tex, n, d_p.p, d_d.p, d_s.p);
@@ -218,8 +218,8 @@ int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol,
     if (ev_march_begin) PH_CHECK(hipEventRecord(ev_march_begin, stream));
     if (!plan.persistent) return march_launch_extra(plan.algorithm, dim3(plan.grid), dim3(plan.block), stream, vol->dev, plan.n_rays, s->ws, s->d_counters);
     MarchArgs margs{};
-    if (s->d_profile && s->prof_next < kProfileLaunches)     // wave timing of this launch, while there are free slots
-        margs.profile = s->d_profile + (size_t)(s->prof_next++) * kProfileSub * PF_N;
+    if (s->profile.p && s->prof_next < kProfileLaunches)     // wave timing of this launch, while there are free slots
+        margs.profile = s->profile.p + (size_t)(s->prof_next++) * kProfileSub * PF_N;
     if (plan.segmented) {
         // the per-group flags carry the launch's epoch, so they are zeroed once (epoch 0: fresh from ensure_resume_state) and when
         // the 24-bit epoch wraps, not per launch
@@ -230,11 +230,11 @@ int launch_march(photon_scene *s, const SceneDev &dev, const photon_volume *vol,
         s->march_epoch++;
         memcpy(margs.seg_begin, plan.seg_begin, sizeof margs.seg_begin);
     }
-    margs.vol = vol->dev; margs.tex = plan.interp == 2 ? vol->d_coeffs : vol->d_texels; margs.n_rays = plan.n_rays; margs.st = s->ws;
+    margs.vol = vol->dev; margs.tex = plan.interp == 2 ? vol->coeffs.p : vol->texels.p; margs.n_rays = plan.n_rays; margs.st = s->ws;
     margs.counters = s->d_counters; margs.noise = dev.noise; margs.ray_base = ray_base; margs.idump = idump; margs.queue = s->d_queue;
     margs.segments = plan.segments; margs.epoch = s->march_epoch; margs.error = scene_error_word(s); margs.chunk_shift = plan.chunk_shift;
     if (plan.fold) { margs.gen = 1u; margs.src_begin = src_begin; margs.scene = dev; }
-    if (const int rc = plan.interp == 1 ? march_launch<1>(plan, stream, margs) : march_launch<2>(plan, stream, margs)) return rc;
+    PH_TRY(plan.interp == 1 ? march_launch<1>(plan, stream, margs) : march_launch<2>(plan, stream, margs));
     PH_CHECK(hipGetLastError());
     return 0;
 }
@@ -255,7 +255,7 @@ int march_error_check(photon_scene *scene) {
 // march launch after that takes the next one.
 int profile_reset(photon_scene *s, hipStream_t stream) {
     s->prof_next = 0;
-    if (s->d_profile) PH_CHECK(hipMemsetAsync(s->d_profile, 0, (size_t)kProfileLaunches * kProfileSub * PF_N * sizeof(unsigned long long), stream));
+    if (s->profile.p) PH_CHECK(hipMemsetAsync(s->profile.p, 0, (size_t)kProfileLaunches * kProfileSub * PF_N * sizeof(unsigned long long), stream));
     return 0;
 }
 
@@ -270,21 +270,16 @@ extern "C" int photon_trace_volume_rays_queued(const photon_volume_t *vol, int r
     if (n == 0) return 0;
     return guarded("photon_trace_volume_rays_queued", [&]() -> int {
         photon_scene sc;                                        // a bare scene: only what the march launch touches
-        struct Cleanup { photon_scene *s; ~Cleanup() {
-            scene_quiesce(s);
-            pool_free(s->ws.px); pool_free(s->ws.radiance); free_resume_state(s);
-            pool_free(s->d_counters); pool_free(s->d_queue);
-        } } cleanup{&sc};
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess) {
             sc.device = dev;
             if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0) sc.num_cus = cus;
         }
-        PH_CHECK(pool_malloc((void **)&sc.d_counters, (size_t)kCounterSlots * kCounterStride * sizeof(unsigned long long)));
-        PH_CHECK(device_zero(sc.d_counters, (size_t)kCounterSlots * kCounterStride * sizeof(unsigned long long)));
-        PH_CHECK(pool_malloc((void **)&sc.d_queue, kQueues * kQueueStride * sizeof(unsigned)));
+        PH_TRY(scene_block(&sc, kCounterBytes, &sc.d_counters));
+        PH_CHECK(device_zero(sc.d_counters, kCounterBytes));
+        PH_TRY(scene_block(&sc, kQueues * kQueueStride * sizeof(unsigned), &sc.d_queue));
         PH_CHECK(device_zero(sc.d_queue, kQueues * kQueueStride * sizeof(unsigned)));      // zero once: every march launch leaves them zero
-        { const int rc = ensure_workspace(&sc, (size_t)n); if (rc) return rc; }
+        PH_TRY(ensure_workspace(&sc, (size_t)n));
         std::vector<float> soa((size_t)n * 6);
         for (int i = 0; i < n; i++)
             for (int c = 0; c < 3; c++) { soa[(size_t)c * n + i] = pos[3 * i + c]; soa[(size_t)(3 + c) * n + i] = dir[3 * i + c]; }
@@ -292,11 +287,11 @@ extern "C" int photon_trace_volume_rays_queued(const photon_volume_t *vol, int r
         for (int c = 0; c < 6; c++) PH_CHECK(hipMemcpy(arrays[c], soa.data() + (size_t)c * n, (size_t)n * sizeof(float), hipMemcpyHostToDevice));
         const InterDump no_dump{nullptr, nullptr, 0, 0, 0u};
         const MarchPlan plan = plan_march((unsigned)n, sc.num_cus, vol->dev, ray_tracing_algorithm, false, false, 0, true, march_knobs(segments));
-        if (plan.segmented) { const int rc = ensure_resume_state(&sc, plan.interp == 1); if (rc) return rc; }
+        if (plan.segmented) PH_TRY(ensure_resume_state(&sc, plan.interp == 1));
         sc.launched = true;
-        { const int rc = launch_march(&sc, sc.dev, vol, plan, 0ull, no_dump, 0, nullptr, nullptr); if (rc) return rc; }
+        PH_TRY(launch_march(&sc, sc.dev, vol, plan, 0ull, no_dump, 0, nullptr, nullptr));
         PH_CHECK(hipDeviceSynchronize());
-        { const int rc = march_error_check(&sc); if (rc) return rc; }
+        PH_TRY(march_error_check(&sc));
         for (int c = 0; c < 6; c++) PH_CHECK(hipMemcpy(soa.data() + (size_t)c * n, arrays[c], (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
         for (int i = 0; i < n; i++)
             for (int c = 0; c < 3; c++) { pos[3 * i + c] = soa[(size_t)c * n + i]; dir[3 * i + c] = soa[(size_t)(3 + c) * n + i]; }
@@ -349,13 +344,12 @@ extern "C" int photon_scene_set_march_profile(photon_scene_t *scene, int on) {
     if (!scene) return 1;
     return guarded("photon_scene_set_march_profile", [&]() -> int {
         DeviceScope on_scene_device(scene->device);
-        if (on && !scene->d_profile) {
-            PH_CHECK(pool_malloc((void **)&scene->d_profile, (size_t)kProfileLaunches * kProfileSub * PF_N * sizeof(unsigned long long)));
-            PH_CHECK(device_zero(scene->d_profile, (size_t)kProfileLaunches * kProfileSub * PF_N * sizeof(unsigned long long)));
-        } else if (!on && scene->d_profile) {
+        if (on && !scene->profile.p) {
+            PH_CHECK(scene->profile.alloc((size_t)kProfileLaunches * kProfileSub * PF_N));
+            PH_CHECK(device_zero(scene->profile.p, (size_t)kProfileLaunches * kProfileSub * PF_N * sizeof(unsigned long long)));
+        } else if (!on && scene->profile.p) {
             PH_CHECK(hipDeviceSynchronize());
-            pool_free(scene->d_profile);
-            scene->d_profile = nullptr;
+            scene->profile.reset();
         }
         scene->prof_next = 0;
         return 0;
@@ -371,11 +365,11 @@ extern "C" int photon_scene_march_profile(photon_scene_t *scene, photon_march_pr
         const uint32_t size = out->struct_size;
         memset(out, 0, sizeof *out);
         out->struct_size = size;
-        if (!scene->d_profile || scene->prof_next == 0) return 0;
+        if (!scene->profile.p || scene->prof_next == 0) return 0;
         const unsigned launches = std::min(scene->prof_next, kProfileLaunches);
         std::vector<unsigned long long> h((size_t)launches * kProfileSub * PF_N);
         PH_CHECK(hipDeviceSynchronize());
-        PH_CHECK(hipMemcpy(h.data(), scene->d_profile, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+        PH_CHECK(hipMemcpy(h.data(), scene->profile.p, h.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
         double span = 0, start_mean = 0, start_max = 0, end_min = 0, end_mean = 0, waves_sum = 0;
         unsigned used = 0;
         for (unsigned l = 0; l < launches; l++) {
@@ -416,8 +410,8 @@ extern "C" int photon_scene_march_profile(photon_scene_t *scene, photon_march_pr
 // The raw wave-timing slots of one profiled launch (64 sub-slots x 8 words: PF_*; sub-slot = workgroup index % 64, so
 // sub-slot & 7 is the XCD the workgroup ran on): for tools that look at the launch's end per XCD.
 extern "C" int photon_scene_march_profile_raw(photon_scene_t *scene, unsigned launch, unsigned long long *out) {
-    if (!scene || !out || !scene->d_profile || launch >= std::min(scene->prof_next, kProfileLaunches)) return 1;
+    if (!scene || !out || !scene->profile.p || launch >= std::min(scene->prof_next, kProfileLaunches)) return 1;
     PH_CHECK(hipDeviceSynchronize());
-    PH_CHECK(hipMemcpy(out, scene->d_profile + (size_t)launch * kProfileSub * PF_N, (size_t)kProfileSub * PF_N * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    PH_CHECK(hipMemcpy(out, scene->profile.p + (size_t)launch * kProfileSub * PF_N, (size_t)kProfileSub * PF_N * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return 0;
 }

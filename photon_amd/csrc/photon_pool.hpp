@@ -27,25 +27,46 @@ hipError_t device_malloc(void **out, size_t bytes);
 // this library that is not a hipMemsetAsync on the stream of its consumer goes through here (tests/test_sources_lint.py holds the line).
 hipError_t device_zero(void *p, size_t bytes);
 
-// a device allocation that is released on every return path
+// The two owners of device memory: every block of the library is a member or a local of one of them and is released with it,
+// on every return path (tests/test_sources_lint.py holds the line).  n: the elements the block was asked for.  alloc(n) lets
+// go of the old block and takes one of exactly n elements (one element for n = 0: a valid address); reserve(n) keeps a block
+// that already holds n.  Neither waits for the device: whoever regrows a block that kernels may still use waits first
+// (photon_internal.hpp, scene_reserve).
+// An allocation outside the cache (hipFree waits for the device by itself):
 template <typename T>
 struct DeviceBuffer {
     T *p = nullptr;
+    size_t n = 0;
     DeviceBuffer() = default;
-    DeviceBuffer(const DeviceBuffer &) = delete;
-    DeviceBuffer &operator=(const DeviceBuffer &) = delete;
-    ~DeviceBuffer() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return device_malloc((void **)&p, (n ? n : 1) * sizeof(T)); }
+    DeviceBuffer(DeviceBuffer &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { if (this != &o) { reset(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+    ~DeviceBuffer() { reset(); }
+    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    hipError_t alloc(size_t count) {
+        reset();
+        const hipError_t e = device_malloc((void **)&p, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    hipError_t reserve(size_t count) { return p && n >= count ? hipSuccess : alloc(count); }
 };
 // the same for a block of the cache
 template <typename T>
 struct PoolBuffer {
     T *p = nullptr;
+    size_t n = 0;
     PoolBuffer() = default;
-    PoolBuffer(const PoolBuffer &) = delete;
-    PoolBuffer &operator=(const PoolBuffer &) = delete;
-    ~PoolBuffer() { pool_free(p); }
-    hipError_t alloc(size_t n) { return pool_malloc((void **)&p, (n ? n : 1) * sizeof(T)); }
+    PoolBuffer(PoolBuffer &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
+    PoolBuffer &operator=(PoolBuffer &&o) noexcept { if (this != &o) { reset(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
+    ~PoolBuffer() { reset(); }
+    void reset() { pool_free(p); p = nullptr; n = 0; }
+    hipError_t alloc(size_t count) {
+        reset();
+        const hipError_t e = pool_malloc((void **)&p, (count ? count : 1) * sizeof(T));
+        if (e == hipSuccess) n = count;
+        return e;
+    }
+    hipError_t reserve(size_t count) { return p && n >= count ? hipSuccess : alloc(count); }
 };
 
 // Peer access from device `dev` to the memory of device `peer`, decided ONCE per ordered pair and process

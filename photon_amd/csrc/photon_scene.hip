@@ -55,8 +55,7 @@ static int upload(photon_scene *s, UploadPack &pack, const T *host, size_t n, co
     const size_t bytes = n * sizeof(T);
     if (bytes > kPackLimit) {
         T *d = nullptr;
-        PH_CHECK(pool_malloc((void **)&d, bytes));
-        s->allocs.push_back(d);
+        PH_TRY(scene_block(s, bytes, &d));
         PH_CHECK(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
         *dev_out = d;
         return 0;
@@ -79,8 +78,7 @@ static void reserve_zeroed(UploadPack &pack, size_t n, T **dev_out) {
 static int flush_uploads(photon_scene *s, UploadPack &pack) {
     if (pack.items.empty()) return 0;
     char *d = nullptr;
-    PH_CHECK(pool_malloc((void **)&d, pack.host.size()));
-    s->allocs.push_back(d);
+    PH_TRY(scene_block(s, pack.host.size(), &d));
     PH_CHECK(hipMemcpy(d, pack.host.data(), pack.host.size(), hipMemcpyHostToDevice));
     for (const auto &it : pack.items) *it.slot = d + it.offset;
     return 0;
@@ -89,8 +87,7 @@ static int flush_uploads(photon_scene *s, UploadPack &pack) {
 template <typename T>
 static int copy_device(photon_scene *s, const T *dev_src, size_t n, const T **dev_out) {
     T *d = nullptr;
-    PH_CHECK(pool_malloc((void **)&d, std::max<size_t>(n, 1) * sizeof(T)));
-    s->allocs.push_back(d);
+    PH_TRY(scene_block(s, std::max<size_t>(n, 1) * sizeof(T), &d));
     if (n) PH_CHECK(hipMemcpyAsync(d, dev_src, n * sizeof(T), hipMemcpyDeviceToDevice, nullptr));     // the caller waits for the null stream
     *dev_out = d;
     return 0;
@@ -145,53 +142,27 @@ int photon_rand_table(int n, float *r1, float *r2) {
 
 void photon_scene_free(photon_scene_t *s) {
     if (!s) return;
-    // The blocks below go back to the CACHE, not to the runtime (whose hipFree would wait for the device): the next scene of
-    // the same shape may be handed them at once and overwrite them with copies on the null stream, which does not wait for
-    // kernels of this scene still running on a non-blocking stream.  So wait here; microseconds on an idle device.
-    photon::DeviceScope on_scene_device(s->device);             // the caller may have another device current: wait on, and free into, the scene's
-    scene_quiesce(s);
-    for (void *p : s->allocs) pool_free(p);
-    pool_free(s->ws.px);
-    pool_free(s->ws.radiance);
-    free_resume_state(s);
-    pool_free(s->d_profile);                                    // (d_counters and d_queue live in the upload block: allocs)
-    pool_free(s->d_acc);
-    pool_free(s->d_mom);
-    for (auto &p : s->perms) pool_free(p.d_perm);
-    photon_sort_scratch_free(&s->sort_scratch);
-    for (auto &e : s->ev) if (e) (void)hipEventDestroy(e);
-    for (auto &e : s->win_events) if (e) (void)hipEventDestroy(e);
-    delete s;
+    photon::DeviceScope on_scene_device(s->device);             // the caller may have another device current: wait on, and free into, the scene's --
+    delete s;                                                   // for the whole delete: the members go after the destructor's body
 }
 
 // ---------------------------------------------------------------------------------------------
 // light-field sources generated on the device
 // ---------------------------------------------------------------------------------------------
-void photon_sources_free(photon_sources_t *src) {
-    if (!src) return;
-    if (src->x) (void)hipFree(src->x);
-    if (src->y) (void)hipFree(src->y);
-    if (src->z) (void)hipFree(src->z);
-    if (src->radiance) (void)hipFree(src->radiance);
-    if (src->diameter_index) (void)hipFree(src->diameter_index);
-    delete src;
-}
+void photon_sources_free(photon_sources_t *src) { delete src; }
 
 }  // extern "C"
 
-int photon::sources_alloc(long long n, photon_sources **out) {
-    photon_sources *src = new photon_sources();
+int photon::sources_alloc(long long n, std::unique_ptr<photon_sources> *out) {
+    std::unique_ptr<photon_sources> src(new photon_sources());
     src->n = n;
-    const size_t m = (size_t)std::max<long long>(n, 1);
-    if (device_malloc((void **)&src->x, m * sizeof(float)) != hipSuccess || device_malloc((void **)&src->y, m * sizeof(float)) != hipSuccess ||
-        device_malloc((void **)&src->z, m * sizeof(float)) != hipSuccess ||
-        device_malloc((void **)&src->radiance, m * sizeof(double)) != hipSuccess ||
-        device_malloc((void **)&src->diameter_index, m * sizeof(int)) != hipSuccess) {
+    const size_t m = (size_t)n;
+    if (src->x.alloc(m) != hipSuccess || src->y.alloc(m) != hipSuccess || src->z.alloc(m) != hipSuccess ||
+        src->radiance.alloc(m) != hipSuccess || src->diameter_index.alloc(m) != hipSuccess) {
         fprintf(stderr, "photon: sources: device allocation failed\n");
-        photon_sources_free(src);
         return 3;
     }
-    *out = src;
+    *out = std::move(src);
     return 0;
 }
 
@@ -214,25 +185,21 @@ int photon_sources_bos(const double *dot_x, const double *dot_y, int n_dots, con
         return 1;
     }
     const long long n = (long long)n_dots * n_tmpl;
-    photon_sources *src = nullptr;
-    int rc = sources_alloc(n, &src);
-    if (rc) return rc;
-    double *d_in = nullptr;                                             // dot_x | dot_y | tmpl_x | tmpl_y
-    const size_t total = 2 * (size_t)n_dots + 2 * (size_t)n_tmpl;
-    auto fail = [&](int code) { if (d_in) (void)hipFree(d_in); photon_sources_free(src); return code; };
-    if (device_malloc((void **)&d_in, total * sizeof(double)) != hipSuccess) return fail(3);
-    double *d_dx = d_in, *d_dy = d_in + n_dots, *d_tx = d_in + 2 * (size_t)n_dots, *d_ty = d_tx + n_tmpl;
+    std::unique_ptr<photon_sources> src;
+    PH_TRY(sources_alloc(n, &src));
+    DeviceBuffer<double> d_in;                                          // dot_x | dot_y | tmpl_x | tmpl_y
+    if (d_in.alloc(2 * (size_t)n_dots + 2 * (size_t)n_tmpl) != hipSuccess) return 3;
+    double *d_dx = d_in.p, *d_dy = d_dx + n_dots, *d_tx = d_dx + 2 * (size_t)n_dots, *d_ty = d_tx + n_tmpl;
     if ((n_dots && (hipMemcpy(d_dx, dot_x, n_dots * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
                     hipMemcpy(d_dy, dot_y, n_dots * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)) ||
         hipMemcpy(d_tx, tmpl_x, n_tmpl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_ty, tmpl_y, n_tmpl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(4);
+        hipMemcpy(d_ty, tmpl_y, n_tmpl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
     if (n) {
         hipLaunchKernelGGL(sources_bos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_dx, d_dy, (long long)n_dots,
-                           d_tx, d_ty, n_tmpl, z, radiance, src->x, src->y, src->z, src->radiance, src->diameter_index);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(4);
+                           d_tx, d_ty, n_tmpl, z, radiance, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;
     }
-    (void)hipFree(d_in);
-    *out = src;
+    *out = src.release();
     return 0;
 }
 
@@ -244,27 +211,24 @@ int photon_sources_piv(uint64_t seed, long long n, const double box_min[3], cons
         fprintf(stderr, "photon: photon_sources_piv: bad arguments\n");
         return 1;
     }
-    photon_sources *src = nullptr;
-    int rc = sources_alloc(n, &src);
-    if (rc) return rc;
+    std::unique_ptr<photon_sources> src;
+    PH_TRY(sources_alloc(n, &src));
     const PivFieldDev f = piv_field_setup(box_min, box_max, z_object, beam_fwhm, irradiance_constant, n_diameters);
-    double *d_cdf = nullptr;
-    auto fail = [&](int code) { if (d_cdf) (void)hipFree(d_cdf); photon_sources_free(src); return code; };
+    DeviceBuffer<double> d_cdf;
     if (n_diameters > 0) {
-        if (device_malloc((void **)&d_cdf, n_diameters * sizeof(double)) != hipSuccess) return fail(3);
-        if (hipMemcpy(d_cdf, diameter_cdf, n_diameters * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return fail(4);
+        if (d_cdf.alloc((size_t)n_diameters) != hipSuccess) return 3;
+        if (hipMemcpy(d_cdf.p, diameter_cdf, n_diameters * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
     }
     if (n) {
         hipLaunchKernelGGL(sources_piv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (unsigned long long)seed, n, f,
-                           d_cdf, src->x, src->y, src->z, src->radiance, src->diameter_index);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return fail(4);
+                           d_cdf.p, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p);
+        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;
     }
-    if (d_cdf) (void)hipFree(d_cdf);
     {   // the box the particles were drawn from (sources_piv_kernel: X, Y uniform in the box, z = Z + z_object)
         const double ax = std::max(fabs(box_min[0]), fabs(box_max[0])), ay = std::max(fabs(box_min[1]), fabs(box_max[1]));
-        sources_set_extent(src, ax, ay, std::min(box_min[2], box_max[2]) + z_object, std::max(box_min[2], box_max[2]) + z_object);
+        sources_set_extent(src.get(), ax, ay, std::min(box_min[2], box_max[2]) + z_object, std::max(box_min[2], box_max[2]) + z_object);
     }
-    *out = src;
+    *out = src.release();
     return 0;
 }
 
@@ -275,11 +239,11 @@ int photon_sources_download(const photon_sources_t *src, float *x, float *y, flo
     if (!src) return 1;
     const size_t n = (size_t)src->n;
     if (!n) return 0;
-    if (x) PH_CHECK(hipMemcpy(x, src->x, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (y) PH_CHECK(hipMemcpy(y, src->y, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (z) PH_CHECK(hipMemcpy(z, src->z, n * sizeof(float), hipMemcpyDeviceToHost));
-    if (radiance) PH_CHECK(hipMemcpy(radiance, src->radiance, n * sizeof(double), hipMemcpyDeviceToHost));
-    if (diameter_index) PH_CHECK(hipMemcpy(diameter_index, src->diameter_index, n * sizeof(int), hipMemcpyDeviceToHost));
+    if (x) PH_CHECK(hipMemcpy(x, src->x.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (y) PH_CHECK(hipMemcpy(y, src->y.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (z) PH_CHECK(hipMemcpy(z, src->z.p, n * sizeof(float), hipMemcpyDeviceToHost));
+    if (radiance) PH_CHECK(hipMemcpy(radiance, src->radiance.p, n * sizeof(double), hipMemcpyDeviceToHost));
+    if (diameter_index) PH_CHECK(hipMemcpy(diameter_index, src->diameter_index.p, n * sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -343,12 +307,11 @@ static int scene_create_impl(float lens_pitch, float image_distance, const scatt
         fprintf(stderr, "photon: bad ray / source counts\n");
         return 1;
     }
-    photon_scene *s = new photon_scene();
-    (void)hipGetDevice(&s->device);                             // first: the failure paths below free into this device's block cache
+    std::unique_ptr<photon_scene> owner(new photon_scene());   // the caller's device is current and stays so: a failure path frees into its block cache
+    photon_scene *s = owner.get();
+    (void)hipGetDevice(&s->device);
     SceneDev &d = s->dev;
     UploadPack pack;
-    int rc = 0;
-    auto bail = [&](int code) { photon_scene_free(s); return code; };
     d.lens_pitch = lens_pitch; d.image_distance = image_distance; d.beam_wavelength = beam_wavelength;
     d.f_number = aperture_f_number; d.ratio = ray_cone_pitch_ratio;
     d.scattering_type = strcmp(scattering_type_str, "mie") == 0 ? 1 : 0;       // .cu:3192
@@ -356,18 +319,18 @@ static int scene_create_impl(float lens_pitch, float image_distance, const scatt
     const size_t ns = (size_t)n_sources;
     d.num_sources = (int)ns;
     if (generated) {                                    // already in HBM: device-to-device, no host arrays
-        if ((rc = copy_device<float>(s, generated->x, ns, &d.sx))) return bail(rc);
-        if ((rc = copy_device<float>(s, generated->y, ns, &d.sy))) return bail(rc);
-        if ((rc = copy_device<float>(s, generated->z, ns, &d.sz))) return bail(rc);
-        if ((rc = copy_device<double>(s, generated->radiance, ns, &d.sradiance))) return bail(rc);
-        if ((rc = copy_device<int>(s, generated->diameter_index, ns, &d.sdia))) return bail(rc);
-        if (hipStreamSynchronize(nullptr) != hipSuccess) return bail(4);        // complete before the scene is handed out: its launches may use any stream
+        PH_TRY(copy_device<float>(s, generated->x.p, ns, &d.sx));
+        PH_TRY(copy_device<float>(s, generated->y.p, ns, &d.sy));
+        PH_TRY(copy_device<float>(s, generated->z.p, ns, &d.sz));
+        PH_TRY(copy_device<double>(s, generated->radiance.p, ns, &d.sradiance));
+        PH_TRY(copy_device<int>(s, generated->diameter_index.p, ns, &d.sdia));
+        if (hipStreamSynchronize(nullptr) != hipSuccess) return 4;        // complete before the scene is handed out: its launches may use any stream
     } else {
-        if ((rc = upload(s, pack, lsp->x, ns, &d.sx))) return bail(rc);
-        if ((rc = upload(s, pack, lsp->y, ns, &d.sy))) return bail(rc);
-        if ((rc = upload(s, pack, lsp->z, ns, &d.sz))) return bail(rc);
-        if ((rc = upload(s, pack, lsp->radiance, ns, &d.sradiance))) return bail(rc);
-        if ((rc = upload(s, pack, lsp->diameter_index, ns, &d.sdia))) return bail(rc);
+        PH_TRY(upload(s, pack, lsp->x, ns, &d.sx));
+        PH_TRY(upload(s, pack, lsp->y, ns, &d.sy));
+        PH_TRY(upload(s, pack, lsp->z, ns, &d.sz));
+        PH_TRY(upload(s, pack, lsp->radiance, ns, &d.sradiance));
+        PH_TRY(upload(s, pack, lsp->diameter_index, ns, &d.sdia));
     }
     d.z_offset = lsp->z_offset; d.object_distance = lsp->object_distance;
     memcpy(d.mie_inv_rot, sdp->inverse_rotation_matrix, sizeof d.mie_inv_rot);
@@ -376,11 +339,10 @@ static int scene_create_impl(float lens_pitch, float image_distance, const scatt
     if (d.scattering_type) {
         if (sdp->num_angles < 2 || sdp->num_diameters < 1 || !sdp->scattering_angle || !sdp->scattering_irradiance) {
             fprintf(stderr, "photon: \"mie\" scattering needs an angle/irradiance table\n");
-            return bail(1);
+            return 1;
         }
-        if ((rc = upload(s, pack, sdp->scattering_angle, (size_t)sdp->num_angles, &d.mie_angle))) return bail(rc);
-        if ((rc = upload(s, pack, sdp->scattering_irradiance, (size_t)sdp->num_angles * sdp->num_diameters, &d.mie_irr)))
-            return bail(rc);
+        PH_TRY(upload(s, pack, sdp->scattering_angle, (size_t)sdp->num_angles, &d.mie_angle));
+        PH_TRY(upload(s, pack, sdp->scattering_irradiance, (size_t)sdp->num_angles * sdp->num_diameters, &d.mie_irr));
     }
     photon::LensCull source_cull;
     std::vector<float> r1(lightray_number_per_particle), r2(lightray_number_per_particle);
@@ -398,15 +360,15 @@ static int scene_create_impl(float lens_pitch, float image_distance, const scatt
             lx[k] = (float)(d.ratio * 1.0 * d.lens_pitch * r1[k] * cs);
             ly[k] = (float)(d.ratio * 1.0 * d.lens_pitch * r1[k] * sn);
         }
-        if ((rc = upload(s, pack, lx.data(), lx.size(), &d.lens_x))) return bail(rc);
-        if ((rc = upload(s, pack, ly.data(), ly.size(), &d.lens_y))) return bail(rc);
+        PH_TRY(upload(s, pack, lx.data(), lx.size(), &d.lens_x));
+        PH_TRY(upload(s, pack, ly.data(), ly.size(), &d.lens_y));
         // Which lens samples can reach the first element's aperture at all (photon_cull.hip, live_lens_samples): the rest need not be
         // launched on the volume-free path -- half of a full-aperture cone.
         std::vector<int> live = live_lens_samples(lx, ly, lsp, generated, ns, image_distance, num_elements, edp, element_center,
                                                   element_plane_parameters);
         s->live_count = (int)live.size();
         s->live_host = live;
-        if (live.size() < lx.size() && (rc = upload(s, pack, live.data(), live.size(), &s->d_live))) return bail(rc);
+        if (live.size() < lx.size()) PH_TRY(upload(s, pack, live.data(), live.size(), &s->d_live));
         // ... and which SOURCES can reach the sensor at all (photon_cull.hip, source_misses_sensor): decided on the device once the sources are there
         s->live_sources_known = false;
         if (ns > 0 && lx.size() >= 2)
@@ -429,10 +391,10 @@ static int scene_create_impl(float lens_pitch, float image_distance, const scatt
         d.train_mode = 0;
         d.source_base = 0;                                      // (slot_rays, slot_map, src_list, src_perm, ray_order, doom_margin: per launch, launch_chunk)
         s->lens_z = (float)element_center[0][2];
-        if ((rc = upload(s, pack, edp, (size_t)num_elements, &d.all_elems))) return bail(rc);
-        if ((rc = upload(s, pack, centers.data(), centers.size(), &d.all_centers))) return bail(rc);
-        if ((rc = upload(s, pack, planes.data(), planes.size(), &d.all_planes))) return bail(rc);
-        if ((rc = upload(s, pack, element_system_index, (size_t)num_elements, &d.all_sys_index))) return bail(rc);
+        PH_TRY(upload(s, pack, edp, (size_t)num_elements, &d.all_elems));
+        PH_TRY(upload(s, pack, centers.data(), centers.size(), &d.all_centers));
+        PH_TRY(upload(s, pack, planes.data(), planes.size(), &d.all_planes));
+        PH_TRY(upload(s, pack, element_system_index, (size_t)num_elements, &d.all_sys_index));
     }
     // The statistics counters (the march's error word among them: scene_error_word) and the work queues start at zero --
     // every march launch leaves the queues so -- and are zeroed HERE, as part of the one host-to-device copy, which is
@@ -444,26 +406,26 @@ static int scene_create_impl(float lens_pitch, float image_distance, const scatt
     // image off by 6e-5 with none).
     reserve_zeroed(pack, kCounterBytes / sizeof(unsigned long long), &s->d_counters);
     reserve_zeroed(pack, (size_t)kQueues * kQueueStride, &s->d_queue);
-    if ((rc = flush_uploads(s, pack))) return bail(rc);
+    PH_TRY(flush_uploads(s, pack));
     s->source_cull = source_cull;                               // the device pass runs with the first volume-free trace (photon_cull.hip, ensure_live_sources)
     d.cam = *cam;
     d.noise = NoiseDev{0, 0, 0.f, 0.f, 0ull};
     if (cam->x_pixel_number < 1 || cam->y_pixel_number < 1) {
         fprintf(stderr, "photon: sensor needs at least one pixel\n");
-        return bail(1);
+        return 1;
     }
-    hipError_t e = pool_malloc((void **)&s->d_acc, (size_t)cam->x_pixel_number * cam->y_pixel_number * sizeof(double));
-    if (e != hipSuccess) { fprintf(stderr, "photon: hipMalloc failed: %s\n", hipGetErrorString(e)); return bail((int)e); }
+    hipError_t e = s->acc.alloc((size_t)cam->x_pixel_number * cam->y_pixel_number);
+    if (e != hipSuccess) { fprintf(stderr, "photon: hipMalloc failed: %s\n", hipGetErrorString(e)); return (int)e; }
     {
         int dev = 0, cus = 0;
         if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && cus > 0)
             s->num_cus = cus;
     }
     for (auto &ev : s->ev) {
-        e = hipEventCreate(&ev);
-        if (e != hipSuccess) { fprintf(stderr, "photon: hipEventCreate failed: %s\n", hipGetErrorString(e)); return bail((int)e); }
+        e = ev.create();
+        if (e != hipSuccess) { fprintf(stderr, "photon: hipEventCreate failed: %s\n", hipGetErrorString(e)); return (int)e; }
     }
-    *out = s;
+    *out = owner.release();
     return 0;
 }
 
@@ -530,42 +492,42 @@ void scene_quiesce(photon_scene *s) {
     s->launched = false;
 }
 
-void free_resume_state(photon_scene *s) {
-    if (s->ws.ctr) { pool_free(s->ws.ctr); s->ws.ctr = nullptr; }
-    if (s->ws.vprev) { pool_free(s->ws.vprev); s->ws.vprev = nullptr; }
-    s->ws.spins = nullptr; s->ws.seg_flag = nullptr;
-}
-
 // What a segmented march keeps per ray between segments (MarchResume) and the per-group flags; allocated with the first
-// segmented launch of a workspace size.  The flags carry the launch's epoch: epoch 0 = not zeroed yet (launch_march does it,
-// on the launch's stream).
+// segmented launch of a workspace size (ensure_workspace drops both blocks when it regrows).  The flags carry the launch's
+// epoch: epoch 0 = not zeroed yet (launch_march does it, on the launch's stream).
 int ensure_resume_state(photon_scene *s, bool linear) {
     const size_t rays = s->ws_rays, groups = (rays + 63) / 64;
-    if (!s->ws.ctr) {
-        unsigned *u = nullptr;
-        PH_CHECK(pool_malloc((void **)&u, (2 * rays + groups) * sizeof(unsigned)));
+    if (!s->resume.p) {
+        PH_CHECK(s->resume.alloc(2 * rays + groups));
+        unsigned *u = s->resume.p;
         s->ws.ctr = u; s->ws.spins = u + rays; s->ws.seg_flag = u + 2 * rays;
         s->march_epoch = 0;
     }
-    if (linear && !s->ws.vprev) PH_CHECK(pool_malloc((void **)&s->ws.vprev, 4 * rays * sizeof(float)));
+    if (linear && !s->vprev.p) PH_CHECK(s->vprev.alloc(4 * rays));
+    s->ws.vprev = s->vprev.p;
     return 0;
 }
 
 int ensure_workspace(photon_scene *s, size_t rays) {
     if (s->ws_rays >= rays) return 0;
-    scene_quiesce(s);                                           // a smaller launch of this scene may still be using the old blocks
-    if (s->ws.px) { pool_free(s->ws.px); s->ws.px = nullptr; }
-    if (s->ws.radiance) { pool_free(s->ws.radiance); s->ws.radiance = nullptr; }
-    free_resume_state(s);
     s->ws_rays = 0;
-    float *f = nullptr;
-    PH_CHECK(pool_malloc((void **)&f, rays * 6 * sizeof(float)));
+    PH_TRY(scene_reserve(s, s->ray_state, rays * 6));           // a smaller launch of this scene may still be using the old blocks
+    s->resume.reset(); s->vprev.reset();                        // sized by the workspace: the next segmented launch makes them anew
+    s->ws.ctr = s->ws.spins = s->ws.seg_flag = nullptr; s->ws.vprev = nullptr;
+    PH_TRY(scene_reserve(s, s->radiance, rays));
+    float *f = s->ray_state.p;
     s->ws.px = f; s->ws.py = f + rays; s->ws.pz = f + 2 * rays;
     s->ws.dx = f + 3 * rays; s->ws.dy = f + 4 * rays; s->ws.dz = f + 5 * rays;
-    PH_CHECK(pool_malloc((void **)&s->ws.radiance, rays * sizeof(double)));
+    s->ws.radiance = s->radiance.p;
     s->ws_rays = rays;
     s->ws.stride = (unsigned)rays;
     return 0;
 }
 
 }  // namespace photon
+
+// The scene's blocks go back to the CACHE, not to the runtime (whose free would wait for the device): the next scene of the
+// same shape may be handed them at once and overwrite them with copies on the null stream, which does not wait for kernels
+// of this scene still running on a non-blocking stream.  So wait here (microseconds on an idle device); the members then
+// release themselves.
+photon_scene::~photon_scene() { photon::scene_quiesce(this); }

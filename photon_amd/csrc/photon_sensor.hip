@@ -168,7 +168,7 @@ template <bool MOM>
 static void launch_sensor_kernel(photon_scene *s, const SceneDev &dev, bool from_state, bool taps_only, long long src_begin, unsigned n,
                                  const DumpDev &dump, hipStream_t stream, const MomentsDev &mom) {
     const dim3 block(256), grid((n + 255) / 256);
-#define PH_SENSOR_ARGS grid, block, 0, stream, dev, src_begin, n, s->ws, s->d_acc, dump, s->d_counters, mom
+#define PH_SENSOR_ARGS grid, block, 0, stream, dev, src_begin, n, s->ws, s->acc.p, dump, s->d_counters, mom
     if (taps_only && !from_state) hipLaunchKernelGGL((sensor_kernel<false, false, 2, MOM>), PH_SENSOR_ARGS);
     else if (taps_only) hipLaunchKernelGGL((sensor_kernel<true, false, 2, MOM>), PH_SENSOR_ARGS);
     else if (from_state) {
@@ -193,7 +193,7 @@ int launch_sensor(photon_scene *s, const SceneDev &dev, bool from_state, long lo
 
 int launch_finalize(photon_scene *s, float *d_image, hipStream_t stream) {
     const size_t npix = (size_t)s->dev.cam.x_pixel_number * s->dev.cam.y_pixel_number;
-    hipLaunchKernelGGL(finalize_image_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, d_image, s->d_acc, npix);
+    hipLaunchKernelGGL(finalize_image_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, stream, d_image, s->acc.p, npix);
     PH_CHECK(hipGetLastError());
     s->acc_clean = true;
     return 0;

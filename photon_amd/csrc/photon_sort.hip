@@ -12,12 +12,9 @@
 // sources.
 //
 // Own translation unit: nothing of it rides in the march kernels' compile.
-#include "photon_sort.hpp"
-#include <hip/hip_runtime.h>
-
 #include <cfloat>
-#include <cstdint>
-#include <cstdio>
+
+#include "photon_internal.hpp"
 
 namespace {
 
@@ -181,49 +178,26 @@ __global__ __launch_bounds__(64) void radix_scatter_kernel(const unsigned *__res
 
 }  // namespace
 
-void photon_sort_scratch_free(photon_sort_scratch *s) {
-    if (!s) return;
-    if (s->box) (void)hipFree(s->box);
-    if (s->keys) (void)hipFree(s->keys);
-    if (s->idx) (void)hipFree(s->idx);
-    if (s->tmp) (void)hipFree(s->tmp);
-    *s = photon_sort_scratch{};
-}
-
 int photon_morton_order(const float *d_x, const float *d_y, int first, long long n, int *d_perm_out, hipStream_t stream,
                         photon_sort_scratch *sc) {
     if (n <= 0) return 0;
-    hipError_t e = hipSuccess;
-#define PS_CHECK(expr) do { e = (expr); if (e != hipSuccess) { fprintf(stderr, "photon: HIP error %d (%s) at %s:%d\n", (int)e, hipGetErrorString(e), __FILE__, __LINE__); return (int)e; } } while (0)
     const int tile = radix_tile(n);
     const unsigned n_tiles = (unsigned)((n + tile - 1) / tile);
-    const size_t need_tmp = ((size_t)kRadix * n_tiles + kRadix) * sizeof(unsigned);        // the (digit, tile) counts of one pass + the row totals
-    if (!sc->box) PS_CHECK(hipMalloc((void **)&sc->box, 4 * sizeof(unsigned)));
-    if (sc->capacity < (size_t)n) {
-        if (sc->keys) { (void)hipFree(sc->keys); sc->keys = nullptr; }
-        if (sc->idx) { (void)hipFree(sc->idx); sc->idx = nullptr; }
-        sc->capacity = 0;
-        PS_CHECK(hipMalloc((void **)&sc->keys, 2 * (size_t)n * sizeof(unsigned)));
-        PS_CHECK(hipMalloc((void **)&sc->idx, (size_t)n * sizeof(int)));
-        sc->capacity = (size_t)n;
-    }
-    if (sc->tmp_bytes < need_tmp || !sc->tmp) {
-        if (sc->tmp) { (void)hipFree(sc->tmp); sc->tmp = nullptr; }
-        sc->tmp_bytes = 0;
-        PS_CHECK(hipMalloc(&sc->tmp, need_tmp));
-        sc->tmp_bytes = need_tmp;
-    }
-    // two buffers of pairs: A = (sc->keys, sc->idx), B = (sc->keys + capacity, d_perm_out).  The keys are written into B and the
+    PH_CHECK(sc->box.reserve(4));
+    PH_CHECK(sc->keys.reserve(2 * (size_t)n));
+    PH_CHECK(sc->idx.reserve((size_t)n));
+    PH_CHECK(sc->tmp.reserve((size_t)kRadix * n_tiles + kRadix));          // the (digit, tile) counts of one pass + the row totals
+    // two buffers of pairs: A = (keys, idx), B = (keys + idx.n, d_perm_out).  The keys are written into B and the
     // four passes go B -> A -> B -> A -> B: the sorted indices end where the caller wants them.
-    unsigned *keys_a = sc->keys, *keys_b = sc->keys + sc->capacity, *counts = (unsigned *)sc->tmp;
-    int *vals_a = sc->idx, *vals_b = d_perm_out;
-    hipLaunchKernelGGL(init_box_kernel, dim3(1), dim3(64), 0, stream, sc->box);
-    PS_CHECK(hipGetLastError());
+    unsigned *keys_a = sc->keys.p, *keys_b = sc->keys.p + sc->idx.n, *counts = sc->tmp.p;
+    int *vals_a = sc->idx.p, *vals_b = d_perm_out;
+    hipLaunchKernelGGL(init_box_kernel, dim3(1), dim3(64), 0, stream, sc->box.p);
+    PH_CHECK(hipGetLastError());
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    hipLaunchKernelGGL(bbox_kernel, dim3(blocks < 128u ? blocks : 128u), dim3(256), 0, stream, d_x + first, d_y + first, n, sc->box);
-    PS_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(morton_keys_kernel, dim3(blocks), dim3(256), 0, stream, d_x + first, d_y + first, n, sc->box, first, keys_b, vals_b);
-    PS_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(bbox_kernel, dim3(blocks < 128u ? blocks : 128u), dim3(256), 0, stream, d_x + first, d_y + first, n, sc->box.p);
+    PH_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(morton_keys_kernel, dim3(blocks), dim3(256), 0, stream, d_x + first, d_y + first, n, sc->box.p, first, keys_b, vals_b);
+    PH_CHECK(hipGetLastError());
     for (int pass = 0; pass < 32 / kRadixBits; pass++) {
         const unsigned *kin = (pass & 1) ? keys_a : keys_b;
         const int *vin = (pass & 1) ? vals_a : vals_b;
@@ -231,34 +205,26 @@ int photon_morton_order(const float *d_x, const float *d_y, int first, long long
         int *vout = (pass & 1) ? vals_b : vals_a;
         const int shift = pass * kRadixBits;
         hipLaunchKernelGGL(radix_hist_kernel, dim3(n_tiles), dim3(64), 0, stream, kin, n, shift, n_tiles, tile, counts);
-        PS_CHECK(hipGetLastError());
+        PH_CHECK(hipGetLastError());
         hipLaunchKernelGGL(radix_rowscan_kernel, dim3(kRadix / 4), dim3(256), 0, stream, counts, n_tiles);
-        PS_CHECK(hipGetLastError());
+        PH_CHECK(hipGetLastError());
         hipLaunchKernelGGL(radix_scatter_kernel, dim3(n_tiles), dim3(64), 0, stream, kin, vin, kout, vout, n, shift, n_tiles, tile, counts);
-        PS_CHECK(hipGetLastError());
+        PH_CHECK(hipGetLastError());
     }
-#undef PS_CHECK
     return 0;
 }
 
 // Self-test hook (include/parallel_ray_tracing.h): the Morton order of host arrays, through the device path above.
 extern "C" int photon_selftest_morton_order(const float *x, const float *y, long long n_total, long long first, long long n, int *perm_out) {
     if (!x || !y || !perm_out || n_total <= 0 || first < 0 || n <= 0 || first + n > n_total || n_total > 0x7fffffffLL) return 1;
-    float *dx = nullptr, *dy = nullptr;
-    int *dp = nullptr;
+    photon::DeviceBuffer<float> dx, dy;
+    photon::DeviceBuffer<int> dp;
     photon_sort_scratch sc;
-    int rc = 1;
-    if (hipMalloc((void **)&dx, (size_t)n_total * sizeof(float)) == hipSuccess && hipMalloc((void **)&dy, (size_t)n_total * sizeof(float)) == hipSuccess &&
-        hipMalloc((void **)&dp, (size_t)n * sizeof(int)) == hipSuccess &&
-        hipMemcpy(dx, x, (size_t)n_total * sizeof(float), hipMemcpyHostToDevice) == hipSuccess &&
-        hipMemcpy(dy, y, (size_t)n_total * sizeof(float), hipMemcpyHostToDevice) == hipSuccess) {
-        rc = photon_morton_order(dx, dy, (int)first, n, dp, nullptr, &sc);
-        if (!rc) rc = hipMemcpy(perm_out, dp, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;      // waits for the null stream
-    }
+    if (dx.alloc((size_t)n_total) != hipSuccess || dy.alloc((size_t)n_total) != hipSuccess || dp.alloc((size_t)n) != hipSuccess ||
+        hipMemcpy(dx.p, x, (size_t)n_total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(dy.p, y, (size_t)n_total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return 1;
+    int rc = photon_morton_order(dx.p, dy.p, (int)first, n, dp.p, nullptr, &sc);
+    if (!rc) rc = hipMemcpy(perm_out, dp.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;      // waits for the null stream
     (void)hipDeviceSynchronize();
-    photon_sort_scratch_free(&sc);
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-    if (dp) (void)hipFree(dp);
     return rc;
 }

@@ -5,16 +5,15 @@
 
 #include <cstddef>
 
+#include "photon_pool.hpp"
+
 // Scratch of the sort, owned by the caller (the scene) and grown on demand: with it a sort allocates nothing and never
 // waits for the host -- photon_trace stays asynchronous on its stream when a lens-major launch has to order a new range.
+// Outside the block cache (device_malloc): a regrow hands the old blocks to the runtime, whose free waits for the device.
 struct photon_sort_scratch {
-    unsigned *box = nullptr, *keys = nullptr;       // keys: 2 x capacity (in, out)
-    int *idx = nullptr;
-    void *tmp = nullptr;
-    size_t capacity = 0, tmp_bytes = 0;
+    photon::DeviceBuffer<unsigned> box, keys, tmp;      // keys: 2 x idx.n (in, out); tmp: the counts of one radix pass
+    photon::DeviceBuffer<int> idx;
 };
-
-void photon_sort_scratch_free(photon_sort_scratch *scratch);
 
 // perm_out[k] (device, n entries) = index, in the CALLER's source numbering, of the k-th source of
 // [first, first + n) in Morton order.  x, y: device pointers to the whole source arrays.  Asynchronous on

@@ -26,22 +26,16 @@ static int source_order_slot(photon_scene *s, long long src_begin, long long src
     s->perm_clock++;
     PermEntry *slot = nullptr;
     for (auto &p : s->perms)
-        if (p.d_perm && p.begin == src_begin && p.end == src_end) { p.stamp = s->perm_clock; *out = &p; return 0; }
+        if (p.perm.p && p.begin == src_begin && p.end == src_end) { p.stamp = s->perm_clock; *out = &p; return 0; }
     for (auto &p : s->perms)                                            // least recently used (an empty one first)
-        if (!slot || (!p.d_perm && slot->d_perm) || (!!p.d_perm == !!slot->d_perm && p.stamp < slot->stamp)) slot = &p;
+        if (!slot || (!p.perm.p && slot->perm.p) || (!!p.perm.p == !!slot->perm.p && p.stamp < slot->stamp)) slot = &p;
     slot->begin = slot->end = -1;
-    if (slot->capacity < n || !slot->d_perm) {
-        if (slot->d_perm) { scene_quiesce(s); pool_free(slot->d_perm); slot->d_perm = nullptr; }     // an earlier launch may still read it
-        slot->capacity = 0;
-        PH_CHECK(pool_malloc((void **)&slot->d_perm, std::max<size_t>(n, 1) * sizeof(int)));
-        slot->capacity = n;
-    }
+    PH_TRY(scene_reserve(s, slot->perm, n));                            // an earlier launch may still read the old one
     *out = slot;
     return 0;
 }
 static int sort_sources(photon_scene *s, PermEntry *slot, long long src_begin, long long src_end, hipStream_t stream) {
-    const int rc = photon_morton_order(s->dev.sx, s->dev.sy, (int)src_begin, src_end - src_begin, slot->d_perm, stream, &s->sort_scratch);
-    if (rc) return rc;
+    PH_TRY(photon_morton_order(s->dev.sx, s->dev.sy, (int)src_begin, src_end - src_begin, slot->perm.p, stream, &s->sort_scratch));
     slot->begin = src_begin; slot->end = src_end; slot->stamp = s->perm_clock;
     return 0;
 }
@@ -54,14 +48,9 @@ static int moments_block(photon_scene *s, size_t rays, MomentsDev *out) {
         fprintf(stderr, "photon: a moments block of %zu rays exceeds the %u-ray limit per launch\n", rays, kMaxRaysPerLaunch);
         return 1;
     }
-    if (s->mom_rays < rays) {
-        if (s->d_mom) { scene_quiesce(s); pool_free(s->d_mom); s->d_mom = nullptr; }     // an earlier launch may still use it
-        s->mom_rays = 0;
-        PH_CHECK(pool_malloc((void **)&s->d_mom, rays * 6 * sizeof(float)));
-        s->mom_rays = rays;
-    }
-    float *f = s->d_mom;
-    const size_t stride = s->mom_rays;
+    PH_TRY(scene_reserve(s, s->mom, rays * 6));                         // an earlier launch may still use the old one
+    float *f = s->mom.p;
+    const size_t stride = s->mom.n / 6;
     *out = MomentsDev{f, f + stride, f + 2 * stride, f + 3 * stride, f + 4 * stride, f + 5 * stride};
     return 0;
 }
@@ -71,7 +60,7 @@ namespace photon {
 int begin_accumulate(photon_scene *s, hipStream_t stream) {
     const size_t npix = (size_t)s->dev.cam.x_pixel_number * s->dev.cam.y_pixel_number;
     s->launched = true;                                     // the fill and, later, the finalize kernel use d_acc even when no source is traced
-    if (!s->acc_clean) PH_CHECK(hipMemsetAsync(s->d_acc, 0, npix * sizeof(double), stream));      // else: left zeroed by the last finalize
+    if (!s->acc_clean) PH_CHECK(hipMemsetAsync(s->acc.p, 0, npix * sizeof(double), stream));      // else: left zeroed by the last finalize
     s->acc_clean = false;
     return 0;
 }
@@ -91,36 +80,35 @@ int launch_chunk(photon_scene *s, const photon_volume *vol, int algorithm, const
     const size_t mom_rays = (size_t)places * (unsigned)s->dev.rays_per_source;
     MomentsDev mom{};
     PermEntry *order = nullptr;
-    if (d_records) { const int rc = moments_block(s, mom_rays, &mom); if (rc) return rc; }
-    if (plan.lens_major) { const int rc = source_order_slot(s, src_begin, src_end, &order); if (rc) return rc; }
+    if (d_records) PH_TRY(moments_block(s, mom_rays, &mom));
+    if (plan.lens_major) PH_TRY(source_order_slot(s, src_begin, src_end, &order));
     MarchPlan march{};
     if (vol) {
         march = plan_march(n, s->num_cus, vol->dev, algorithm, dump.inter_pos != nullptr, s->dev.noise.add_ngrad != 0, order ? 1 : 0, false, plan.march);
-        { const int rc = ensure_workspace(s, n); if (rc) return rc; }
-        if (march.segmented) { const int rc = ensure_resume_state(s, march.interp == 1); if (rc) return rc; }
+        PH_TRY(ensure_workspace(s, n));
+        if (march.segmented) PH_TRY(ensure_resume_state(s, march.interp == 1));
     }
     // ... then the launch: from here on kernels of this scene may be in flight
     s->launched = true;
     if (d_records) PH_CHECK(hipMemsetAsync(mom.x, 0xFF, mom_rays * sizeof(float), stream));       // all-ones = NaN: "did not arrive"
-    if (order && order->begin < 0) { const int rc = sort_sources(s, order, src_begin, src_end, stream); if (rc) return rc; }
+    if (order && order->begin < 0) PH_TRY(sort_sources(s, order, src_begin, src_end, stream));
     SceneDev dev = s->dev;                                      // the scene as this launch sees it
     dev.slot_rays = plan.slot_rays;
     dev.slot_map = plan.live_samples_only ? s->d_live : nullptr;
     dev.src_list = range.src_list;
     dev.doom_margin = plan.doom_margin;
     dev.ray_order = order ? 1 : 0;
-    dev.src_perm = order ? order->d_perm : nullptr;
+    dev.src_perm = order ? order->perm.p : nullptr;
     const MomentsDev *mom_p = d_records ? &mom : nullptr;
     if (vol) {
         // ray generation: the prologue of the march's first piece for Euler and RK4, a kernel of its own for the others
-        if (!march.fold) { const int rc = launch_raygen(s, dev, src_begin, n, stream); if (rc) return rc; }
+        if (!march.fold) PH_TRY(launch_raygen(s, dev, src_begin, n, stream));
         const unsigned long long ray_base = (unsigned long long)(dev.source_base + src_begin) * (unsigned)dev.rays_per_source;
         const InterDump idump{dump.inter_pos, dump.inter_dir, dump.inter_slots, dump.num_save, 0u};
-        const int rc = launch_march(s, dev, vol, march, ray_base, idump, src_begin, stream, ev_march_begin);
-        if (rc) return rc;
+        PH_TRY(launch_march(s, dev, vol, march, ray_base, idump, src_begin, stream, ev_march_begin));
         if (ev_march_end) PH_CHECK(hipEventRecord(ev_march_end, stream));
     }
-    { const int rc = launch_sensor(s, dev, vol != nullptr, src_begin, n, dump, stream, mom_p); if (rc) return rc; }
+    PH_TRY(launch_sensor(s, dev, vol != nullptr, src_begin, n, dump, stream, mom_p));
     if (!d_records) return 0;
     return launch_moments(mom, places, (unsigned)dev.rays_per_source, src_begin, dev.src_list, d_records, stream);
 }
@@ -132,9 +120,9 @@ constexpr unsigned kWindowMaxTraces = 1u << 16;        // traces per statistics 
 // An event of the open statistics window (created on first use, kept for the next window).
 static int window_event(photon_scene *s, size_t *index_out) {
     if (s->win_used == s->win_events.size()) {
-        hipEvent_t e = nullptr;
-        PH_CHECK(hipEventCreate(&e));
-        s->win_events.push_back(e);
+        Event e;
+        PH_CHECK(e.create());
+        s->win_events.push_back(std::move(e));
     }
     *index_out = s->win_used++;
     return 0;
@@ -153,8 +141,8 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
     float march_ms = 0.f;
     const DumpDev no_dump{nullptr, nullptr, 0, nullptr, nullptr, 0};
     const TracePlan plan = make_trace_plan(scene, vol, ray_tracing_algorithm, false, d_records != nullptr);
-    { const int rc = begin_accumulate(scene, stream); if (rc) return rc; }
-    if (d_records) { const int rc = clear_records(d_records, src_begin, src_end, stream); if (rc) return rc; }
+    PH_TRY(begin_accumulate(scene, stream));
+    if (d_records) PH_TRY(clear_records(d_records, src_begin, src_end, stream));
     for (long long b = src_begin; b < src_end;) {
         const LaunchRange r = next_launch(scene, plan, b, src_end);
         b = r.end;
@@ -162,12 +150,11 @@ int trace_accumulate(photon_scene *scene, const photon_volume *vol, int ray_trac
         if (timed == 1 && vol) { e0 = scene->ev[1]; e1 = scene->ev[2]; }
         size_t i0 = 0, i1 = 0;
         if (timed == 2 && vol) {
-            { const int rc = window_event(scene, &i0); if (rc) return rc; }
-            { const int rc = window_event(scene, &i1); if (rc) return rc; }
+            PH_TRY(window_event(scene, &i0));
+            PH_TRY(window_event(scene, &i1));
             e0 = scene->win_events[i0]; e1 = scene->win_events[i1];
         }
-        const int rc = launch_chunk(scene, vol, ray_tracing_algorithm, plan, r, no_dump, stream, e0, e1, d_records);
-        if (rc) return rc;
+        PH_TRY(launch_chunk(scene, vol, ray_tracing_algorithm, plan, r, no_dump, stream, e0, e1, d_records));
         if (timed == 2 && vol) scene->win_march.emplace_back(i0, i1);      // only pairs whose events were recorded
         if (timed == 1 && vol) {
             PH_CHECK(hipEventSynchronize(scene->ev[2]));
@@ -189,7 +176,7 @@ static int read_counters(photon_scene *scene, bool have_volume, photon_trace_sta
     unsigned long long c[CNT_N] = {};
     for (int k = 0; k < kCounterSlots; k++)
         for (int j = 0; j < CNT_N; j++) c[j] += slots[(size_t)k * kCounterStride + j];
-    { const int rc = march_error_check(scene); if (rc) return rc; }
+    PH_TRY(march_error_check(scene));
     stats->rays_on_sensor = c[CNT_ON_SENSOR];
     stats->rk_iterations = c[CNT_ITER];
     stats->volume_samples = c[CNT_SAMPLES];
@@ -225,22 +212,22 @@ static int trace_call(photon_scene_t *scene, const photon_volume_t *vol, int ray
         size_t w0 = 0, w1 = 0;
         if (stats) {
             PH_CHECK(hipMemsetAsync(scene->d_counters, 0, kCounterBytes, stream));
-            { const int rc = profile_reset(scene, stream); if (rc) return rc; }
+            PH_TRY(profile_reset(scene, stream));
             PH_CHECK(hipEventRecord(scene->ev[0], stream));
         } else if (scene->win_open) {
-            { const int rc = window_event(scene, &w0); if (rc) return rc; }
-            { const int rc = window_event(scene, &w1); if (rc) return rc; }
+            PH_TRY(window_event(scene, &w0));
+            PH_TRY(window_event(scene, &w1));
             PH_CHECK(hipEventRecord(scene->win_events[w0], stream));
         }
         float march_ms = 0.f;
         const int timed = stats ? 1 : (scene->win_open ? 2 : 0);
-        { const int rc = trace_accumulate(scene, vol, ray_tracing_algorithm, src_begin, src_end, stream, timed, &march_ms, d_records); if (rc) return rc; }
-        { const int rc = launch_finalize(scene, d_image, stream); if (rc) return rc; }
+        PH_TRY(trace_accumulate(scene, vol, ray_tracing_algorithm, src_begin, src_end, stream, timed, &march_ms, d_records));
+        PH_TRY(launch_finalize(scene, d_image, stream));
         if (stats) {
             PH_CHECK(hipEventRecord(scene->ev[3], stream));
             PH_CHECK(hipEventSynchronize(scene->ev[3]));
             memset(stats, 0, sizeof *stats);
-            { const int rc = read_counters(scene, vol != nullptr, stats); if (rc) return rc; }
+            PH_TRY(read_counters(scene, vol != nullptr, stats));
             stats->rays_launched = (uint64_t)(src_end - src_begin) * rps;
             stats->march_ms = march_ms;
             stats->traces = 1;
@@ -287,7 +274,7 @@ extern "C" int photon_scene_stats_begin(photon_scene_t *scene, void *stream_p) {
         photon::DeviceScope on_scene_device(scene->device);
         hipStream_t stream = (hipStream_t)stream_p;
         PH_CHECK(hipMemsetAsync(scene->d_counters, 0, kCounterBytes, stream));
-        { const int rc = profile_reset(scene, stream); if (rc) return rc; }
+        PH_TRY(profile_reset(scene, stream));
         scene->win_used = 0;
         scene->win_march.clear();
         scene->win_total.clear();
@@ -316,7 +303,7 @@ extern "C" int photon_scene_stats_end(photon_scene_t *scene, void *stream_p, pho
         scene->win_open = false;
         PH_CHECK(hipStreamSynchronize((hipStream_t)stream_p));
         memset(stats, 0, sizeof *stats);
-        { const int rc = read_counters(scene, scene->win_have_volume, stats); if (rc) return rc; }
+        PH_TRY(read_counters(scene, scene->win_have_volume, stats));
         double march = 0.0, total = 0.0;
         for (const auto &pr : scene->win_march) {
             float ms = 0.f;

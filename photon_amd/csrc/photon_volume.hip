@@ -250,12 +250,7 @@ static bool parse_nrrd(const char *path, std::vector<float> &rho, int dims[3], d
 
 extern "C" {
 
-void photon_volume_free(photon_volume_t *vol) {
-    if (!vol) return;
-    if (vol->d_texels) (void)hipFree(vol->d_texels);
-    if (vol->d_coeffs) (void)hipFree(vol->d_coeffs);
-    delete vol;
-}
+void photon_volume_free(photon_volume_t *vol) { delete vol; }
 
 // Where the density comes from: a host array (NRRD / caller) or a field evaluated on the device
 // (photon_volume_gaussian): rho0 + amp * gz[k] * (gy[j] * gx[i]) from three device-resident axis profiles.
@@ -284,7 +279,7 @@ int photon_volume_from_density(const float *rho, int nx, int ny, int nz, const d
 // n^3 grid in HBM -- no host array, no file, no upload (BASELINE C3 / C4's volume).
 // the three axis profiles of the separable Gaussian, on the device
 static int gaussian_profiles(int nx, int ny, int nz, const double spacing[3], const double origin[3],
-                             const double centre[3], double sigma, double *d_prof[3]) {
+                             const double centre[3], double sigma, DeviceBuffer<double> d_prof[3]) {
     const int dims[3] = {nx, ny, nz};
     for (int a = 0; a < 3; a++) {
         std::vector<double> prof(dims[a]);
@@ -292,8 +287,8 @@ static int gaussian_profiles(int nx, int ny, int nz, const double spacing[3], co
             const double x = origin[a] + spacing[a] * (double)i;
             prof[i] = photon_det_exp(-((x - centre[a]) * (x - centre[a])) / (2 * (sigma * sigma)));
         }
-        if (device_malloc((void **)&d_prof[a], dims[a] * sizeof(double)) != hipSuccess ||
-            hipMemcpy(d_prof[a], prof.data(), dims[a] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 3;
+        if (d_prof[a].alloc((size_t)dims[a]) != hipSuccess ||
+            hipMemcpy(d_prof[a].p, prof.data(), dims[a] * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 3;
     }
     return 0;
 }
@@ -305,17 +300,16 @@ int photon_volume_gaussian(int nx, int ny, int nz, const double spacing[3], cons
         fprintf(stderr, "photon: photon_volume_gaussian: bad arguments\n");
         return 1;
     }
-    double *d_prof[3] = {nullptr, nullptr, nullptr};
+    DeviceBuffer<double> d_prof[3];
     int rc = guarded("photon_volume_gaussian", [&]() -> int { return gaussian_profiles(nx, ny, nz, spacing, origin, centre, sigma, d_prof); });
     if (!rc) {
         DensitySource src;
-        src.d_gx = d_prof[0]; src.d_gy = d_prof[1]; src.d_gz = d_prof[2];
+        src.d_gx = d_prof[0].p; src.d_gy = d_prof[1].p; src.d_gz = d_prof[2].p;
         src.rho0 = rho0; src.amp = amp;
         rc = guarded("photon_volume_gaussian", [&]() -> int { return volume_build(src, nx, ny, nz, spacing, origin, interpolation, out); });
     } else {
         fprintf(stderr, "photon: photon_volume_gaussian: device allocation failed\n");
     }
-    for (double *p : d_prof) if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -329,22 +323,20 @@ int photon_density_gaussian_write_nrrd(const char *path, int nx, int ny, int nz,
         fprintf(stderr, "photon: photon_density_gaussian_write_nrrd: bad arguments\n");
         return 1;
     }
-    double *d_prof[3] = {nullptr, nullptr, nullptr};
-    float *d_rho = nullptr;
+    DeviceBuffer<double> d_prof[3];
+    DeviceBuffer<float> d_rho;
     const size_t n = (size_t)nx * ny * nz;
     std::vector<float> rho;
     int rc = guarded("photon_density_gaussian_write_nrrd", [&]() -> int {
         rho.resize(n);
         return gaussian_profiles(nx, ny, nz, spacing, origin, centre, sigma, d_prof);
     });
-    if (!rc && device_malloc((void **)&d_rho, n * sizeof(float)) != hipSuccess) rc = 3;
+    if (!rc && d_rho.alloc(n) != hipSuccess) rc = 3;
     if (!rc) {
-        hipLaunchKernelGGL(separable_density_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_prof[0], d_prof[1],
-                           d_prof[2], nx, ny, nz, rho0, amp, d_rho);
-        if (hipGetLastError() != hipSuccess || hipMemcpy(rho.data(), d_rho, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = 4;
+        hipLaunchKernelGGL(separable_density_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_prof[0].p, d_prof[1].p,
+                           d_prof[2].p, nx, ny, nz, rho0, amp, d_rho.p);
+        if (hipGetLastError() != hipSuccess || hipMemcpy(rho.data(), d_rho.p, n * sizeof(float), hipMemcpyDeviceToHost) != hipSuccess) rc = 4;
     }
-    for (double *p : d_prof) if (p) (void)hipFree(p);
-    if (d_rho) (void)hipFree(d_rho);
     if (rc) {
         fprintf(stderr, "photon: photon_density_gaussian_write_nrrd: HIP error\n");
         return rc;
@@ -376,28 +368,26 @@ static int volume_build(const DensitySource &src, int nx, int ny, int nz, const 
         fprintf(stderr, "photon: volume of %d x %d x %d texels exceeds the 2^31-texel limit of the samplers\n", nx, ny, nz);
         return 1;
     }
-    photon_volume *v = new photon_volume();
+    std::unique_ptr<photon_volume> v(new photon_volume());
     const size_t n = (size_t)nx * ny * nz;
-    float *d_rho = nullptr, *d_min = nullptr;
+    DeviceBuffer<float> d_rho, d_min;
     const unsigned blocks = (unsigned)((n + 255) / 256);
-    auto fail = [&](int code) { if (d_rho) (void)hipFree(d_rho); if (d_min) (void)hipFree(d_min); photon_volume_free(v); return code; };
-#define PH_VCHECK(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) { fprintf(stderr, "photon: HIP error %d (%s) at %s:%d\n", (int)_e, hipGetErrorString(_e), __FILE__, __LINE__); return fail((int)_e); } } while (0)
-    PH_VCHECK(device_malloc((void **)&v->d_texels, n * sizeof(f4)));
-    PH_VCHECK(device_malloc((void **)&d_rho, n * sizeof(float)));
-    PH_VCHECK(device_malloc((void **)&d_min, 2 * (size_t)blocks * sizeof(float)));      // block minima of n-1 | block maxima of |grad n|
+    PH_CHECK(v->texels.alloc(n));
+    PH_CHECK(d_rho.alloc(n));
+    PH_CHECK(d_min.alloc(2 * (size_t)blocks));      // block minima of n-1 | block maxima of |grad n|
     if (src.host_rho) {
-        PH_VCHECK(hipMemcpy(d_rho, src.host_rho, n * sizeof(float), hipMemcpyHostToDevice));
+        PH_CHECK(hipMemcpy(d_rho.p, src.host_rho, n * sizeof(float), hipMemcpyHostToDevice));
     } else {
         hipLaunchKernelGGL(separable_density_kernel, dim3(blocks), dim3(256), 0, 0, src.d_gx, src.d_gy, src.d_gz, nx, ny, nz,
-                           src.rho0, src.amp, d_rho);
-        PH_VCHECK(hipGetLastError());
+                           src.rho0, src.amp, d_rho.p);
+        PH_CHECK(hipGetLastError());
     }
     const float gx = (float)spacing[0], gy = (float)spacing[1], gz = (float)spacing[2];
-    hipLaunchKernelGGL(build_volume_kernel, dim3(blocks), dim3(256), 0, 0, d_rho, nx, ny, nz, gx, gy, gz, v->d_texels,
-                       d_min);
-    PH_VCHECK(hipGetLastError());
+    hipLaunchKernelGGL(build_volume_kernel, dim3(blocks), dim3(256), 0, 0, d_rho.p, nx, ny, nz, gx, gy, gz, v->texels.p,
+                       d_min.p);
+    PH_CHECK(hipGetLastError());
     std::vector<float> mins(2 * (size_t)blocks);
-    PH_VCHECK(hipMemcpy(mins.data(), d_min, mins.size() * sizeof(float), hipMemcpyDeviceToHost));
+    PH_CHECK(hipMemcpy(mins.data(), d_min.p, mins.size() * sizeof(float), hipMemcpyDeviceToHost));
     float data_min = FLT_MAX, grad_max = 0.f;
     for (unsigned k = 0; k < blocks; k++) {
         if (mins[k] < data_min) data_min = mins[k];
@@ -405,20 +395,17 @@ static int volume_build(const DensitySource &src, int nx, int ny, int nz, const 
     }
     v->grad_max = grad_max;
     if (interpolation == 2) {
-        PH_VCHECK(device_malloc((void **)&v->d_coeffs, n * sizeof(f4)));
-        PH_VCHECK(hipMemcpyAsync(v->d_coeffs, v->d_texels, n * sizeof(f4), hipMemcpyDeviceToDevice, nullptr));     // null stream, like the prefilter passes behind it
+        PH_CHECK(v->coeffs.alloc(n));
+        PH_CHECK(hipMemcpyAsync(v->coeffs.p, v->texels.p, n * sizeof(f4), hipMemcpyDeviceToDevice, nullptr));     // null stream, like the prefilter passes behind it
         const size_t sx = 1, sy = (size_t)nx, sz = (size_t)nx * ny;
         auto nblk = [](size_t lines) { return dim3((unsigned)((lines + 255) / 256)); };
         // x lines: (y inner, z outer); y lines: (x inner, z outer); z lines: (x inner, y outer)
-        hipLaunchKernelGGL(prefilter_lines_kernel, nblk((size_t)ny * nz), dim3(256), 0, 0, v->d_coeffs, nx, sx, ny, sy, nz, sz);
-        hipLaunchKernelGGL(prefilter_lines_kernel, nblk((size_t)nx * nz), dim3(256), 0, 0, v->d_coeffs, ny, sy, nx, sx, nz, sz);
-        hipLaunchKernelGGL(prefilter_lines_kernel, nblk((size_t)nx * ny), dim3(256), 0, 0, v->d_coeffs, nz, sz, nx, sx, ny, sy);
-        PH_VCHECK(hipGetLastError());
+        hipLaunchKernelGGL(prefilter_lines_kernel, nblk((size_t)ny * nz), dim3(256), 0, 0, v->coeffs.p, nx, sx, ny, sy, nz, sz);
+        hipLaunchKernelGGL(prefilter_lines_kernel, nblk((size_t)nx * nz), dim3(256), 0, 0, v->coeffs.p, ny, sy, nx, sx, nz, sz);
+        hipLaunchKernelGGL(prefilter_lines_kernel, nblk((size_t)nx * ny), dim3(256), 0, 0, v->coeffs.p, nz, sz, nx, sx, ny, sy);
+        PH_CHECK(hipGetLastError());
     }
-    PH_VCHECK(hipDeviceSynchronize());
-    (void)hipFree(d_rho); d_rho = nullptr;
-    (void)hipFree(d_min); d_min = nullptr;
-#undef PH_VCHECK
+    PH_CHECK(hipDeviceSynchronize());
     float step = (float)fmin(spacing[0], spacing[1]);                   // .h:2086-2098
     step = step < spacing[2] ? step : (float)spacing[2];
     VolumeDev &d = v->dev;
@@ -430,15 +417,15 @@ static int volume_build(const DensitySource &src, int nx, int ny, int nz, const 
     d.interpolation = interpolation;
     d.weight_inv = 1.0f / 256.f;
     d.weight_scale = 256.f;             // trilinear weights as the reference's texture unit holds them (photon_volume_set_weight_bits)
-    d.texels = v->d_texels;
-    d.coeffs = v->d_coeffs;
+    d.texels = v->texels.p;
+    d.coeffs = v->coeffs.p;
     photon_volume_info_t &info = v->info;
     info.min_bound[0] = d.min_bound.x; info.min_bound[1] = d.min_bound.y; info.min_bound[2] = d.min_bound.z;
     info.max_bound[0] = d.max_bound.x; info.max_bound[1] = d.max_bound.y; info.max_bound[2] = d.max_bound.z;
     info.nx = nx; info.ny = ny; info.nz = nz;
     info.grid_spacing[0] = gx; info.grid_spacing[1] = gy; info.grid_spacing[2] = gz;
     info.step_size = step; info.data_min = data_min; info.interpolation = interpolation;
-    *out = v;
+    *out = v.release();
     return 0;
 }
 
@@ -475,7 +462,7 @@ int photon_volume_info(const photon_volume_t *vol, photon_volume_info_t *info) {
 
 int photon_volume_download(const photon_volume_t *vol, int coefficients, float *out) {
     if (!vol || !out) return 1;
-    const f4 *src = (coefficients && vol->d_coeffs) ? vol->d_coeffs : vol->d_texels;
+    const f4 *src = (coefficients && vol->coeffs.p) ? vol->coeffs.p : vol->texels.p;
     const size_t n = (size_t)vol->dev.nx * vol->dev.ny * vol->dev.nz;
     PH_CHECK(hipMemcpy(out, src, n * sizeof(f4), hipMemcpyDeviceToHost));
     return 0;

@@ -153,3 +153,55 @@ def test_resume_state_room_is_made_before_the_launch(photon, volume_file):
     scene.free()
     for v in vols.values():
         v.free()
+
+
+def test_blocks_regrow_behind_launches_in_flight(photon, volume_file):
+    """Every block a scene grows on demand regrows while earlier launches of the scene may still use the old one, with no
+    host wait between the calls: the workspace and the resume state (a larger range), the moments block (its first
+    allocation), the order slots of lens-major launches (five ranges for four slots: the fifth evicts one) and the sort's
+    scratch.  One stream, every call into an image of its own, one check at the end.  Each image is that of the same call
+    on a fresh scene that waits after every call, up to the order of the f64 sums; the moment records are its bits.
+    (Ray order 1 makes these launches lens-major: make_trace_plan asks for a volume, no dumps and two rays per source.)"""
+    import torch
+    call = scenes.bos_scene(n_dots=6, points_per_dot=20, rays_per_source=100, density_grad_filename=volume_file)
+    assert call.num_sources == 120 and call.num_rays == 12000
+    vol = photon.volume_load_nrrd(volume_file, 2)
+    H, W = call.image_shape
+    ranges = [(0, 120), (0, 60), (60, 120), (0, 30), (30, 120), (0, 120)]
+
+    def run(wait):
+        scene = photon.scene_create(call)
+        stream = torch.cuda.Stream()
+        images = [torch.zeros(H * W, dtype=torch.float32, device="cuda") for _ in range(3 + len(ranges))]
+        records = torch.zeros(call.num_sources * 8, dtype=torch.float64, device="cuda")
+        torch.cuda.synchronize()                                # the fills above ran on torch's stream, not on this one
+        todo = iter(images)
+
+        def trace(begin, end, with_records=False):
+            if with_records:
+                scene.trace_moments(next(todo).data_ptr(), records.data_ptr(), vol, 2, begin, end, stream=stream.cuda_stream)
+            else:
+                scene.trace(next(todo).data_ptr(), vol, 2, begin, end, stream=stream.cuda_stream)
+            if wait:
+                torch.cuda.synchronize()
+
+        scene.set_march_segments(3)
+        trace(0, 60)
+        trace(0, 120)                                           # the workspace and the resume state regrow
+        trace(0, 120, with_records=True)                        # the moments block's first allocation
+        scene.set_ray_order(1)
+        for begin, end in ranges:
+            trace(begin, end)
+        scene.check(stream.cuda_stream)
+        out = [img.cpu().numpy().astype(np.float64) for img in images], records.cpu().numpy()
+        scene.free()
+        return out
+
+    ref_images, ref_records = run(wait=True)
+    images, records = run(wait=False)
+    assert np.isfinite(ref_records).any() and all(img.any() for img in ref_images)
+    for k, (img, ref) in enumerate(zip(images, ref_images)):
+        print(f"call {k}: rel_l2 = {rel_l2(img, ref):.3e}")
+        assert rel_l2(img, ref) <= 1e-12, k
+    assert np.array_equal(records.view(np.uint64), ref_records.view(np.uint64))
+    vol.free()

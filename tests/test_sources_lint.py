@@ -36,3 +36,29 @@ def test_no_host_side_device_to_device_hipmemcpy():
             if "hipMemcpyDeviceToDevice" in m.group(1) or "hipMemcpyDefault" in m.group(1):
                 offenders.append(f"{os.path.basename(path)}: hipMemcpy({' '.join(m.group(1).split())[:100]}")
     assert not offenders, "host-asynchronous device-to-device hipMemcpy on the null stream:\n" + "\n".join(offenders)
+
+
+def _calls_outside_the_pool(names):
+    offenders = []
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))):
+        if os.path.basename(path) in ("photon_pool.hip", "photon_pool.hpp"):
+            continue
+        for no, code in code_lines(path):
+            if re.search(r"\b(" + "|".join(names) + r")\s*\(", code):
+                offenders.append(f"{os.path.basename(path)}:{no}: {code.strip()}")
+    return offenders
+
+
+def test_no_hipmalloc_or_hipfree_outside_the_pool():
+    """Device memory is asked for and given back in photon_pool.hip / photon_pool.hpp alone: everywhere else a block is a
+    DeviceBuffer or a PoolBuffer, released with its owner on every return path, and allocated through device_malloc, which
+    empties the block cache and tries again before it reports the device out of memory."""
+    offenders = _calls_outside_the_pool(["hipMalloc", "hipFree"])
+    assert not offenders, "raw hipMalloc / hipFree outside photon_pool.*:\n" + "\n".join(offenders)
+
+
+def test_no_pool_malloc_or_pool_free_outside_the_pool():
+    """The same for blocks of the cache: pool_malloc and pool_free are PoolBuffer's business.  A block that somebody frees
+    by hand is a block that leaks on the return path somebody forgot."""
+    offenders = _calls_outside_the_pool(["pool_malloc", "pool_free"])
+    assert not offenders, "pool_malloc / pool_free outside photon_pool.*:\n" + "\n".join(offenders)
