@@ -654,8 +654,13 @@ int photon_postprocess_u16(float *d_image, int width, int height, float pixel_ga
  *   d_vectors device f32[n][4]: dx = ox + sx* + delta_x (columns), dy = oy + sy* + delta_y (rows) -- im2(p + d) ~ im1(p),
  *             a pattern moving right / down gives positive values; peak = Cn(s*); ratio = C(s*) / max{C(s) :
  *             |s - s*|_inf >= 2}, +inf when there is no such shift or that maximum is <= 0
- *   d_flags   device int[n], bits: 1 peak on the search edge, 2 flat window (either energy 0: every output of the
- *             window, its plane included, NaN), 4 a pixel the window needs lies outside im2
+ *   d_flags   device int[n], bits: 1 peak on the search edge, 2 flat window (every output of the window, its plane
+ *             included, NaN), 4 a pixel the window needs lies outside im2
+ *             A window is flat when all win^2 pixels of a are equal, or when the in-image pixels of b at zero shift are
+ *             all equal or there are none: for finite pixels, exactly when an energy of the definition is 0.  This is
+ *             decided from the smallest and the largest pixel, not from the f32 energies (an f32 mean of equal pixels
+ *             need not reproduce them).  A contrast too small for f32 -- either f32 energy not above 0 -- counts as
+ *             flat as well.
  *   d_planes  device f32[n][(2R+1)^2] Cn, row-major (sy, then sx), or NULL
  * d_vectors == NULL: only *n_rows / *n_cols are written (ask for the size first); nothing is launched.
  * Refused (1, one stderr line, nothing written, no launch): win not 16 / 32 / 64, R out of range, step < 1, an

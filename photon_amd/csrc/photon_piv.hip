@@ -62,6 +62,32 @@ __device__ __forceinline__ float block_max(float v, float *red) {
     return v;
 }
 
+// block_sum2 with a third value riding on the same two barriers (its wave totals sit in the argmax's index words)
+__device__ __forceinline__ void block_sum3(float &a, float &b, float &c, float *red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        a += __shfl_xor(a, o, 64);
+        b += __shfl_xor(b, o, 64);
+        c += __shfl_xor(c, o, 64);
+    }
+    const int nw = blockDim.x >> 6, w = threadIdx.x >> 6;
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) {
+        red[w] = a;
+        red[16 + w] = b;
+        red[32 + w] = c;
+    }
+    __syncthreads();
+    a = 0.f;
+    b = 0.f;
+    c = 0.f;
+    for (int i = 0; i < nw; i++) {
+        a += red[i];
+        b += red[16 + i];
+        c += red[32 + i];
+    }
+}
+
 // argmax with the tie rule: the larger value, then the smaller index
 __device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
 
@@ -123,22 +149,30 @@ __global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float 
     const int ox = offset ? offset[2 * win_id] : 0, oy = offset ? offset[2 * win_id + 1] : 0;
     const int tid = threadIdx.x, B = blockDim.x;
 
-    // ---- means: a over the window; b over the in-image pixels of the zero-shift window (outside pixels read as that mean)
-    float sum_a = 0.f, sum_b = 0.f, cnt_b = 0.f;
+    // ---- means: a over the window; b over the in-image pixels of the zero-shift window (outside pixels read as that mean);
+    //      and how many pixels of each differ from its first one, which decides flatness exactly: an f32 mean of equal
+    //      pixels need not reproduce them (counts up to win^2 are exact in f32)
+    const float ref_a = im1[(size_t)wy0 * W + wx0];
+    const float ref_b = im2[(size_t)min(max(wy0 + oy, 0), H - 1) * W + min(max(wx0 + ox, 0), W - 1)];     // in the window if any pixel is
+    float sum_a = 0.f, sum_b = 0.f, cnt_b = 0.f, dif_a = 0.f, dif_b = 0.f;
     for (int i = tid; i < WIN * WIN; i += B) {
         const int y = i / WIN, x = i % WIN;
         const float v = im1[(size_t)(wy0 + y) * W + (wx0 + x)];
         sa[i] = v;
         sum_a += v;
+        dif_a += v != ref_a ? 1.f : 0.f;
         const int gy = wy0 + oy + y, gx = wx0 + ox + x;
         if (gy >= 0 && gy < H && gx >= 0 && gx < W) {
-            sum_b += im2[(size_t)gy * W + gx];
+            const float u = im2[(size_t)gy * W + gx];
+            sum_b += u;
             cnt_b += 1.f;
+            dif_b += u != ref_b ? 1.f : 0.f;
         }
     }
     block_sum2(sum_a, sum_b, red);
-    float cnt = cnt_b, dummy = 0.f;
-    block_sum2(cnt, dummy, red);
+    float cnt = cnt_b;
+    block_sum3(cnt, dif_a, dif_b, red);
+    const bool all_equal = dif_a == 0.f || dif_b == 0.f;        // all pixels of a equal, or all (or none) of b at zero shift
     const float mean_a = sum_a / (float)(WIN * WIN);
     const float mean_b = cnt > 0.f ? sum_b / cnt : 0.f;
 
@@ -163,7 +197,8 @@ __global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float 
     block_sum2(ea, eb, red);           // (its barriers also publish sa and sb)
 
     const bool outside = wy0 + oy - R < 0 || wx0 + ox - R < 0 || wy0 + oy + WIN - 1 + R >= H || wx0 + ox + WIN - 1 + R >= W;
-    if (!(ea > 0.f) || !(eb > 0.f)) {                           // flat window (block-uniform)
+    // flat window (block-uniform): by its pixels, or a contrast too small for the f32 energies (1 / sqrt(0) below)
+    if (all_equal || !(ea > 0.f) || !(eb > 0.f)) {
         const float qnan = __builtin_nanf("");
         if (tid == 0) {
             vectors[4 * (size_t)win_id + 0] = qnan;

@@ -25,7 +25,7 @@ from . import deflections
 
 WINDOW_SIZES = (16, 32, 64)
 FLAG_EDGE_PEAK = 1          # the integer peak lies on the edge of the search square (no subpixel fit in that axis)
-FLAG_FLAT = 2               # an energy is 0: every output of the window is NaN
+FLAG_FLAT = 2               # an energy is 0 (all pixels of a, or of b at zero shift, equal): every output of the window is NaN
 FLAG_OUTSIDE = 4            # a pixel of im2 the window needs lies outside the image (it reads as the window's mean)
 
 
@@ -70,7 +70,10 @@ def _subpixel(cm, c0, cp):
 def correlate_model(im1, im2, win: int, step: int, radius: int, offset=None, planes: bool = False):
     """Host model of photon_piv_correlate in f64.  im1, im2: [height, width]; offset: integer (ox, oy) per window,
     [n_rows, n_cols, 2] or [n][2], or None.  Returns (vectors [n_rows, n_cols, 4], flags [n_rows, n_cols] int32) and, with
-    planes=True, the normalised planes [n_rows, n_cols, 2R+1, 2R+1] (row-major: sy, then sx) as a third item."""
+    planes=True, the normalised planes [n_rows, n_cols, 2R+1, 2R+1] (row-major: sy, then sx) as a third item.
+    A window is flat where an f64 energy is 0, which for finite pixels is where all pixels of a, or all in-image pixels of b
+    at zero shift, are equal; the device decides that from the pixels' extremes and also calls flat a window whose f32
+    energies are not above 0, a contrast below f32 that this model still correlates."""
     im1 = np.asarray(im1, np.float64)
     im2 = np.asarray(im2, np.float64)
     if im1.ndim != 2 or im1.shape != im2.shape:

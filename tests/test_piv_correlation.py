@@ -215,3 +215,79 @@ def test_axis_mapping_helpers():
     assert np.array_equal(pc.sensor_displacements(v, erf), [[-1.5, -2.0]])
     assert np.array_equal(pc.image_positions(np.array([10.0, 20.0]), four), [9.0, 19.0])
     assert np.array_equal(pc.image_positions(np.array([10.0, 20.0]), erf), [52.0, 20.0])
+
+
+# ---- the exact-arithmetic families of piv_correlation_cases.py: what the GPU test runs, shown from the model alone -----------
+import piv_correlation_cases as cases      # noqa: E402
+
+
+def _paths(name):
+    c = cases.all_cases()[name]
+    return c, cases.classify(c, *cases.model(name))
+
+
+@pytest.mark.parametrize("name", cases.names())
+def test_every_case_meets_the_exactness_condition(name):
+    """From the images alone -- and the windows that are flat by their pixels are the model's flat windows."""
+    c = cases.all_cases()[name]
+    cases.assert_exact(c)
+    s = cases.window_stats(c)
+    _, flags, _ = cases.model(name)
+    assert np.array_equal((flags & pc.FLAG_FLAT) != 0, s["flat_a"] | s["flat_b"])
+    assert np.array_equal((flags & pc.FLAG_OUTSIDE) != 0, s["outside"])
+
+
+def test_the_every_plan_family_covers_every_radius_with_a_plain_window():
+    """Every (win, R) the ABI accepts, one launch each, with at least one window that is neither flat nor on the edge; steps
+    that divide win, steps that do not, and step == win."""
+    plan = [cases.all_cases()[n] for n in cases.names("plan")]
+    assert sorted((c.win, c.R) for c in plan) == [(w, r) for w in (16, 32, 64) for r in range(1, w // 2 + 1)]
+    for c in plan:
+        assert _paths(c.name)[1]["inner"].any(), c.name
+    for win in (16, 32, 64):
+        steps = {c.step for c in plan if c.win == win}
+        assert win in steps and any(win % s for s in steps) and any(win % s == 0 and s < win for s in steps)
+
+
+def test_the_families_take_every_path_of_the_definition():
+    """Counted over all cases from the model's outputs.  The zero-denominator branch of the fit is the one path no finite
+    input reaches: the peak is the FIRST maximum, so C- (an earlier shift, in either axis) is strictly below C0 and C+ is at
+    most C0 -- C- - 2 C0 + C+ < 0, and ln C- - 2 ln C0 + ln C+ < 0 likewise.  It stays a guard."""
+    total = {}
+    by_win = {}
+    for name in cases.names():
+        c, p = _paths(name)
+        for key, mask in p.items():
+            if mask.dtype == bool:
+                total[key] = total.get(key, 0) + int(mask.sum())
+                by_win[key, c.win] = by_win.get((key, c.win), 0) + int(mask.sum())
+    print({k: v for k, v in sorted(total.items())})
+    for key in ("gauss_nonzero_x", "gauss_nonzero_y", "parabolic_x", "parabolic_y", "parabolic_nonzero_x", "parabolic_nonzero_y",
+                "edge_x_only", "edge_y_only", "edge_both", "tie", "tie_other_tile", "ratio_one", "ratio_inf_no_far_shift",
+                "ratio_inf_far_not_positive", "flat_a", "flat_b", "flat_outside", "flat_constant_a", "flat_constant_b"):
+        assert total.get(key, 0) > 0, key
+    assert total["zero_den_x"] == 0 and total["zero_den_y"] == 0
+    assert pc._subpixel(np.array([2.0, 4.0]), np.array([2.0, 4.0]), np.array([2.0, 4.0])).tolist() == [0.0, 0.0]      # the guard
+    for win in (16, 32, 64):                                    # every window size: the Gaussian fit, each edge, a tie, flat
+        for key in ("gauss_nonzero_x", "gauss_nonzero_y", "edge_x_only", "edge_y_only", "edge_both", "tie_other_tile",
+                    "ratio_inf_no_far_shift", "flat_a", "flat_b", "flat_outside"):
+            assert by_win.get((key, win), 0) > 0, (key, win)
+    for win in (32, 64):
+        assert by_win["flat_constant_a", win] > 0 and by_win["flat_constant_b", win] > 0
+    # the tie at R = win / 2 goes to the earlier shift, -R
+    for win in (16, 32, 64):
+        c, p = _paths(f"plan_w{win}_r{win // 2}_s{cases.STEPS[win][(win // 2 - 1) % 8]}")
+        assert p["tie"].any() and (p["px"][p["tie"]] == 0).all()
+
+
+def test_constants_are_chosen_where_an_f32_mean_misses_them():
+    """The replay of the kernel's own f32 sums: each constant of the constant family is one whose replayed mean differs from
+    it (f32 energies above 0 on a window of equal pixels), and is not an integer."""
+    for win, R, which in cases.CONSTANT_CONFIGS:
+        c = cases.pick_constant(win, R, seed=win + R)
+        assert c.dtype == np.float32 and c != np.rint(c)
+        assert cases.replay_mean(c, win, cases.plan_threads(win, R)) != c
+        case = cases.all_cases()[f"constant_{which}_w{win}_r{R}"]
+        assert ((case.im1 if which == "a" else case.im2) == c).sum() >= 2 * win * win
+    assert cases.replay_mean(np.float32(3.0), 64, 512) == np.float32(3.0)          # small integers: every sum is exact
+    assert cases.replay_mean(np.float32(0.1), 16, 64) == np.float32(0.1)           # 4 copies a lane, then doublings: exact

@@ -195,3 +195,108 @@ def test_two_passes_are_no_worse_than_one(photon):
     m1, m2 = np.median(np.hypot(*e1.T)), np.median(np.hypot(*e2.T))
     print(f"median |error|: 1 pass {m1:.4f} px ({n1} windows), 2 passes {m2:.4f} px ({n2} windows)")
     assert m2 <= m1 + 0.01, (m1, m2)
+
+
+# ---- the exact-arithmetic families of piv_correlation_cases.py: every window of every case, bit for bit --------------------
+import piv_correlation_cases as cases      # noqa: E402
+
+TAIL, SENTINEL = 3, 7
+
+
+def device_correlate_with_tail(photon, case, planes=True):
+    """photon_piv_correlate on buffers TAIL windows longer than the grid, filled with a sentinel: (vectors [n, 4], flags [n],
+    planes [n, nS, nS] or None, the three tails)."""
+    import torch
+    n_rows, n_cols = case.grid
+    n, ns2 = n_rows * n_cols, (2 * case.R + 1) ** 2
+    a, b = torch.tensor(case.im1).cuda(), torch.tensor(case.im2).cuda()          # (copies: the cases are read-only)
+    off = torch.from_numpy(np.ascontiguousarray(case.offset, np.int32)).cuda() if case.offset is not None else None
+    vec = torch.full(((n + TAIL) * 4,), float(SENTINEL), dtype=torch.float32, device="cuda")
+    flg = torch.full((n + TAIL,), SENTINEL, dtype=torch.int32, device="cuda")
+    pl = torch.full(((n + TAIL) * ns2,), float(SENTINEL), dtype=torch.float32, device="cuda") if planes else None
+    p = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+    r, c = ctypes.c_int(0), ctypes.c_int(0)
+    h, w = case.im1.shape
+    rc = photon.lib.photon_piv_correlate(p(a), p(b), w, h, case.win, case.step, case.R, p(off), p(vec), p(flg), p(pl),
+                                         ctypes.byref(r), ctypes.byref(c), None)
+    torch.cuda.synchronize()
+    assert rc == 0 and (r.value, c.value) == (n_rows, n_cols)
+    vec, flg = vec.cpu().numpy(), flg.cpu().numpy()
+    pl = pl.cpu().numpy() if planes else None
+    tails = (vec[4 * n:], flg[n:], pl[n * ns2:] if planes else None)
+    return vec[:4 * n].reshape(n, 4), flg[:n], (pl[:n * ns2].reshape(n, 2 * case.R + 1, 2 * case.R + 1) if planes else None), tails
+
+
+def bits(x):
+    return np.ascontiguousarray(x, np.float32).view(np.int32)
+
+
+def assert_matches_the_model_exactly(case, got_v, got_f, got_p, tails):
+    """Every window against correlate_model: flags, planes, peak and ratio bit for bit (as f32); dx and dy bit for bit on
+    the edge and parabolic paths and within 1 ulp on the Gaussian path (the f64 log); flat windows all NaN; the tails
+    untouched.  Returns the number of Gaussian-path components that differ by that one ulp."""
+    want_v, want_f, want_p = cases.model(case.name)
+    path = cases.classify(case, want_v, want_f, want_p)
+    flat, live = path["flat"], path["live"]
+    assert np.array_equal(got_f, want_f), np.flatnonzero(got_f != want_f)[:5]
+    assert np.isnan(got_v[flat]).all()
+    want32 = want_v.astype(np.float32)
+    if got_p is not None:
+        assert np.isnan(got_p[flat]).all()
+        diff = bits(got_p[live]) != bits(want_p[live].astype(np.float32))
+        assert not diff.any(), (int(diff.sum()), np.argwhere(diff)[:5])
+    for col, what in ((2, "peak"), (3, "ratio")):
+        assert np.array_equal(bits(got_v[live, col]), bits(want32[live, col])), what
+    one_ulp = 0
+    for col, ax in ((0, "x"), (1, "y")):
+        gauss = path["gauss_" + ax]
+        rest = live & ~gauss                                    # the edge, parabolic (and zero-denominator) paths
+        assert np.array_equal(bits(got_v[rest, col]), bits(want32[rest, col])), ("d" + ax, "exact paths")
+        g, w = got_v[gauss, col], want32[gauss, col]
+        near = (g == w) | (g == np.nextafter(w, np.float32(np.inf))) | (g == np.nextafter(w, np.float32(-np.inf)))
+        assert near.all(), ("d" + ax, "Gaussian path", g[~near][:5], w[~near][:5])
+        one_ulp += int((g != w).sum())
+    for t in tails:
+        assert t is None or (t == SENTINEL).all()
+    return one_ulp
+
+
+@pytest.mark.parametrize("name", cases.names())
+def test_every_window_of_the_exact_families_matches_the_model(photon, name):
+    case = cases.all_cases()[name]
+    cases.assert_exact(case)
+    one_ulp = assert_matches_the_model_exactly(case, *device_correlate_with_tail(photon, case))
+    print(f"{name}: {case.grid[0] * case.grid[1]} windows, {one_ulp} Gaussian-path components one ulp from the model")
+
+
+@pytest.mark.parametrize("name", ["plan_w16_r5_s7", "plan_w32_r16_s32", "planted_w64_r9", "constant_a_w64_r32"])
+def test_without_planes_the_vectors_and_flags_are_the_same_bits(photon, name):
+    case = cases.all_cases()[name]
+    v1, f1, _, _ = device_correlate_with_tail(photon, case, planes=True)
+    v0, f0, p0, tails = device_correlate_with_tail(photon, case, planes=False)
+    assert p0 is None and v0.tobytes() == v1.tobytes() and f0.tobytes() == f1.tobytes()
+    assert_matches_the_model_exactly(case, v0, f0, None, tails)
+
+
+@pytest.mark.parametrize("win", [32, 64])
+def test_a_constant_region_is_flat_through_correlate_and_gets_no_weight(photon, win):
+    """What the flag is for: a masked or saturated rectangle of a particle pair -- a constant that is no dyadic number and
+    that an f32 mean of the window does not reproduce -- through both passes of PhotonLibrary.correlate.  Every window wholly
+    inside it carries flag 2 and NaN, and weights_from_correlation gives it weight 0."""
+    from photon_amd import bos_density as bd
+    step = win // 2
+    c = cases.pick_constant(64, 32, seed=7)       # (at win 32, R 16 every lane adds 2 pixels and no sum rounds: win 64's value)
+    im1, im2 = particle_pair((256, 256), (2.4, -1.7), seed=21)
+    y0, y1, x0, x1 = 64, 64 + 3 * win // 2 + win, 32, 32 + 2 * win + win // 2      # windows of several grid rows and columns
+    im1[y0:y1, x0:x1] = c
+    im2[y0:y1, x0:x1] = c
+    n_rows, n_cols = pc.grid_shape(im1.shape, win, step)
+    i, j = np.meshgrid(np.arange(n_rows), np.arange(n_cols), indexing="ij")
+    inside = (i * step >= y0) & (i * step + win <= y1) & (j * step >= x0) & (j * step + win <= x1)
+    assert inside.sum() >= 4
+    for passes in (1, 2):
+        vec, flags = photon.correlate(im1, im2, win=win, step=step, passes=passes)
+        assert ((flags[inside] & pc.FLAG_FLAT) != 0).all(), (passes, flags[inside])
+        assert np.isnan(vec[inside]).all(), passes
+        weights = bd.weights_from_correlation(vec, flags, pc.normalized_median_test(vec))
+        assert (weights[inside] == 0.0).all() and weights[~inside].sum() > 0
