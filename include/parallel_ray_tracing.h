@@ -871,6 +871,79 @@ int photon_dots_window_means(const float *d_dots1, const int *d_pair, const floa
                              int width, int height, int win, int step, int min_count, int anchor, float *d_vectors,
                              int *d_flags, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 9: tomography -- the 3-D field f (rho - rho_0 on a voxel grid) from several views' projected density
+ * P = int (rho - rho_0) ds (section 6's result): a ray-driven projector A, its exact adjoint, and a conjugate-gradient
+ * solver of the regularised weighted normal equations.  Host model: photon_amd/tomography.py (numpy f64, the same
+ * operations in the same order).
+ *
+ * Grid.  nx x ny x nz nodes of f64, voxel (i, j, k) at (k ny + j) nx + i (the order of the NRRD volumes); node position
+ * origin + (i, j, k) spacing in world microns; every dimension >= 2, nx ny nz <= INT_MAX.
+ * Rays.  n_rays infinite lines: d_origins f64[n_rays][3], d_dirs f64[n_rays][3] (need not be unit vectors).
+ *
+ * Projector (Joseph's method), per ray, every step one IEEE f64 operation in the order written (the library is built
+ * without contraction):
+ *   1. n2 = (dx dx + dy dy) + dz dz;  len = sqrt(n2);  e = (dx / len, dy / len, dz / len).  The ray is a miss when one of
+ *      its six numbers is not finite, or when len is not finite or not > 0.
+ *   2. Dominant axis a: a = x; a = y when |e_y| > |e_x|; a = z when |e_z| > |e_a| (ties keep the first axis).  b < c are
+ *      the other two axes.  scale = spacing_a / |e_a|.
+ *   3. For every plane kappa = 0 .. n_a - 1 in ascending order: plane = origin_a + kappa spacing_a;
+ *      t = (plane - o_a) / e_a;  u = ((o_b + t e_b) - origin_b) / spacing_b;  v = ((o_c + t e_c) - origin_c) / spacing_c.
+ *      The plane counts when 0 <= u <= n_b - 1 and 0 <= v <= n_c - 1 (closed; a NaN fails).
+ *      i_b = min(floor(u), n_b - 2), f_b = u - i_b, g_b = 1 - f_b; likewise i_c, f_c, g_c.
+ *   4. The four taps of a counted plane, in this order, with their weights:
+ *      (i_b, i_c): (g_b g_c) scale;  (i_b + 1, i_c): (f_b g_c) scale;  (i_b, i_c + 1): (g_b f_c) scale;
+ *      (i_b + 1, i_c + 1): (f_b f_c) scale, each at voxel kappa along a.
+ *   5. P = sum of weight * f[tap], one product and one addition per tap, from 0, in the order of the planes and taps.
+ *      A ray with no counted plane, and a miss, gives P = 0.
+ * photon_tomo_project writes d_p f64[n_rays] = A f.  It equals the model bit for bit wherever the host's sqrt, floor and
+ * division are correctly rounded.
+ *
+ * Adjoint.  photon_tomo_backproject ADDS A^T y into d_v f64[nx ny nz]: d_v[tap] += weight * d_y[ray] over exactly the
+ * taps above (a ray whose y is 0 adds nothing).  The caller zeroes d_v when it wants A^T y alone.  The adds are f64
+ * atomics: the order in which the terms of one voxel arrive is not fixed, so two calls may differ in the last bits.  No
+ * bit-repeatability is claimed for photon_tomo_backproject or photon_tomo_reconstruct.
+ * Both are asynchronous on `stream`; every pointer is a device pointer (spacing and origin are host arrays of three).
+ * Refused (1, one stderr line, nothing written, no launch): a dimension < 2, nx ny nz > INT_MAX, n_rays < 1, a spacing
+ * that is not finite or not > 0, an origin that is not finite, a null pointer.
+ *
+ * Solver.  photon_tomo_reconstruct minimises  sum_i w_i (A f - p)_i^2 + lambda h^2 |G f|^2  over f with f = 0 wherever
+ * the support mask is 0: h = min(spacing); lambda >= 0 has no unit; G the forward first differences along the three
+ * axes, unscaled, so that G^T G is the 6-neighbour graph Laplacian  (G^T G q)_c = sum over the neighbours n of c inside
+ * the grid of (q_c - q_n), added in the order -x, +x, -y, +y, -z, +z.
+ *   d_p        f64[n_rays] the measured projections
+ *   d_w        f64[n_rays] weights, or NULL (1).  A ray whose p or w is not finite, or whose w <= 0, has weight 0 and its
+ *              p reads as 0.
+ *   d_support  u8[nx ny nz] (nonzero = unknown), or NULL (every voxel).  m below is the 0/1 mask.
+ *   d_f        f64[nx ny nz] out: the solution, exactly 0 off the support
+ * Conjugate gradients on the normal equations from x = 0, in f64:
+ *   b = m (A^T (W p));  r = b;  q = r;  rho = r.r.   |b| = 0: 0 iterations, converged.
+ *   per iteration:  s = m (A^T (W (A q)) + (lambda h h) G^T G q);  alpha = rho / (q.s), 0 when q.s = 0;  x += alpha q;
+ *   r -= alpha s;  rho' = r.r;  beta = rho' / rho, 0 when rho = 0;  q = r + beta q.
+ * |r| <= tol |b| is checked before the first iteration and then every PHOTON_TOMO_CHECK_EVERY iterations; with tol > 0
+ * the solver stops at the first check that holds, else after exactly max_iter iterations (tol = 0: always max_iter).
+ * alpha and beta stay on the device; the dot products are summed in an order the grid size alone fixes (the adjoint's
+ * sums are not, see above).  Plain stream launches, no graph; `stream` is synchronised before the call returns.
+ *   stats      iterations run; converged = final |r| <= tol |b|; residual = final |r| / |b| (0 when |b| = 0); unknowns =
+ *              support voxels; rays_used = rays of weight > 0 with at least one counted plane.  May be NULL.
+ * Refused as above, and: lambda < 0 or NaN, tol < 0 or NaN, max_iter < 0, a null d_p, d_origins, d_dirs or d_f. */
+#define PHOTON_TOMO_CHECK_EVERY 8
+
+typedef struct photon_tomo_stats_t {
+    int iterations, converged;
+    long long unknowns, rays_used;
+    double residual;
+} photon_tomo_stats_t;
+
+int photon_tomo_project(const double *d_f, int nx, int ny, int nz, const double spacing[3], const double origin[3],
+                        const double *d_origins, const double *d_dirs, long long n_rays, double *d_p, void *stream);
+int photon_tomo_backproject(const double *d_y, int nx, int ny, int nz, const double spacing[3], const double origin[3],
+                            const double *d_origins, const double *d_dirs, long long n_rays, double *d_v, void *stream);
+int photon_tomo_reconstruct(const double *d_p, const double *d_w, const unsigned char *d_support, int nx, int ny, int nz,
+                            const double spacing[3], const double origin[3], const double *d_origins, const double *d_dirs,
+                            long long n_rays, double lambda, double tol, int max_iter, double *d_f,
+                            photon_tomo_stats_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

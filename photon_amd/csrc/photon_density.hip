@@ -17,14 +17,12 @@
 #include <cmath>
 #include <vector>
 
+#include "fixed_sum.hpp"
 #include "photon_internal.hpp"
 
 using namespace photon;
 
 namespace {
-
-constexpr int kThreads = 256;
-constexpr int kMaxBlocks = 1024;            // the partial arrays hold at most this many values (4 per thread to sum)
 
 constexpr unsigned char kEdgeE = 1;          // live edge (i,j)->(i,j+1)
 constexpr unsigned char kEdgeS = 2;          // live edge (i,j)->(i+1,j)
@@ -32,26 +30,6 @@ constexpr unsigned char kEdgeW = 4;          // live edge (i,j-1)->(i,j)
 constexpr unsigned char kEdgeN = 8;          // live edge (i-1,j)->(i,j)
 constexpr unsigned char kFixed = 16;
 constexpr unsigned char kSolve = 32;         // set by the host: a reachable unknown node
-
-// Fixed-order block sum: a butterfly inside each wave (every lane ends with the same bits: a + b == b + a), then the wave
-// totals in wave order.  blockDim.x == kThreads.
-__device__ __forceinline__ double block_sum(double v, double *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-    for (int i = 1; i < kThreads / 64; i++) v += red[i];
-    return v;
-}
-
-// the sum of a partial array of n <= kMaxBlocks values, the same bits in every block
-__device__ __forceinline__ double sum_parts(const double *__restrict__ part, int n, double *red) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < n; i += kThreads) s += part[i];
-    return block_sum(s, red);
-}
 
 struct Inputs {
     const double *gx, *gy, *w;

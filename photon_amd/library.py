@@ -39,6 +39,8 @@ DECLARED_SYMBOLS = (
     # section 8: dot tracking
     "photon_dots_detect_scratch_bytes", "photon_dots_match_scratch_bytes", "photon_dots_image_max", "photon_dots_detect", "photon_dots_fit",
     "photon_dots_match", "photon_dots_window_means",
+    # section 9: tomography
+    "photon_tomo_project", "photon_tomo_backproject", "photon_tomo_reconstruct",
 )
 
 
@@ -63,6 +65,14 @@ class photon_trace_stats_t(ctypes.Structure):
 class photon_integrate_stats_t(ctypes.Structure):
     _fields_ = [("iterations", ctypes.c_int), ("converged", ctypes.c_int), ("unknowns", ctypes.c_int),
                 ("unreachable", ctypes.c_int), ("residual", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class photon_tomo_stats_t(ctypes.Structure):
+    _fields_ = [("iterations", ctypes.c_int), ("converged", ctypes.c_int), ("unknowns", ctypes.c_longlong),
+                ("rays_used", ctypes.c_longlong), ("residual", ctypes.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -262,6 +272,11 @@ class PhotonLibrary:
         L.photon_dots_match.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ctypes.c_float, ci, ci, vp, vp, vp, vp,
                                         ctypes.c_size_t, vp]
         L.photon_dots_window_means.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
+        grid_and_rays = [ci, ci, ci, vp, vp, vp, vp, ctypes.c_longlong]      # nx, ny, nz, spacing, origin, d_origins, d_dirs, n_rays
+        L.photon_tomo_project.argtypes = [vp] + grid_and_rays + [vp, vp]
+        L.photon_tomo_backproject.argtypes = [vp] + grid_and_rays + [vp, vp]
+        L.photon_tomo_reconstruct.argtypes = [vp, vp, vp] + grid_and_rays + [ctypes.c_double, ctypes.c_double, ci, vp,
+                                                                            ctypes.POINTER(photon_tomo_stats_t), vp]
 
     # ---- helpers --------------------------------------------------------------------------
     @staticmethod
@@ -669,6 +684,80 @@ class PhotonLibrary:
                                             tw.data_ptr() if tw is not None else 0, tf.data_ptr() if tf is not None else 0,
                                             tv.data_ptr() if tv is not None else 0, hx, hy, tol, max_iter, stream=stream)
         return phi.cpu().numpy(), stats
+
+    # ---- tomography on the device (include/parallel_ray_tracing.h, section 9) ----------------------------------------
+    @staticmethod
+    def _tomo_grid(dims, spacing, origin):
+        sp = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float64), (3,)))
+        og = np.ascontiguousarray(origin, dtype=np.float64)
+        if og.shape != (3,):
+            raise ValueError("origin must hold three values")
+        nx, ny, nz = (int(n) for n in dims)
+        return nx, ny, nz, sp, og
+
+    def tomo_project(self, d_f_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, n_rays: int, d_p_ptr: int,
+                     stream: int = 0):
+        """P = A f on raw device pointers (f64: f [nz, ny, nx], origins and dirs [n_rays, 3], p [n_rays]; dims = (nx, ny,
+        nz)).  Asynchronous on `stream`."""
+        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        rc = self.lib.photon_tomo_project(self._vp(d_f_ptr), nx, ny, nz, _ptr(sp), _ptr(og), self._vp(d_origins_ptr),
+                                          self._vp(d_dirs_ptr), int(n_rays), self._vp(d_p_ptr), self._vp(stream))
+        self._check(rc, "photon_tomo_project")
+
+    def tomo_backproject(self, d_y_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, n_rays: int, d_v_ptr: int,
+                         stream: int = 0):
+        """v += A^T y on raw device pointers (f64: y [n_rays], v [nz, ny, nx]): adds into v.  Asynchronous on `stream`."""
+        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        rc = self.lib.photon_tomo_backproject(self._vp(d_y_ptr), nx, ny, nz, _ptr(sp), _ptr(og), self._vp(d_origins_ptr),
+                                              self._vp(d_dirs_ptr), int(n_rays), self._vp(d_v_ptr), self._vp(stream))
+        self._check(rc, "photon_tomo_backproject")
+
+    def tomo_reconstruct_ptr(self, d_p_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, n_rays: int, d_f_ptr: int,
+                             d_w_ptr: int = 0, d_support_ptr: int = 0, lam: float = 1.0, tol: float = 1e-6,
+                             max_iter: Optional[int] = None, stream: int = 0) -> dict:
+        """Solve for the device f64 field at d_f_ptr [nz, ny, nx] from the projections at d_p_ptr (raw pointers: f64 p, w,
+        origins, dirs; u8 support; 0 = NULL).  Returns the stats as a dict; the call has synchronised `stream`.  max_iter
+        None = tomography.DEFAULT_MAX_ITER."""
+        from .tomography import DEFAULT_MAX_ITER
+        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        st = photon_tomo_stats_t()
+        rc = self.lib.photon_tomo_reconstruct(self._vp(d_p_ptr), self._vp(d_w_ptr), self._vp(d_support_ptr), nx, ny, nz, _ptr(sp),
+                                              _ptr(og), self._vp(d_origins_ptr), self._vp(d_dirs_ptr), int(n_rays), float(lam),
+                                              float(tol), DEFAULT_MAX_ITER if max_iter is None else int(max_iter),
+                                              self._vp(d_f_ptr), ctypes.byref(st), self._vp(stream))
+        self._check(rc, "photon_tomo_reconstruct")
+        return st.as_dict()
+
+    def tomo_reconstruct(self, p, dims, spacing, origin, origins, dirs, w=None, support=None, lam: float = 1.0, tol: float = 1e-6,
+                         max_iter: Optional[int] = None):
+        """The 3-D field from projections along rays, on the device (numpy arrays or torch device tensors): p, w [n_rays]
+        (w None = 1; a ray whose p or w is not finite or whose w <= 0 takes no part), origins and dirs [n_rays, 3] world
+        microns, support [nz, ny, nx] (None = every voxel), lam the dimensionless smoothness weight.  Returns (f numpy f64
+        [nz, ny, nx], stats dict).  The definition: include/parallel_ray_tracing.h, section 9 (photon_amd.tomography: host
+        model, and view_rays / grid_of for the geometry)."""
+        import torch
+        from . import tomography
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        def on_device(a, dtype):
+            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
+
+        nx, ny, nz = (int(n) for n in dims)
+        to, td = on_device(origins, torch.float64).reshape(-1, 3), on_device(dirs, torch.float64).reshape(-1, 3)
+        tp, tw = on_device(p, torch.float64).reshape(-1), on_device(w, torch.float64)
+        n_rays = tp.numel()
+        if to.shape != (n_rays, 3) or td.shape != (n_rays, 3) or (tw is not None and tw.numel() != n_rays):
+            raise ValueError("p and w hold one value per ray, origins and dirs three")
+        ts = None if support is None else on_device(torch.as_tensor(support) != 0, torch.uint8)
+        if ts is not None and tuple(ts.shape) != (nz, ny, nx):
+            raise ValueError(f"support must be [nz, ny, nx] = {(nz, ny, nx)}")
+        max_iter = tomography.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
+        tomography.check_arguments(dims, np.broadcast_to(np.asarray(spacing, np.float64), (3,)), origin, n_rays, lam, tol, max_iter)
+        f = torch.empty((nz, ny, nx), dtype=torch.float64, device=dev)
+        stats = self.tomo_reconstruct_ptr(tp.data_ptr(), dims, spacing, origin, to.data_ptr(), td.data_ptr(), n_rays, f.data_ptr(),
+                                          tw.data_ptr() if tw is not None else 0, ts.data_ptr() if ts is not None else 0, lam, tol,
+                                          max_iter, stream=torch.cuda.current_stream(dev).cuda_stream)
+        return f.cpu().numpy(), stats
 
     # ---- volumes ------------------------------------------------------------------------------
     def volume_load_nrrd(self, path: str, interpolation: int = 1) -> "Volume":

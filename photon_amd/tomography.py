@@ -1,0 +1,259 @@
+"""Tomographic BOS: the 3-D field from several views' projected density (pure numpy, f64: usable without a GPU).
+
+The device form is section 9 of include/parallel_ray_tracing.h (``PhotonLibrary.tomo_project``, ``tomo_backproject``,
+``tomo_reconstruct``).  This module holds
+
+* ``ray_taps``: the taps of the definition -- Joseph's method: per ray the grid planes along its dominant axis, four
+  bilinear taps in each -- by the same f64 operations in the same order as the device;
+* ``project_model``, ``backproject_model``, ``reconstruct_model``: the projector A, its adjoint and the conjugate-gradient
+  solver of section 9 on those taps (vectorised over the rays, a loop over the planes, sums by ``np.bincount``, which adds
+  in array order: the projector's sums run in the order of the definition);
+* the geometry that carries a camera's measurement into it: ``view_rays`` (the world chief rays of a camera's grid nodes)
+  and ``grid_of`` (a volume's grid in the same frame).
+
+Arrays over the voxels are indexed [z, y, x] (x fastest), as the volumes are; dims = (nx, ny, nz).
+"""
+from __future__ import annotations
+
+from typing import NamedTuple, Optional
+
+import numpy as np
+
+CHECK_EVERY = 8                 # PHOTON_TOMO_CHECK_EVERY
+DEFAULT_MAX_ITER = 100
+
+
+def check_arguments(dims, spacing, origin, n_rays, lam=0.0, tol=0.0, max_iter=0):
+    """The arguments section 9 refuses, as a ValueError (null pointers aside)."""
+    nx, ny, nz = (int(v) for v in dims)
+    if min(nx, ny, nz) < 2:
+        raise ValueError(f"nx, ny and nz must be >= 2, not {nx} x {ny} x {nz}")
+    if nx * ny * nz > 2 ** 31 - 1:
+        raise ValueError(f"{nx} x {ny} x {nz} is more than INT_MAX voxels")
+    if int(n_rays) < 1:
+        raise ValueError("n_rays must be >= 1")
+    spacing, origin = np.asarray(spacing, np.float64), np.asarray(origin, np.float64)
+    if spacing.shape != (3,) or origin.shape != (3,):
+        raise ValueError("spacing and origin must hold three values each")
+    if not (np.isfinite(spacing).all() and (spacing > 0).all()):
+        raise ValueError(f"every spacing must be finite and > 0, not {spacing}")
+    if not np.isfinite(origin).all():
+        raise ValueError(f"every origin must be finite, not {origin}")
+    if not lam >= 0:
+        raise ValueError(f"lam must be >= 0, not {lam}")
+    if not tol >= 0:
+        raise ValueError(f"tol must be >= 0, not {tol}")
+    if int(max_iter) < 0:
+        raise ValueError(f"max_iter must be >= 0, not {max_iter}")
+
+
+def _rays(origins, dirs):
+    o = np.ascontiguousarray(origins, np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(dirs, np.float64).reshape(-1, 3)
+    if o.shape != d.shape:
+        raise ValueError("origins and dirs must both be [n_rays, 3]")
+    return o, d
+
+
+class Taps(NamedTuple):
+    """Every tap of a set of rays through a grid: tap i adds weight[i] * f[voxel[i]] to ray[i].  The taps of one ray follow
+    each other in the order of the definition (planes ascending, four taps per plane); planes[r] is the number of counted
+    planes of ray r."""
+    ray: np.ndarray
+    voxel: np.ndarray
+    weight: np.ndarray
+    planes: np.ndarray
+    n_voxels: int
+
+
+def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
+    """The taps of section 9's projector, every step the definition's f64 operation."""
+    o, d = _rays(origins, dirs)
+    check_arguments(dims, spacing, origin, o.shape[0])
+    n = tuple(int(v) for v in dims)
+    h = tuple(float(v) for v in np.asarray(spacing, np.float64))
+    g = tuple(float(v) for v in np.asarray(origin, np.float64))
+    stride = (1, n[0], n[0] * n[1])
+    with np.errstate(all="ignore"):
+        length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
+        hit = np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1) & np.isfinite(length) & (length > 0)
+        e = d / length[:, None]
+    mag = np.abs(e)
+    axis = np.zeros(o.shape[0], np.int64)
+    top = mag[:, 0].copy()
+    for a in (1, 2):
+        more = mag[:, a] > top
+        axis[more] = a
+        top = np.where(more, mag[:, a], top)
+    rays, voxels, weights = [], [], []
+    planes = np.zeros(o.shape[0], np.int64)
+    for a, (b, c) in ((0, (1, 2)), (1, (0, 2)), (2, (0, 1))):
+        idx = np.nonzero(hit & (axis == a))[0]
+        if idx.size == 0:
+            continue
+        oa, ob, oc = o[idx, a], o[idx, b], o[idx, c]
+        ea, eb, ec = e[idx, a], e[idx, b], e[idx, c]
+        scale = h[a] / top[idx]
+        for kappa in range(n[a]):
+            plane = g[a] + float(kappa) * h[a]
+            t = (plane - oa) / ea
+            u = ((ob + t * eb) - g[b]) / h[b]
+            v = ((oc + t * ec) - g[c]) / h[c]
+            ok = (u >= 0.0) & (u <= n[b] - 1) & (v >= 0.0) & (v <= n[c] - 1)
+            if not ok.any():
+                continue
+            u, v, s, r = u[ok], v[ok], scale[ok], idx[ok]
+            ib, ic = np.minimum(np.floor(u), n[b] - 2), np.minimum(np.floor(v), n[c] - 2)
+            fb, fc = u - ib, v - ic
+            hb, hc = 1.0 - fb, 1.0 - fc
+            base = kappa * stride[a] + ib.astype(np.int64) * stride[b] + ic.astype(np.int64) * stride[c]
+            voxels.append(np.stack([base, base + stride[b], base + stride[c], base + stride[b] + stride[c]], axis=1))
+            weights.append(np.stack([(hb * hc) * s, (fb * hc) * s, (hb * fc) * s, (fb * fc) * s], axis=1))
+            rays.append(np.repeat(r, 4).reshape(-1, 4))
+            planes[r] += 1
+    if not rays:
+        empty = np.zeros(0, np.int64)
+        return Taps(empty, empty, np.zeros(0), planes, n[0] * n[1] * n[2])
+    return Taps(np.concatenate(rays).ravel(), np.concatenate(voxels).ravel(), np.concatenate(weights).ravel(), planes,
+                n[0] * n[1] * n[2])
+
+
+def _apply(taps: Taps, f: np.ndarray) -> np.ndarray:
+    return np.bincount(taps.ray, taps.weight * f[taps.voxel], minlength=taps.planes.size)
+
+
+def _adjoint(taps: Taps, y: np.ndarray) -> np.ndarray:
+    return np.bincount(taps.voxel, taps.weight * y[taps.ray], minlength=taps.n_voxels)
+
+
+def project_model(f, spacing, origin, origins, dirs, taps: Optional[Taps] = None) -> np.ndarray:
+    """Host model of photon_tomo_project: P = A f, f [nz, ny, nx].  taps: ray_taps of the same grid and rays, when the
+    caller has them."""
+    f = np.asarray(f, np.float64)
+    if f.ndim != 3:
+        raise ValueError("f must be [nz, ny, nx]")
+    if taps is None:
+        taps = ray_taps(f.shape[::-1], spacing, origin, origins, dirs)
+    return _apply(taps, f.ravel())
+
+
+def backproject_model(y, dims, spacing, origin, origins, dirs, v=None, taps: Optional[Taps] = None) -> np.ndarray:
+    """Host model of photon_tomo_backproject: v + A^T y as a new array [nz, ny, nx] (v None = 0)."""
+    y = np.asarray(y, np.float64).ravel()
+    if taps is None:
+        taps = ray_taps(dims, spacing, origin, origins, dirs)
+    nx, ny, nz = (int(n) for n in dims)
+    out = _adjoint(taps, y).reshape(nz, ny, nx)
+    return out if v is None else np.asarray(v, np.float64).reshape(nz, ny, nx) + out
+
+
+def graph_laplacian(q: np.ndarray) -> np.ndarray:
+    """G^T G q on [nz, ny, nx]: per voxel the sum over its neighbours inside the grid of (q_c - q_n), added in the order
+    -x, +x, -y, +y, -z, +z."""
+    lap = np.zeros_like(q)
+    lap[:, :, 1:] += q[:, :, 1:] - q[:, :, :-1]
+    lap[:, :, :-1] += q[:, :, :-1] - q[:, :, 1:]
+    lap[:, 1:, :] += q[:, 1:, :] - q[:, :-1, :]
+    lap[:, :-1, :] += q[:, :-1, :] - q[:, 1:, :]
+    lap[1:, :, :] += q[1:, :, :] - q[:-1, :, :]
+    lap[:-1, :, :] += q[:-1, :, :] - q[1:, :, :]
+    return lap
+
+
+def reconstruct_model(p, dims, spacing, origin, origins, dirs, w=None, support=None, lam: float = 1.0, tol: float = 1e-6,
+                      max_iter: int = DEFAULT_MAX_ITER, taps: Optional[Taps] = None):
+    """Host model of photon_tomo_reconstruct (section 9: the same iteration and check cadence).  p, w [n_rays] (w None =
+    1); support [nz, ny, nx] (None = every voxel).  Returns (f [nz, ny, nx], stats dict: iterations, converged, unknowns,
+    rays_used, residual)."""
+    o, d = _rays(origins, dirs)
+    check_arguments(dims, spacing, origin, o.shape[0], lam, tol, max_iter)
+    nx, ny, nz = (int(n) for n in dims)
+    p = np.asarray(p, np.float64).ravel()
+    w = np.ones_like(p) if w is None else np.asarray(w, np.float64).ravel()
+    if p.shape != (o.shape[0],) or w.shape != p.shape:
+        raise ValueError("p and w must hold one value per ray")
+    m = np.ones(nx * ny * nz, bool) if support is None else np.asarray(support).ravel() != 0
+    if m.shape != (nx * ny * nz,):
+        raise ValueError("support must have the shape of the grid")
+    if taps is None:
+        taps = ray_taps(dims, spacing, origin, o, d)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(p) & np.isfinite(w) & (w > 0)
+    weight = np.where(ok, w, 0.0)
+    wp = np.where(ok, w * np.where(ok, p, 0.0), 0.0)
+    h = float(np.min(np.asarray(spacing, np.float64)))
+    lam_h2 = float(lam) * (h * h)
+
+    x = np.zeros(nx * ny * nz)
+    r = np.where(m, _adjoint(taps, wp), 0.0)
+    q = r.copy()
+    rho = float(np.dot(r, r))
+    bnorm = np.sqrt(rho)
+    it = 0
+    if bnorm > 0:
+        while True:
+            if it % CHECK_EVERY == 0 and tol > 0 and np.sqrt(rho) <= tol * bnorm:
+                break
+            if it == max_iter:
+                break
+            t = np.where(weight > 0, weight * _apply(taps, q), 0.0)
+            s = np.where(m, _adjoint(taps, t) + lam_h2 * graph_laplacian(q.reshape(nz, ny, nx)).ravel(), 0.0)
+            qs = float(np.dot(q, s))
+            alpha = rho / qs if qs != 0 else 0.0
+            x = x + alpha * q
+            r = r - alpha * s
+            rho_new = float(np.dot(r, r))
+            beta = rho_new / rho if rho != 0 else 0.0
+            q = r + beta * q
+            rho = rho_new
+            it += 1
+    stats = dict(iterations=it, converged=int(bool(bnorm == 0 or np.sqrt(rho) <= tol * bnorm)), unknowns=int(m.sum()),
+                 rays_used=int(((weight > 0) & (taps.planes > 0)).sum()), residual=float(np.sqrt(rho) / bnorm) if bnorm > 0 else 0.0)
+    return x.reshape(nz, ny, nx), stats
+
+
+# ---- geometry ------------------------------------------------------------------------------------------------------------
+WORLD_Z_SHIFT = 750e3           # camera z = world z + z_offset + 750e3 (photon_amd/csrc/device_optics.hpp)
+
+
+def rotate_about(points, rotation, pivot=None) -> np.ndarray:
+    """R (x - pivot) + pivot for points [..., 3] (pivot None = the origin)."""
+    R = np.asarray(rotation, np.float64).reshape(3, 3)
+    c = np.zeros(3) if pivot is None else np.asarray(pivot, np.float64)
+    return (np.asarray(points, np.float64) - c) @ R.T + c
+
+
+def view_rays(call, target_xy, rotation=None, pivot=None):
+    """The world chief rays of a camera's grid nodes: (origins, dirs), each [..., 3] like X_t.  target_xy = (X_t, Y_t), the
+    nodes' target-plane points (bos_density.node_geometry).  The chief-ray model of bos_density.chief_ray_projection: from
+    the target point at object_distance straight through the lens centre; carried into the world frame as the device
+    carries its rays (z -= z_offset + 750e3, then the camera's inverse_rotation_matrix), then rotated by `rotation` (3 x 3)
+    about `pivot` (None = the world origin) when one is given.  The origins are the target points."""
+    Xt, Yt = (np.asarray(a, np.float64) for a in target_xy)
+    z_lens = float(call.z_offset)
+    target = np.stack([Xt, Yt, np.full(Xt.shape, z_lens + float(call.object_distance))], axis=-1)
+    lens = np.array([0.0, 0.0, z_lens])
+    shift = np.array([0.0, 0.0, float(call.z_offset) + WORLD_Z_SHIFT])
+    inv = np.asarray(call.camera.get("inverse_rotation_matrix", np.eye(3)), np.float32).astype(np.float64).reshape(3, 3)
+    origins = (target - shift) @ inv.T
+    dirs = np.broadcast_to(lens - shift, target.shape) @ inv.T - origins
+    if rotation is not None:
+        R = np.asarray(rotation, np.float64).reshape(3, 3)
+        origins, dirs = rotate_about(origins, R, pivot), dirs @ R.T
+    return origins, dirs
+
+
+def grid_of(volume_info):
+    """(dims (nx, ny, nz), spacing, origin) of a Volume (its info()) in the frame of view_rays: the bounds a volume reports
+    are world coordinates already."""
+    v = volume_info
+    return ((int(v.nx), int(v.ny), int(v.nz)), np.array([float(s) for s in v.grid_spacing]),
+            np.array([float(s) for s in v.min_bound]))
+
+
+def line_distance_sq(origins, dirs, point) -> np.ndarray:
+    """Squared distance from `point` to each line origins + t dirs."""
+    o, d = np.asarray(origins, np.float64), np.asarray(dirs, np.float64)
+    rel = np.asarray(point, np.float64) - o
+    along = (rel * d).sum(axis=-1) / (d * d).sum(axis=-1)
+    return ((rel - along[..., None] * d) ** 2).sum(axis=-1)
