@@ -944,6 +944,64 @@ int photon_tomo_reconstruct(const double *d_p, const double *d_w, const unsigned
                             long long n_rays, double lambda, double tol, int max_iter, double *d_f,
                             photon_tomo_stats_t *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 10: tomography from deflections -- the 3-D field f from the measured ray deflections themselves (section 6's
+ * input, bos_density.gradients_from_displacements: int grad_perp (rho - rho_0) ds along each chief ray), without first
+ * integrating every view to a projected density.  Host model: photon_amd/tomography.py (deflection_taps, deflect_model,
+ * deflect_adjoint_model, reconstruct_deflections_model; the same operations in the same order).
+ *
+ * Grid and rays as in section 9.  Per ray two transverse vectors d_t1, d_t2 f64[n_rays][3] in world coordinates; they
+ * need not be unit vectors and need not be perpendicular to the ray.  A zero vector is allowed: that component is then 0
+ * for every f (single-component data).  A ray with an entry of t1 or t2 that is not finite is a miss.
+ *
+ * Operator.  D_tau is the exact derivative of section 9's projector under a parallel shift of the ray:
+ *   (D_tau f)(o, d) = d/d delta  (A f)(o + delta tau, d)  at delta = 0.
+ * Inside a cell A is bilinear in (u, v), so D_tau has the four taps of every plane that counts for A with differentiated
+ * weights.  Steps 1 to 3 of section 9 are unchanged (the same planes count, the same i_b, f_b, g_b, i_c, f_c, g_c and
+ * scale).  Then, every step one IEEE f64 operation in the order written:
+ *   3a. per ray and vector tau, a the dominant axis:  r = tau_a / e_a;
+ *       p_u = ((tau_b - r e_b) / spacing_b) scale;  p_v = ((tau_c - r e_c) / spacing_c) scale.
+ *   4.  per counted plane  A = g_c p_u,  B = g_b p_v,  C = f_c p_u,  E = f_b p_v,  and the weights of section 9's taps in
+ *       section 9's order:  (i_b, i_c): (-A) - B;  (i_b + 1, i_c): A - E;  (i_b, i_c + 1): B - C;  (i_b + 1, i_c + 1): C + E.
+ *   5.  g = sum of weight * f[tap], one product and one addition per tap, from 0, in the order of the planes and taps.
+ * The four weights of a plane sum to 0 (D_tau annihilates constants); only the part of tau perpendicular to the ray
+ * matters (tau parallel to e gives 0 up to rounding); and for a ray whose shifted copies o +- delta tau stay in the cells
+ * of the original, (A f(o + delta tau) - A f(o - delta tau)) / (2 delta) = D_tau f up to rounding, because A is quadratic
+ * along a shift inside a cell.
+ *
+ * photon_tomo_deflect writes d_g1 = D_t1 f and d_g2 = D_t2 f, f64[n_rays] each (one walk per ray); 0 for a miss and for
+ * a ray with no counted plane.  It equals the model bit for bit under section 9's condition.
+ * photon_tomo_deflect_adjoint ADDS D_t1^T y1 + D_t2^T y2 into d_v f64[nx ny nz]: per tap ONE value,
+ * weight1 y1 + weight2 y2 (two products, one addition), so the number of atomic adds is photon_tomo_backproject's, not
+ * twice it.  A ray with y1 = y2 = 0 adds nothing.  As in section 9 the order in which a voxel's terms arrive is not fixed:
+ * no bit-repeatability is claimed for photon_tomo_deflect_adjoint or photon_tomo_reconstruct_deflections.
+ * Both are asynchronous on `stream`.  Refused as section 9's operators (1, one stderr line, nothing written, no launch),
+ * a null d_t1, d_t2, d_g1, d_g2, d_y1 or d_y2 included.
+ *
+ * Solver.  photon_tomo_reconstruct_deflections minimises
+ *   sum_i w_i ((D_t1 f - g1)_i^2 + (D_t2 f - g2)_i^2) + lambda |G f|^2
+ * over f with f = 0 off the support; G as in section 9.  There is NO h^2 on the regulariser: D carries 1 / length against
+ * A, so lambda stays without a unit and comparable to section 9's.  A ray whose g1, g2 or w is not finite, or whose
+ * w <= 0, has weight 0 and its data read as 0.  The iteration is section 9's with
+ *   b = m (D_t1^T (W g1) + D_t2^T (W g2));  s = m (D_t1^T (W (D_t1 q)) + D_t2^T (W (D_t2 q)) + lambda G^T G q),
+ * both adjoints in one photon_tomo_deflect_adjoint; the check cadence, the stats (rays_used = rays of weight > 0 that are
+ * no miss and have a counted plane), alpha and beta on the device and the single wait at the end are section 9's.
+ * With d_support == NULL the constant of f is undetermined by the data (D annihilates constants, and so does G): CG from 0
+ * stays orthogonal to the constants and returns the solution of zero mean.  A support whose border lies in the ambient
+ * fluid (f = 0 off it) fixes the constant.
+ * Refused as photon_tomo_reconstruct, and: a null d_g1, d_g2, d_t1 or d_t2. */
+int photon_tomo_deflect(const double *d_f, int nx, int ny, int nz, const double spacing[3], const double origin[3],
+                        const double *d_origins, const double *d_dirs, const double *d_t1, const double *d_t2, long long n_rays,
+                        double *d_g1, double *d_g2, void *stream);
+int photon_tomo_deflect_adjoint(const double *d_y1, const double *d_y2, int nx, int ny, int nz, const double spacing[3],
+                                const double origin[3], const double *d_origins, const double *d_dirs, const double *d_t1,
+                                const double *d_t2, long long n_rays, double *d_v, void *stream);
+int photon_tomo_reconstruct_deflections(const double *d_g1, const double *d_g2, const double *d_w, const unsigned char *d_support,
+                                        int nx, int ny, int nz, const double spacing[3], const double origin[3],
+                                        const double *d_origins, const double *d_dirs, const double *d_t1, const double *d_t2,
+                                        long long n_rays, double lambda, double tol, int max_iter, double *d_f,
+                                        photon_tomo_stats_t *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -283,12 +283,12 @@ def gaussian_projection(r2, amplitude: float, sigma: float):
     return amplitude * sigma * np.sqrt(2.0 * np.pi) * np.exp(-np.asarray(r2, np.float64) / (2.0 * sigma ** 2))
 
 
-def integrate_vectors(lib, vectors, flags, shape, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16,
-                      weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
-    """Projected density from a correlation's vectors [n_rows, n_cols, >= 2] and flags on an image of `shape`: weights
-    (`weights`: "median" = weights_from_correlation after the normalised median test, "unit" = 1 wherever the vector is
-    finite), gradients, integration on the device with the frame fixed at P = 0 (the frame must lie where the density is
-    ambient).  Returns (phi [n_rows, n_cols] kg/m^3 um, mid-plane nodes (X, Y), stats dict)."""
+def measured_gradients(vectors, flags, shape, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16,
+                       weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+    """What a correlation measures, before any integration: (gx, gy, w, target-plane nodes (X_t, Y_t), mid-plane nodes
+    (X, Y), spacing h).  gx, gy [n_rows, n_cols]: int grad (rho - rho_0) ds along each node's chief ray, along the grid's
+    columns and rows; w the weights (`weights`: "median" = weights_from_correlation after the normalised median test,
+    "unit" = 1 wherever the vector is finite)."""
     from . import piv_correlation as pc
     if weights == "median":
         w = weights_from_correlation(vectors, flags, pc.normalized_median_test(vectors))
@@ -298,7 +298,17 @@ def integrate_vectors(lib, vectors, flags, shape, call, origin_z: float, extent_
         raise ValueError(f"weights must be 'median' or 'unit', not {weights!r}")
     gx, gy = gradients_from_displacements(pc.sensor_displacements(vectors, call.camera), call.camera,
                                           displacement_factor(call, origin_z, extent_z, K, rho_0))
-    _, mid, h = node_geometry(shape, win, step, call, origin_z, extent_z)
+    target, mid, h = node_geometry(shape, win, step, call, origin_z, extent_z)
+    return gx, gy, w, target, mid, h
+
+
+def integrate_vectors(lib, vectors, flags, shape, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16,
+                      weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+    """Projected density from a correlation's vectors [n_rows, n_cols, >= 2] and flags on an image of `shape`: weights
+    (`weights`: "median" = weights_from_correlation after the normalised median test, "unit" = 1 wherever the vector is
+    finite), gradients, integration on the device with the frame fixed at P = 0 (the frame must lie where the density is
+    ambient).  Returns (phi [n_rows, n_cols] kg/m^3 um, mid-plane nodes (X, Y), stats dict)."""
+    gx, gy, w, _, mid, h = measured_gradients(vectors, flags, shape, call, origin_z, extent_z, win, step, weights, K, rho_0)
     phi, stats = lib.integrate_gradient(gx, gy, w, hx=h, hy=h, tol=tol)
     return phi, mid, stats
 
@@ -309,6 +319,19 @@ def reconstruct(lib, im1, im2, call, origin_z: float, extent_z: float, win: int 
     ``PhotonLibrary.correlate`` (`passes`), then integrate_vectors.  Returns (phi, mid-plane nodes (X, Y), stats)."""
     vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
     return integrate_vectors(lib, vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step, weights, tol, K, rho_0)
+
+
+def deflection_data(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, passes: int = 2,
+                    weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+    """The deflections of a BOS image pair, for tomography without the per-view integral (``reconstruct`` up to, but
+    excluding, the integration): ``PhotonLibrary.correlate`` (`passes`), then measured_gradients.  Returns (g1, g2, w,
+    target-plane nodes (X_t, Y_t)), g1 = gx and g2 = gy [n_rows, n_cols]: the data of
+    ``PhotonLibrary.tomo_reconstruct_deflections`` with the rays of tomography.view_rays and the vectors of
+    tomography.view_frames at the same nodes."""
+    vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
+    gx, gy, w, target, _, _ = measured_gradients(vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step,
+                                                 weights, K, rho_0)
+    return gx, gy, w, target
 
 
 def reconstruct_tracked(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, threshold: float = 0.25,

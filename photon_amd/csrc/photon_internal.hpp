@@ -14,7 +14,8 @@
 //   photon_piv.hip           cross-correlation of image pairs: PIV / BOS displacement fields
 //   photon_dots.hip          BOS dot tracking: per-dot shifts from an image pair
 //   photon_density.hip       BOS displacement fields integrated into projected density
-//   photon_tomo.hip          tomography: projector, adjoint and CG solver from several views' projected density to the 3-D field
+//   photon_tomo.hip          tomography: projector, adjoint and CG solver from several views' projected density to the 3-D field;
+//                            the projector's shift derivative, its adjoint and the same solver from the views' deflections
 //   photon_abi.hip           start_ray_tracing, PHOTON_DEVICES (several devices inside one call)
 //   photon_sort.hip          Morton order of a range of sources
 //   photon_moments.hip       per-source sensor moments: the reduction of a launch's moments block into records

@@ -15,6 +15,12 @@
 //   update:    alpha = rho / q.s, x += alpha q, r -= alpha s, partials of r.r
 //   direction: beta = rho' / rho, q = r + beta q
 // The host reads one f64 (|r|^2) every PHOTON_TOMO_CHECK_EVERY iterations.
+//
+// Section 10 (tomography from deflections) is the same walk with differentiated weights: D_tau f is the derivative of A f
+// under a parallel shift of the ray along tau, so a counted plane has the same four taps and, per vector tau, the weights
+// of ShiftRates::weights.  tomo_deflect_kernel sums both components in one walk, tomo_deflect_adjoint_kernel adds one
+// value per tap (w1 y1 + w2 y2: the atomics of tomo_backproject_kernel, not twice them), and the solver is the one above
+// (solve<Op>) with the operator pair of DeflectionOp and no h^2 on the regulariser.
 #include <climits>
 #include <cmath>
 
@@ -33,7 +39,7 @@ struct Grid {
 // One ray's walk through the grid (the definition's steps 1 to 4): init, then plane(kappa) for kappa = 0 .. na - 1.
 struct RayWalk {
     // axis a, then the other two in axis order (b, c): extent, voxel stride, ray origin, unit direction, grid origin, spacing
-    int na, nb, nc, sa, sb, sc;
+    int axis, na, nb, nc, sa, sb, sc;
     double oa, ob, oc, ea, eb, ec, ga, gb, gc, ha, hb, hc, scale;
 
     // false: the ray is a miss
@@ -59,19 +65,30 @@ struct RayWalk {
             na = g.nz; nb = g.nx; nc = g.ny; sa = sz; sb = 1; sc = sy;
             oa = oz; ob = ox; oc = oy; ea = ez; eb = ex; ec = ey; ga = g.gz; gb = g.gx; gc = g.gy; ha = g.hz; hb = g.hx; hc = g.hy;
         }
+        axis = a;
         scale = ha / ma;
         return true;
     }
 
-    // Does plane kappa count?  Then its taps are the voxels c, c + sb, c + sc, c + sb + sc with the weights w[0 .. 3].
-    __device__ __forceinline__ bool plane(int kappa, int &c, double (&w)[4]) const {
+    // Does plane kappa count?  Then its taps are the voxels c, c + sb, c + sc, c + sb + sc, and (fb, fc) is where the ray
+    // crosses the plane inside that cell (step 3 of the definition).
+    __device__ __forceinline__ bool cell(int kappa, int &c, double &fb, double &fc) const {
         const double at = ga + (double)kappa * ha;
         const double t = (at - oa) / ea;
         const double u = ((ob + t * eb) - gb) / hb, v = ((oc + t * ec) - gc) / hc;
         if (!(u >= 0.0 && u <= (double)(nb - 1) && v >= 0.0 && v <= (double)(nc - 1))) return false;
         const int ib = min((int)floor(u), nb - 2), ic = min((int)floor(v), nc - 2);     // 0 <= ib <= nb - 2: every tap is a voxel
-        const double fb = u - (double)ib, fc = v - (double)ic, hb1 = 1.0 - fb, hc1 = 1.0 - fc;
+        fb = u - (double)ib;
+        fc = v - (double)ic;
         c = kappa * sa + ib * sb + ic * sc;
+        return true;
+    }
+
+    // a counted plane's taps with the projector's weights w[0 .. 3] (step 4)
+    __device__ __forceinline__ bool plane(int kappa, int &c, double (&w)[4]) const {
+        double fb, fc;
+        if (!cell(kappa, c, fb, fc)) return false;
+        const double hb1 = 1.0 - fb, hc1 = 1.0 - fc;
         w[0] = (hb1 * hc1) * scale;
         w[1] = (fb * hc1) * scale;
         w[2] = (hb1 * fc) * scale;
@@ -178,6 +195,133 @@ __global__ __launch_bounds__(kThreads) void tomo_rays_kernel(Grid g, const doubl
             int c;
             double wt[4];
             for (int kappa = 0; kappa < rw.na && !used; kappa++) used = rw.plane(kappa, c, wt);
+        }
+        count += used ? 1.0 : 0.0;
+    }
+    count = block_sum(count, red);                              // whole numbers below 2^53: exact in any order
+    if (threadIdx.x == 0 && count > 0.0) atomicAdd(rays_used, (unsigned long long)count);
+}
+
+// ---- section 10: the derivative of the projector under a parallel shift of the ray ----------------------------------------
+// Per ray and vector tau: how fast the crossing point (u, v) of every plane moves under the shift, times scale.
+struct ShiftRates {
+    double pu, pv;
+
+    // false: an entry of tau is not finite (the ray is a miss)
+    __device__ __forceinline__ bool init(const RayWalk &rw, const double *__restrict__ tau, long long ray) {
+        const double tx = tau[3 * ray], ty = tau[3 * ray + 1], tz = tau[3 * ray + 2];
+        if (!(isfinite(tx) && isfinite(ty) && isfinite(tz))) return false;
+        const double ta = rw.axis == 0 ? tx : (rw.axis == 1 ? ty : tz);
+        const double tb = rw.axis == 0 ? ty : tx;
+        const double tc = rw.axis == 2 ? ty : tz;
+        const double r = ta / rw.ea;
+        pu = ((tb - r * rw.eb) / rw.hb) * rw.scale;
+        pv = ((tc - r * rw.ec) / rw.hc) * rw.scale;
+        return true;
+    }
+
+    // the weights of a counted plane's four taps, in the projector's tap order
+    __device__ __forceinline__ void weights(double fb, double fc, double (&w)[4]) const {
+        const double gb = 1.0 - fb, gc = 1.0 - fc;
+        const double gcu = gc * pu, gbv = gb * pv, fcu = fc * pu, fbv = fb * pv;
+        w[0] = -gcu - gbv;
+        w[1] = gcu - fbv;
+        w[2] = gbv - fcu;
+        w[3] = fcu + fbv;
+    }
+};
+
+// g1 = D_t1 f, g2 = D_t2 f; with `weight` (the solver): weight (D f), 0 where the weight is 0
+__global__ __launch_bounds__(kThreads) void tomo_deflect_kernel(Grid g, const double *__restrict__ f, const double *__restrict__ origins,
+                                                                const double *__restrict__ dirs, const double *__restrict__ t1,
+                                                                const double *__restrict__ t2, long long n_rays,
+                                                                const double *__restrict__ weight, double *__restrict__ g1,
+                                                                double *__restrict__ g2) {
+    for (long long ray = (long long)blockIdx.x * kThreads + threadIdx.x; ray < n_rays; ray += (long long)gridDim.x * kThreads) {
+        const double w = weight ? weight[ray] : 1.0;
+        double acc1 = 0.0, acc2 = 0.0;
+        RayWalk rw;
+        ShiftRates s1, s2;
+        if (w > 0.0 && rw.init(g, origins, dirs, ray) && s1.init(rw, t1, ray) && s2.init(rw, t2, ray)) {
+            for (int kappa = 0; kappa < rw.na; kappa++) {
+                int c;
+                double fb, fc, w1[4], w2[4];
+                if (!rw.cell(kappa, c, fb, fc)) continue;
+                s1.weights(fb, fc, w1);
+                s2.weights(fb, fc, w2);
+                const double f0 = f[c], f1 = f[c + rw.sb], f2 = f[c + rw.sc], f3 = f[c + rw.sb + rw.sc];
+                acc1 += w1[0] * f0;
+                acc1 += w1[1] * f1;
+                acc1 += w1[2] * f2;
+                acc1 += w1[3] * f3;
+                acc2 += w2[0] * f0;
+                acc2 += w2[1] * f1;
+                acc2 += w2[2] * f2;
+                acc2 += w2[3] * f3;
+            }
+        }
+        g1[ray] = weight ? (w > 0.0 ? w * acc1 : 0.0) : acc1;
+        g2[ray] = weight ? (w > 0.0 ? w * acc2 : 0.0) : acc2;
+    }
+}
+
+// v += D_t1^T y1 + D_t2^T y2, one add per tap: w1 y1 + w2 y2.  The lanes of a wave walk together as in
+// tomo_backproject_kernel.
+__global__ __launch_bounds__(kThreads) void tomo_deflect_adjoint_kernel(Grid g, const double *__restrict__ y1, const double *__restrict__ y2,
+                                                                        const double *__restrict__ origins, const double *__restrict__ dirs,
+                                                                        const double *__restrict__ t1, const double *__restrict__ t2,
+                                                                        long long n_rays, double *__restrict__ v) {
+    for (long long base = (long long)blockIdx.x * kThreads; base < n_rays; base += (long long)gridDim.x * kThreads) {
+        const long long ray = base + threadIdx.x;
+        const double ya = ray < n_rays ? y1[ray] : 0.0, yb = ray < n_rays ? y2[ray] : 0.0;
+        RayWalk rw;
+        ShiftRates s1, s2;
+        // a ray whose y1 and y2 are 0 adds nothing
+        const bool live = (ya != 0.0 || yb != 0.0) && rw.init(g, origins, dirs, ray) && s1.init(rw, t1, ray) && s2.init(rw, t2, ray);
+        const int mine = live ? rw.na : 0;
+        int planes = 0;                                         // the wave's maximum of `mine`: one of the three extents
+        if (__ballot(mine == g.nx)) planes = g.nx;
+        if (__ballot(mine == g.ny)) planes = max(planes, g.ny);
+        if (__ballot(mine == g.nz)) planes = max(planes, g.nz);
+        for (int kappa = 0; kappa < planes; kappa++) {
+            int c = 0;
+            double fb = 0.0, fc = 0.0, w1[4] = {0.0, 0.0, 0.0, 0.0}, w2[4] = {0.0, 0.0, 0.0, 0.0};
+            const bool counts = kappa < mine && rw.cell(kappa, c, fb, fc);
+            if (counts) {
+                s1.weights(fb, fc, w1);
+                s2.weights(fb, fc, w2);
+            }
+            wave_add(v, counts ? c : -1, w1[0] * ya + w2[0] * yb);
+            wave_add(v, counts ? c + rw.sb : -1, w1[1] * ya + w2[1] * yb);
+            wave_add(v, counts ? c + rw.sc : -1, w1[2] * ya + w2[2] * yb);
+            wave_add(v, counts ? c + rw.sb + rw.sc : -1, w1[3] * ya + w2[3] * yb);
+        }
+    }
+}
+
+// the deflection solver's rays: weight = w where g1, g2 and w are finite and w > 0, else 0; wg = weight g (0 at weight 0);
+// counts the rays of positive weight that are no miss (their vectors included) and cross the grid
+__global__ __launch_bounds__(kThreads) void tomo_deflect_rays_kernel(Grid g, const double *__restrict__ g1, const double *__restrict__ g2,
+                                                                     const double *__restrict__ w, const double *__restrict__ origins,
+                                                                     const double *__restrict__ dirs, const double *__restrict__ t1,
+                                                                     const double *__restrict__ t2, long long n_rays,
+                                                                     double *__restrict__ weight, double *__restrict__ wg1,
+                                                                     double *__restrict__ wg2, unsigned long long *__restrict__ rays_used) {
+    __shared__ double red[kThreads / 64];
+    double count = 0.0;
+    for (long long ray = (long long)blockIdx.x * kThreads + threadIdx.x; ray < n_rays; ray += (long long)gridDim.x * kThreads) {
+        const double ga = g1[ray], gb = g2[ray], wi = w ? w[ray] : 1.0;
+        const bool ok = isfinite(ga) && isfinite(gb) && isfinite(wi) && wi > 0.0;
+        weight[ray] = ok ? wi : 0.0;
+        wg1[ray] = ok ? wi * ga : 0.0;
+        wg2[ray] = ok ? wi * gb : 0.0;
+        RayWalk rw;
+        ShiftRates s1, s2;
+        bool used = false;
+        if (ok && rw.init(g, origins, dirs, ray) && s1.init(rw, t1, ray) && s2.init(rw, t2, ray)) {
+            int c;
+            double fb, fc;
+            for (int kappa = 0; kappa < rw.na && !used; kappa++) used = rw.cell(kappa, c, fb, fc);
         }
         count += used ? 1.0 : 0.0;
     }
@@ -308,15 +452,76 @@ int launch_backproject(const Grid &g, const double *d_y, const double *d_origins
     return 0;
 }
 
-// the device work vectors of one solve: r, q, s over the voxels; weight, t over the rays; parts: 3 kMaxBlocks + 1; 2 counters
+int launch_deflect(const Grid &g, const double *d_f, const double *d_origins, const double *d_dirs, const double *d_t1, const double *d_t2,
+                   long long n_rays, const double *d_weight, double *d_g1, double *d_g2, hipStream_t stream) {
+    hipLaunchKernelGGL(tomo_deflect_kernel, dim3(ray_blocks(n_rays)), dim3(kThreads), 0, stream, g, d_f, d_origins, d_dirs, d_t1, d_t2,
+                       n_rays, d_weight, d_g1, d_g2);
+    PH_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_deflect_adjoint(const Grid &g, const double *d_y1, const double *d_y2, const double *d_origins, const double *d_dirs,
+                           const double *d_t1, const double *d_t2, long long n_rays, double *d_v, hipStream_t stream) {
+    hipLaunchKernelGGL(tomo_deflect_adjoint_kernel, dim3(ray_blocks(n_rays)), dim3(kThreads), 0, stream, g, d_y1, d_y2, d_origins, d_dirs,
+                       d_t1, d_t2, n_rays, d_v);
+    PH_CHECK(hipGetLastError());
+    return 0;
+}
+
+// the device work vectors of one solve: r, q, s over the voxels; weight, t (and t2: the second component of section 10) over
+// the rays; parts: 3 kMaxBlocks + 1; 2 counters
 struct Work {
-    double *r, *q, *s, *weight, *t, *parts;
+    double *r, *q, *s, *weight, *t, *t2, *parts;
     unsigned long long *counters;
 };
 
-int solve(hipStream_t stream, const Grid &g, const double *d_p, const double *d_w, const unsigned char *d_support, const double *d_origins,
-          const double *d_dirs, long long n_rays, double lam_h2, double tol, int max_iter, double *x, const Work &w,
+// The operator pair of a solve.  An Op knows the grid, the rays and the data, and has
+//   prepare(w, stream):  weight and the weighted data over the rays (w.weight, w.t[, w.t2]), the used rays in w.counters[0]
+//   forward(q, w, stream):  w.t[, w.t2] = weight (Op q)
+//   adjoint(w, v, stream):  v += Op^T (w.t[, w.t2])
+// Section 9: the projector and the backprojector on the projections d_p.
+struct ProjectionOp {
+    Grid g;
+    const double *d_p, *d_w, *d_origins, *d_dirs;
+    long long n_rays;
+
+    int prepare(const Work &w, hipStream_t stream) const {
+        hipLaunchKernelGGL(tomo_rays_kernel, dim3(ray_blocks(n_rays)), dim3(kThreads), 0, stream, g, d_p, d_w, d_origins, d_dirs, n_rays,
+                           w.weight, w.t, w.counters);
+        PH_CHECK(hipGetLastError());
+        return 0;
+    }
+    int forward(const double *q, const Work &w, hipStream_t stream) const {
+        return launch_project(g, q, d_origins, d_dirs, n_rays, w.weight, w.t, stream);
+    }
+    int adjoint(const Work &w, double *v, hipStream_t stream) const { return launch_backproject(g, w.t, d_origins, d_dirs, n_rays, v, stream); }
+};
+
+// Section 10: the two shift derivatives on the deflections d_g1, d_g2.
+struct DeflectionOp {
+    Grid g;
+    const double *d_g1, *d_g2, *d_w, *d_origins, *d_dirs, *d_t1, *d_t2;
+    long long n_rays;
+
+    int prepare(const Work &w, hipStream_t stream) const {
+        hipLaunchKernelGGL(tomo_deflect_rays_kernel, dim3(ray_blocks(n_rays)), dim3(kThreads), 0, stream, g, d_g1, d_g2, d_w, d_origins, d_dirs,
+                           d_t1, d_t2, n_rays, w.weight, w.t, w.t2, w.counters);
+        PH_CHECK(hipGetLastError());
+        return 0;
+    }
+    int forward(const double *q, const Work &w, hipStream_t stream) const {
+        return launch_deflect(g, q, d_origins, d_dirs, d_t1, d_t2, n_rays, w.weight, w.t, w.t2, stream);
+    }
+    int adjoint(const Work &w, double *v, hipStream_t stream) const {
+        return launch_deflect_adjoint(g, w.t, w.t2, d_origins, d_dirs, d_t1, d_t2, n_rays, v, stream);
+    }
+};
+
+// CG on  m (Op^T W Op + reg G^T G) m x = m Op^T W data  from x = 0 (the iteration of section 9)
+template <typename Op>
+int solve(hipStream_t stream, const Op &op, const unsigned char *d_support, double reg, double tol, int max_iter, double *x, const Work &w,
           photon_tomo_stats_t *stats) {
+    const Grid &g = op.g;
     const unsigned N = (unsigned)g.nx * (unsigned)g.ny * (unsigned)g.nz;
     const int blocks = (int)std::min<unsigned>(kMaxBlocks, (N + kThreads - 1) / kThreads);
     double *rho_part[2] = {w.parts, w.parts + kMaxBlocks};
@@ -324,10 +529,8 @@ int solve(hipStream_t stream, const Grid &g, const double *d_p, const double *d_
 
     PH_CHECK(hipMemsetAsync(w.counters, 0, 2 * sizeof(unsigned long long), stream));
     PH_CHECK(hipMemsetAsync(w.r, 0, (size_t)N * sizeof(double), stream));
-    hipLaunchKernelGGL(tomo_rays_kernel, dim3(ray_blocks(n_rays)), dim3(kThreads), 0, stream, g, d_p, d_w, d_origins, d_dirs, n_rays,
-                       w.weight, w.t, w.counters);
-    PH_CHECK(hipGetLastError());
-    PH_TRY(launch_backproject(g, w.t, d_origins, d_dirs, n_rays, w.r, stream));
+    PH_TRY(op.prepare(w, stream));
+    PH_TRY(op.adjoint(w, w.r, stream));
     hipLaunchKernelGGL(cg_init_kernel, dim3(blocks), dim3(kThreads), 0, stream, N, d_support, x, w.r, w.q, rho_part[0], w.counters + 1);
     PH_CHECK(hipGetLastError());
 
@@ -354,10 +557,10 @@ int solve(hipStream_t stream, const Grid &g, const double *d_p, const double *d_
                 if (it % PHOTON_TOMO_CHECK_EVERY != 0) PH_TRY(residual_sq(rho_part[cur], &rr));    // a run that stops between checks
                 break;
             }
-            PH_TRY(launch_project(g, w.q, d_origins, d_dirs, n_rays, w.weight, w.t, stream));
+            PH_TRY(op.forward(w.q, w, stream));
             PH_CHECK(hipMemsetAsync(w.s, 0, (size_t)N * sizeof(double), stream));
-            PH_TRY(launch_backproject(g, w.t, d_origins, d_dirs, n_rays, w.s, stream));
-            hipLaunchKernelGGL(cg_apply_kernel, dim3(blocks), dim3(kThreads), 0, stream, N, g.nx, g.ny, g.nz, d_support, lam_h2, w.q, w.s,
+            PH_TRY(op.adjoint(w, w.s, stream));
+            hipLaunchKernelGGL(cg_apply_kernel, dim3(blocks), dim3(kThreads), 0, stream, N, g.nx, g.ny, g.nz, d_support, reg, w.q, w.s,
                                qs_part);
             PH_CHECK(hipGetLastError());
             hipLaunchKernelGGL(cg_update_kernel, dim3(blocks), dim3(kThreads), 0, stream, N, x, w.r, w.q, w.s, rho_part[cur], qs_part, blocks,
@@ -379,6 +582,14 @@ int solve(hipStream_t stream, const Grid &g, const double *d_p, const double *d_
         stats->unknowns = (long long)counters[1];
     }
     return 0;
+}
+
+// what both solvers refuse about lambda, tol and max_iter
+const char *solver_refusal(double lambda, double tol, int max_iter) {
+    if (!(lambda >= 0.0)) return "lambda must be >= 0";
+    if (!(tol >= 0.0)) return "tol must be >= 0";
+    if (max_iter < 0) return "max_iter must be >= 0";
+    return nullptr;
 }
 
 void refuse(const char *what, const char *bad, int nx, int ny, int nz, long long n_rays) {
@@ -414,12 +625,8 @@ extern "C" int photon_tomo_reconstruct(const double *d_p, const double *d_w, con
                                        long long n_rays, double lambda, double tol, int max_iter, double *d_f,
                                        photon_tomo_stats_t *stats, void *stream_p) {
     const char *bad = grid_refusal(nx, ny, nz, spacing, origin, n_rays);
-    if (!bad) {
-        if (!(lambda >= 0.0)) bad = "lambda must be >= 0";
-        else if (!(tol >= 0.0)) bad = "tol must be >= 0";
-        else if (max_iter < 0) bad = "max_iter must be >= 0";
-        else if (!d_p || !d_origins || !d_dirs || !d_f) bad = "null d_p, d_origins, d_dirs or d_f";
-    }
+    if (!bad) bad = solver_refusal(lambda, tol, max_iter);
+    if (!bad && (!d_p || !d_origins || !d_dirs || !d_f)) bad = "null d_p, d_origins, d_dirs or d_f";
     if (bad) {
         refuse("photon_tomo_reconstruct", bad, nx, ny, nz, n_rays);
         return 1;
@@ -437,8 +644,70 @@ extern "C" int photon_tomo_reconstruct(const double *d_p, const double *d_w, con
         PH_CHECK(parts.alloc(3 * kMaxBlocks + 1));
         PH_CHECK(counters.alloc(2));
         const double h = std::min(spacing[0], std::min(spacing[1], spacing[2]));
-        const int rc = solve(stream, make_grid(nx, ny, nz, spacing, origin), d_p, d_w, d_support, d_origins, d_dirs, n_rays, lambda * (h * h),
-                             tol, max_iter, d_f, Work{r.p, q.p, s.p, weight.p, t.p, parts.p, counters.p}, stats);
+        const ProjectionOp op{make_grid(nx, ny, nz, spacing, origin), d_p, d_w, d_origins, d_dirs, n_rays};
+        const int rc = solve(stream, op, d_support, lambda * (h * h), tol, max_iter, d_f,
+                             Work{r.p, q.p, s.p, weight.p, t.p, nullptr, parts.p, counters.p}, stats);
+        if (rc) (void)hipStreamSynchronize(stream);          // the blocks go back to the cache: nothing may still use them
+        return rc;
+    });
+}
+
+// ---- section 10 --------------------------------------------------------------------------------------------------------------
+extern "C" int photon_tomo_deflect(const double *d_f, int nx, int ny, int nz, const double spacing[3], const double origin[3],
+                                   const double *d_origins, const double *d_dirs, const double *d_t1, const double *d_t2, long long n_rays,
+                                   double *d_g1, double *d_g2, void *stream) {
+    const char *bad = grid_refusal(nx, ny, nz, spacing, origin, n_rays);
+    if (!bad && (!d_f || !d_origins || !d_dirs || !d_t1 || !d_t2 || !d_g1 || !d_g2)) bad = "null d_f, d_origins, d_dirs, d_t1, d_t2, d_g1 or d_g2";
+    if (bad) {
+        refuse("photon_tomo_deflect", bad, nx, ny, nz, n_rays);
+        return 1;
+    }
+    return launch_deflect(make_grid(nx, ny, nz, spacing, origin), d_f, d_origins, d_dirs, d_t1, d_t2, n_rays, nullptr, d_g1, d_g2,
+                          (hipStream_t)stream);
+}
+
+extern "C" int photon_tomo_deflect_adjoint(const double *d_y1, const double *d_y2, int nx, int ny, int nz, const double spacing[3],
+                                           const double origin[3], const double *d_origins, const double *d_dirs, const double *d_t1,
+                                           const double *d_t2, long long n_rays, double *d_v, void *stream) {
+    const char *bad = grid_refusal(nx, ny, nz, spacing, origin, n_rays);
+    if (!bad && (!d_y1 || !d_y2 || !d_origins || !d_dirs || !d_t1 || !d_t2 || !d_v)) bad = "null d_y1, d_y2, d_origins, d_dirs, d_t1, d_t2 or d_v";
+    if (bad) {
+        refuse("photon_tomo_deflect_adjoint", bad, nx, ny, nz, n_rays);
+        return 1;
+    }
+    return launch_deflect_adjoint(make_grid(nx, ny, nz, spacing, origin), d_y1, d_y2, d_origins, d_dirs, d_t1, d_t2, n_rays, d_v,
+                                  (hipStream_t)stream);
+}
+
+extern "C" int photon_tomo_reconstruct_deflections(const double *d_g1, const double *d_g2, const double *d_w, const unsigned char *d_support,
+                                                   int nx, int ny, int nz, const double spacing[3], const double origin[3],
+                                                   const double *d_origins, const double *d_dirs, const double *d_t1, const double *d_t2,
+                                                   long long n_rays, double lambda, double tol, int max_iter, double *d_f,
+                                                   photon_tomo_stats_t *stats, void *stream_p) {
+    const char *bad = grid_refusal(nx, ny, nz, spacing, origin, n_rays);
+    if (!bad) bad = solver_refusal(lambda, tol, max_iter);
+    if (!bad && (!d_g1 || !d_g2 || !d_origins || !d_dirs || !d_t1 || !d_t2 || !d_f)) bad = "null d_g1, d_g2, d_origins, d_dirs, d_t1, d_t2 or d_f";
+    if (bad) {
+        refuse("photon_tomo_reconstruct_deflections", bad, nx, ny, nz, n_rays);
+        return 1;
+    }
+    return guarded("photon_tomo_reconstruct_deflections", [&]() -> int {
+        hipStream_t stream = (hipStream_t)stream_p;
+        const size_t N = (size_t)nx * ny * nz;
+        PoolBuffer<double> r, q, s, weight, t, t2, parts;
+        PoolBuffer<unsigned long long> counters;
+        PH_CHECK(r.alloc(N));
+        PH_CHECK(q.alloc(N));
+        PH_CHECK(s.alloc(N));
+        PH_CHECK(weight.alloc((size_t)n_rays));
+        PH_CHECK(t.alloc((size_t)n_rays));
+        PH_CHECK(t2.alloc((size_t)n_rays));
+        PH_CHECK(parts.alloc(3 * kMaxBlocks + 1));
+        PH_CHECK(counters.alloc(2));
+        const DeflectionOp op{make_grid(nx, ny, nz, spacing, origin), d_g1, d_g2, d_w, d_origins, d_dirs, d_t1, d_t2, n_rays};
+        // no h^2: D carries 1 / length against A, so lambda weighs G^T G as it does in section 9
+        const int rc = solve(stream, op, d_support, lambda, tol, max_iter, d_f,
+                             Work{r.p, q.p, s.p, weight.p, t.p, t2.p, parts.p, counters.p}, stats);
         if (rc) (void)hipStreamSynchronize(stream);          // the blocks go back to the cache: nothing may still use them
         return rc;
     });

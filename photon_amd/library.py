@@ -41,6 +41,8 @@ DECLARED_SYMBOLS = (
     "photon_dots_match", "photon_dots_window_means",
     # section 9: tomography
     "photon_tomo_project", "photon_tomo_backproject", "photon_tomo_reconstruct",
+    # section 10: tomography from deflections
+    "photon_tomo_deflect", "photon_tomo_deflect_adjoint", "photon_tomo_reconstruct_deflections",
 )
 
 
@@ -277,6 +279,11 @@ class PhotonLibrary:
         L.photon_tomo_backproject.argtypes = [vp] + grid_and_rays + [vp, vp]
         L.photon_tomo_reconstruct.argtypes = [vp, vp, vp] + grid_and_rays + [ctypes.c_double, ctypes.c_double, ci, vp,
                                                                             ctypes.POINTER(photon_tomo_stats_t), vp]
+        grid_rays_frames = grid_and_rays[:-1] + [vp, vp, ctypes.c_longlong]     # ..., d_dirs, d_t1, d_t2, n_rays
+        L.photon_tomo_deflect.argtypes = [vp] + grid_rays_frames + [vp, vp, vp]
+        L.photon_tomo_deflect_adjoint.argtypes = [vp, vp] + grid_rays_frames + [vp, vp]
+        L.photon_tomo_reconstruct_deflections.argtypes = [vp, vp, vp, vp] + grid_rays_frames + [
+            ctypes.c_double, ctypes.c_double, ci, vp, ctypes.POINTER(photon_tomo_stats_t), vp]
 
     # ---- helpers --------------------------------------------------------------------------
     @staticmethod
@@ -757,6 +764,77 @@ class PhotonLibrary:
         stats = self.tomo_reconstruct_ptr(tp.data_ptr(), dims, spacing, origin, to.data_ptr(), td.data_ptr(), n_rays, f.data_ptr(),
                                           tw.data_ptr() if tw is not None else 0, ts.data_ptr() if ts is not None else 0, lam, tol,
                                           max_iter, stream=torch.cuda.current_stream(dev).cuda_stream)
+        return f.cpu().numpy(), stats
+
+    # ---- tomography from deflections (include/parallel_ray_tracing.h, section 10) -------------------------------------
+    def tomo_deflect(self, d_f_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, d_t1_ptr: int, d_t2_ptr: int,
+                     n_rays: int, d_g1_ptr: int, d_g2_ptr: int, stream: int = 0):
+        """g1 = D_t1 f, g2 = D_t2 f on raw device pointers (f64: f [nz, ny, nx]; origins, dirs, t1, t2 [n_rays, 3]; g1, g2
+        [n_rays]).  Asynchronous on `stream`."""
+        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        rc = self.lib.photon_tomo_deflect(self._vp(d_f_ptr), nx, ny, nz, _ptr(sp), _ptr(og), self._vp(d_origins_ptr), self._vp(d_dirs_ptr),
+                                          self._vp(d_t1_ptr), self._vp(d_t2_ptr), int(n_rays), self._vp(d_g1_ptr), self._vp(d_g2_ptr),
+                                          self._vp(stream))
+        self._check(rc, "photon_tomo_deflect")
+
+    def tomo_deflect_adjoint(self, d_y1_ptr: int, d_y2_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int,
+                             d_t1_ptr: int, d_t2_ptr: int, n_rays: int, d_v_ptr: int, stream: int = 0):
+        """v += D_t1^T y1 + D_t2^T y2 on raw device pointers (f64: y1, y2 [n_rays], v [nz, ny, nx]): adds into v.
+        Asynchronous on `stream`."""
+        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        rc = self.lib.photon_tomo_deflect_adjoint(self._vp(d_y1_ptr), self._vp(d_y2_ptr), nx, ny, nz, _ptr(sp), _ptr(og),
+                                                  self._vp(d_origins_ptr), self._vp(d_dirs_ptr), self._vp(d_t1_ptr), self._vp(d_t2_ptr),
+                                                  int(n_rays), self._vp(d_v_ptr), self._vp(stream))
+        self._check(rc, "photon_tomo_deflect_adjoint")
+
+    def tomo_reconstruct_deflections_ptr(self, d_g1_ptr: int, d_g2_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int,
+                                         d_t1_ptr: int, d_t2_ptr: int, n_rays: int, d_f_ptr: int, d_w_ptr: int = 0,
+                                         d_support_ptr: int = 0, lam: float = 1.0, tol: float = 1e-6, max_iter: Optional[int] = None,
+                                         stream: int = 0) -> dict:
+        """Solve for the device f64 field at d_f_ptr [nz, ny, nx] from the deflections at d_g1_ptr, d_g2_ptr (raw pointers:
+        f64 g1, g2, w, origins, dirs, t1, t2; u8 support; 0 = NULL).  Returns the stats as a dict; the call has synchronised
+        `stream`.  max_iter None = tomography.DEFAULT_MAX_ITER."""
+        from .tomography import DEFAULT_MAX_ITER
+        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        st = photon_tomo_stats_t()
+        rc = self.lib.photon_tomo_reconstruct_deflections(
+            self._vp(d_g1_ptr), self._vp(d_g2_ptr), self._vp(d_w_ptr), self._vp(d_support_ptr), nx, ny, nz, _ptr(sp), _ptr(og),
+            self._vp(d_origins_ptr), self._vp(d_dirs_ptr), self._vp(d_t1_ptr), self._vp(d_t2_ptr), int(n_rays), float(lam), float(tol),
+            DEFAULT_MAX_ITER if max_iter is None else int(max_iter), self._vp(d_f_ptr), ctypes.byref(st), self._vp(stream))
+        self._check(rc, "photon_tomo_reconstruct_deflections")
+        return st.as_dict()
+
+    def tomo_reconstruct_deflections(self, g1, g2, dims, spacing, origin, origins, dirs, t1, t2, w=None, support=None, lam: float = 1.0,
+                                     tol: float = 1e-6, max_iter: Optional[int] = None):
+        """The 3-D field from the deflections measured along rays, on the device (numpy arrays or torch device tensors):
+        g1, g2, w [n_rays] (g_j the integral of grad f . t_j along the ray; w None = 1; a ray whose g1, g2 or w is not
+        finite or whose w <= 0 takes no part), origins, dirs, t1, t2 [n_rays, 3] world microns, support [nz, ny, nx] (None
+        = every voxel: the mean of f is then 0), lam the dimensionless smoothness weight.  Returns (f numpy f64 [nz, ny,
+        nx], stats dict).  The definition: include/parallel_ray_tracing.h, section 10 (photon_amd.tomography: host model,
+        and view_rays / view_frames / grid_of for the geometry)."""
+        import torch
+        from . import tomography
+        dev = torch.device("cuda", torch.cuda.current_device())
+
+        def on_device(a, dtype):
+            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
+
+        nx, ny, nz = (int(n) for n in dims)
+        rays = [on_device(a, torch.float64).reshape(-1, 3) for a in (origins, dirs, t1, t2)]
+        tg1, tg2, tw = on_device(g1, torch.float64).reshape(-1), on_device(g2, torch.float64).reshape(-1), on_device(w, torch.float64)
+        n_rays = tg1.numel()
+        if any(a.shape != (n_rays, 3) for a in rays) or tg2.numel() != n_rays or (tw is not None and tw.numel() != n_rays):
+            raise ValueError("g1, g2 and w hold one value per ray, origins, dirs, t1 and t2 three")
+        ts = None if support is None else on_device(torch.as_tensor(support) != 0, torch.uint8)
+        if ts is not None and tuple(ts.shape) != (nz, ny, nx):
+            raise ValueError(f"support must be [nz, ny, nx] = {(nz, ny, nx)}")
+        max_iter = tomography.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
+        tomography.check_arguments(dims, np.broadcast_to(np.asarray(spacing, np.float64), (3,)), origin, n_rays, lam, tol, max_iter)
+        f = torch.empty((nz, ny, nx), dtype=torch.float64, device=dev)
+        stats = self.tomo_reconstruct_deflections_ptr(
+            tg1.data_ptr(), tg2.data_ptr(), dims, spacing, origin, rays[0].data_ptr(), rays[1].data_ptr(), rays[2].data_ptr(),
+            rays[3].data_ptr(), n_rays, f.data_ptr(), tw.data_ptr() if tw is not None else 0, ts.data_ptr() if ts is not None else 0,
+            lam, tol, max_iter, stream=torch.cuda.current_stream(dev).cuda_stream)
         return f.cpu().numpy(), stats
 
     # ---- volumes ------------------------------------------------------------------------------

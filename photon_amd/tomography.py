@@ -8,8 +8,12 @@ The device form is section 9 of include/parallel_ray_tracing.h (``PhotonLibrary.
 * ``project_model``, ``backproject_model``, ``reconstruct_model``: the projector A, its adjoint and the conjugate-gradient
   solver of section 9 on those taps (vectorised over the rays, a loop over the planes, sums by ``np.bincount``, which adds
   in array order: the projector's sums run in the order of the definition);
-* the geometry that carries a camera's measurement into it: ``view_rays`` (the world chief rays of a camera's grid nodes)
-  and ``grid_of`` (a volume's grid in the same frame).
+* section 10, tomography from the deflections themselves: ``deflection_taps`` (the same taps with the weights of the
+  projector's derivative under a parallel shift of the ray along two transverse vectors), ``deflect_model``,
+  ``deflect_adjoint_model`` and ``reconstruct_deflections_model``;
+* the geometry that carries a camera's measurement into it: ``view_rays`` (the world chief rays of a camera's grid nodes),
+  ``view_frames`` (the world directions along which the camera measures its two deflection components) and ``grid_of`` (a
+  volume's grid in the same frame).
 
 Arrays over the voxels are indexed [z, y, x] (x fastest), as the volumes are; dims = (nx, ny, nz).
 """
@@ -23,8 +27,9 @@ CHECK_EVERY = 8                 # PHOTON_TOMO_CHECK_EVERY
 DEFAULT_MAX_ITER = 100
 
 
-def check_arguments(dims, spacing, origin, n_rays, lam=0.0, tol=0.0, max_iter=0):
-    """The arguments section 9 refuses, as a ValueError (null pointers aside)."""
+def check_arguments(dims, spacing, origin, n_rays, lam=0.0, tol=0.0, max_iter=0, frames=None):
+    """The arguments sections 9 and 10 refuse, as a ValueError (null pointers aside).  frames: section 10's (t1, t2), which
+    must both be there and hold three values per ray."""
     nx, ny, nz = (int(v) for v in dims)
     if min(nx, ny, nz) < 2:
         raise ValueError(f"nx, ny and nz must be >= 2, not {nx} x {ny} x {nz}")
@@ -45,6 +50,11 @@ def check_arguments(dims, spacing, origin, n_rays, lam=0.0, tol=0.0, max_iter=0)
         raise ValueError(f"tol must be >= 0, not {tol}")
     if int(max_iter) < 0:
         raise ValueError(f"max_iter must be >= 0, not {max_iter}")
+    if frames is not None:
+        if len(frames) != 2 or any(t is None for t in frames):
+            raise ValueError("t1 and t2 must both be given")
+        if any(np.shape(t) != (int(n_rays), 3) for t in frames):
+            raise ValueError("t1 and t2 must both be [n_rays, 3]")
 
 
 def _rays(origins, dirs):
@@ -66,10 +76,10 @@ class Taps(NamedTuple):
     n_voxels: int
 
 
-def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
-    """The taps of section 9's projector, every step the definition's f64 operation."""
-    o, d = _rays(origins, dirs)
-    check_arguments(dims, spacing, origin, o.shape[0])
+def _walk(dims, spacing, origin, o, d, frames=()):
+    """Steps 1 to 3 of section 9 for rays o, d [n, 3], every step the definition's f64 operation: yields per dominant axis a
+    and plane kappa the rays r that count it, their four voxels [len(r), 4], f_b, f_c, g_b, g_c and scale, and for every
+    tau [n, 3] of `frames` section 10's (p_u, p_v) of those rays (a ray with a tau that is not finite is a miss)."""
     n = tuple(int(v) for v in dims)
     h = tuple(float(v) for v in np.asarray(spacing, np.float64))
     g = tuple(float(v) for v in np.asarray(origin, np.float64))
@@ -78,6 +88,8 @@ def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
         length = np.sqrt((d[:, 0] * d[:, 0] + d[:, 1] * d[:, 1]) + d[:, 2] * d[:, 2])
         hit = np.isfinite(o).all(axis=1) & np.isfinite(d).all(axis=1) & np.isfinite(length) & (length > 0)
         e = d / length[:, None]
+    for tau in frames:
+        hit = hit & np.isfinite(tau).all(axis=1)
     mag = np.abs(e)
     axis = np.zeros(o.shape[0], np.int64)
     top = mag[:, 0].copy()
@@ -85,8 +97,6 @@ def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
         more = mag[:, a] > top
         axis[more] = a
         top = np.where(more, mag[:, a], top)
-    rays, voxels, weights = [], [], []
-    planes = np.zeros(o.shape[0], np.int64)
     for a, (b, c) in ((0, (1, 2)), (1, (0, 2)), (2, (0, 1))):
         idx = np.nonzero(hit & (axis == a))[0]
         if idx.size == 0:
@@ -94,6 +104,10 @@ def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
         oa, ob, oc = o[idx, a], o[idx, b], o[idx, c]
         ea, eb, ec = e[idx, a], e[idx, b], e[idx, c]
         scale = h[a] / top[idx]
+        rates = []
+        for tau in frames:
+            r = tau[idx, a] / ea
+            rates.append((((tau[idx, b] - r * eb) / h[b]) * scale, ((tau[idx, c] - r * ec) / h[c]) * scale))
         for kappa in range(n[a]):
             plane = g[a] + float(kappa) * h[a]
             t = (plane - oa) / ea
@@ -107,15 +121,70 @@ def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
             fb, fc = u - ib, v - ic
             hb, hc = 1.0 - fb, 1.0 - fc
             base = kappa * stride[a] + ib.astype(np.int64) * stride[b] + ic.astype(np.int64) * stride[c]
-            voxels.append(np.stack([base, base + stride[b], base + stride[c], base + stride[b] + stride[c]], axis=1))
-            weights.append(np.stack([(hb * hc) * s, (fb * hc) * s, (hb * fc) * s, (fb * fc) * s], axis=1))
-            rays.append(np.repeat(r, 4).reshape(-1, 4))
-            planes[r] += 1
+            voxels = np.stack([base, base + stride[b], base + stride[c], base + stride[b] + stride[c]], axis=1)
+            yield r, voxels, fb, fc, hb, hc, s, [(pu[ok], pv[ok]) for pu, pv in rates]
+
+
+def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
+    """The taps of section 9's projector, every step the definition's f64 operation."""
+    o, d = _rays(origins, dirs)
+    check_arguments(dims, spacing, origin, o.shape[0])
+    n = tuple(int(v) for v in dims)
+    rays, voxels, weights = [], [], []
+    planes = np.zeros(o.shape[0], np.int64)
+    for r, vox, fb, fc, hb, hc, s, _ in _walk(dims, spacing, origin, o, d):
+        voxels.append(vox)
+        weights.append(np.stack([(hb * hc) * s, (fb * hc) * s, (hb * fc) * s, (fb * fc) * s], axis=1))
+        rays.append(np.repeat(r, 4).reshape(-1, 4))
+        planes[r] += 1
     if not rays:
         empty = np.zeros(0, np.int64)
         return Taps(empty, empty, np.zeros(0), planes, n[0] * n[1] * n[2])
     return Taps(np.concatenate(rays).ravel(), np.concatenate(voxels).ravel(), np.concatenate(weights).ravel(), planes,
                 n[0] * n[1] * n[2])
+
+
+class DeflectionTaps(NamedTuple):
+    """Every tap of section 10's operator pair: tap i adds weight1[i] * f[voxel[i]] to g1[ray[i]] and weight2[i] *
+    f[voxel[i]] to g2[ray[i]].  Order and planes as in Taps."""
+    ray: np.ndarray
+    voxel: np.ndarray
+    weight1: np.ndarray
+    weight2: np.ndarray
+    planes: np.ndarray
+    n_voxels: int
+
+
+def _frames(t1, t2, n_rays):
+    if t1 is None or t2 is None:
+        raise ValueError("t1 and t2 must both be given")
+    t1 = np.ascontiguousarray(t1, np.float64).reshape(-1, 3)
+    t2 = np.ascontiguousarray(t2, np.float64).reshape(-1, 3)
+    check_arguments((2, 2, 2), (1.0, 1.0, 1.0), (0.0, 0.0, 0.0), n_rays, frames=(t1, t2))
+    return t1, t2
+
+
+def deflection_taps(dims, spacing, origin, origins, dirs, t1, t2) -> DeflectionTaps:
+    """The taps of section 10's D_t1 and D_t2 (the derivative of section 9's projector under a parallel shift of the ray
+    along t1, t2 [n_rays, 3]), every step the definition's f64 operation."""
+    o, d = _rays(origins, dirs)
+    check_arguments(dims, spacing, origin, o.shape[0])
+    t1, t2 = _frames(t1, t2, o.shape[0])
+    n = tuple(int(v) for v in dims)
+    rays, voxels, weights = [], [], ([], [])
+    planes = np.zeros(o.shape[0], np.int64)
+    for r, vox, fb, fc, gb, gc, _, rates in _walk(dims, spacing, origin, o, d, frames=(t1, t2)):
+        voxels.append(vox)
+        rays.append(np.repeat(r, 4).reshape(-1, 4))
+        planes[r] += 1
+        for out, (pu, pv) in zip(weights, rates):
+            gcu, gbv, fcu, fbv = gc * pu, gb * pv, fc * pu, fb * pv
+            out.append(np.stack([-gcu - gbv, gcu - fbv, gbv - fcu, fcu + fbv], axis=1))
+    if not rays:
+        empty = np.zeros(0, np.int64)
+        return DeflectionTaps(empty, empty, np.zeros(0), np.zeros(0), planes, n[0] * n[1] * n[2])
+    return DeflectionTaps(np.concatenate(rays).ravel(), np.concatenate(voxels).ravel(), np.concatenate(weights[0]).ravel(),
+                          np.concatenate(weights[1]).ravel(), planes, n[0] * n[1] * n[2])
 
 
 def _apply(taps: Taps, f: np.ndarray) -> np.ndarray:
@@ -160,6 +229,47 @@ def graph_laplacian(q: np.ndarray) -> np.ndarray:
     return lap
 
 
+def _conjugate_gradients(normal, b, m, reg, shape, tol, max_iter):
+    """The iteration of section 9 on  m (normal + reg G^T G) m x = b  from x = 0: normal(q) = Op^T W Op q over the voxels.
+    Returns (x, iterations, rho, |b|)."""
+    x = np.zeros(b.size)
+    r = b
+    q = r.copy()
+    rho = float(np.dot(r, r))
+    bnorm = np.sqrt(rho)
+    it = 0
+    if bnorm > 0:
+        while True:
+            if it % CHECK_EVERY == 0 and tol > 0 and np.sqrt(rho) <= tol * bnorm:
+                break
+            if it == max_iter:
+                break
+            s = np.where(m, normal(q) + reg * graph_laplacian(q.reshape(shape)).ravel(), 0.0)
+            qs = float(np.dot(q, s))
+            alpha = rho / qs if qs != 0 else 0.0
+            x = x + alpha * q
+            r = r - alpha * s
+            rho_new = float(np.dot(r, r))
+            beta = rho_new / rho if rho != 0 else 0.0
+            q = r + beta * q
+            rho = rho_new
+            it += 1
+    return x, it, rho, bnorm
+
+
+def _stats(it, rho, bnorm, tol, m, used):
+    return dict(iterations=it, converged=int(bool(bnorm == 0 or np.sqrt(rho) <= tol * bnorm)), unknowns=int(m.sum()),
+                rays_used=int(used.sum()), residual=float(np.sqrt(rho) / bnorm) if bnorm > 0 else 0.0)
+
+
+def _support(support, dims):
+    nx, ny, nz = (int(n) for n in dims)
+    m = np.ones(nx * ny * nz, bool) if support is None else np.asarray(support).ravel() != 0
+    if m.shape != (nx * ny * nz,):
+        raise ValueError("support must have the shape of the grid")
+    return m
+
+
 def reconstruct_model(p, dims, spacing, origin, origins, dirs, w=None, support=None, lam: float = 1.0, tol: float = 1e-6,
                       max_iter: int = DEFAULT_MAX_ITER, taps: Optional[Taps] = None):
     """Host model of photon_tomo_reconstruct (section 9: the same iteration and check cadence).  p, w [n_rays] (w None =
@@ -172,9 +282,7 @@ def reconstruct_model(p, dims, spacing, origin, origins, dirs, w=None, support=N
     w = np.ones_like(p) if w is None else np.asarray(w, np.float64).ravel()
     if p.shape != (o.shape[0],) or w.shape != p.shape:
         raise ValueError("p and w must hold one value per ray")
-    m = np.ones(nx * ny * nz, bool) if support is None else np.asarray(support).ravel() != 0
-    if m.shape != (nx * ny * nz,):
-        raise ValueError("support must have the shape of the grid")
+    m = _support(support, dims)
     if taps is None:
         taps = ray_taps(dims, spacing, origin, o, d)
     with np.errstate(invalid="ignore"):
@@ -184,32 +292,75 @@ def reconstruct_model(p, dims, spacing, origin, origins, dirs, w=None, support=N
     h = float(np.min(np.asarray(spacing, np.float64)))
     lam_h2 = float(lam) * (h * h)
 
-    x = np.zeros(nx * ny * nz)
-    r = np.where(m, _adjoint(taps, wp), 0.0)
-    q = r.copy()
-    rho = float(np.dot(r, r))
-    bnorm = np.sqrt(rho)
-    it = 0
-    if bnorm > 0:
-        while True:
-            if it % CHECK_EVERY == 0 and tol > 0 and np.sqrt(rho) <= tol * bnorm:
-                break
-            if it == max_iter:
-                break
-            t = np.where(weight > 0, weight * _apply(taps, q), 0.0)
-            s = np.where(m, _adjoint(taps, t) + lam_h2 * graph_laplacian(q.reshape(nz, ny, nx)).ravel(), 0.0)
-            qs = float(np.dot(q, s))
-            alpha = rho / qs if qs != 0 else 0.0
-            x = x + alpha * q
-            r = r - alpha * s
-            rho_new = float(np.dot(r, r))
-            beta = rho_new / rho if rho != 0 else 0.0
-            q = r + beta * q
-            rho = rho_new
-            it += 1
-    stats = dict(iterations=it, converged=int(bool(bnorm == 0 or np.sqrt(rho) <= tol * bnorm)), unknowns=int(m.sum()),
-                 rays_used=int(((weight > 0) & (taps.planes > 0)).sum()), residual=float(np.sqrt(rho) / bnorm) if bnorm > 0 else 0.0)
-    return x.reshape(nz, ny, nx), stats
+    def normal(q):
+        return _adjoint(taps, np.where(weight > 0, weight * _apply(taps, q), 0.0))
+
+    x, it, rho, bnorm = _conjugate_gradients(normal, np.where(m, _adjoint(taps, wp), 0.0), m, lam_h2, (nz, ny, nx), tol, max_iter)
+    return x.reshape(nz, ny, nx), _stats(it, rho, bnorm, tol, m, (weight > 0) & (taps.planes > 0))
+
+
+# ---- section 10: the operator pair of the deflections -----------------------------------------------------------------------
+def _deflect(taps: DeflectionTaps, f: np.ndarray):
+    n = taps.planes.size
+    return (np.bincount(taps.ray, taps.weight1 * f[taps.voxel], minlength=n),
+            np.bincount(taps.ray, taps.weight2 * f[taps.voxel], minlength=n))
+
+
+def _deflect_adjoint(taps: DeflectionTaps, y1: np.ndarray, y2: np.ndarray) -> np.ndarray:
+    return np.bincount(taps.voxel, taps.weight1 * y1[taps.ray] + taps.weight2 * y2[taps.ray], minlength=taps.n_voxels)
+
+
+def deflect_model(f, spacing, origin, origins, dirs, t1, t2, taps: Optional[DeflectionTaps] = None):
+    """Host model of photon_tomo_deflect: (g1, g2) = (D_t1 f, D_t2 f), f [nz, ny, nx].  taps: deflection_taps of the same
+    grid, rays and vectors, when the caller has them."""
+    f = np.asarray(f, np.float64)
+    if f.ndim != 3:
+        raise ValueError("f must be [nz, ny, nx]")
+    if taps is None:
+        taps = deflection_taps(f.shape[::-1], spacing, origin, origins, dirs, t1, t2)
+    return _deflect(taps, f.ravel())
+
+
+def deflect_adjoint_model(y1, y2, dims, spacing, origin, origins, dirs, t1, t2, v=None,
+                          taps: Optional[DeflectionTaps] = None) -> np.ndarray:
+    """Host model of photon_tomo_deflect_adjoint: v + D_t1^T y1 + D_t2^T y2 as a new array [nz, ny, nx] (v None = 0)."""
+    y1, y2 = np.asarray(y1, np.float64).ravel(), np.asarray(y2, np.float64).ravel()
+    if taps is None:
+        taps = deflection_taps(dims, spacing, origin, origins, dirs, t1, t2)
+    nx, ny, nz = (int(n) for n in dims)
+    out = _deflect_adjoint(taps, y1, y2).reshape(nz, ny, nx)
+    return out if v is None else np.asarray(v, np.float64).reshape(nz, ny, nx) + out
+
+
+def reconstruct_deflections_model(g1, g2, dims, spacing, origin, origins, dirs, t1, t2, w=None, support=None, lam: float = 1.0,
+                                  tol: float = 1e-6, max_iter: int = DEFAULT_MAX_ITER, taps: Optional[DeflectionTaps] = None):
+    """Host model of photon_tomo_reconstruct_deflections (section 10: section 9's iteration on the operator pair, lam on
+    G^T G without h^2).  g1, g2, w [n_rays] (w None = 1); support [nz, ny, nx] (None = every voxel: the solution has zero
+    mean).  Returns (f [nz, ny, nx], stats dict) as reconstruct_model does."""
+    o, d = _rays(origins, dirs)
+    check_arguments(dims, spacing, origin, o.shape[0], lam, tol, max_iter)
+    t1, t2 = _frames(t1, t2, o.shape[0])
+    nx, ny, nz = (int(n) for n in dims)
+    g1, g2 = np.asarray(g1, np.float64).ravel(), np.asarray(g2, np.float64).ravel()
+    w = np.ones_like(g1) if w is None else np.asarray(w, np.float64).ravel()
+    if g1.shape != (o.shape[0],) or g2.shape != g1.shape or w.shape != g1.shape:
+        raise ValueError("g1, g2 and w must hold one value per ray")
+    m = _support(support, dims)
+    if taps is None:
+        taps = deflection_taps(dims, spacing, origin, o, d, t1, t2)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(g1) & np.isfinite(g2) & np.isfinite(w) & (w > 0)
+    weight = np.where(ok, w, 0.0)
+    wg1 = np.where(ok, w * np.where(ok, g1, 0.0), 0.0)
+    wg2 = np.where(ok, w * np.where(ok, g2, 0.0), 0.0)
+
+    def normal(q):
+        a1, a2 = _deflect(taps, q)
+        return _deflect_adjoint(taps, np.where(weight > 0, weight * a1, 0.0), np.where(weight > 0, weight * a2, 0.0))
+
+    x, it, rho, bnorm = _conjugate_gradients(normal, np.where(m, _deflect_adjoint(taps, wg1, wg2), 0.0), m, float(lam), (nz, ny, nx),
+                                             tol, max_iter)
+    return x.reshape(nz, ny, nx), _stats(it, rho, bnorm, tol, m, (weight > 0) & (taps.planes > 0))
 
 
 # ---- geometry ------------------------------------------------------------------------------------------------------------
@@ -241,6 +392,21 @@ def view_rays(call, target_xy, rotation=None, pivot=None):
         R = np.asarray(rotation, np.float64).reshape(3, 3)
         origins, dirs = rotate_about(origins, R, pivot), dirs @ R.T
     return origins, dirs
+
+
+def view_frames(call, target_xy, rotation=None):
+    """The world directions along which bos_density.gradients_from_displacements measures gx and gy at a camera's grid
+    nodes: (t1, t2), each [..., 3] like X_t.  gx and gy run along the grid's columns and rows, which lie along the camera's
+    X and Y axes in the sense of bos_density.axis_signs; the axes are carried into the world frame as view_rays carries its
+    directions (the camera's inverse_rotation_matrix, then `rotation`) and are the same at every node: section 10's operator
+    keeps only the part of each that is perpendicular to the node's ray."""
+    from .bos_density import axis_signs
+    Xt = np.asarray(target_xy[0], np.float64)
+    inv = np.asarray(call.camera.get("inverse_rotation_matrix", np.eye(3)), np.float32).astype(np.float64).reshape(3, 3)
+    axes = (np.asarray(axis_signs(call.camera))[:, None] * np.eye(3)[:2]) @ inv.T
+    if rotation is not None:
+        axes = axes @ np.asarray(rotation, np.float64).reshape(3, 3).T
+    return tuple(np.ascontiguousarray(np.broadcast_to(axes[j], Xt.shape + (3,))) for j in range(2))
 
 
 def grid_of(volume_info):

@@ -1,4 +1,4 @@
-"""Tomographic BOS on the device (include/parallel_ray_tracing.h section 9).  Prints JSON lines for two measurements:
+"""Tomographic BOS on the device (include/parallel_ray_tracing.h sections 9 and 10).  Prints JSON lines for two measurements:
 
 1. timing of photon_tomo_project, photon_tomo_backproject and one solver iteration at 128^3 and 256^3 voxels with
    8 x 512^2 rays (the rotated views of tests/tomography_cases.py at that size): ms per call from device events around
@@ -12,9 +12,15 @@
    integrated (bos_density.reconstruct), the views' P at the valid nodes fed with tomography.view_rays(rotation = R_k^T,
    pivot = centre) to tomo_reconstruct: relative L2 error over the voxels above 10 % of the peak for K = 4, 8, 16.
 
+With --deflections both also measure section 10 (tomography from the deflections themselves): photon_tomo_deflect,
+photon_tomo_deflect_adjoint and one iteration of photon_tomo_reconstruct_deflections in the same alternating windows as the
+projector and its adjoint (the frames of tests/deflection_cases.py, the blob's analytic deflections), and the rendered
+study a second time from bos_density.deflection_data with tomography.view_rays and view_frames straight into
+tomo_reconstruct_deflections ("route": "direct" next to "two_step").
+
 Kernel times under a profiler come from a separate run.  Run it on a GPU box under a time limit:
 
-    timeout -k 10 900 python tools/bos_tomography.py [--skip-timing] [--skip-study] [--compare-library build/variants/lib_tomo_plain.so]
+    timeout -k 10 900 python tools/bos_tomography.py [--skip-timing] [--skip-study] [--deflections] [--compare-library build/variants/lib_tomo_plain.so]
 """
 import argparse
 import json
@@ -29,6 +35,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402  (first: one HIP runtime per process)
 import bos_density_cases as bc  # noqa: E402
+import deflection_cases as dc  # noqa: E402
 import tomography_cases as tc  # noqa: E402
 from photon_amd import bos_density as bd  # noqa: E402
 from photon_amd import scenes  # noqa: E402
@@ -103,9 +110,9 @@ def spread(r: dict) -> str:
     return f"{r['median']:.3f} ({r['min']:.3f}-{r['max']:.3f}, {r['calls_per_window']} calls per window)"
 
 
-def operator_timing(lib, n: int, n_side: int = 512, other=None) -> dict:
+def operator_timing(lib, n: int, n_side: int = 512, other=None, deflections: bool = False) -> dict:
     """other: a second build of the library (--compare-library) whose adjoint is timed in alternation and held against
-    this one's result."""
+    this one's result.  deflections: section 10's operators and solver iteration too, in the same windows."""
     c = tc.view_case(n, n_side)
     o, d = dev(c.origins), dev(c.dirs)
     stream = torch.cuda.current_stream().cuda_stream
@@ -121,6 +128,14 @@ def operator_timing(lib, n: int, n_side: int = 512, other=None) -> dict:
     fns = {"project": lambda: lib.tomo_project(f.data_ptr(), *grid_rays, p.data_ptr(), stream=stream),
            "backproject": lambda: lib.tomo_backproject(p.data_ptr(), *grid_rays, v.data_ptr(), stream=stream)}
     extra = {}
+    if deflections:
+        cd = dc.view_frames_of(c)
+        t1, t2 = dev(cd.t1), dev(cd.t2)
+        frame_rays = (*c.grid, o.data_ptr(), d.data_ptr(), t1.data_ptr(), t2.data_ptr(), c.n_rays)
+        g1, g2 = torch.empty_like(p), torch.empty_like(p)
+        lib.tomo_deflect(f.data_ptr(), *frame_rays, g1.data_ptr(), g2.data_ptr(), stream=stream)
+        fns["deflect"] = lambda: lib.tomo_deflect(f.data_ptr(), *frame_rays, g1.data_ptr(), g2.data_ptr(), stream=stream)
+        fns["deflect_adjoint"] = lambda: lib.tomo_deflect_adjoint(g1.data_ptr(), g2.data_ptr(), *frame_rays, v.data_ptr(), stream=stream)
     if other is not None:
         fns["backproject_other"] = lambda: other.tomo_backproject(p.data_ptr(), *grid_rays, v.data_ptr(), stream=stream)
         va, vb = torch.zeros_like(v), torch.zeros_like(v)
@@ -150,13 +165,38 @@ def operator_timing(lib, n: int, n_side: int = 512, other=None) -> dict:
         return 1e3 * (time.perf_counter() - t0), st
     solve(2)
     short, long_ = 4, 20
-    per_it = []
+    if deflections:
+        ga = [dev(g) for g in dc.blob_deflections(cd)]
+        out_d = torch.empty_like(out)
+
+        def solve_direct(iterations):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st = lib.tomo_reconstruct_deflections_ptr(ga[0].data_ptr(), ga[1].data_ptr(), *frame_rays, out_d.data_ptr(), lam=1.0, tol=0.0,
+                                                      max_iter=iterations, stream=stream)
+            return 1e3 * (time.perf_counter() - t0), st
+        solve_direct(2)
+    per_it, per_it_d = [], []
     for _ in range(5):
         ms_short, _ = solve(short)
         ms_long, st = solve(long_)
         per_it.append((ms_long - ms_short) / (long_ - short))
+        if deflections:
+            ms_short, _ = solve_direct(short)
+            ms_long, st_d = solve_direct(long_)
+            per_it_d.append((ms_long - ms_short) / (long_ - short))
     ms_it = float(np.median(per_it))
     err = tc.rel_l2(out.cpu().numpy(), tc.blob_field(c))
+    if deflections:
+        ms_d, ms_a, ms_it_d = t["deflect"]["median"], t["deflect_adjoint"]["median"], float(np.median(per_it_d))
+        field, got = tc.blob_field(c), out_d.cpu().numpy()
+        extra.update(deflect_ms=spread(t["deflect"]), deflect_adjoint_ms=spread(t["deflect_adjoint"]),
+                     deflect_over_project=round(ms_d / ms_p, 2), deflect_adjoint_over_backproject=round(ms_a / ms_b, 2),
+                     deflect_gtaps_per_s=round(taps / (ms_d * 1e-3) / 1e9, 2), deflect_adjoint_gtaps_per_s=round(taps / (ms_a * 1e-3) / 1e9, 2),
+                     direct_solver_iteration_ms=f"{ms_it_d:.3f} ({min(per_it_d):.3f}-{max(per_it_d):.3f}, 5 pairs of {short} and {long_} "
+                                                f"iterations)",
+                     direct_operators_share_of_iteration=round((ms_d + ms_a) / ms_it_d, 3), direct_residual_after_20=st_d["residual"],
+                     direct_rel_l2_error_after_20_mean_removed=round(tc.rel_l2(got - got.mean(), field - field.mean()), 4))
     tbs = taps * 8 / (ms_b * 1e-3) / 1e12
     return dict(extra, measurement="operators", voxels=f"{n}^3", rays=c.n_rays, taps=taps, project_ms=spread(t["project"]),
                 backproject_ms=spread(t["backproject"]), shader_clock_under_load=clock_read,
@@ -209,16 +249,20 @@ def render_views(lib, n_pix: int = bc.N_PIX):
     return call, im1, frames, rotations
 
 
-def rendered_study(lib, lams, n_pix: int = bc.N_PIX):
+def rendered_study(lib, lams, n_pix: int = bc.N_PIX, deflections: bool = False):
     call, im1, frames, rotations = render_views(lib, n_pix)
     shape = (n_pix, n_pix)
     target, _, h_nodes = bd.node_geometry(shape, bc.WIN, bc.STEP, call, bc.ORIGIN_Z, bc.EXTENT)
     centre_world = CENTRE - np.array([0.0, 0.0, tm.WORLD_Z_SHIFT])
-    views = []
+    views, direct = [], []
     for im2, R in zip(frames, rotations):
         phi, _, st = bd.reconstruct(lib, im1, im2, call, bc.ORIGIN_Z, bc.EXTENT, bc.WIN, bc.STEP, passes=2)
         o, d = tm.view_rays(call, target, rotation=R.T, pivot=centre_world)
         views.append((phi.ravel(), np.where(np.isfinite(phi), 1.0, 0.0).ravel(), o.reshape(-1, 3), d.reshape(-1, 3)))
+        if deflections:
+            g1, g2, w, nodes = bd.deflection_data(lib, im1, im2, call, bc.ORIGIN_Z, bc.EXTENT, bc.WIN, bc.STEP, passes=2)
+            t1, t2 = tm.view_frames(call, nodes, rotation=R.T)
+            direct.append((g1.ravel(), g2.ravel(), w.ravel(), o.reshape(-1, 3), d.reshape(-1, 3), t1.reshape(-1, 3), t2.reshape(-1, 3)))
     hg = RECON_EXTENT / (RECON_N - 1)
     case = tc.Case((RECON_N,) * 3, (hg, hg, hg), centre_world - RECON_EXTENT / 2, views[0][2], views[0][3])
     x, y, z = case.nodes()
@@ -233,7 +277,21 @@ def rendered_study(lib, lams, n_pix: int = bc.N_PIX):
             f, st = lib.tomo_reconstruct(p, *case.grid, o, d, w=w, support=support.astype(np.uint8), lam=lam, tol=1e-6, max_iter=500)
             ms = 1e3 * (time.perf_counter() - t0)
             rel = float(np.linalg.norm((f - truth)[high]) / np.linalg.norm(truth[high]))
-            yield dict(measurement="rendered_study", views=K, sensor=f"{n_pix}x{n_pix}", nodes_per_view=int(views[0][0].size),
+            yield dict(measurement="rendered_study", route="two_step", views=K, sensor=f"{n_pix}x{n_pix}", nodes_per_view=int(views[0][0].size),
+                       node_spacing_um=round(float(h_nodes), 1), voxels=f"{RECON_N}^3", voxel_spacing_um=round(hg, 1), lam=lam,
+                       rays_used=st["rays_used"], unknowns=st["unknowns"], iterations=st["iterations"], converged=st["converged"],
+                       solve_ms_with_copies=round(ms, 1), rel_l2_error_above_10pct=round(rel, 4),
+                       peak_recovered=round(float(f.max() / truth.max()), 3))
+        if not deflections:
+            continue
+        g1, g2, w, o, d, t1, t2 = (np.concatenate([v[i] for v in direct[::K_MAX // K]]) for i in range(7))
+        for lam in lams:
+            t0 = time.perf_counter()
+            f, st = lib.tomo_reconstruct_deflections(g1, g2, *case.grid, o, d, t1, t2, w=w, support=support.astype(np.uint8), lam=lam,
+                                                     tol=1e-6, max_iter=500)
+            ms = 1e3 * (time.perf_counter() - t0)
+            rel = float(np.linalg.norm((f - truth)[high]) / np.linalg.norm(truth[high]))
+            yield dict(measurement="rendered_study", route="direct", views=K, sensor=f"{n_pix}x{n_pix}", nodes_per_view=int(direct[0][0].size),
                        node_spacing_um=round(float(h_nodes), 1), voxels=f"{RECON_N}^3", voxel_spacing_um=round(hg, 1), lam=lam,
                        rays_used=st["rays_used"], unknowns=st["unknowns"], iterations=st["iterations"], converged=st["converged"],
                        solve_ms_with_copies=round(ms, 1), rel_l2_error_above_10pct=round(rel, 4),
@@ -247,6 +305,9 @@ def main():
     ap.add_argument("--sizes", default="128,256")
     ap.add_argument("--rays-side", type=int, default=512)
     ap.add_argument("--lams", default="0.1,1,10")
+    ap.add_argument("--deflections", action="store_true",
+                    help="section 10 too: its operators and solver iteration in the timing's windows, and the rendered study from the "
+                         "deflections themselves next to the two-step one")
     ap.add_argument("--compare-library", default=None,
                     help="a second build of the library whose adjoint is timed in alternation with this one's and checked against it, "
                          "e.g. the one-atomic-per-tap form: python tools/build_variant.py tomo_plain -DPHOTON_TOMO_MERGE_LANES=0")
@@ -256,9 +317,9 @@ def main():
     other = PhotonLibrary(a.compare_library, build=False) if a.compare_library else None
     if not a.skip_timing:
         for n in (int(v) for v in a.sizes.split(",")):
-            print(json.dumps(operator_timing(lib, n, a.rays_side, other)), flush=True)
+            print(json.dumps(operator_timing(lib, n, a.rays_side, other, a.deflections)), flush=True)
     if not a.skip_study:
-        for row in rendered_study(lib, [float(v) for v in a.lams.split(",")]):
+        for row in rendered_study(lib, [float(v) for v in a.lams.split(",")], deflections=a.deflections):
             print(json.dumps(row), flush=True)
 
 
