@@ -1,7 +1,8 @@
 // fixed_sum.hpp - dot products whose bits depend on the grid size alone: what the iterative solvers (photon_density.hip,
 // photon_tomo.hip) share.  A launch of at most kMaxBlocks blocks of kThreads threads strides over the elements; every block
 // leaves one partial (block_sum), and whoever needs the total sums the partial array itself (sum_parts): every block of
-// every later launch holds the same bits, so a scalar such as CG's alpha never has to leave the device.
+// every later launch holds the same bits, so a scalar such as CG's alpha never has to leave the device.  The host's look at
+// a total (the residual, every few iterations) is read_sum.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -28,6 +29,22 @@ __device__ __forceinline__ double sum_parts(const double *__restrict__ part, int
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += kThreads) s += part[i];
     return block_sum(s, red);
+}
+
+// the same total for the host's check: one block.  Internal linkage: every unit that includes this has its own.
+static __global__ __launch_bounds__(kThreads) void sum_parts_kernel(const double *__restrict__ part, int n_parts,
+                                                                    double *__restrict__ out) {
+    __shared__ double red[kThreads / 64];
+    const double s = sum_parts(part, n_parts, red);
+    if (threadIdx.x == 0) *out = s;
+}
+
+// *out = the sum of part[0 .. n_parts) by way of the device scalar d_scalar; synchronises the stream
+static inline hipError_t read_sum(const double *part, int n_parts, double *d_scalar, double *out, hipStream_t stream) {
+    hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(kThreads), 0, stream, part, n_parts, d_scalar);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out, d_scalar, sizeof(double), hipMemcpyDeviceToHost, stream);
+    return e == hipSuccess ? hipStreamSynchronize(stream) : e;
 }
 
 }  // namespace photon

@@ -208,13 +208,6 @@ __global__ __launch_bounds__(kThreads) void pcg_update_kernel(unsigned N, const 
     }
 }
 
-// ||r||^2 for the host's check: one block
-__global__ __launch_bounds__(kThreads) void sum_parts_kernel(const double *__restrict__ part, int n_parts, double *__restrict__ out) {
-    __shared__ double red[kThreads / 64];
-    const double s = sum_parts(part, n_parts, red);
-    if (threadIdx.x == 0) *out = s;
-}
-
 // phi: fixed nodes their value, solved nodes x (already in place), every other node NaN
 __global__ __launch_bounds__(kThreads) void finalize_kernel(unsigned N, const unsigned char *__restrict__ mask,
                                                             const double *__restrict__ value, double *__restrict__ phi) {
@@ -254,12 +247,6 @@ std::pair<long long, long long> reachability(std::vector<unsigned char> &mask, i
     return {unknowns, unreachable};
 }
 
-int read_scalar(const double *d, double *h, hipStream_t stream) {
-    PH_CHECK(hipMemcpyAsync(h, d, sizeof(double), hipMemcpyDeviceToHost, stream));
-    PH_CHECK(hipStreamSynchronize(stream));
-    return 0;
-}
-
 // the device work vectors of one call (N values each; parts: 4 kMaxBlocks + 1)
 struct Work {
     double *wh, *wv, *diag, *r, *z, *p0, *p1, *q, *parts;
@@ -285,9 +272,8 @@ int solve(hipStream_t stream, unsigned N, int blocks, int nx, int ny, double hx,
                        rz_part[0], rr_part);
     PH_CHECK(hipGetLastError());
     auto residual_sq = [&](double *out) -> int {
-        hipLaunchKernelGGL(sum_parts_kernel, dim3(1), dim3(kThreads), 0, stream, rr_part, blocks, d_scalar);
-        PH_CHECK(hipGetLastError());
-        return read_scalar(d_scalar, out, stream);
+        PH_CHECK(read_sum(rr_part, blocks, d_scalar, out, stream));
+        return 0;
     };
     double rr = 0.0;
     if (int e = residual_sq(&rr)) return e;

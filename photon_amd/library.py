@@ -123,6 +123,12 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _on_device(a, dtype, dev):
+    """a (a numpy array or a torch tensor; None stays None) as a contiguous torch tensor of `dtype` on `dev`."""
+    import torch
+    return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
+
+
 def _one_hip_runtime_per_process():
     """PyTorch-ROCm bundles its own libamdhip64; the library's RUNPATH names the system's.  A process that ends up with
     both mapped has two HIP runtimes, and whichever touches the GPU second finds no device (seen both ways round on
@@ -671,16 +677,12 @@ class PhotonLibrary:
         import torch
         from . import bos_density
         dev = torch.device("cuda", torch.cuda.current_device())
-
-        def on_device(a, dtype):
-            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
-
-        tgx, tgy = on_device(gx, torch.float64), on_device(gy, torch.float64)
+        tgx, tgy = _on_device(gx, torch.float64, dev), _on_device(gy, torch.float64, dev)
         if tgx.dim() != 2 or tgx.shape != tgy.shape:
             raise ValueError("gx and gy must be two 2-d arrays of one shape")
         ny, nx = tgx.shape
-        tw, tv = on_device(w, torch.float64), on_device(value, torch.float64)
-        tf = None if fixed is None else on_device(torch.as_tensor(fixed) != 0, torch.uint8)
+        tw, tv = _on_device(w, torch.float64, dev), _on_device(value, torch.float64, dev)
+        tf = None if fixed is None else _on_device(torch.as_tensor(fixed) != 0, torch.uint8, dev)
         for name, t in (("w", tw), ("fixed", tf), ("value", tv)):
             if t is not None and t.shape != tgx.shape:
                 raise ValueError(f"{name} must have the shape of gx, {tuple(tgx.shape)}")
@@ -719,21 +721,52 @@ class PhotonLibrary:
                                               self._vp(d_dirs_ptr), int(n_rays), self._vp(d_v_ptr), self._vp(stream))
         self._check(rc, "photon_tomo_backproject")
 
+    def _tomo_solve_ptr(self, entry: str, d_data_ptrs, dims, spacing, origin, d_ray_ptrs, n_rays, d_f_ptr, d_w_ptr, d_support_ptr, lam, tol,
+                        max_iter, stream) -> dict:
+        """photon_tomo_reconstruct or photon_tomo_reconstruct_deflections (`entry`) on raw pointers: d_data_ptrs the data
+        over the rays (p, or g1 and g2), d_ray_ptrs origins and dirs (and t1, t2)."""
+        from .tomography import DEFAULT_MAX_ITER
+        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        st = photon_tomo_stats_t()
+        rc = getattr(self.lib, entry)(*(self._vp(d) for d in d_data_ptrs), self._vp(d_w_ptr), self._vp(d_support_ptr), nx, ny, nz, _ptr(sp),
+                                      _ptr(og), *(self._vp(d) for d in d_ray_ptrs), int(n_rays), float(lam), float(tol),
+                                      DEFAULT_MAX_ITER if max_iter is None else int(max_iter), self._vp(d_f_ptr), ctypes.byref(st),
+                                      self._vp(stream))
+        self._check(rc, entry)
+        return st.as_dict()
+
+    def _tomo_solve(self, entry: str, data, names: str, dims, spacing, origin, rays, ray_names: str, w, support, lam, tol, max_iter):
+        """tomo_reconstruct and tomo_reconstruct_deflections: `data` the arrays over the rays (p, or g1 and g2), `rays` those
+        of three values per ray (origins and dirs, and t1, t2); the names are the message's."""
+        import torch
+        from . import tomography
+        dev = torch.device("cuda", torch.cuda.current_device())
+        nx, ny, nz = (int(n) for n in dims)
+        rays = [_on_device(a, torch.float64, dev).reshape(-1, 3) for a in rays]
+        data = [_on_device(a, torch.float64, dev).reshape(-1) for a in data]
+        tw = _on_device(w, torch.float64, dev)
+        n_rays = data[0].numel()
+        if any(a.shape != (n_rays, 3) for a in rays) or any(a.numel() != n_rays for a in data) or (tw is not None and tw.numel() != n_rays):
+            raise ValueError(f"{names} and w hold one value per ray, {ray_names} three")
+        ts = None if support is None else _on_device(torch.as_tensor(support) != 0, torch.uint8, dev)
+        if ts is not None and tuple(ts.shape) != (nz, ny, nx):
+            raise ValueError(f"support must be [nz, ny, nx] = {(nz, ny, nx)}")
+        max_iter = tomography.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
+        tomography.check_arguments(dims, np.broadcast_to(np.asarray(spacing, np.float64), (3,)), origin, n_rays, lam, tol, max_iter)
+        f = torch.empty((nz, ny, nx), dtype=torch.float64, device=dev)
+        stats = self._tomo_solve_ptr(entry, [a.data_ptr() for a in data], dims, spacing, origin, [a.data_ptr() for a in rays], n_rays,
+                                     f.data_ptr(), tw.data_ptr() if tw is not None else 0, ts.data_ptr() if ts is not None else 0, lam, tol,
+                                     max_iter, torch.cuda.current_stream(dev).cuda_stream)
+        return f.cpu().numpy(), stats
+
     def tomo_reconstruct_ptr(self, d_p_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, n_rays: int, d_f_ptr: int,
                              d_w_ptr: int = 0, d_support_ptr: int = 0, lam: float = 1.0, tol: float = 1e-6,
                              max_iter: Optional[int] = None, stream: int = 0) -> dict:
         """Solve for the device f64 field at d_f_ptr [nz, ny, nx] from the projections at d_p_ptr (raw pointers: f64 p, w,
         origins, dirs; u8 support; 0 = NULL).  Returns the stats as a dict; the call has synchronised `stream`.  max_iter
         None = tomography.DEFAULT_MAX_ITER."""
-        from .tomography import DEFAULT_MAX_ITER
-        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
-        st = photon_tomo_stats_t()
-        rc = self.lib.photon_tomo_reconstruct(self._vp(d_p_ptr), self._vp(d_w_ptr), self._vp(d_support_ptr), nx, ny, nz, _ptr(sp),
-                                              _ptr(og), self._vp(d_origins_ptr), self._vp(d_dirs_ptr), int(n_rays), float(lam),
-                                              float(tol), DEFAULT_MAX_ITER if max_iter is None else int(max_iter),
-                                              self._vp(d_f_ptr), ctypes.byref(st), self._vp(stream))
-        self._check(rc, "photon_tomo_reconstruct")
-        return st.as_dict()
+        return self._tomo_solve_ptr("photon_tomo_reconstruct", (d_p_ptr,), dims, spacing, origin, (d_origins_ptr, d_dirs_ptr), n_rays,
+                                    d_f_ptr, d_w_ptr, d_support_ptr, lam, tol, max_iter, stream)
 
     def tomo_reconstruct(self, p, dims, spacing, origin, origins, dirs, w=None, support=None, lam: float = 1.0, tol: float = 1e-6,
                          max_iter: Optional[int] = None):
@@ -742,29 +775,8 @@ class PhotonLibrary:
         microns, support [nz, ny, nx] (None = every voxel), lam the dimensionless smoothness weight.  Returns (f numpy f64
         [nz, ny, nx], stats dict).  The definition: include/parallel_ray_tracing.h, section 9 (photon_amd.tomography: host
         model, and view_rays / grid_of for the geometry)."""
-        import torch
-        from . import tomography
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-        def on_device(a, dtype):
-            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
-
-        nx, ny, nz = (int(n) for n in dims)
-        to, td = on_device(origins, torch.float64).reshape(-1, 3), on_device(dirs, torch.float64).reshape(-1, 3)
-        tp, tw = on_device(p, torch.float64).reshape(-1), on_device(w, torch.float64)
-        n_rays = tp.numel()
-        if to.shape != (n_rays, 3) or td.shape != (n_rays, 3) or (tw is not None and tw.numel() != n_rays):
-            raise ValueError("p and w hold one value per ray, origins and dirs three")
-        ts = None if support is None else on_device(torch.as_tensor(support) != 0, torch.uint8)
-        if ts is not None and tuple(ts.shape) != (nz, ny, nx):
-            raise ValueError(f"support must be [nz, ny, nx] = {(nz, ny, nx)}")
-        max_iter = tomography.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
-        tomography.check_arguments(dims, np.broadcast_to(np.asarray(spacing, np.float64), (3,)), origin, n_rays, lam, tol, max_iter)
-        f = torch.empty((nz, ny, nx), dtype=torch.float64, device=dev)
-        stats = self.tomo_reconstruct_ptr(tp.data_ptr(), dims, spacing, origin, to.data_ptr(), td.data_ptr(), n_rays, f.data_ptr(),
-                                          tw.data_ptr() if tw is not None else 0, ts.data_ptr() if ts is not None else 0, lam, tol,
-                                          max_iter, stream=torch.cuda.current_stream(dev).cuda_stream)
-        return f.cpu().numpy(), stats
+        return self._tomo_solve("photon_tomo_reconstruct", (p,), "p", dims, spacing, origin, (origins, dirs), "origins and dirs", w, support,
+                                lam, tol, max_iter)
 
     # ---- tomography from deflections (include/parallel_ray_tracing.h, section 10) -------------------------------------
     def tomo_deflect(self, d_f_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, d_t1_ptr: int, d_t2_ptr: int,
@@ -794,15 +806,9 @@ class PhotonLibrary:
         """Solve for the device f64 field at d_f_ptr [nz, ny, nx] from the deflections at d_g1_ptr, d_g2_ptr (raw pointers:
         f64 g1, g2, w, origins, dirs, t1, t2; u8 support; 0 = NULL).  Returns the stats as a dict; the call has synchronised
         `stream`.  max_iter None = tomography.DEFAULT_MAX_ITER."""
-        from .tomography import DEFAULT_MAX_ITER
-        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
-        st = photon_tomo_stats_t()
-        rc = self.lib.photon_tomo_reconstruct_deflections(
-            self._vp(d_g1_ptr), self._vp(d_g2_ptr), self._vp(d_w_ptr), self._vp(d_support_ptr), nx, ny, nz, _ptr(sp), _ptr(og),
-            self._vp(d_origins_ptr), self._vp(d_dirs_ptr), self._vp(d_t1_ptr), self._vp(d_t2_ptr), int(n_rays), float(lam), float(tol),
-            DEFAULT_MAX_ITER if max_iter is None else int(max_iter), self._vp(d_f_ptr), ctypes.byref(st), self._vp(stream))
-        self._check(rc, "photon_tomo_reconstruct_deflections")
-        return st.as_dict()
+        return self._tomo_solve_ptr("photon_tomo_reconstruct_deflections", (d_g1_ptr, d_g2_ptr), dims, spacing, origin,
+                                    (d_origins_ptr, d_dirs_ptr, d_t1_ptr, d_t2_ptr), n_rays, d_f_ptr, d_w_ptr, d_support_ptr, lam, tol,
+                                    max_iter, stream)
 
     def tomo_reconstruct_deflections(self, g1, g2, dims, spacing, origin, origins, dirs, t1, t2, w=None, support=None, lam: float = 1.0,
                                      tol: float = 1e-6, max_iter: Optional[int] = None):
@@ -812,30 +818,8 @@ class PhotonLibrary:
         = every voxel: the mean of f is then 0), lam the dimensionless smoothness weight.  Returns (f numpy f64 [nz, ny,
         nx], stats dict).  The definition: include/parallel_ray_tracing.h, section 10 (photon_amd.tomography: host model,
         and view_rays / view_frames / grid_of for the geometry)."""
-        import torch
-        from . import tomography
-        dev = torch.device("cuda", torch.cuda.current_device())
-
-        def on_device(a, dtype):
-            return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
-
-        nx, ny, nz = (int(n) for n in dims)
-        rays = [on_device(a, torch.float64).reshape(-1, 3) for a in (origins, dirs, t1, t2)]
-        tg1, tg2, tw = on_device(g1, torch.float64).reshape(-1), on_device(g2, torch.float64).reshape(-1), on_device(w, torch.float64)
-        n_rays = tg1.numel()
-        if any(a.shape != (n_rays, 3) for a in rays) or tg2.numel() != n_rays or (tw is not None and tw.numel() != n_rays):
-            raise ValueError("g1, g2 and w hold one value per ray, origins, dirs, t1 and t2 three")
-        ts = None if support is None else on_device(torch.as_tensor(support) != 0, torch.uint8)
-        if ts is not None and tuple(ts.shape) != (nz, ny, nx):
-            raise ValueError(f"support must be [nz, ny, nx] = {(nz, ny, nx)}")
-        max_iter = tomography.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
-        tomography.check_arguments(dims, np.broadcast_to(np.asarray(spacing, np.float64), (3,)), origin, n_rays, lam, tol, max_iter)
-        f = torch.empty((nz, ny, nx), dtype=torch.float64, device=dev)
-        stats = self.tomo_reconstruct_deflections_ptr(
-            tg1.data_ptr(), tg2.data_ptr(), dims, spacing, origin, rays[0].data_ptr(), rays[1].data_ptr(), rays[2].data_ptr(),
-            rays[3].data_ptr(), n_rays, f.data_ptr(), tw.data_ptr() if tw is not None else 0, ts.data_ptr() if ts is not None else 0,
-            lam, tol, max_iter, stream=torch.cuda.current_stream(dev).cuda_stream)
-        return f.cpu().numpy(), stats
+        return self._tomo_solve("photon_tomo_reconstruct_deflections", (g1, g2), "g1, g2", dims, spacing, origin, (origins, dirs, t1, t2),
+                                "origins, dirs, t1 and t2", w, support, lam, tol, max_iter)
 
     # ---- volumes ------------------------------------------------------------------------------
     def volume_load_nrrd(self, path: str, interpolation: int = 1) -> "Volume":

@@ -66,14 +66,18 @@ def _rays(origins, dirs):
 
 
 class Taps(NamedTuple):
-    """Every tap of a set of rays through a grid: tap i adds weight[i] * f[voxel[i]] to ray[i].  The taps of one ray follow
-    each other in the order of the definition (planes ascending, four taps per plane); planes[r] is the number of counted
-    planes of ray r."""
+    """Every tap of a set of rays through a grid, for an operator of K = len(weights) components per ray (section 9's
+    projector: 1; section 10's pair: 2): tap i adds weights[k][i] * f[voxel[i]] to component k of ray[i].  The taps of one
+    ray follow each other in the order of the definition (planes ascending, four taps per plane); planes[r] is the number
+    of counted planes of ray r."""
     ray: np.ndarray
     voxel: np.ndarray
-    weight: np.ndarray
+    weights: tuple
     planes: np.ndarray
     n_voxels: int
+
+
+DeflectionTaps = Taps           # the name section 10's taps had as a type of their own: kept for callers' annotations
 
 
 def _walk(dims, spacing, origin, o, d, frames=()):
@@ -125,34 +129,36 @@ def _walk(dims, spacing, origin, o, d, frames=()):
             yield r, voxels, fb, fc, hb, hc, s, [(pu[ok], pv[ok]) for pu, pv in rates]
 
 
-def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
-    """The taps of section 9's projector, every step the definition's f64 operation."""
+def _taps(dims, spacing, origin, origins, dirs, frames=None) -> Taps:
+    """The taps of section 9's projector (frames None) or of section 10's D_t1 and D_t2 (frames = (t1, t2)), every step the
+    definition's f64 operation."""
     o, d = _rays(origins, dirs)
     check_arguments(dims, spacing, origin, o.shape[0])
+    if frames is not None:
+        frames = _frames(*frames, o.shape[0])
     n = tuple(int(v) for v in dims)
-    rays, voxels, weights = [], [], []
+    rays, voxels = [], []
+    weights = tuple([] for _ in (frames or (None,)))
     planes = np.zeros(o.shape[0], np.int64)
-    for r, vox, fb, fc, hb, hc, s, _ in _walk(dims, spacing, origin, o, d):
+    for r, vox, fb, fc, gb, gc, s, rates in _walk(dims, spacing, origin, o, d, frames=frames or ()):
         voxels.append(vox)
-        weights.append(np.stack([(hb * hc) * s, (fb * hc) * s, (hb * fc) * s, (fb * fc) * s], axis=1))
         rays.append(np.repeat(r, 4).reshape(-1, 4))
         planes[r] += 1
+        if frames is None:
+            weights[0].append(np.stack([(gb * gc) * s, (fb * gc) * s, (gb * fc) * s, (fb * fc) * s], axis=1))
+        for out, (pu, pv) in zip(weights, rates):
+            gcu, gbv, fcu, fbv = gc * pu, gb * pv, fc * pu, fb * pv
+            out.append(np.stack([-gcu - gbv, gcu - fbv, gbv - fcu, fcu + fbv], axis=1))
     if not rays:
         empty = np.zeros(0, np.int64)
-        return Taps(empty, empty, np.zeros(0), planes, n[0] * n[1] * n[2])
-    return Taps(np.concatenate(rays).ravel(), np.concatenate(voxels).ravel(), np.concatenate(weights).ravel(), planes,
-                n[0] * n[1] * n[2])
+        return Taps(empty, empty, tuple(np.zeros(0) for _ in weights), planes, n[0] * n[1] * n[2])
+    return Taps(np.concatenate(rays).ravel(), np.concatenate(voxels).ravel(), tuple(np.concatenate(w).ravel() for w in weights),
+                planes, n[0] * n[1] * n[2])
 
 
-class DeflectionTaps(NamedTuple):
-    """Every tap of section 10's operator pair: tap i adds weight1[i] * f[voxel[i]] to g1[ray[i]] and weight2[i] *
-    f[voxel[i]] to g2[ray[i]].  Order and planes as in Taps."""
-    ray: np.ndarray
-    voxel: np.ndarray
-    weight1: np.ndarray
-    weight2: np.ndarray
-    planes: np.ndarray
-    n_voxels: int
+def ray_taps(dims, spacing, origin, origins, dirs) -> Taps:
+    """The taps of section 9's projector, every step the definition's f64 operation."""
+    return _taps(dims, spacing, origin, origins, dirs)
 
 
 def _frames(t1, t2, n_rays):
@@ -164,56 +170,52 @@ def _frames(t1, t2, n_rays):
     return t1, t2
 
 
-def deflection_taps(dims, spacing, origin, origins, dirs, t1, t2) -> DeflectionTaps:
+def deflection_taps(dims, spacing, origin, origins, dirs, t1, t2) -> Taps:
     """The taps of section 10's D_t1 and D_t2 (the derivative of section 9's projector under a parallel shift of the ray
     along t1, t2 [n_rays, 3]), every step the definition's f64 operation."""
-    o, d = _rays(origins, dirs)
-    check_arguments(dims, spacing, origin, o.shape[0])
-    t1, t2 = _frames(t1, t2, o.shape[0])
-    n = tuple(int(v) for v in dims)
-    rays, voxels, weights = [], [], ([], [])
-    planes = np.zeros(o.shape[0], np.int64)
-    for r, vox, fb, fc, gb, gc, _, rates in _walk(dims, spacing, origin, o, d, frames=(t1, t2)):
-        voxels.append(vox)
-        rays.append(np.repeat(r, 4).reshape(-1, 4))
-        planes[r] += 1
-        for out, (pu, pv) in zip(weights, rates):
-            gcu, gbv, fcu, fbv = gc * pu, gb * pv, fc * pu, fb * pv
-            out.append(np.stack([-gcu - gbv, gcu - fbv, gbv - fcu, fcu + fbv], axis=1))
-    if not rays:
-        empty = np.zeros(0, np.int64)
-        return DeflectionTaps(empty, empty, np.zeros(0), np.zeros(0), planes, n[0] * n[1] * n[2])
-    return DeflectionTaps(np.concatenate(rays).ravel(), np.concatenate(voxels).ravel(), np.concatenate(weights[0]).ravel(),
-                          np.concatenate(weights[1]).ravel(), planes, n[0] * n[1] * n[2])
+    return _taps(dims, spacing, origin, origins, dirs, frames=(t1, t2))
 
 
-def _apply(taps: Taps, f: np.ndarray) -> np.ndarray:
-    return np.bincount(taps.ray, taps.weight * f[taps.voxel], minlength=taps.planes.size)
+def _forward(taps: Taps, f: np.ndarray) -> tuple:
+    """Op f over the voxels: one array over the rays per component."""
+    return tuple(np.bincount(taps.ray, w * f[taps.voxel], minlength=taps.planes.size) for w in taps.weights)
 
 
-def _adjoint(taps: Taps, y: np.ndarray) -> np.ndarray:
-    return np.bincount(taps.voxel, taps.weight * y[taps.ray], minlength=taps.n_voxels)
+def _adjoint(taps: Taps, ys) -> np.ndarray:
+    """Op^T ys over the voxels, one value per tap: w_1 y_1 (+ w_2 y_2)."""
+    value = taps.weights[0] * ys[0][taps.ray]
+    for w, y in zip(taps.weights[1:], ys[1:]):
+        value = value + w * y[taps.ray]
+    return np.bincount(taps.voxel, value, minlength=taps.n_voxels)
+
+
+def _field(f):
+    f = np.asarray(f, np.float64)
+    if f.ndim != 3:
+        raise ValueError("f must be [nz, ny, nx]")
+    return f
+
+
+def _adjoint_model(ys, dims, v, taps):
+    nx, ny, nz = (int(n) for n in dims)
+    out = _adjoint(taps, [np.asarray(y, np.float64).ravel() for y in ys]).reshape(nz, ny, nx)
+    return out if v is None else np.asarray(v, np.float64).reshape(nz, ny, nx) + out
 
 
 def project_model(f, spacing, origin, origins, dirs, taps: Optional[Taps] = None) -> np.ndarray:
     """Host model of photon_tomo_project: P = A f, f [nz, ny, nx].  taps: ray_taps of the same grid and rays, when the
     caller has them."""
-    f = np.asarray(f, np.float64)
-    if f.ndim != 3:
-        raise ValueError("f must be [nz, ny, nx]")
+    f = _field(f)
     if taps is None:
         taps = ray_taps(f.shape[::-1], spacing, origin, origins, dirs)
-    return _apply(taps, f.ravel())
+    return _forward(taps, f.ravel())[0]
 
 
 def backproject_model(y, dims, spacing, origin, origins, dirs, v=None, taps: Optional[Taps] = None) -> np.ndarray:
     """Host model of photon_tomo_backproject: v + A^T y as a new array [nz, ny, nx] (v None = 0)."""
-    y = np.asarray(y, np.float64).ravel()
     if taps is None:
         taps = ray_taps(dims, spacing, origin, origins, dirs)
-    nx, ny, nz = (int(n) for n in dims)
-    out = _adjoint(taps, y).reshape(nz, ny, nx)
-    return out if v is None else np.asarray(v, np.float64).reshape(nz, ny, nx) + out
+    return _adjoint_model((y,), dims, v, taps)
 
 
 def graph_laplacian(q: np.ndarray) -> np.ndarray:
@@ -270,6 +272,29 @@ def _support(support, dims):
     return m
 
 
+def _reconstruct(data, names, dims, w, support, reg, tol, max_iter, taps: Taps):
+    """The solver of sections 9 and 10 on the taps of either: data the K arrays over the rays (`names` for the message), reg
+    the weight of G^T G."""
+    nx, ny, nz = (int(n) for n in dims)
+    data = [np.asarray(a, np.float64).ravel() for a in data]
+    w = np.ones_like(data[0]) if w is None else np.asarray(w, np.float64).ravel()
+    if any(a.shape != taps.planes.shape for a in data + [w]):
+        raise ValueError(f"{names} and w must hold one value per ray")
+    m = _support(support, dims)
+    with np.errstate(invalid="ignore"):
+        ok = np.isfinite(w) & (w > 0)
+        for a in data:
+            ok = ok & np.isfinite(a)
+    weight = np.where(ok, w, 0.0)
+    wdata = [np.where(ok, w * np.where(ok, a, 0.0), 0.0) for a in data]
+
+    def normal(q):
+        return _adjoint(taps, [np.where(weight > 0, weight * a, 0.0) for a in _forward(taps, q)])
+
+    x, it, rho, bnorm = _conjugate_gradients(normal, np.where(m, _adjoint(taps, wdata), 0.0), m, reg, (nz, ny, nx), tol, max_iter)
+    return x.reshape(nz, ny, nx), _stats(it, rho, bnorm, tol, m, (weight > 0) & (taps.planes > 0))
+
+
 def reconstruct_model(p, dims, spacing, origin, origins, dirs, w=None, support=None, lam: float = 1.0, tol: float = 1e-6,
                       max_iter: int = DEFAULT_MAX_ITER, taps: Optional[Taps] = None):
     """Host model of photon_tomo_reconstruct (section 9: the same iteration and check cadence).  p, w [n_rays] (w None =
@@ -277,90 +302,40 @@ def reconstruct_model(p, dims, spacing, origin, origins, dirs, w=None, support=N
     rays_used, residual)."""
     o, d = _rays(origins, dirs)
     check_arguments(dims, spacing, origin, o.shape[0], lam, tol, max_iter)
-    nx, ny, nz = (int(n) for n in dims)
-    p = np.asarray(p, np.float64).ravel()
-    w = np.ones_like(p) if w is None else np.asarray(w, np.float64).ravel()
-    if p.shape != (o.shape[0],) or w.shape != p.shape:
-        raise ValueError("p and w must hold one value per ray")
-    m = _support(support, dims)
     if taps is None:
         taps = ray_taps(dims, spacing, origin, o, d)
-    with np.errstate(invalid="ignore"):
-        ok = np.isfinite(p) & np.isfinite(w) & (w > 0)
-    weight = np.where(ok, w, 0.0)
-    wp = np.where(ok, w * np.where(ok, p, 0.0), 0.0)
     h = float(np.min(np.asarray(spacing, np.float64)))
-    lam_h2 = float(lam) * (h * h)
-
-    def normal(q):
-        return _adjoint(taps, np.where(weight > 0, weight * _apply(taps, q), 0.0))
-
-    x, it, rho, bnorm = _conjugate_gradients(normal, np.where(m, _adjoint(taps, wp), 0.0), m, lam_h2, (nz, ny, nx), tol, max_iter)
-    return x.reshape(nz, ny, nx), _stats(it, rho, bnorm, tol, m, (weight > 0) & (taps.planes > 0))
+    return _reconstruct((p,), "p", dims, w, support, float(lam) * (h * h), tol, max_iter, taps)
 
 
 # ---- section 10: the operator pair of the deflections -----------------------------------------------------------------------
-def _deflect(taps: DeflectionTaps, f: np.ndarray):
-    n = taps.planes.size
-    return (np.bincount(taps.ray, taps.weight1 * f[taps.voxel], minlength=n),
-            np.bincount(taps.ray, taps.weight2 * f[taps.voxel], minlength=n))
-
-
-def _deflect_adjoint(taps: DeflectionTaps, y1: np.ndarray, y2: np.ndarray) -> np.ndarray:
-    return np.bincount(taps.voxel, taps.weight1 * y1[taps.ray] + taps.weight2 * y2[taps.ray], minlength=taps.n_voxels)
-
-
-def deflect_model(f, spacing, origin, origins, dirs, t1, t2, taps: Optional[DeflectionTaps] = None):
+def deflect_model(f, spacing, origin, origins, dirs, t1, t2, taps: Optional[Taps] = None):
     """Host model of photon_tomo_deflect: (g1, g2) = (D_t1 f, D_t2 f), f [nz, ny, nx].  taps: deflection_taps of the same
     grid, rays and vectors, when the caller has them."""
-    f = np.asarray(f, np.float64)
-    if f.ndim != 3:
-        raise ValueError("f must be [nz, ny, nx]")
+    f = _field(f)
     if taps is None:
         taps = deflection_taps(f.shape[::-1], spacing, origin, origins, dirs, t1, t2)
-    return _deflect(taps, f.ravel())
+    return _forward(taps, f.ravel())
 
 
-def deflect_adjoint_model(y1, y2, dims, spacing, origin, origins, dirs, t1, t2, v=None,
-                          taps: Optional[DeflectionTaps] = None) -> np.ndarray:
+def deflect_adjoint_model(y1, y2, dims, spacing, origin, origins, dirs, t1, t2, v=None, taps: Optional[Taps] = None) -> np.ndarray:
     """Host model of photon_tomo_deflect_adjoint: v + D_t1^T y1 + D_t2^T y2 as a new array [nz, ny, nx] (v None = 0)."""
-    y1, y2 = np.asarray(y1, np.float64).ravel(), np.asarray(y2, np.float64).ravel()
     if taps is None:
         taps = deflection_taps(dims, spacing, origin, origins, dirs, t1, t2)
-    nx, ny, nz = (int(n) for n in dims)
-    out = _deflect_adjoint(taps, y1, y2).reshape(nz, ny, nx)
-    return out if v is None else np.asarray(v, np.float64).reshape(nz, ny, nx) + out
+    return _adjoint_model((y1, y2), dims, v, taps)
 
 
 def reconstruct_deflections_model(g1, g2, dims, spacing, origin, origins, dirs, t1, t2, w=None, support=None, lam: float = 1.0,
-                                  tol: float = 1e-6, max_iter: int = DEFAULT_MAX_ITER, taps: Optional[DeflectionTaps] = None):
+                                  tol: float = 1e-6, max_iter: int = DEFAULT_MAX_ITER, taps: Optional[Taps] = None):
     """Host model of photon_tomo_reconstruct_deflections (section 10: section 9's iteration on the operator pair, lam on
     G^T G without h^2).  g1, g2, w [n_rays] (w None = 1); support [nz, ny, nx] (None = every voxel: the solution has zero
     mean).  Returns (f [nz, ny, nx], stats dict) as reconstruct_model does."""
     o, d = _rays(origins, dirs)
     check_arguments(dims, spacing, origin, o.shape[0], lam, tol, max_iter)
     t1, t2 = _frames(t1, t2, o.shape[0])
-    nx, ny, nz = (int(n) for n in dims)
-    g1, g2 = np.asarray(g1, np.float64).ravel(), np.asarray(g2, np.float64).ravel()
-    w = np.ones_like(g1) if w is None else np.asarray(w, np.float64).ravel()
-    if g1.shape != (o.shape[0],) or g2.shape != g1.shape or w.shape != g1.shape:
-        raise ValueError("g1, g2 and w must hold one value per ray")
-    m = _support(support, dims)
     if taps is None:
         taps = deflection_taps(dims, spacing, origin, o, d, t1, t2)
-    with np.errstate(invalid="ignore"):
-        ok = np.isfinite(g1) & np.isfinite(g2) & np.isfinite(w) & (w > 0)
-    weight = np.where(ok, w, 0.0)
-    wg1 = np.where(ok, w * np.where(ok, g1, 0.0), 0.0)
-    wg2 = np.where(ok, w * np.where(ok, g2, 0.0), 0.0)
-
-    def normal(q):
-        a1, a2 = _deflect(taps, q)
-        return _deflect_adjoint(taps, np.where(weight > 0, weight * a1, 0.0), np.where(weight > 0, weight * a2, 0.0))
-
-    x, it, rho, bnorm = _conjugate_gradients(normal, np.where(m, _deflect_adjoint(taps, wg1, wg2), 0.0), m, float(lam), (nz, ny, nx),
-                                             tol, max_iter)
-    return x.reshape(nz, ny, nx), _stats(it, rho, bnorm, tol, m, (weight > 0) & (taps.planes > 0))
+    return _reconstruct((g1, g2), "g1, g2", dims, w, support, float(lam), tol, max_iter, taps)
 
 
 # ---- geometry ------------------------------------------------------------------------------------------------------------

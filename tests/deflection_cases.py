@@ -25,7 +25,7 @@ class DeflectionCase:
         self.rays = (self.origins, self.dirs, self.t1, self.t2)
 
     @functools.cached_property
-    def taps(self) -> tm.DeflectionTaps:
+    def taps(self) -> tm.Taps:
         return tm.deflection_taps(*self.grid, *self.rays)
 
 

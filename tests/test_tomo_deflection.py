@@ -24,12 +24,12 @@ def test_taps_are_the_projectors_and_sum_to_zero_per_ray(name):
     assert (t.planes == np.where(hit, base.planes, 0)).all()
     keep = hit[base.ray]
     assert (t.ray == base.ray[keep]).all() and (t.voxel == base.voxel[keep]).all()
-    for w in (t.weight1, t.weight2):
+    for w in (t.weights[0], t.weights[1]):
         total = np.abs(np.bincount(t.ray, w, minlength=c.n_rays)).max() / np.abs(w).max()
         print(f"{name}: largest per-ray sum of weights / max |weight| = {total:.1e}")
         assert total <= 1e-12                                   # D annihilates constants (3e-15 measured)
     g1, g2 = tm.deflect_model(np.full(c.shape, 3.25), c.spacing, c.origin, *c.rays, taps=c.taps)
-    assert max(np.abs(g1).max(), np.abs(g2).max()) <= 1e-11 * 3.25 * np.abs(t.weight1).max()
+    assert max(np.abs(g1).max(), np.abs(g2).max()) <= 1e-11 * 3.25 * np.abs(t.weights[0]).max()
 
 
 @pytest.mark.parametrize("name", ["random", "views"])

@@ -17,7 +17,7 @@ def test_random_rays_all_hit():
     assert (planes > 0).all()
     assert 4 * int(planes.sum()) == 22168
     assert c.taps.voxel.min() >= 0 and c.taps.voxel.max() < c.taps.n_voxels
-    assert (c.taps.weight >= 0).all()
+    assert (c.taps.weights[0] >= 0).all()
 
 
 def test_hand_made_rays():
@@ -34,7 +34,7 @@ def test_hand_made_rays():
     assert planes[k] == c.dims[0]
     sel = c.taps.ray == k
     j = (c.taps.voxel[sel] // c.dims[0]) % c.dims[1]
-    assert (c.taps.weight[sel][j != c.dims[1] - 1] == 0).all() and (c.taps.weight[sel][j == c.dims[1] - 1] > 0).any()
+    assert (c.taps.weights[0][sel][j != c.dims[1] - 1] == 0).all() and (c.taps.weights[0][sel][j == c.dims[1] - 1] > 0).any()
     # the tie |d_x| = |d_y| walks the x planes (10 of them lie inside; the y planes would give 8)
     assert planes[tc.edge_ray("tie_xy")] == 10
     # the body diagonal is steepest along z (11 000 um against 8400 and 7200): it enters and leaves through corners and

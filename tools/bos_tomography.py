@@ -3,7 +3,8 @@
 1. timing of photon_tomo_project, photon_tomo_backproject and one solver iteration at 128^3 and 256^3 voxels with
    8 x 512^2 rays (the rotated views of tests/tomography_cases.py at that size): ms per call from device events around
    five windows of about a quarter of a second each (median, smallest and largest), the shader clock read from hwmon while
-   they run, with --compare-library a second build's adjoint in alternating windows, taps per second (the taps counted by
+   they run, with --compare-library a second build's operators in the same alternating windows and its solver iterations
+   in alternating pairs ("this_over_other": the ratio of the medians per quantity), taps per second (the taps counted by
    the projector itself: a field of ones projects to planes x spacing / |e_a|), the adjoint's atomic bytes per second (8 per tap) next to the two f32 rates of the
    microarchitecture guide (1.3 TB/s contiguous, 0.08 TB/s scattered), the projector's gathered bytes per second, and the
    time of a solver iteration from five pairs of fixed-iteration solves of different length;
@@ -111,8 +112,9 @@ def spread(r: dict) -> str:
 
 
 def operator_timing(lib, n: int, n_side: int = 512, other=None, deflections: bool = False) -> dict:
-    """other: a second build of the library (--compare-library) whose adjoint is timed in alternation and held against
-    this one's result.  deflections: section 10's operators and solver iteration too, in the same windows."""
+    """other: a second build of the library (--compare-library): every operator and solver iteration this run times is timed
+    for it too, in alternation, and held against this one's (its adjoint's result as well).  deflections: section 10's
+    operators and solver iteration too, in the same windows."""
     c = tc.view_case(n, n_side)
     o, d = dev(c.origins), dev(c.dirs)
     stream = torch.cuda.current_stream().cuda_stream
@@ -125,8 +127,11 @@ def operator_timing(lib, n: int, n_side: int = 512, other=None, deflections: boo
     e = np.abs(c.dirs / np.linalg.norm(c.dirs, axis=1, keepdims=True)).max(axis=1)
     taps = 4 * int(np.rint(p.cpu().numpy() * e / c.spacing[0]).sum())
     lib.tomo_project(f.data_ptr(), *grid_rays, p.data_ptr(), stream=stream)
-    fns = {"project": lambda: lib.tomo_project(f.data_ptr(), *grid_rays, p.data_ptr(), stream=stream),
-           "backproject": lambda: lib.tomo_backproject(p.data_ptr(), *grid_rays, v.data_ptr(), stream=stream)}
+    libs = {"": lib} if other is None else {"": lib, "_other": other}
+    fns = {}
+    for tag, L in libs.items():
+        fns["project" + tag] = lambda L=L: L.tomo_project(f.data_ptr(), *grid_rays, p.data_ptr(), stream=stream)
+        fns["backproject" + tag] = lambda L=L: L.tomo_backproject(p.data_ptr(), *grid_rays, v.data_ptr(), stream=stream)
     extra = {}
     if deflections:
         cd = dc.view_frames_of(c)
@@ -134,10 +139,11 @@ def operator_timing(lib, n: int, n_side: int = 512, other=None, deflections: boo
         frame_rays = (*c.grid, o.data_ptr(), d.data_ptr(), t1.data_ptr(), t2.data_ptr(), c.n_rays)
         g1, g2 = torch.empty_like(p), torch.empty_like(p)
         lib.tomo_deflect(f.data_ptr(), *frame_rays, g1.data_ptr(), g2.data_ptr(), stream=stream)
-        fns["deflect"] = lambda: lib.tomo_deflect(f.data_ptr(), *frame_rays, g1.data_ptr(), g2.data_ptr(), stream=stream)
-        fns["deflect_adjoint"] = lambda: lib.tomo_deflect_adjoint(g1.data_ptr(), g2.data_ptr(), *frame_rays, v.data_ptr(), stream=stream)
+        for tag, L in libs.items():
+            fns["deflect" + tag] = lambda L=L: L.tomo_deflect(f.data_ptr(), *frame_rays, g1.data_ptr(), g2.data_ptr(), stream=stream)
+            fns["deflect_adjoint" + tag] = lambda L=L: L.tomo_deflect_adjoint(g1.data_ptr(), g2.data_ptr(), *frame_rays, v.data_ptr(),
+                                                                              stream=stream)
     if other is not None:
-        fns["backproject_other"] = lambda: other.tomo_backproject(p.data_ptr(), *grid_rays, v.data_ptr(), stream=stream)
         va, vb = torch.zeros_like(v), torch.zeros_like(v)
         lib.tomo_backproject(p.data_ptr(), *grid_rays, va.data_ptr(), stream=stream)
         other.tomo_backproject(p.data_ptr(), *grid_rays, vb.data_ptr(), stream=stream)
@@ -151,51 +157,54 @@ def operator_timing(lib, n: int, n_side: int = 512, other=None, deflections: boo
     t = timed(fns)
     clock_read = clock.stop()
     ms_p, ms_b = t["project"]["median"], t["backproject"]["median"]
-    if other is not None:
-        extra.update(backproject_other_ms=spread(t["backproject_other"]),
-                     other_over_this=round(t["backproject_other"]["median"] / ms_b, 2))
     # one solver iteration: pairs of solves of fixed length on the analytic projections, host clock around the synchronised call
     pa = dev(tc.blob_projection(c))
     out = torch.empty(c.shape, dtype=torch.float64, device="cuda")
-
-    def solve(iterations):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        st = lib.tomo_reconstruct_ptr(pa.data_ptr(), *grid_rays, out.data_ptr(), lam=1.0, tol=0.0, max_iter=iterations, stream=stream)
-        return 1e3 * (time.perf_counter() - t0), st
-    solve(2)
-    short, long_ = 4, 20
+    solves = {"solver_iteration": lambda L, its: L.tomo_reconstruct_ptr(pa.data_ptr(), *grid_rays, out.data_ptr(), lam=1.0, tol=0.0,
+                                                                         max_iter=its, stream=stream)}
     if deflections:
         ga = [dev(g) for g in dc.blob_deflections(cd)]
         out_d = torch.empty_like(out)
+        solves["direct_solver_iteration"] = lambda L, its: L.tomo_reconstruct_deflections_ptr(
+            ga[0].data_ptr(), ga[1].data_ptr(), *frame_rays, out_d.data_ptr(), lam=1.0, tol=0.0, max_iter=its, stream=stream)
 
-        def solve_direct(iterations):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            st = lib.tomo_reconstruct_deflections_ptr(ga[0].data_ptr(), ga[1].data_ptr(), *frame_rays, out_d.data_ptr(), lam=1.0, tol=0.0,
-                                                      max_iter=iterations, stream=stream)
-            return 1e3 * (time.perf_counter() - t0), st
-        solve_direct(2)
-    per_it, per_it_d = [], []
+    def solve_ms(run, L, iterations):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st = run(L, iterations)
+        return 1e3 * (time.perf_counter() - t0), st
+    short, long_ = 4, 20
+    per_it, last = {name + tag: [] for name in solves for tag in libs}, {}
+    for name, run in solves.items():
+        for L in libs.values():
+            solve_ms(run, L, 2)
     for _ in range(5):
-        ms_short, _ = solve(short)
-        ms_long, st = solve(long_)
-        per_it.append((ms_long - ms_short) / (long_ - short))
-        if deflections:
-            ms_short, _ = solve_direct(short)
-            ms_long, st_d = solve_direct(long_)
-            per_it_d.append((ms_long - ms_short) / (long_ - short))
-    ms_it = float(np.median(per_it))
+        for name, run in solves.items():
+            for tag, L in reversed(libs.items()):               # this library last: its result is what is reported below
+                ms_short, _ = solve_ms(run, L, short)
+                ms_long, last[name] = solve_ms(run, L, long_)
+                per_it[name + tag].append((ms_long - ms_short) / (long_ - short))
+
+    def iteration(name):
+        return f"{np.median(per_it[name]):.3f} ({min(per_it[name]):.3f}-{max(per_it[name]):.3f}, 5 pairs of {short} and {long_} iterations)"
+    ms_it, st = float(np.median(per_it["solver_iteration"])), last["solver_iteration"]
     err = tc.rel_l2(out.cpu().numpy(), tc.blob_field(c))
+    if other is not None:
+        medians = {name: r["median"] for name, r in t.items()}
+        medians.update({name: float(np.median(v)) for name, v in per_it.items()})
+        extra.update({name + "_ms": spread(t[name]) for name in t if name.endswith("_other")},
+                     **{name + "_ms": iteration(name) for name in per_it if name.endswith("_other")},
+                     this_over_other={name: round(ms / medians[name + "_other"], 4) for name, ms in medians.items()
+                                      if not name.endswith("_other")})
     if deflections:
-        ms_d, ms_a, ms_it_d = t["deflect"]["median"], t["deflect_adjoint"]["median"], float(np.median(per_it_d))
+        ms_d, ms_a, ms_it_d = t["deflect"]["median"], t["deflect_adjoint"]["median"], float(np.median(per_it["direct_solver_iteration"]))
         field, got = tc.blob_field(c), out_d.cpu().numpy()
         extra.update(deflect_ms=spread(t["deflect"]), deflect_adjoint_ms=spread(t["deflect_adjoint"]),
                      deflect_over_project=round(ms_d / ms_p, 2), deflect_adjoint_over_backproject=round(ms_a / ms_b, 2),
                      deflect_gtaps_per_s=round(taps / (ms_d * 1e-3) / 1e9, 2), deflect_adjoint_gtaps_per_s=round(taps / (ms_a * 1e-3) / 1e9, 2),
-                     direct_solver_iteration_ms=f"{ms_it_d:.3f} ({min(per_it_d):.3f}-{max(per_it_d):.3f}, 5 pairs of {short} and {long_} "
-                                                f"iterations)",
-                     direct_operators_share_of_iteration=round((ms_d + ms_a) / ms_it_d, 3), direct_residual_after_20=st_d["residual"],
+                     direct_solver_iteration_ms=iteration("direct_solver_iteration"),
+                     direct_operators_share_of_iteration=round((ms_d + ms_a) / ms_it_d, 3),
+                     direct_residual_after_20=last["direct_solver_iteration"]["residual"],
                      direct_rel_l2_error_after_20_mean_removed=round(tc.rel_l2(got - got.mean(), field - field.mean()), 4))
     tbs = taps * 8 / (ms_b * 1e-3) / 1e12
     return dict(extra, measurement="operators", voxels=f"{n}^3", rays=c.n_rays, taps=taps, project_ms=spread(t["project"]),
@@ -204,8 +213,7 @@ def operator_timing(lib, n: int, n_side: int = 512, other=None, deflections: boo
                 project_gather_tb_per_s=round(taps * 8 / (ms_p * 1e-3) / 1e12, 3), backproject_atomic_tb_per_s=round(tbs, 3),
                 atomic_rate_vs_f32_contiguous=round(tbs / F32_ATOMIC_TBS["contiguous"], 3),
                 atomic_rate_vs_f32_scattered=round(tbs / F32_ATOMIC_TBS["scattered"], 2),
-                solver_iteration_ms=f"{ms_it:.3f} ({min(per_it):.3f}-{max(per_it):.3f}, 5 pairs of {short} and {long_} iterations)",
-                operators_share_of_iteration=round((ms_p + ms_b) / ms_it, 3),
+                solver_iteration_ms=iteration("solver_iteration"), operators_share_of_iteration=round((ms_p + ms_b) / ms_it, 3),
                 residual_after_20=st["residual"], rel_l2_error_after_20=round(err, 4))
 
 
@@ -309,8 +317,9 @@ def main():
                     help="section 10 too: its operators and solver iteration in the timing's windows, and the rendered study from the "
                          "deflections themselves next to the two-step one")
     ap.add_argument("--compare-library", default=None,
-                    help="a second build of the library whose adjoint is timed in alternation with this one's and checked against it, "
-                         "e.g. the one-atomic-per-tap form: python tools/build_variant.py tomo_plain -DPHOTON_TOMO_MERGE_LANES=0")
+                    help="a second build of the library: its operators and solver iterations are timed in alternation with this one's "
+                         "(this_over_other) and its adjoint is checked against this one's, e.g. the one-atomic-per-tap form: "
+                         "python tools/build_variant.py tomo_plain -DPHOTON_TOMO_MERGE_LANES=0")
     a = ap.parse_args()
     lib = PhotonLibrary(build=False)
     lib.set_device(0)

@@ -106,7 +106,7 @@ def main():
             op = s.split()[0]
             instrs.append((op, s))
             mix[classify(op)] += 1
-        short = re.sub(r"\(.*", "", dm.get(n, n)).replace("void ", "")
+        short = re.sub(r"\(.*", "", dm.get(n, n).replace("(anonymous namespace)::", "")).replace("void ", "")
         r_ = res[n]
         print(f"{short:32s} VGPRs {r_.get('VGPRs')} spill {r_.get('VGPRs Spill')} (SGPR spill {r_.get('SGPRs Spill')}) scratch {r_.get('ScratchSize')} B "
               f"occupancy {r_.get('Occupancy')} | static: valu {mix['valu']} salu {mix['salu']} lds {mix['lds']} vmem {mix['vmem']} scratch {mix['scratch']} wait {mix['wait']}")
