@@ -1,8 +1,15 @@
-"""Load libparallel_ray_tracing.so and bind its C-ABI (include/parallel_ray_tracing.h).
+"""The Python binding of libparallel_ray_tracing.so (C-ABI: include/parallel_ray_tracing.h).
 
-``PhotonLibrary`` is a thin ctypes veneer: every method is one call into the HIP library.
-There is no Python or CPU fallback -- if the library is missing or a HIP call fails, you get an
-exception.
+Three layers, top to bottom of the file:
+  * ``SIGNATURES``: restype and argtypes of every symbol the header declares, applied by ``apply_signatures`` to any
+    loaded library.  The header is the source of truth; tests/test_abi.py holds the table against its prototypes.
+  * ``PhotonLibrary``: one method per entry point -- marshalling only, raw device pointers in, return code checked -- and
+    on top of those the pipelines that chain several calls on torch-allocated device buffers on the current stream
+    (``correlate``, ``correlate_deform``, ``correlation_predictor``, ``track_dots``, ``integrate_gradient``, the
+    tomography solvers).
+  * ``Volume``, ``Sources``, ``Flow``, ``Scene``: the library's handles.
+All arithmetic is the HIP library's.  There is no Python or CPU fallback -- if the library is missing or a call fails,
+you get an exception.
 """
 from __future__ import annotations
 
@@ -13,37 +20,8 @@ from typing import Optional
 import numpy as np
 
 from . import build as _build
-from .ray_tracing import (RayTracingCall, bind_start_ray_tracing, camera_design_struct, element_data_struct,
+from .ray_tracing import (START_RAY_TRACING_ARGTYPES, RayTracingCall, camera_design_struct, element_data_struct,
                           lightfield_source_struct, scattering_data_struct)
-
-# every symbol include/parallel_ray_tracing.h declares
-DECLARED_SYMBOLS = (
-    "start_ray_tracing", "photon_set_device", "photon_device_pci_bus_id", "photon_rand_table", "photon_volume_load_nrrd",
-    "photon_volume_from_density", "photon_volume_info", "photon_volume_set_weight_bits", "photon_volume_download", "photon_volume_sample",
-    "photon_volume_free", "photon_scene_create", "photon_scene_free", "photon_scene_set_noise", "photon_scene_set_element_train", "photon_scene_set_ray_order", "photon_scene_set_skip_doomed", "photon_scene_live_rays", "photon_scene_live_samples", "photon_scene_live_sources", "photon_sources_missing_sensor", "photon_scene_set_source_base", "photon_march_queue_group", "photon_march_queue_count", "photon_march_queue_chunk", "photon_march_queue_size",
-    "photon_scene_set_march_segments", "photon_march_segments_plan", "photon_march_launch_plan", "photon_trim_caches", "photon_trace", "photon_trace_moments", "photon_start_ray_tracing_moments",
-    "photon_scene_stats_begin", "photon_scene_stats_end", "photon_scene_check", "photon_scene_set_march_profile", "photon_scene_march_profile", "photon_scene_march_profile_raw",
-    "photon_trace_volume_rays", "photon_trace_volume_rays_queued", "photon_version",
-    # section 3: scene generation on the device
-    "photon_sources_bos", "photon_sources_piv", "photon_flow_from_grid", "photon_flow_free", "photon_sources_piv_advected",
-    "photon_sources_count", "photon_sources_download", "photon_sources_free",
-    "photon_scene_create_from_sources", "photon_volume_gaussian", "photon_density_gaussian_write_nrrd",
-    # section 4: sensor post-processing on the device
-    "photon_postprocess_u16", "photon_measure_copy_gbs", "photon_selftest_normal_range_math", "photon_selftest_morton_order",
-    # section 5: image-pair cross-correlation on the device
-    "photon_piv_correlate",
-    # section 6: gradient-field integration on the device
-    "photon_integrate_gradient",
-    # section 7: iterative image-deformation correlation
-    "photon_piv_bspline_coefficients", "photon_piv_deform", "photon_piv_validate",
-    # section 8: dot tracking
-    "photon_dots_detect_scratch_bytes", "photon_dots_match_scratch_bytes", "photon_dots_image_max", "photon_dots_detect", "photon_dots_fit",
-    "photon_dots_match", "photon_dots_window_means",
-    # section 9: tomography
-    "photon_tomo_project", "photon_tomo_backproject", "photon_tomo_reconstruct",
-    # section 10: tomography from deflections
-    "photon_tomo_deflect", "photon_tomo_deflect_adjoint", "photon_tomo_reconstruct_deflections",
-)
 
 
 class photon_volume_info_t(ctypes.Structure):
@@ -53,31 +31,27 @@ class photon_volume_info_t(ctypes.Structure):
                 ("data_min", ctypes.c_float), ("interpolation", ctypes.c_int)]
 
 
-class photon_trace_stats_t(ctypes.Structure):
+class _Stats(ctypes.Structure):
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class photon_trace_stats_t(_Stats):
     _fields_ = [("rays_launched", ctypes.c_uint64), ("rays_on_sensor", ctypes.c_uint64),
                 ("rk_iterations", ctypes.c_uint64), ("volume_samples", ctypes.c_uint64),
                 ("sensor_taps", ctypes.c_uint64), ("march_ms", ctypes.c_float), ("total_ms", ctypes.c_float),
                 ("rays_marched", ctypes.c_uint64), ("shader_clock_mhz", ctypes.c_float), ("traces", ctypes.c_uint32),
                 ("march_wave_ms", ctypes.c_float)]
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
-
-class photon_integrate_stats_t(ctypes.Structure):
+class photon_integrate_stats_t(_Stats):
     _fields_ = [("iterations", ctypes.c_int), ("converged", ctypes.c_int), ("unknowns", ctypes.c_int),
                 ("unreachable", ctypes.c_int), ("residual", ctypes.c_double)]
 
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
-
-class photon_tomo_stats_t(ctypes.Structure):
+class photon_tomo_stats_t(_Stats):
     _fields_ = [("iterations", ctypes.c_int), ("converged", ctypes.c_int), ("unknowns", ctypes.c_longlong),
                 ("rays_used", ctypes.c_longlong), ("residual", ctypes.c_double)]
-
-    def as_dict(self):
-        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class photon_march_profile_t(ctypes.Structure):
@@ -98,21 +72,117 @@ class photon_march_plan_t(ctypes.Structure):
                 ("segmented", ctypes.c_int), ("generates_rays", ctypes.c_int)]
 
 
-def bind_march_launch_plan(lib):
-    """photon_march_launch_plan of a loaded library (host arithmetic: needs no GPU), as
-    f(n_rays, dims, algorithm, interpolation, num_cus=256, scene_segments=-1, flags=0) -> photon_march_plan_t."""
-    f = lib.photon_march_launch_plan
-    f.argtypes = [ctypes.c_uint] + [ctypes.c_int] * 8 + [ctypes.POINTER(photon_march_plan_t)]
+def _signatures():
+    """(restype, argtypes) of every symbol include/parallel_ray_tracing.h declares, in the header's order.  Device and host
+    arrays, handles and streams are c_void_p; a struct or a scalar the call writes through is a POINTER."""
+    vp, cs, ci, cu, cf, cd = ctypes.c_void_p, ctypes.c_char_p, ctypes.c_int, ctypes.c_uint, ctypes.c_float, ctypes.c_double
+    i64, u64, ll, sz, P = ctypes.c_int64, ctypes.c_uint64, ctypes.c_longlong, ctypes.c_size_t, ctypes.POINTER
+    scene = [cf, cf, P(scattering_data_struct), cs, P(lightfield_source_struct), ci, cf, cf, ci, vp, P(element_data_struct), vp, vp,
+             P(camera_design_struct), cf, P(vp)]           # photon_scene_create; _from_sources: the sources after the fifth
+    piv = [u64, ll, vp, vp, cd, cd, cd, vp, ci]            # seed, n, box_min, box_max, z_object, beam_fwhm, irradiance_constant, cdf, n_diameters
+    grid_rays = [ci, ci, ci, vp, vp, vp, vp, ll]           # nx, ny, nz, spacing, origin, d_origins, d_dirs, n_rays
+    grid_frames = grid_rays[:-1] + [vp, vp, ll]            # ..., d_dirs, d_t1, d_t2, n_rays
+    solve = [cd, cd, ci, vp, P(photon_tomo_stats_t), vp]   # lambda, tol, max_iter, d_f, stats, stream
+    return {
+        "start_ray_tracing": (None, START_RAY_TRACING_ARGTYPES),
+        "photon_set_device": (ci, [ci]),
+        "photon_device_pci_bus_id": (ci, [cs, ci]),
+        "photon_rand_table": (ci, [ci, vp, vp]),
+        "photon_volume_load_nrrd": (ci, [cs, ci, P(vp)]),
+        "photon_volume_from_density": (ci, [vp, ci, ci, ci, vp, vp, ci, P(vp)]),
+        "photon_volume_info": (ci, [vp, P(photon_volume_info_t)]),
+        "photon_volume_set_weight_bits": (ci, [vp, ci]),
+        "photon_volume_download": (ci, [vp, ci, vp]),
+        "photon_volume_sample": (ci, [vp, ci, vp, vp]),
+        "photon_volume_free": (None, [vp]),
+        "photon_scene_create": (ci, scene),
+        "photon_scene_free": (None, [vp]),
+        "photon_scene_set_noise": (ci, [vp, ci, cf, ci, cf, u64]),
+        "photon_scene_set_element_train": (ci, [vp, ci]),
+        "photon_scene_set_ray_order": (ci, [vp, ci]),
+        "photon_scene_set_skip_doomed": (ci, [vp, ci]),
+        "photon_scene_live_rays": (ci, [vp]),
+        "photon_scene_live_samples": (ci, [vp, vp, ci]),
+        "photon_scene_live_sources": (ll, [vp, vp, ll]),
+        "photon_sources_missing_sensor": (ci, [vp, vp, ci, cf, cf, ci] + [vp] * 8 + [ll, vp]),
+        "photon_scene_set_source_base": (ci, [vp, i64]),
+        "photon_march_queue_group": (cu, [cu] * 4),
+        "photon_march_queue_count": (cu, []),
+        "photon_march_queue_chunk": (cu, [ci]),
+        "photon_march_queue_size": (cu, [cu] * 4),
+        "photon_scene_set_march_segments": (ci, [vp, ci]),
+        "photon_march_segments_plan": (ci, [cu, ci, ci, ci, ci, P(ci)]),
+        "photon_march_launch_plan": (ci, [cu] + [ci] * 8 + [P(photon_march_plan_t)]),
+        "photon_trim_caches": (None, []),
+        "photon_trace": (ci, [vp, vp, ci, i64, i64, vp, vp, P(photon_trace_stats_t)]),
+        "photon_trace_moments": (ci, [vp, vp, ci, i64, i64, vp, vp, vp]),
+        # start_ray_tracing's 29 arguments + double *source_moments (host f64[num_particles][8])
+        "photon_start_ray_tracing_moments": (ci, START_RAY_TRACING_ARGTYPES + [vp]),
+        "photon_scene_stats_begin": (ci, [vp, vp]),
+        "photon_scene_stats_end": (ci, [vp, vp, P(photon_trace_stats_t)]),
+        "photon_scene_check": (ci, [vp, vp]),
+        "photon_scene_set_march_profile": (ci, [vp, ci]),
+        "photon_scene_march_profile": (ci, [vp, P(photon_march_profile_t)]),
+        "photon_scene_march_profile_raw": (ci, [vp, cu, vp]),
+        "photon_trace_volume_rays": (ci, [vp, ci, ci, vp, vp, vp]),
+        "photon_trace_volume_rays_queued": (ci, [vp, ci, ci, vp, vp, ci]),
+        "photon_version": (cs, []),
+        # section 3: scene generation on the device
+        "photon_sources_bos": (ci, [vp, vp, ci, vp, vp, ci, cd, cd, P(vp)]),
+        "photon_sources_piv": (ci, piv + [P(vp)]),
+        "photon_flow_from_grid": (ci, [vp] * 3 + [ci] * 3 + [vp, vp, P(vp)]),
+        "photon_flow_free": (None, [vp]),
+        "photon_sources_piv_advected": (ci, piv + [vp, cd, ci, vp, P(vp)]),
+        "photon_sources_count": (ll, [vp]),
+        "photon_sources_download": (ci, [vp] * 6),
+        "photon_sources_free": (None, [vp]),
+        "photon_scene_create_from_sources": (ci, scene[:5] + [vp] + scene[5:]),
+        "photon_volume_gaussian": (ci, [ci, ci, ci, vp, vp, cd, cd, vp, cd, ci, P(vp)]),
+        "photon_density_gaussian_write_nrrd": (ci, [cs, ci, ci, ci, vp, vp, cd, cd, vp, cd]),
+        # section 4: sensor post-processing on the device
+        "photon_postprocess_u16": (ci, [vp, ci, ci, cf, ci, ci, cf, u64, ci, ci, vp, P(ci), P(ci), vp]),
+        "photon_measure_copy_gbs": (ci, [sz, ci, P(cd)]),
+        "photon_selftest_normal_range_math": (ci, [ci] + [vp] * 5),
+        "photon_selftest_morton_order": (ci, [vp, vp, ll, ll, ll, vp]),
+        # section 5: image-pair cross-correlation on the device
+        "photon_piv_correlate": (ci, [vp, vp] + [ci] * 5 + [vp] * 4 + [P(ci), P(ci), vp]),
+        # section 6: gradient-field integration on the device
+        "photon_integrate_gradient": (ci, [vp] * 5 + [ci, ci, cd, cd, cd, ci, vp, P(photon_integrate_stats_t), vp]),
+        # section 7: iterative image-deformation correlation
+        "photon_piv_bspline_coefficients": (ci, [vp, ci, ci, vp, vp]),
+        "photon_piv_deform": (ci, [vp, ci, ci, vp] + [ci] * 5 + [cf, vp, vp]),
+        "photon_piv_validate": (ci, [vp] * 3 + [ci, ci, cd, cd] + [vp] * 4),
+        # section 8: dot tracking
+        "photon_dots_detect_scratch_bytes": (sz, [ci, ci]),
+        "photon_dots_match_scratch_bytes": (sz, [ci, ci, cf, ci, ci]),
+        "photon_dots_image_max": (ci, [vp, ci, ci, vp, vp]),
+        "photon_dots_detect": (ci, [vp, ci, ci, cf, vp, ci, vp, vp, vp, sz, vp]),
+        "photon_dots_fit": (ci, [vp, ci, ci, vp, vp, ci, ci, cd, ci, cd, vp, vp, vp]),
+        "photon_dots_match": (ci, [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, cf, ci, ci, vp, vp, vp, vp, sz, vp]),
+        "photon_dots_window_means": (ci, [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]),
+        # section 9: tomography
+        "photon_tomo_project": (ci, [vp] + grid_rays + [vp, vp]),
+        "photon_tomo_backproject": (ci, [vp] + grid_rays + [vp, vp]),
+        "photon_tomo_reconstruct": (ci, [vp, vp, vp] + grid_rays + solve),
+        # section 10: tomography from deflections
+        "photon_tomo_deflect": (ci, [vp] + grid_frames + [vp, vp, vp]),
+        "photon_tomo_deflect_adjoint": (ci, [vp, vp] + grid_frames + [vp, vp]),
+        "photon_tomo_reconstruct_deflections": (ci, [vp, vp, vp, vp] + grid_frames + solve),
+    }
 
-    def plan(n_rays, dims, algorithm, interpolation, num_cus=256, scene_segments=-1, flags=0):
-        nx, ny, nz = (dims, dims, dims) if np.isscalar(dims) else dims
-        out = photon_march_plan_t(struct_size=ctypes.sizeof(photon_march_plan_t))
-        rc = f(int(n_rays), int(nx), int(ny), int(nz), int(algorithm), int(interpolation), int(num_cus), int(scene_segments),
-               int(flags), ctypes.byref(out))
-        if rc != 0:
-            raise PhotonError(f"photon_march_launch_plan failed with code {rc} (see stderr)")
-        return out
-    return plan
+
+SIGNATURES = _signatures()
+DECLARED_SYMBOLS = tuple(SIGNATURES)    # every symbol include/parallel_ray_tracing.h declares
+
+
+def apply_signatures(cdll):
+    """Declare the types of every header symbol `cdll` exports (a ctypes.CDLL; returned).  A symbol it lacks is skipped:
+    builds from before an entry point existed load the same way (A/B runs through PHOTON_LIBRARY)."""
+    for name, (restype, argtypes) in SIGNATURES.items():
+        if hasattr(cdll, name):
+            f = getattr(cdll, name)
+            f.restype, f.argtypes = restype, list(argtypes)
+    return cdll
 
 
 class PhotonError(RuntimeError):
@@ -123,10 +193,73 @@ def _ptr(a: np.ndarray):
     return a.ctypes.data_as(ctypes.c_void_p)
 
 
+def _vp(ptr: int):
+    """A raw pointer or a stream as the C side takes it (0 = NULL)."""
+    return ctypes.c_void_p(int(ptr)) if ptr else None
+
+
+def _f64x3(v, scalar_ok: bool = False):
+    """v as contiguous f64 for a `const double[3]` argument; scalar_ok: one value stands for all three."""
+    v = np.asarray(v, np.float64)
+    return np.ascontiguousarray(np.broadcast_to(v, (3,)) if scalar_ok else v)
+
+
+def _dims(n):
+    """n or (nx, ny, nz) as three ints."""
+    nx, ny, nz = (n, n, n) if np.isscalar(n) else n
+    return int(nx), int(ny), int(nz)
+
+
+def _gaussian_args(n, spacing, origin, rho0, amp, centre, sigma):
+    """What volume_gaussian and density_gaussian_write_nrrd share: the grid, then the field (_ptr keeps its array alive)."""
+    return (*_dims(n), _ptr(_f64x3(spacing, scalar_ok=True)), _ptr(_f64x3(origin)), float(rho0), float(amp), _ptr(_f64x3(centre)),
+            float(sigma))
+
+
+def _piv_args(seed, n, box_min, box_max, z_object, beam_fwhm, irradiance_constant, diameter_cdf):
+    """What sources_piv and sources_piv_advected share: seed, count, box, sheet and the diameter CDF (None = NULL, 0)."""
+    cdf = None if diameter_cdf is None else np.ascontiguousarray(diameter_cdf, dtype=np.float64)
+    return (int(seed), int(n), _ptr(_f64x3(box_min)), _ptr(_f64x3(box_max)), float(z_object), float(beam_fwhm),
+            float(irradiance_constant), None if cdf is None else _ptr(cdf), 0 if cdf is None else int(cdf.size))
+
+
 def _on_device(a, dtype, dev):
     """a (a numpy array or a torch tensor; None stays None) as a contiguous torch tensor of `dtype` on `dev`."""
     import torch
     return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
+
+
+def _device_and_stream():
+    """torch's current device and the raw handle of its current stream: where every pipeline allocates and runs."""
+    import torch
+    dev = torch.device("cuda", torch.cuda.current_device())
+    return dev, torch.cuda.current_stream(dev).cuda_stream
+
+
+def _image_pair(im1, im2):
+    """(dev, stream, a, b, h, w): the two images as contiguous f32 device tensors [h, w] on the current device."""
+    import torch
+    dev, stream = _device_and_stream()
+    a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
+    if a.dim() != 2 or a.shape != b.shape:
+        raise ValueError("im1 and im2 must be two 2-d images of one shape")
+    return (dev, stream, a, b, *a.shape)
+
+
+def bind_march_launch_plan(lib):
+    """photon_march_launch_plan of a loaded library (host arithmetic: needs no GPU), as
+    f(n_rays, dims, algorithm, interpolation, num_cus=256, scene_segments=-1, flags=0) -> photon_march_plan_t."""
+    f = lib.photon_march_launch_plan
+    f.restype, f.argtypes = SIGNATURES["photon_march_launch_plan"]
+
+    def plan(n_rays, dims, algorithm, interpolation, num_cus=256, scene_segments=-1, flags=0):
+        out = photon_march_plan_t(struct_size=ctypes.sizeof(photon_march_plan_t))
+        rc = f(int(n_rays), *_dims(dims), int(algorithm), int(interpolation), int(num_cus), int(scene_segments), int(flags),
+               ctypes.byref(out))
+        if rc != 0:
+            raise PhotonError(f"photon_march_launch_plan failed with code {rc} (see stderr)")
+        return out
+    return plan
 
 
 def _one_hip_runtime_per_process():
@@ -176,120 +309,19 @@ class PhotonLibrary:
                               "(there is no CPU fallback)")
         self.path = path
         _one_hip_runtime_per_process()
-        self.lib = ctypes.CDLL(path)
+        self.lib = L = apply_signatures(ctypes.CDLL(path))
         self.hip_runtimes = mapped_hip_runtimes()
         if os.environ.get("PHOTON_VERBOSE") or len(self.hip_runtimes) > 1:
             import sys
             print(f"photon: {path} runs on {', '.join(self.hip_runtimes) or 'an unidentified HIP runtime'}"
                   + (" -- TWO HIP runtimes in one process: import torch before the library" if len(self.hip_runtimes) > 1 else ""),
                   file=sys.stderr)
-        L = self.lib
-        self.start_ray_tracing = bind_start_ray_tracing(L)
-        # start_ray_tracing's 29 arguments + double *source_moments (host f64[num_particles][8]); returns 0 or non-zero
-        self.start_ray_tracing_moments = bind_start_ray_tracing(L, "photon_start_ray_tracing_moments", [ctypes.c_void_p])
-        self.start_ray_tracing_moments.restype = ctypes.c_int
-        L.photon_version.restype = ctypes.c_char_p
-        L.photon_set_device.argtypes = [ctypes.c_int]
-        L.photon_rand_table.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.photon_volume_load_nrrd.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-        L.photon_volume_from_density.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                 ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int,
-                                                 ctypes.POINTER(ctypes.c_void_p)]
-        L.photon_volume_info.argtypes = [ctypes.c_void_p, ctypes.POINTER(photon_volume_info_t)]
-        L.photon_volume_set_weight_bits.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.photon_volume_download.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
-        L.photon_volume_sample.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.photon_volume_free.argtypes = [ctypes.c_void_p]
-        L.photon_volume_free.restype = None
-        L.photon_scene_create.argtypes = [
-            ctypes.c_float, ctypes.c_float, ctypes.POINTER(scattering_data_struct), ctypes.c_char_p,
-            ctypes.POINTER(lightfield_source_struct), ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int,
-            ctypes.c_void_p, ctypes.POINTER(element_data_struct), ctypes.c_void_p, ctypes.c_void_p,
-            ctypes.POINTER(camera_design_struct), ctypes.c_float, ctypes.POINTER(ctypes.c_void_p)]
-        L.photon_scene_free.argtypes = [ctypes.c_void_p]
-        L.photon_scene_free.restype = None
-        L.photon_scene_set_noise.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_float,
-                                             ctypes.c_uint64]
-        L.photon_scene_set_element_train.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.photon_scene_set_ray_order.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        L.photon_scene_set_skip_doomed.argtypes = [ctypes.c_void_p, ctypes.c_int]
-        if hasattr(L, "photon_scene_set_source_base"):
-            L.photon_scene_set_source_base.argtypes = [ctypes.c_void_p, ctypes.c_int64]
-        L.photon_trace.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(photon_trace_stats_t)]
-        L.photon_trace_moments.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_int64,
-                                           ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        self.start_ray_tracing = L.start_ray_tracing
+        self.start_ray_tracing_moments = L.photon_start_ray_tracing_moments       # returns 0 or non-zero
         self.has_stats_window = hasattr(L, "photon_scene_stats_begin")     # absent from libraries built before round 3 (A/B runs)
-        if self.has_stats_window:
-            L.photon_scene_stats_begin.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-            L.photon_scene_stats_end.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(photon_trace_stats_t)]
-        if hasattr(L, "photon_scene_set_march_segments"):
-            L.photon_scene_set_march_segments.argtypes = [ctypes.c_void_p, ctypes.c_int]
         if hasattr(L, "photon_march_launch_plan"):                           # absent from older libraries (A/B runs)
             self.march_launch_plan = bind_march_launch_plan(L)
         self.has_march_profile = hasattr(L, "photon_scene_march_profile")  # round 4
-        if self.has_march_profile:
-            L.photon_scene_set_march_profile.argtypes = [ctypes.c_void_p, ctypes.c_int]
-            L.photon_scene_march_profile.argtypes = [ctypes.c_void_p, ctypes.POINTER(photon_march_profile_t)]
-        L.photon_trace_volume_rays.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                               ctypes.c_void_p, ctypes.c_void_p]
-        L.photon_sources_bos.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(ctypes.c_void_p)]
-        L.photon_sources_piv.argtypes = [ctypes.c_uint64, ctypes.c_longlong, ctypes.c_void_p, ctypes.c_void_p,
-                                         ctypes.c_double, ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_int,
-                                         ctypes.POINTER(ctypes.c_void_p)]
-        L.photon_flow_from_grid.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p, ctypes.c_void_p,
-                                                                                     ctypes.POINTER(ctypes.c_void_p)]
-        L.photon_flow_free.argtypes = [ctypes.c_void_p]
-        L.photon_flow_free.restype = None
-        L.photon_sources_piv_advected.argtypes = (L.photon_sources_piv.argtypes[:-1] +
-                                                  [ctypes.c_void_p, ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
-                                                   ctypes.POINTER(ctypes.c_void_p)])
-        L.photon_sources_count.argtypes = [ctypes.c_void_p]
-        L.photon_sources_count.restype = ctypes.c_longlong
-        L.photon_sources_download.argtypes = [ctypes.c_void_p] + [ctypes.c_void_p] * 5
-        L.photon_sources_free.argtypes = [ctypes.c_void_p]
-        L.photon_sources_free.restype = None
-        L.photon_scene_create_from_sources.argtypes = (L.photon_scene_create.argtypes[:5] + [ctypes.c_void_p] +
-                                                       L.photon_scene_create.argtypes[5:])
-        L.photon_volume_gaussian.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p,
-                                             ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_double,
-                                             ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]
-
-        L.photon_postprocess_u16.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_int,
-                                             ctypes.c_float, ctypes.c_uint64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
-                                             ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
-        L.photon_piv_correlate.argtypes = [ctypes.c_void_p, ctypes.c_void_p] + [ctypes.c_int] * 5 + [ctypes.c_void_p] * 4 + [
-            ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.c_void_p]
-        L.photon_integrate_gradient.argtypes = [ctypes.c_void_p] * 5 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                                                        ctypes.c_double, ctypes.c_int, ctypes.c_void_p,
-                                                                        ctypes.POINTER(photon_integrate_stats_t), ctypes.c_void_p]
-        L.photon_piv_bspline_coefficients.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-        L.photon_piv_deform.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p] + [ctypes.c_int] * 5 + [
-            ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
-        L.photon_piv_validate.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double] + [
-            ctypes.c_void_p] * 4
-        vp, ci = ctypes.c_void_p, ctypes.c_int
-        L.photon_dots_detect_scratch_bytes.argtypes = [ci, ci]
-        L.photon_dots_detect_scratch_bytes.restype = ctypes.c_size_t
-        L.photon_dots_match_scratch_bytes.argtypes = [ci, ci, ctypes.c_float, ci, ci]
-        L.photon_dots_match_scratch_bytes.restype = ctypes.c_size_t
-        L.photon_dots_image_max.argtypes = [vp, ci, ci, vp, vp]
-        L.photon_dots_detect.argtypes = [vp, ci, ci, ctypes.c_float, vp, ci, vp, vp, vp, ctypes.c_size_t, vp]
-        L.photon_dots_fit.argtypes = [vp, ci, ci, vp, vp, ci, ci, ctypes.c_double, ci, ctypes.c_double, vp, vp, vp]
-        L.photon_dots_match.argtypes = [vp, vp, vp, ci, vp, vp, vp, ci, ci, vp, ci, ci, ci, ci, ci, ctypes.c_float, ci, ci, vp, vp, vp, vp,
-                                        ctypes.c_size_t, vp]
-        L.photon_dots_window_means.argtypes = [vp, vp, vp, vp, ci, ci, ci, ci, ci, ci, ci, vp, vp, vp]
-        grid_and_rays = [ci, ci, ci, vp, vp, vp, vp, ctypes.c_longlong]      # nx, ny, nz, spacing, origin, d_origins, d_dirs, n_rays
-        L.photon_tomo_project.argtypes = [vp] + grid_and_rays + [vp, vp]
-        L.photon_tomo_backproject.argtypes = [vp] + grid_and_rays + [vp, vp]
-        L.photon_tomo_reconstruct.argtypes = [vp, vp, vp] + grid_and_rays + [ctypes.c_double, ctypes.c_double, ci, vp,
-                                                                            ctypes.POINTER(photon_tomo_stats_t), vp]
-        grid_rays_frames = grid_and_rays[:-1] + [vp, vp, ctypes.c_longlong]     # ..., d_dirs, d_t1, d_t2, n_rays
-        L.photon_tomo_deflect.argtypes = [vp] + grid_rays_frames + [vp, vp, vp]
-        L.photon_tomo_deflect_adjoint.argtypes = [vp, vp] + grid_rays_frames + [vp, vp]
-        L.photon_tomo_reconstruct_deflections.argtypes = [vp, vp, vp, vp] + grid_rays_frames + [
-            ctypes.c_double, ctypes.c_double, ci, vp, ctypes.POINTER(photon_tomo_stats_t), vp]
 
     # ---- helpers --------------------------------------------------------------------------
     @staticmethod
@@ -297,16 +329,20 @@ class PhotonLibrary:
         if rc != 0:
             raise PhotonError(f"{what} failed with code {rc} (see stderr)")
 
+    def _call(self, entry: str, *args):
+        """One call of an entry point that returns 0 or an error code."""
+        self._check(getattr(self.lib, entry)(*args), entry)
+
     def version(self) -> str:
         return self.lib.photon_version().decode()
 
     def set_device(self, device: int):
-        self._check(self.lib.photon_set_device(int(device)), "photon_set_device")
+        self._call("photon_set_device", int(device))
 
     def rand_table(self, n: int):
         r1 = np.empty(n, np.float32)
         r2 = np.empty(n, np.float32)
-        self._check(self.lib.photon_rand_table(n, _ptr(r1), _ptr(r2)), "photon_rand_table")
+        self._call("photon_rand_table", n, _ptr(r1), _ptr(r2))
         return r1, r2
 
     def morton_order(self, x, y, first: int = 0, n: Optional[int] = None):
@@ -315,9 +351,7 @@ class PhotonLibrary:
         y = np.ascontiguousarray(y, np.float32)
         n = x.size - first if n is None else int(n)
         out = np.empty(n, np.int32)
-        f = self.lib.photon_selftest_morton_order
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_void_p]
-        self._check(f(_ptr(x), _ptr(y), int(x.size), int(first), n, _ptr(out)), "photon_selftest_morton_order")
+        self._call("photon_selftest_morton_order", _ptr(x), _ptr(y), int(x.size), int(first), n, _ptr(out))
         return out
 
     def sources_missing_sensor(self, call: RayTracingCall, lens_x, lens_y):
@@ -328,13 +362,10 @@ class PhotonLibrary:
         ly = np.ascontiguousarray(lens_y, np.float32)
         x, y, z = (np.ascontiguousarray(a, np.float32) for a in (call.src_x, call.src_y, call.src_z))
         off = np.zeros(x.size, np.uint8)
-        f = self.lib.photon_sources_missing_sensor
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_int, ctypes.c_void_p,
-                      ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                      ctypes.c_longlong, ctypes.c_void_p]
-        rc = f(_ptr(lx), _ptr(ly), int(lx.size), float(call.image_distance), float(call.beam_wavelength), len(call.elements),
-               ctypes.cast(elems, ctypes.c_void_p), _ptr(centers), _ptr(planes), _ptr(sysidx), ctypes.addressof(cam), _ptr(x), _ptr(y), _ptr(z),
-               int(x.size), _ptr(off))
+        rc = self.lib.photon_sources_missing_sensor(
+            _ptr(lx), _ptr(ly), int(lx.size), float(call.image_distance), float(call.beam_wavelength), len(call.elements),
+            ctypes.cast(elems, ctypes.c_void_p), _ptr(centers), _ptr(planes), _ptr(sysidx), ctypes.addressof(cam), _ptr(x), _ptr(y), _ptr(z),
+            int(x.size), _ptr(off))
         if rc == 1:
             return None
         self._check(rc, "photon_sources_missing_sensor")
@@ -364,14 +395,12 @@ class PhotonLibrary:
         if not hasattr(self.lib, "photon_device_pci_bus_id"):
             return ""
         buf = ctypes.create_string_buffer(64)
-        self.lib.photon_device_pci_bus_id.argtypes = [ctypes.c_char_p, ctypes.c_int]
         return buf.value.decode().lower() if self.lib.photon_device_pci_bus_id(buf, 64) == 0 else ""
 
     def measure_copy_gbs(self, nbytes: int = 1 << 30, reps: int = 5) -> float:
         """Device-to-device float4 copy rate (read + write), GB/s."""
         out = ctypes.c_double(0.0)
-        self.lib.photon_measure_copy_gbs.argtypes = [ctypes.c_size_t, ctypes.c_int, ctypes.POINTER(ctypes.c_double)]
-        self._check(self.lib.photon_measure_copy_gbs(int(nbytes), int(reps), ctypes.byref(out)), "photon_measure_copy_gbs")
+        self._call("photon_measure_copy_gbs", int(nbytes), int(reps), ctypes.byref(out))
         return out.value
 
     # ---- sensor post-processing on the device (perform_ray_tracing_03.py:2190-2259) -----------------
@@ -380,11 +409,9 @@ class PhotonLibrary:
                         crop_rows: int = 0, crop_cols: int = 0, stream: int = 0):
         """Device f32 image -> device uint16 picture (raw pointers); returns (rows, cols) of the result."""
         r, c = ctypes.c_int(0), ctypes.c_int(0)
-        rc = self.lib.photon_postprocess_u16(ctypes.c_void_p(int(d_image_ptr)), int(width), int(height), float(pixel_gain),
-                                             int(pixel_bit_depth), int(bool(intensity_rescaling)), float(image_noise),
-                                             int(noise_seed), int(crop_rows), int(crop_cols), ctypes.c_void_p(int(d_out_ptr)),
-                                             ctypes.byref(r), ctypes.byref(c), ctypes.c_void_p(int(stream)) if stream else None)
-        self._check(rc, "photon_postprocess_u16")
+        self._call("photon_postprocess_u16", _vp(d_image_ptr), int(width), int(height), float(pixel_gain), int(pixel_bit_depth),
+                   int(bool(intensity_rescaling)), float(image_noise), int(noise_seed), int(crop_rows), int(crop_cols), _vp(d_out_ptr),
+                   ctypes.byref(r), ctypes.byref(c), _vp(stream))
         return r.value, c.value
 
     # ---- image-pair cross-correlation on the device (photon_piv_correlate) ------------------------------
@@ -395,20 +422,16 @@ class PhotonLibrary:
         ratio; flags [n_rows, n_cols] int32; planes [n_rows, n_cols, 2R+1, 2R+1] or None), filled asynchronously on
         `stream`.  The definition: include/parallel_ray_tracing.h, section 5 (photon_amd.piv_correlation: host model)."""
         import torch
-        f = self.lib.photon_piv_correlate
         rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = (ctypes.c_void_p(int(d_im1_ptr)), ctypes.c_void_p(int(d_im2_ptr)), int(width), int(height), int(win), int(step),
-                int(radius))
-        self._check(f(*args, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None), "photon_piv_correlate")
+        args = ("photon_piv_correlate", _vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(radius))
+        self._call(*args, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
         r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev, _ = _device_and_stream()
         vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
         flags = torch.empty((r, c), dtype=torch.int32, device=dev)
         pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
-        rc = f(*args, ctypes.c_void_p(int(d_offset_ptr)) if d_offset_ptr else None, ctypes.c_void_p(vectors.data_ptr()),
-               ctypes.c_void_p(flags.data_ptr()), ctypes.c_void_p(pl.data_ptr()) if planes else None, None, None,
-               ctypes.c_void_p(int(stream)) if stream else None)
-        self._check(rc, "photon_piv_correlate")
+        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(pl.data_ptr()) if planes else None, None,
+                   None, _vp(stream))
         return vectors, flags, pl
 
     def correlate(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1):
@@ -421,12 +444,7 @@ class PhotonLibrary:
         if int(passes) not in (1, 2):
             raise ValueError(f"passes must be 1 or 2, not {passes}")
         radius = int(win) // 2 if radius is None else int(radius)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
-        if a.dim() != 2 or a.shape != b.shape:
-            raise ValueError("im1 and im2 must be two 2-d images of one shape")
-        h, w = a.shape
-        stream = torch.cuda.current_stream(dev).cuda_stream
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
         vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
         vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         if int(passes) == 2:
@@ -437,30 +455,36 @@ class PhotonLibrary:
         return vectors, flags
 
     # ---- iterative image-deformation correlation on the device (section 7) ---------------------------------------------
-    @staticmethod
-    def _vp(ptr: int):
-        return ctypes.c_void_p(int(ptr)) if ptr else None
-
     def bspline_coefficients(self, d_im_ptr: int, width: int, height: int, d_coef_ptr: int, stream: int = 0):
         """photon_piv_bspline_coefficients on raw device pointers (f32 [height, width] in and out), asynchronous on `stream`."""
-        rc = self.lib.photon_piv_bspline_coefficients(self._vp(d_im_ptr), int(width), int(height), self._vp(d_coef_ptr), self._vp(stream))
-        self._check(rc, "photon_piv_bspline_coefficients")
+        self._call("photon_piv_bspline_coefficients", _vp(d_im_ptr), int(width), int(height), _vp(d_coef_ptr), _vp(stream))
 
     def piv_deform(self, d_coef_ptr: int, width: int, height: int, d_field_ptr: int, field_stride: int, n_rows: int, n_cols: int,
                    win: int, step: int, scale: float, d_out_ptr: int, stream: int = 0):
         """photon_piv_deform on raw device pointers: the image of the coefficients warped by scale x the grid's field
         (f32, `field_stride` 2 or 4 floats per vector), asynchronous on `stream`."""
-        rc = self.lib.photon_piv_deform(self._vp(d_coef_ptr), int(width), int(height), self._vp(d_field_ptr), int(field_stride),
-                                        int(n_rows), int(n_cols), int(win), int(step), float(scale), self._vp(d_out_ptr), self._vp(stream))
-        self._check(rc, "photon_piv_deform")
+        self._call("photon_piv_deform", _vp(d_coef_ptr), int(width), int(height), _vp(d_field_ptr), int(field_stride), int(n_rows), int(n_cols),
+                   int(win), int(step), float(scale), _vp(d_out_ptr), _vp(stream))
 
     def piv_validate(self, d_pred_ptr: int, d_vectors_ptr: int, d_flags_ptr: int, n_rows: int, n_cols: int, d_field_ptr: int,
                      d_smooth_ptr: int, d_status_ptr: int, eps: float = 0.1, threshold: float = 2.0, stream: int = 0):
         """photon_piv_validate on raw device pointers (d_pred_ptr, d_smooth_ptr: 0 = NULL), asynchronous on `stream`."""
-        rc = self.lib.photon_piv_validate(self._vp(d_pred_ptr), self._vp(d_vectors_ptr), self._vp(d_flags_ptr), int(n_rows), int(n_cols),
-                                          float(eps), float(threshold), self._vp(d_field_ptr), self._vp(d_smooth_ptr),
-                                          self._vp(d_status_ptr), self._vp(stream))
-        self._check(rc, "photon_piv_validate")
+        self._call("photon_piv_validate", _vp(d_pred_ptr), _vp(d_vectors_ptr), _vp(d_flags_ptr), int(n_rows), int(n_cols), float(eps),
+                   float(threshold), _vp(d_field_ptr), _vp(d_smooth_ptr), _vp(d_status_ptr), _vp(stream))
+
+    def _correlate_validated(self, a, b, win, step, radius, eps, threshold, dev, stream, pairs=()):
+        """Pass 0 of correlate_deform, all of correlation_predictor: correlate the device images a, b, then validate with no
+        predictor.  Returns (vec, field, smoothed, status); field and smoothed are [*pairs, n_rows, n_cols, 2] and the
+        validation fills their first [n_rows, n_cols, 2] (pairs=(2,): the ping-pong pairs of correlate_deform)."""
+        import torch
+        h, w = a.shape
+        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
+        r, c = flg.shape
+        field, smoothed = (torch.empty((*pairs, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))
+        status = torch.empty((r, c), dtype=torch.int32, device=dev)
+        self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smoothed.data_ptr(), status.data_ptr(), eps, threshold,
+                          stream)
+        return vec, field, smoothed, status
 
     def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
                          residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0):
@@ -475,21 +499,12 @@ class PhotonLibrary:
         if int(iterations) < 0:
             raise ValueError(f"iterations must be >= 0, not {iterations}")
         radius = int(win) // 2 if radius is None else int(radius)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
-        if a.dim() != 2 or a.shape != b.shape:
-            raise ValueError("im1 and im2 must be two 2-d images of one shape")
-        h, w = a.shape
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
         pc.check_arguments((h, w), win, step, radius)
         if int(iterations) > 0:
             pc.check_arguments((h, w), win, step, residual_radius)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
-        r, c = flg.shape
-        field, smoothed = (torch.empty((2, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))     # ping-pong pairs
-        status = torch.empty((r, c), dtype=torch.int32, device=dev)
-        self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field[0].data_ptr(), smoothed[0].data_ptr(), status.data_ptr(),
-                          eps, threshold, stream)
+        vec, field, smoothed, status = self._correlate_validated(a, b, win, step, radius, eps, threshold, dev, stream, pairs=(2,))
+        r, c = status.shape
         cur = 0
         if int(iterations) > 0:
             coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=dev), torch.empty((2, h, w), dtype=torch.float32, device=dev)
@@ -516,45 +531,36 @@ class PhotonLibrary:
 
     def dots_image_max(self, d_im_ptr: int, width: int, height: int, d_max_ptr: int, stream: int = 0):
         """photon_dots_image_max on raw device pointers: the largest finite pixel into the device f32 at d_max_ptr."""
-        rc = self.lib.photon_dots_image_max(self._vp(d_im_ptr), int(width), int(height), self._vp(d_max_ptr), self._vp(stream))
-        self._check(rc, "photon_dots_image_max")
+        self._call("photon_dots_image_max", _vp(d_im_ptr), int(width), int(height), _vp(d_max_ptr), _vp(stream))
 
     def dots_detect(self, d_im_ptr: int, width: int, height: int, threshold: float, d_scale_ptr: int, max_dots: int, d_peaks_ptr: int,
                     d_count_ptr: int, d_scratch_ptr: int, scratch_bytes: int, stream: int = 0):
         """photon_dots_detect on raw device pointers (d_scale_ptr: 0 = NULL), asynchronous on `stream`."""
-        rc = self.lib.photon_dots_detect(self._vp(d_im_ptr), int(width), int(height), float(threshold), self._vp(d_scale_ptr), int(max_dots),
-                                         self._vp(d_peaks_ptr), self._vp(d_count_ptr), self._vp(d_scratch_ptr), int(scratch_bytes),
-                                         self._vp(stream))
-        self._check(rc, "photon_dots_detect")
+        self._call("photon_dots_detect", _vp(d_im_ptr), int(width), int(height), float(threshold), _vp(d_scale_ptr), int(max_dots),
+                   _vp(d_peaks_ptr), _vp(d_count_ptr), _vp(d_scratch_ptr), int(scratch_bytes), _vp(stream))
 
     def dots_fit(self, d_im_ptr: int, width: int, height: int, d_peaks_ptr: int, d_count_ptr: int, max_dots: int, box_radius: int,
                  sigma_w: float, iterations: int, background: float, d_dots_ptr: int, d_status_ptr: int, stream: int = 0):
         """photon_dots_fit on raw device pointers, asynchronous on `stream`."""
-        rc = self.lib.photon_dots_fit(self._vp(d_im_ptr), int(width), int(height), self._vp(d_peaks_ptr), self._vp(d_count_ptr),
-                                      int(max_dots), int(box_radius), float(sigma_w), int(iterations), float(background),
-                                      self._vp(d_dots_ptr), self._vp(d_status_ptr), self._vp(stream))
-        self._check(rc, "photon_dots_fit")
+        self._call("photon_dots_fit", _vp(d_im_ptr), int(width), int(height), _vp(d_peaks_ptr), _vp(d_count_ptr), int(max_dots), int(box_radius),
+                   float(sigma_w), int(iterations), float(background), _vp(d_dots_ptr), _vp(d_status_ptr), _vp(stream))
 
     def dots_match(self, d_dots1_ptr: int, d_status1_ptr: int, d_count1_ptr: int, max1: int, d_dots2_ptr: int, d_status2_ptr: int,
                    d_count2_ptr: int, max2: int, radius: float, width: int, height: int, d_pair_ptr: int, d_shift_ptr: int,
                    d_npaired_ptr: int, d_scratch_ptr: int, scratch_bytes: int, d_field_ptr: int = 0, field_stride: int = 2,
                    n_rows: int = 0, n_cols: int = 0, win: int = 0, step: int = 0, reject_mask: int = 0, stream: int = 0):
         """photon_dots_match on raw device pointers (d_field_ptr: 0 = no predictor), asynchronous on `stream`."""
-        rc = self.lib.photon_dots_match(self._vp(d_dots1_ptr), self._vp(d_status1_ptr), self._vp(d_count1_ptr), int(max1),
-                                        self._vp(d_dots2_ptr), self._vp(d_status2_ptr), self._vp(d_count2_ptr), int(max2), int(reject_mask),
-                                        self._vp(d_field_ptr), int(field_stride), int(n_rows), int(n_cols), int(win), int(step),
-                                        float(radius), int(width), int(height), self._vp(d_pair_ptr), self._vp(d_shift_ptr),
-                                        self._vp(d_npaired_ptr), self._vp(d_scratch_ptr), int(scratch_bytes), self._vp(stream))
-        self._check(rc, "photon_dots_match")
+        self._call("photon_dots_match", _vp(d_dots1_ptr), _vp(d_status1_ptr), _vp(d_count1_ptr), int(max1), _vp(d_dots2_ptr), _vp(d_status2_ptr),
+                   _vp(d_count2_ptr), int(max2), int(reject_mask), _vp(d_field_ptr), int(field_stride), int(n_rows), int(n_cols), int(win),
+                   int(step), float(radius), int(width), int(height), _vp(d_pair_ptr), _vp(d_shift_ptr), _vp(d_npaired_ptr), _vp(d_scratch_ptr),
+                   int(scratch_bytes), _vp(stream))
 
     def dots_window_means(self, d_dots1_ptr: int, d_pair_ptr: int, d_shift_ptr: int, d_count1_ptr: int, max1: int, width: int,
                           height: int, win: int, step: int, min_count: int, anchor: int, d_vectors_ptr: int, d_flags_ptr: int,
                           stream: int = 0):
         """photon_dots_window_means on raw device pointers, asynchronous on `stream`."""
-        rc = self.lib.photon_dots_window_means(self._vp(d_dots1_ptr), self._vp(d_pair_ptr), self._vp(d_shift_ptr), self._vp(d_count1_ptr),
-                                               int(max1), int(width), int(height), int(win), int(step), int(min_count), int(anchor),
-                                               self._vp(d_vectors_ptr), self._vp(d_flags_ptr), self._vp(stream))
-        self._check(rc, "photon_dots_window_means")
+        self._call("photon_dots_window_means", _vp(d_dots1_ptr), _vp(d_pair_ptr), _vp(d_shift_ptr), _vp(d_count1_ptr), int(max1), int(width),
+                   int(height), int(win), int(step), int(min_count), int(anchor), _vp(d_vectors_ptr), _vp(d_flags_ptr), _vp(stream))
 
     def correlation_predictor(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, eps: float = 0.1,
                               threshold: float = 2.0):
@@ -562,23 +568,11 @@ class PhotonLibrary:
         (median test, replacement, 3 x 3 smoothing) -- pass 0 of correlate_deform.  Returns the smoothed field as a torch
         device tensor [n_rows, n_cols, 2], queued on the current stream: hand it to track_dots as predictor=(field, win, step)
         and a displacement larger than the spacing of the dots no longer pairs a dot with its neighbour."""
-        import torch
         from . import piv_correlation as pc
         radius = int(win) // 2 if radius is None else int(radius)
-        dev = torch.device("cuda", torch.cuda.current_device())
-        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
-        if a.dim() != 2 or a.shape != b.shape:
-            raise ValueError("im1 and im2 must be two 2-d images of one shape")
-        h, w = a.shape
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
         pc.check_arguments((h, w), win, step, radius)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
-        r, c = flg.shape
-        field, smoothed = (torch.empty((r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))
-        status = torch.empty((r, c), dtype=torch.int32, device=dev)
-        self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smoothed.data_ptr(), status.data_ptr(), eps, threshold,
-                          stream)
-        return smoothed
+        return self._correlate_validated(a, b, win, step, radius, eps, threshold, dev, stream)[2]
 
     def track_dots(self, im1, im2, threshold: float, box_radius: int = 3, sigma_w: float = 1.0, iterations: int = 4,
                    background: float = 0.0, radius: float = 3.0, predictor=None, max_dots: Optional[int] = None, grid=None,
@@ -595,13 +589,8 @@ class PhotonLibrary:
         import torch
         from . import dot_tracking as dt
         from . import piv_correlation as pc
-        dev = torch.device("cuda", torch.cuda.current_device())
-        a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
-        if a.dim() != 2 or a.shape != b.shape:
-            raise ValueError("im1 and im2 must be two 2-d images of one shape")
-        h, w = a.shape
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
         cap = dt.default_max_dots((h, w)) if max_dots is None else int(max_dots)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         det_bytes = self.dots_scratch_bytes(w, h)
         mat_bytes = self.dots_scratch_bytes(w, h, radius, cap, cap) if cap >= 1 and radius > 0 else 0
         scratch = torch.empty(max(det_bytes, mat_bytes, 16), dtype=torch.uint8, device=dev)   # the calls are ordered on one stream
@@ -661,11 +650,8 @@ class PhotonLibrary:
         from .bos_density import default_max_iter
         max_iter = default_max_iter(nx, ny) if max_iter is None else int(max_iter)
         st = photon_integrate_stats_t()
-        vp = [ctypes.c_void_p(int(v)) if v else None for v in (d_gx_ptr, d_gy_ptr, d_w_ptr, d_fixed_ptr, d_value_ptr)]
-        rc = self.lib.photon_integrate_gradient(*vp, int(nx), int(ny), float(hx), float(hy), float(tol), max_iter,
-                                                ctypes.c_void_p(int(d_phi_ptr)) if d_phi_ptr else None, ctypes.byref(st),
-                                                ctypes.c_void_p(int(stream)) if stream else None)
-        self._check(rc, "photon_integrate_gradient")
+        self._call("photon_integrate_gradient", *(_vp(v) for v in (d_gx_ptr, d_gy_ptr, d_w_ptr, d_fixed_ptr, d_value_ptr)), int(nx), int(ny),
+                   float(hx), float(hy), float(tol), max_iter, _vp(d_phi_ptr), ctypes.byref(st), _vp(stream))
         return st.as_dict()
 
     def integrate_gradient(self, gx, gy, w=None, fixed=None, value=None, hx: float = 1.0, hy: float = 1.0, tol: float = 1e-8,
@@ -676,7 +662,7 @@ class PhotonLibrary:
         unknown nodes that reach no fixed node.  max_iter None = 20 max(nx, ny)."""
         import torch
         from . import bos_density
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev, stream = _device_and_stream()
         tgx, tgy = _on_device(gx, torch.float64, dev), _on_device(gy, torch.float64, dev)
         if tgx.dim() != 2 or tgx.shape != tgy.shape:
             raise ValueError("gx and gy must be two 2-d arrays of one shape")
@@ -688,7 +674,6 @@ class PhotonLibrary:
                 raise ValueError(f"{name} must have the shape of gx, {tuple(tgx.shape)}")
         bos_density.check_arguments(nx, ny, hx, hy, tol, bos_density.default_max_iter(nx, ny) if max_iter is None else max_iter)
         phi = torch.empty((ny, nx), dtype=torch.float64, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         stats = self.integrate_gradient_ptr(tgx.data_ptr(), tgy.data_ptr(), nx, ny, phi.data_ptr(),
                                             tw.data_ptr() if tw is not None else 0, tf.data_ptr() if tf is not None else 0,
                                             tv.data_ptr() if tv is not None else 0, hx, hy, tol, max_iter, stream=stream)
@@ -697,42 +682,35 @@ class PhotonLibrary:
     # ---- tomography on the device (include/parallel_ray_tracing.h, section 9) ----------------------------------------
     @staticmethod
     def _tomo_grid(dims, spacing, origin):
-        sp = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float64), (3,)))
-        og = np.ascontiguousarray(origin, dtype=np.float64)
+        """nx, ny, nz, spacing, origin as the tomography entry points take them (a scalar spacing stands for all three)."""
+        og = _f64x3(origin)
         if og.shape != (3,):
             raise ValueError("origin must hold three values")
         nx, ny, nz = (int(n) for n in dims)
-        return nx, ny, nz, sp, og
+        return nx, ny, nz, _ptr(_f64x3(spacing, scalar_ok=True)), _ptr(og)
 
     def tomo_project(self, d_f_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, n_rays: int, d_p_ptr: int,
                      stream: int = 0):
         """P = A f on raw device pointers (f64: f [nz, ny, nx], origins and dirs [n_rays, 3], p [n_rays]; dims = (nx, ny,
         nz)).  Asynchronous on `stream`."""
-        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
-        rc = self.lib.photon_tomo_project(self._vp(d_f_ptr), nx, ny, nz, _ptr(sp), _ptr(og), self._vp(d_origins_ptr),
-                                          self._vp(d_dirs_ptr), int(n_rays), self._vp(d_p_ptr), self._vp(stream))
-        self._check(rc, "photon_tomo_project")
+        grid = self._tomo_grid(dims, spacing, origin)
+        self._call("photon_tomo_project", _vp(d_f_ptr), *grid, _vp(d_origins_ptr), _vp(d_dirs_ptr), int(n_rays), _vp(d_p_ptr), _vp(stream))
 
     def tomo_backproject(self, d_y_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, n_rays: int, d_v_ptr: int,
                          stream: int = 0):
         """v += A^T y on raw device pointers (f64: y [n_rays], v [nz, ny, nx]): adds into v.  Asynchronous on `stream`."""
-        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
-        rc = self.lib.photon_tomo_backproject(self._vp(d_y_ptr), nx, ny, nz, _ptr(sp), _ptr(og), self._vp(d_origins_ptr),
-                                              self._vp(d_dirs_ptr), int(n_rays), self._vp(d_v_ptr), self._vp(stream))
-        self._check(rc, "photon_tomo_backproject")
+        grid = self._tomo_grid(dims, spacing, origin)
+        self._call("photon_tomo_backproject", _vp(d_y_ptr), *grid, _vp(d_origins_ptr), _vp(d_dirs_ptr), int(n_rays), _vp(d_v_ptr), _vp(stream))
 
     def _tomo_solve_ptr(self, entry: str, d_data_ptrs, dims, spacing, origin, d_ray_ptrs, n_rays, d_f_ptr, d_w_ptr, d_support_ptr, lam, tol,
                         max_iter, stream) -> dict:
         """photon_tomo_reconstruct or photon_tomo_reconstruct_deflections (`entry`) on raw pointers: d_data_ptrs the data
         over the rays (p, or g1 and g2), d_ray_ptrs origins and dirs (and t1, t2)."""
         from .tomography import DEFAULT_MAX_ITER
-        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
+        grid = self._tomo_grid(dims, spacing, origin)
         st = photon_tomo_stats_t()
-        rc = getattr(self.lib, entry)(*(self._vp(d) for d in d_data_ptrs), self._vp(d_w_ptr), self._vp(d_support_ptr), nx, ny, nz, _ptr(sp),
-                                      _ptr(og), *(self._vp(d) for d in d_ray_ptrs), int(n_rays), float(lam), float(tol),
-                                      DEFAULT_MAX_ITER if max_iter is None else int(max_iter), self._vp(d_f_ptr), ctypes.byref(st),
-                                      self._vp(stream))
-        self._check(rc, entry)
+        self._call(entry, *(_vp(d) for d in d_data_ptrs), _vp(d_w_ptr), _vp(d_support_ptr), *grid, *(_vp(d) for d in d_ray_ptrs), int(n_rays),
+                   float(lam), float(tol), DEFAULT_MAX_ITER if max_iter is None else int(max_iter), _vp(d_f_ptr), ctypes.byref(st), _vp(stream))
         return st.as_dict()
 
     def _tomo_solve(self, entry: str, data, names: str, dims, spacing, origin, rays, ray_names: str, w, support, lam, tol, max_iter):
@@ -740,7 +718,7 @@ class PhotonLibrary:
         of three values per ray (origins and dirs, and t1, t2); the names are the message's."""
         import torch
         from . import tomography
-        dev = torch.device("cuda", torch.cuda.current_device())
+        dev, stream = _device_and_stream()
         nx, ny, nz = (int(n) for n in dims)
         rays = [_on_device(a, torch.float64, dev).reshape(-1, 3) for a in rays]
         data = [_on_device(a, torch.float64, dev).reshape(-1) for a in data]
@@ -752,11 +730,11 @@ class PhotonLibrary:
         if ts is not None and tuple(ts.shape) != (nz, ny, nx):
             raise ValueError(f"support must be [nz, ny, nx] = {(nz, ny, nx)}")
         max_iter = tomography.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
-        tomography.check_arguments(dims, np.broadcast_to(np.asarray(spacing, np.float64), (3,)), origin, n_rays, lam, tol, max_iter)
+        tomography.check_arguments(dims, _f64x3(spacing, scalar_ok=True), origin, n_rays, lam, tol, max_iter)
         f = torch.empty((nz, ny, nx), dtype=torch.float64, device=dev)
         stats = self._tomo_solve_ptr(entry, [a.data_ptr() for a in data], dims, spacing, origin, [a.data_ptr() for a in rays], n_rays,
                                      f.data_ptr(), tw.data_ptr() if tw is not None else 0, ts.data_ptr() if ts is not None else 0, lam, tol,
-                                     max_iter, torch.cuda.current_stream(dev).cuda_stream)
+                                     max_iter, stream)
         return f.cpu().numpy(), stats
 
     def tomo_reconstruct_ptr(self, d_p_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int, n_rays: int, d_f_ptr: int,
@@ -783,21 +761,17 @@ class PhotonLibrary:
                      n_rays: int, d_g1_ptr: int, d_g2_ptr: int, stream: int = 0):
         """g1 = D_t1 f, g2 = D_t2 f on raw device pointers (f64: f [nz, ny, nx]; origins, dirs, t1, t2 [n_rays, 3]; g1, g2
         [n_rays]).  Asynchronous on `stream`."""
-        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
-        rc = self.lib.photon_tomo_deflect(self._vp(d_f_ptr), nx, ny, nz, _ptr(sp), _ptr(og), self._vp(d_origins_ptr), self._vp(d_dirs_ptr),
-                                          self._vp(d_t1_ptr), self._vp(d_t2_ptr), int(n_rays), self._vp(d_g1_ptr), self._vp(d_g2_ptr),
-                                          self._vp(stream))
-        self._check(rc, "photon_tomo_deflect")
+        grid = self._tomo_grid(dims, spacing, origin)
+        self._call("photon_tomo_deflect", _vp(d_f_ptr), *grid, _vp(d_origins_ptr), _vp(d_dirs_ptr), _vp(d_t1_ptr),
+                   _vp(d_t2_ptr), int(n_rays), _vp(d_g1_ptr), _vp(d_g2_ptr), _vp(stream))
 
     def tomo_deflect_adjoint(self, d_y1_ptr: int, d_y2_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int,
                              d_t1_ptr: int, d_t2_ptr: int, n_rays: int, d_v_ptr: int, stream: int = 0):
         """v += D_t1^T y1 + D_t2^T y2 on raw device pointers (f64: y1, y2 [n_rays], v [nz, ny, nx]): adds into v.
         Asynchronous on `stream`."""
-        nx, ny, nz, sp, og = self._tomo_grid(dims, spacing, origin)
-        rc = self.lib.photon_tomo_deflect_adjoint(self._vp(d_y1_ptr), self._vp(d_y2_ptr), nx, ny, nz, _ptr(sp), _ptr(og),
-                                                  self._vp(d_origins_ptr), self._vp(d_dirs_ptr), self._vp(d_t1_ptr), self._vp(d_t2_ptr),
-                                                  int(n_rays), self._vp(d_v_ptr), self._vp(stream))
-        self._check(rc, "photon_tomo_deflect_adjoint")
+        grid = self._tomo_grid(dims, spacing, origin)
+        self._call("photon_tomo_deflect_adjoint", _vp(d_y1_ptr), _vp(d_y2_ptr), *grid, _vp(d_origins_ptr), _vp(d_dirs_ptr),
+                   _vp(d_t1_ptr), _vp(d_t2_ptr), int(n_rays), _vp(d_v_ptr), _vp(stream))
 
     def tomo_reconstruct_deflections_ptr(self, d_g1_ptr: int, d_g2_ptr: int, dims, spacing, origin, d_origins_ptr: int, d_dirs_ptr: int,
                                          d_t1_ptr: int, d_t2_ptr: int, n_rays: int, d_f_ptr: int, d_w_ptr: int = 0,
@@ -824,46 +798,28 @@ class PhotonLibrary:
     # ---- volumes ------------------------------------------------------------------------------
     def volume_load_nrrd(self, path: str, interpolation: int = 1) -> "Volume":
         h = ctypes.c_void_p()
-        self._check(self.lib.photon_volume_load_nrrd(path.encode(), int(interpolation), ctypes.byref(h)),
-                    "photon_volume_load_nrrd")
+        self._call("photon_volume_load_nrrd", path.encode(), int(interpolation), ctypes.byref(h))
         return Volume(self, h)
 
     def volume_from_density(self, rho: np.ndarray, spacing, origin, interpolation: int = 1) -> "Volume":
         """rho indexed [z, y, x] (x fastest), float32."""
         rho = np.ascontiguousarray(rho, dtype=np.float32)
         nz, ny, nx = rho.shape
-        sp = np.ascontiguousarray(spacing, dtype=np.float64)
-        og = np.ascontiguousarray(origin, dtype=np.float64)
         h = ctypes.c_void_p()
-        self._check(self.lib.photon_volume_from_density(_ptr(rho), nx, ny, nz, _ptr(sp), _ptr(og), int(interpolation),
-                                                        ctypes.byref(h)), "photon_volume_from_density")
+        self._call("photon_volume_from_density", _ptr(rho), nx, ny, nz, _ptr(_f64x3(spacing)), _ptr(_f64x3(origin)), int(interpolation),
+                   ctypes.byref(h))
         return Volume(self, h)
 
     def volume_gaussian(self, n, spacing, origin, rho0: float, amp: float, centre, sigma: float,
                         interpolation: int = 1) -> "Volume":
         """rho0 + amp exp(-|r - centre|^2 / 2 sigma^2) evaluated on the device (no host array, no file)."""
-        nx, ny, nz = (n, n, n) if np.isscalar(n) else n
-        sp = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float64), (3,)))
-        og = np.ascontiguousarray(origin, dtype=np.float64)
-        c = np.ascontiguousarray(centre, dtype=np.float64)
         h = ctypes.c_void_p()
-        self._check(self.lib.photon_volume_gaussian(int(nx), int(ny), int(nz), _ptr(sp), _ptr(og), float(rho0), float(amp),
-                                                    _ptr(c), float(sigma), int(interpolation), ctypes.byref(h)),
-                    "photon_volume_gaussian")
+        self._call("photon_volume_gaussian", *_gaussian_args(n, spacing, origin, rho0, amp, centre, sigma), int(interpolation), ctypes.byref(h))
         return Volume(self, h)
 
     def density_gaussian_write_nrrd(self, path: str, n, spacing, origin, rho0: float, amp: float, centre, sigma: float) -> str:
         """The field of volume_gaussian as an NRRD file (evaluated on the device)."""
-        nx, ny, nz = (n, n, n) if np.isscalar(n) else n
-        sp = np.ascontiguousarray(np.broadcast_to(np.asarray(spacing, np.float64), (3,)))
-        og = np.ascontiguousarray(origin, dtype=np.float64)
-        c = np.ascontiguousarray(centre, dtype=np.float64)
-        self.lib.photon_density_gaussian_write_nrrd.argtypes = [ctypes.c_char_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                                                ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double,
-                                                                ctypes.c_double, ctypes.c_void_p, ctypes.c_double]
-        self._check(self.lib.photon_density_gaussian_write_nrrd(path.encode(), int(nx), int(ny), int(nz), _ptr(sp), _ptr(og),
-                                                                float(rho0), float(amp), _ptr(c), float(sigma)),
-                    "photon_density_gaussian_write_nrrd")
+        self._call("photon_density_gaussian_write_nrrd", path.encode(), *_gaussian_args(n, spacing, origin, rho0, amp, centre, sigma))
         return path
 
     # ---- sources generated on the device ------------------------------------------------------
@@ -872,20 +828,14 @@ class PhotonLibrary:
         t = np.ascontiguousarray(template_xy, dtype=np.float64).reshape(-1, 2)
         dx, dy, tx, ty = (np.ascontiguousarray(a) for a in (d[:, 0], d[:, 1], t[:, 0], t[:, 1]))
         h = ctypes.c_void_p()
-        self._check(self.lib.photon_sources_bos(_ptr(dx), _ptr(dy), d.shape[0], _ptr(tx), _ptr(ty), t.shape[0], float(z),
-                                                float(radiance), ctypes.byref(h)), "photon_sources_bos")
+        self._call("photon_sources_bos", _ptr(dx), _ptr(dy), d.shape[0], _ptr(tx), _ptr(ty), t.shape[0], float(z), float(radiance), ctypes.byref(h))
         return Sources(self, h)
 
     def sources_piv(self, seed: int, n: int, box_min, box_max, z_object: float, beam_fwhm: float,
                     irradiance_constant: float, diameter_cdf=None) -> "Sources":
-        lo = np.ascontiguousarray(box_min, dtype=np.float64)
-        hi = np.ascontiguousarray(box_max, dtype=np.float64)
-        cdf = None if diameter_cdf is None else np.ascontiguousarray(diameter_cdf, dtype=np.float64)
         h = ctypes.c_void_p()
-        self._check(self.lib.photon_sources_piv(int(seed), int(n), _ptr(lo), _ptr(hi), float(z_object), float(beam_fwhm),
-                                                float(irradiance_constant), _ptr(cdf) if cdf is not None else None,
-                                                0 if cdf is None else int(cdf.size), ctypes.byref(h)),
-                    "photon_sources_piv")
+        self._call("photon_sources_piv", *_piv_args(seed, n, box_min, box_max, z_object, beam_fwhm, irradiance_constant, diameter_cdf),
+                   ctypes.byref(h))
         return Sources(self, h)
 
     def flow_from_grid(self, u, v, w, spacing, origin) -> "Flow":
@@ -895,11 +845,9 @@ class PhotonLibrary:
         if comps[0].ndim != 3 or any(c.shape != comps[0].shape for c in comps):
             raise ValueError("u, v, w must be three arrays of one shape [nz][ny][nx]")
         nz, ny, nx = comps[0].shape
-        sp = np.ascontiguousarray(spacing, dtype=np.float64)
-        og = np.ascontiguousarray(origin, dtype=np.float64)
         h = ctypes.c_void_p()
-        self._check(self.lib.photon_flow_from_grid(_ptr(comps[0]), _ptr(comps[1]), _ptr(comps[2]), nx, ny, nz, _ptr(sp), _ptr(og),
-                                                   ctypes.byref(h)), "photon_flow_from_grid")
+        self._call("photon_flow_from_grid", _ptr(comps[0]), _ptr(comps[1]), _ptr(comps[2]), nx, ny, nz, _ptr(_f64x3(spacing)), _ptr(_f64x3(origin)),
+                   ctypes.byref(h))
         return Flow(self, h)
 
     def sources_piv_advected(self, seed: int, n: int, box_min, box_max, z_object: float, beam_fwhm: float,
@@ -907,45 +855,32 @@ class PhotonLibrary:
                              steps: int = 16, return_world: bool = False):
         """The sources_piv field at time t: every particle moved through `flow` by `steps` RK4 steps
         (photon_sources_piv_advected).  Returns Sources, or (Sources, world_xyz f64 [n][3]) with return_world."""
-        lo = np.ascontiguousarray(box_min, dtype=np.float64)
-        hi = np.ascontiguousarray(box_max, dtype=np.float64)
-        cdf = None if diameter_cdf is None else np.ascontiguousarray(diameter_cdf, dtype=np.float64)
         world = np.empty((max(int(n), 0), 3), np.float64) if return_world else None
         h = ctypes.c_void_p()
-        self._check(self.lib.photon_sources_piv_advected(int(seed), int(n), _ptr(lo), _ptr(hi), float(z_object), float(beam_fwhm),
-                                                         float(irradiance_constant), _ptr(cdf) if cdf is not None else None,
-                                                         0 if cdf is None else int(cdf.size),
-                                                         flow.handle if flow is not None else None, float(t), int(steps),
-                                                         _ptr(world) if world is not None else None, ctypes.byref(h)),
-                    "photon_sources_piv_advected")
+        self._call("photon_sources_piv_advected", *_piv_args(seed, n, box_min, box_max, z_object, beam_fwhm, irradiance_constant, diameter_cdf),
+                   flow.handle if flow is not None else None, float(t), int(steps), _ptr(world) if world is not None else None, ctypes.byref(h))
         return (Sources(self, h), world) if return_world else Sources(self, h)
 
     # ---- scenes -------------------------------------------------------------------------------
     def scene_create_from_sources(self, call: RayTracingCall, sources: "Sources") -> "Scene":
         """Like scene_create, with the light-field sources already in HBM (call's own source arrays unused)."""
-        sd, ls, elems, centers, planes, sysidx, cam = call.pack()
-        h = ctypes.c_void_p()
-        rc = self.lib.photon_scene_create_from_sources(
-            ctypes.c_float(call.lens_pitch), ctypes.c_float(call.image_distance), ctypes.byref(sd),
-            call.scattering_type.encode(), ctypes.byref(ls), sources.handle, int(call.lightray_number_per_particle),
-            ctypes.c_float(call.beam_wavelength), ctypes.c_float(call.aperture_f_number), len(call.elements),
-            _ptr(centers), elems, _ptr(planes), _ptr(sysidx), ctypes.byref(cam),
-            ctypes.c_float(call.ray_cone_pitch_ratio), ctypes.byref(h))
-        self._check(rc, "photon_scene_create_from_sources")
-        scene = Scene(self, h, call)
+        scene = self._scene_create("photon_scene_create_from_sources", call, (sources.handle,))
         scene.num_sources = sources.count()
         return scene
 
     def scene_create(self, call: RayTracingCall) -> "Scene":
+        return self._scene_create("photon_scene_create", call)
+
+    def _scene_create(self, entry: str, call: RayTracingCall, sources=()) -> "Scene":
+        """photon_scene_create, or with sources = (handle,) photon_scene_create_from_sources: the same arguments otherwise."""
         sd, ls, elems, centers, planes, sysidx, cam = call.pack()
         h = ctypes.c_void_p()
-        rc = self.lib.photon_scene_create(
-            ctypes.c_float(call.lens_pitch), ctypes.c_float(call.image_distance), ctypes.byref(sd),
-            call.scattering_type.encode(), ctypes.byref(ls), int(call.lightray_number_per_particle),
+        self._call(
+            entry, ctypes.c_float(call.lens_pitch), ctypes.c_float(call.image_distance), ctypes.byref(sd),
+            call.scattering_type.encode(), ctypes.byref(ls), *sources, int(call.lightray_number_per_particle),
             ctypes.c_float(call.beam_wavelength), ctypes.c_float(call.aperture_f_number), len(call.elements),
             _ptr(centers), elems, _ptr(planes), _ptr(sysidx), ctypes.byref(cam),
             ctypes.c_float(call.ray_cone_pitch_ratio), ctypes.byref(h))
-        self._check(rc, "photon_scene_create")
         return Scene(self, h, call)
 
 
@@ -955,42 +890,37 @@ class Volume:
 
     def info(self) -> photon_volume_info_t:
         i = photon_volume_info_t()
-        self._lib._check(self._lib.lib.photon_volume_info(self.handle, ctypes.byref(i)), "photon_volume_info")
+        self._lib._call("photon_volume_info", self.handle, ctypes.byref(i))
         return i
 
     def set_weight_bits(self, bits: int):
         """Trilinear weights: 0 = exact f32, 8 = the texture unit's 8 fractional bits."""
-        self._lib._check(self._lib.lib.photon_volume_set_weight_bits(self.handle, int(bits)), "photon_volume_set_weight_bits")
+        self._lib._call("photon_volume_set_weight_bits", self.handle, int(bits))
 
     def download(self, coefficients: bool = False) -> np.ndarray:
         i = self.info()
         out = np.empty((i.nz, i.ny, i.nx, 4), np.float32)
-        self._lib._check(self._lib.lib.photon_volume_download(self.handle, int(coefficients), _ptr(out)),
-                         "photon_volume_download")
+        self._lib._call("photon_volume_download", self.handle, int(coefficients), _ptr(out))
         return out
 
     def sample(self, coords: np.ndarray) -> np.ndarray:
         c = np.ascontiguousarray(coords, dtype=np.float32).reshape(-1, 3)
         out = np.empty((c.shape[0], 4), np.float32)
-        self._lib._check(self._lib.lib.photon_volume_sample(self.handle, c.shape[0], _ptr(c), _ptr(out)),
-                         "photon_volume_sample")
+        self._lib._call("photon_volume_sample", self.handle, c.shape[0], _ptr(c), _ptr(out))
         return out
 
     def trace_rays(self, pos: np.ndarray, direction: np.ndarray, algorithm: int = 2):
         p = np.array(pos, dtype=np.float32, order="C").reshape(-1, 3)
         d = np.array(direction, dtype=np.float32, order="C").reshape(-1, 3)
         steps = np.zeros(p.shape[0], np.int32)
-        self._lib._check(self._lib.lib.photon_trace_volume_rays(self.handle, int(algorithm), p.shape[0], _ptr(p),
-                                                                _ptr(d), _ptr(steps)), "photon_trace_volume_rays")
+        self._lib._call("photon_trace_volume_rays", self.handle, int(algorithm), p.shape[0], _ptr(p), _ptr(d), _ptr(steps))
         return p, d, steps
 
     def trace_rays_queued(self, pos: np.ndarray, direction: np.ndarray, algorithm: int = 2, segments: int = -1):
         """The march of trace_rays through the render path's launch (persistent waves, work queues, `segments` pieces)."""
         p = np.array(pos, dtype=np.float32, order="C").reshape(-1, 3)
         d = np.array(direction, dtype=np.float32, order="C").reshape(-1, 3)
-        f = self._lib.lib.photon_trace_volume_rays_queued
-        f.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        self._lib._check(f(self.handle, int(algorithm), p.shape[0], _ptr(p), _ptr(d), int(segments)), "photon_trace_volume_rays_queued")
+        self._lib._call("photon_trace_volume_rays_queued", self.handle, int(algorithm), p.shape[0], _ptr(p), _ptr(d), int(segments))
         return p, d
 
     def free(self):
@@ -1012,9 +942,8 @@ class Sources:
         n = self.count()
         out = dict(x=np.empty(n, np.float32), y=np.empty(n, np.float32), z=np.empty(n, np.float32),
                    radiance=np.empty(n, np.float64), diameter_index=np.empty(n, np.int32))
-        self._lib._check(self._lib.lib.photon_sources_download(self.handle, _ptr(out["x"]), _ptr(out["y"]), _ptr(out["z"]),
-                                                               _ptr(out["radiance"]), _ptr(out["diameter_index"])),
-                         "photon_sources_download")
+        self._lib._call("photon_sources_download", self.handle, _ptr(out["x"]), _ptr(out["y"]), _ptr(out["z"]), _ptr(out["radiance"]),
+                        _ptr(out["diameter_index"]))
         return out
 
     def free(self):
@@ -1046,11 +975,8 @@ class Scene:
         if src_end is None:
             src_end = self.num_sources
         stats = photon_trace_stats_t() if want_stats else None
-        rc = self._lib.lib.photon_trace(self.handle, volume.handle if volume is not None else None, int(algorithm),
-                                        int(src_begin), int(src_end), ctypes.c_void_p(int(d_image_ptr)),
-                                        ctypes.c_void_p(int(stream)) if stream else None,
-                                        ctypes.byref(stats) if stats is not None else None)
-        self._lib._check(rc, "photon_trace")
+        self._lib._call("photon_trace", self.handle, volume.handle if volume is not None else None, int(algorithm), int(src_begin), int(src_end),
+                        _vp(d_image_ptr), _vp(stream), ctypes.byref(stats) if stats is not None else None)
         return stats
 
     def trace_moments(self, d_image_ptr: int, d_records_ptr: int, volume: Optional[Volume] = None, algorithm: int = 0,
@@ -1059,11 +985,8 @@ class Scene:
         to the DEVICE array f64[num_sources][8] at d_records_ptr; every other record is left as it is."""
         if src_end is None:
             src_end = self.num_sources
-        rc = self._lib.lib.photon_trace_moments(self.handle, volume.handle if volume is not None else None, int(algorithm),
-                                                int(src_begin), int(src_end), ctypes.c_void_p(int(d_image_ptr)),
-                                                ctypes.c_void_p(int(d_records_ptr)) if d_records_ptr else None,
-                                                ctypes.c_void_p(int(stream)) if stream else None)
-        self._lib._check(rc, "photon_trace_moments")
+        self._lib._call("photon_trace_moments", self.handle, volume.handle if volume is not None else None, int(algorithm), int(src_begin),
+                        int(src_end), _vp(d_image_ptr), _vp(d_records_ptr), _vp(stream))
 
     @property
     def has_stats_window(self) -> bool:
@@ -1071,94 +994,79 @@ class Scene:
 
     def stats_begin(self, stream: int = 0):
         """Open a statistics window: traces without want_stats record their events and let the counters run."""
-        self._lib._check(self._lib.lib.photon_scene_stats_begin(self.handle, ctypes.c_void_p(int(stream)) if stream else None),
-                         "photon_scene_stats_begin")
+        self._lib._call("photon_scene_stats_begin", self.handle, _vp(stream))
 
     def stats_end(self, stream: int = 0):
         """Wait for the stream and return the window's sums (photon_trace_stats_t; .traces = calls covered)."""
         stats = photon_trace_stats_t()
-        self._lib._check(self._lib.lib.photon_scene_stats_end(self.handle, ctypes.c_void_p(int(stream)) if stream else None,
-                                                              ctypes.byref(stats)), "photon_scene_stats_end")
+        self._lib._call("photon_scene_stats_end", self.handle, _vp(stream), ctypes.byref(stats))
         return stats
 
     def check(self, stream: int = 0):
         """Wait for `stream`; raise if a trace of this scene had a hand-off error between march segments (photon_scene_check)."""
-        f = self._lib.lib.photon_scene_check
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-        self._lib._check(f(self.handle, ctypes.c_void_p(int(stream)) if stream else None), "photon_scene_check")
+        self._lib._call("photon_scene_check", self.handle, _vp(stream))
 
     def set_march_segments(self, segments: int):
         """-1 the library's choice, 1 whole marches, n: cut every march of a large launch into n segments (speed only)."""
-        self._lib._check(self._lib.lib.photon_scene_set_march_segments(self.handle, int(segments)), "photon_scene_set_march_segments")
+        self._lib._call("photon_scene_set_march_segments", self.handle, int(segments))
 
     def set_march_profile(self, on: bool):
         """Record wave entry / first-group / exit times of the march launches (measurement; off by default)."""
-        self._lib._check(self._lib.lib.photon_scene_set_march_profile(self.handle, int(bool(on))), "photon_scene_set_march_profile")
+        self._lib._call("photon_scene_set_march_profile", self.handle, int(bool(on)))
 
     def march_profile(self) -> dict:
         """Means over the march launches since the statistics were last reset (see photon_march_profile_t)."""
         out = photon_march_profile_t()
         out.struct_size = ctypes.sizeof(photon_march_profile_t)
-        self._lib._check(self._lib.lib.photon_scene_march_profile(self.handle, ctypes.byref(out)), "photon_scene_march_profile")
+        self._lib._call("photon_scene_march_profile", self.handle, ctypes.byref(out))
         return out.as_dict()
 
     def set_noise(self, add_pos_noise=False, pos_noise_std=0.0, add_ngrad_noise=False, ngrad_noise_std=0.0, seed=0):
-        self._lib._check(self._lib.lib.photon_scene_set_noise(self.handle, int(bool(add_pos_noise)), float(pos_noise_std),
-                                                              int(bool(add_ngrad_noise)), float(ngrad_noise_std), int(seed)),
-                         "photon_scene_set_noise")
+        self._lib._call("photon_scene_set_noise", self.handle, int(bool(add_pos_noise)), float(pos_noise_std), int(bool(add_ngrad_noise)),
+                        float(ngrad_noise_std), int(seed))
 
     def set_ray_order(self, mode: int):
         """0 source-major (reference order), 1 lens-major over spatially sorted sources, 2 auto (default)."""
-        self._lib._check(self._lib.lib.photon_scene_set_ray_order(self.handle, int(mode)), "photon_scene_set_ray_order")
+        self._lib._call("photon_scene_set_ray_order", self.handle, int(mode))
 
     def set_skip_doomed(self, on: bool):
         """Drop rays that provably die on the first element's aperture before the march (default on)."""
-        self._lib._check(self._lib.lib.photon_scene_set_skip_doomed(self.handle, int(bool(on))), "photon_scene_set_skip_doomed")
+        self._lib._call("photon_scene_set_skip_doomed", self.handle, int(bool(on)))
 
     def live_rays(self) -> int:
         """Lens samples per source a volume-free launch keeps (photon_scene_live_rays); rays_per_source = nothing ruled out."""
-        f = self._lib.lib.photon_scene_live_rays
-        f.argtypes = [ctypes.c_void_p]
-        f.restype = ctypes.c_int
-        return int(f(self.handle))
+        return int(self._lib.lib.photon_scene_live_rays(self.handle))
 
     def live_sources(self):
         """The sources a volume-free launch keeps, ascending (photon_scene_live_sources); None = every source."""
         f = self._lib.lib.photon_scene_live_sources
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_longlong]
-        f.restype = ctypes.c_longlong
         n = f(self.handle, None, 0)
         if n == -1:
             return None
         if n < 0:
             raise PhotonError(f"photon_scene_live_sources returned {n}")
         out = np.empty(int(n), np.int32)
-        got = f(self.handle, out.ctypes.data_as(ctypes.c_void_p), int(n))
+        got = f(self.handle, _ptr(out), int(n))
         if got != n:
             raise PhotonError(f"photon_scene_live_sources returned {got}, expected {n}")
         return out
 
     def live_samples(self):
         """The lens samples a volume-free launch keeps, ascending (photon_scene_live_samples)."""
-        import numpy as np
         n = self.live_rays()
         out = np.zeros(max(n, 1), np.int32)
-        f = self._lib.lib.photon_scene_live_samples
-        f.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        f.restype = ctypes.c_int
-        got = int(f(self.handle, out.ctypes.data, int(out.size)))
+        got = int(self._lib.lib.photon_scene_live_samples(self.handle, _ptr(out), int(out.size)))
         if got != n:
             raise PhotonError(f"photon_scene_live_samples returned {got}, expected {n}")
         return out[:n]
 
     def set_source_base(self, first_source: int):
         """This scene holds the slice of a job's sources that starts at `first_source` (noise ids stay job-wide)."""
-        self._lib._check(self._lib.lib.photon_scene_set_source_base(self.handle, int(first_source)), "photon_scene_set_source_base")
+        self._lib._call("photon_scene_set_source_base", self.handle, int(first_source))
 
     def set_element_train(self, mode: int):
         """0 = the reference's element walk (element 0 only), 1 = the working multi-element train."""
-        self._lib._check(self._lib.lib.photon_scene_set_element_train(self.handle, int(mode)),
-                         "photon_scene_set_element_train")
+        self._lib._call("photon_scene_set_element_train", self.handle, int(mode))
 
     def free(self):
         if self.handle:

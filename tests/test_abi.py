@@ -1,5 +1,6 @@
 """C-ABI checks that need no GPU: struct layouts against what the reference's marshalling code
-produced (tests/golden/abi_*.{json,npz}), symbol export, header/library agreement."""
+produced (tests/golden/abi_*.{json,npz}), symbol export, header/library agreement, and the binding's signature table
+against the header's prototypes."""
 import ctypes
 import json
 import os
@@ -10,7 +11,7 @@ import pytest
 
 from conftest import GOLDEN, ROOT, load_fixture_call
 from photon_amd import ray_tracing as rt
-from photon_amd.library import DECLARED_SYMBOLS
+from photon_amd.library import DECLARED_SYMBOLS, SIGNATURES, apply_signatures
 
 
 def test_struct_sizes_match_reference_marshalling():
@@ -56,26 +57,104 @@ def test_packed_structs_are_byte_identical_to_the_reference(case):
     assert ls.num_particles == a["src_x"].size and ls.source_point_number == 10000
 
 
-def _header_functions():
+def _header_text():
+    """The header without its comments."""
     with open(os.path.join(ROOT, "include", "parallel_ray_tracing.h")) as f:
         text = f.read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return set(re.findall(r"\b((?:start_ray_tracing|photon_[a-z0-9_]+))\s*\(", text))
+    return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+
+
+def _header_functions():
+    return set(re.findall(r"\b((?:start_ray_tracing|photon_[a-z0-9_]+))\s*\(", _header_text()))
+
+
+_C_KINDS = {"int": "int", "unsigned": "unsigned", "unsigned int": "unsigned", "long long": "int64", "int64_t": "int64",
+            "unsigned long long": "uint64", "uint64_t": "uint64", "size_t": "uint64", "float": "float", "double": "double",
+            "bool": "bool"}
+
+
+def _c_kind(decl: str, is_return: bool = False) -> str:
+    """Kind of one parameter ('const double spacing[3]', 'int nx') or of a return type ('const char *')."""
+    if "*" in decl or "[" in decl:
+        return "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    base = " ".join(words if is_return else words[:-1])         # a parameter ends with its name
+    if is_return and base == "void":
+        return "void"
+    assert base in _C_KINDS, f"unknown C type in {decl!r}"
+    return _C_KINDS[base]
+
+
+def _header_prototypes():
+    """{name: (return kind, [parameter kinds])} of every function the header declares: what is left between two ';' once
+    comments, preprocessor lines, struct bodies, typedefs and the extern "C" braces are gone must read `ret name(params)`."""
+    text = re.sub(r"^\s*#.*$", "", _header_text(), flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)
+    text = re.sub(r"typedef\s+struct\s+\w+\s+\w+\s*;", "", text)
+    text = text.replace('extern "C" {', "").replace("}", "")
+    out = {}
+    for stmt in (" ".join(s.split()) for s in text.split(";")):
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.*?)\b(\w+) ?\((.*)\)", stmt)
+        assert m, f"not a prototype: {stmt!r}"
+        ret, name, params = m.groups()
+        assert name not in out, name
+        params = [] if params.strip() == "void" else [p.strip() for p in params.split(",")]
+        out[name] = (_c_kind(ret, is_return=True), [_c_kind(p) for p in params])
+    return out
+
+
+def _ctypes_kind(t) -> str:
+    if t is None:
+        return "void"
+    if issubclass(t, ctypes._Pointer):
+        return "pointer"
+    code = t._type_                                              # the struct-module code of a simple ctypes type
+    if code in "zP":
+        return "pointer"
+    if code in "fd?":
+        return {"f": "float", "d": "double", "?": "bool"}[code]
+    assert code in "iIlLqQ", f"no kind for {t}"
+    return {(4, True): "int", (4, False): "unsigned", (8, True): "int64", (8, False): "uint64"}[ctypes.sizeof(t), code.islower()]
+
+
+_PROTOTYPES = _header_prototypes()
 
 
 def test_header_and_python_binding_declare_the_same_symbols():
-    assert _header_functions() == set(DECLARED_SYMBOLS)
+    assert _header_functions() == set(DECLARED_SYMBOLS) == set(SIGNATURES) == set(_PROTOTYPES)
+    assert len(DECLARED_SYMBOLS) == len(set(DECLARED_SYMBOLS))
+
+
+@pytest.mark.parametrize("name", sorted(_header_functions()))
+def test_signature_table_agrees_with_the_header(name):
+    """Arity, the kind of every parameter and the kind of the return value, symbol by symbol: a Python int handed to a
+    symbol whose pointer or 64-bit parameter is not declared as such is silently cut to a C int."""
+    restype, argtypes = SIGNATURES[name]
+    assert (_ctypes_kind(restype), [_ctypes_kind(t) for t in argtypes]) == _PROTOTYPES[name]
 
 
 def test_library_loads_and_exports_every_declared_symbol():
-    """No compute call: just dlopen + dlsym (works without a GPU)."""
+    """No compute call: just dlopen + dlsym (works without a GPU).  After apply_signatures every symbol is typed."""
     from photon_amd import build
     path = build.build_library()
     lib = ctypes.CDLL(path)
     for name in DECLARED_SYMBOLS:
         assert hasattr(lib, name), name
-    lib.photon_version.restype = ctypes.c_char_p
+    assert apply_signatures(lib) is lib
+    for name in DECLARED_SYMBOLS:
+        f = getattr(lib, name)
+        assert f.argtypes is not None and len(f.argtypes) == len(SIGNATURES[name][1]), name
+        assert f.restype is SIGNATURES[name][0], name
     assert b"gfx950" in lib.photon_version()
+
+
+def test_apply_signatures_skips_symbols_a_library_lacks():
+    """A build from before an entry point existed loads the same way (A/B runs): libc exports none of the table."""
+    import ctypes.util
+    libc = apply_signatures(ctypes.CDLL(ctypes.util.find_library("c")))
+    assert not any(hasattr(libc, name) for name in DECLARED_SYMBOLS)
 
 
 def test_product_does_not_reference_the_oracle():

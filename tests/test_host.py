@@ -103,15 +103,10 @@ def test_march_work_queues_partition_every_launch():
     GPU needed."""
     import ctypes
     from photon_amd import build
-    lib = ctypes.CDLL(build.build_library(verbose=False))
+    from photon_amd.library import apply_signatures
+    lib = apply_signatures(ctypes.CDLL(build.build_library(verbose=False)))
     f = lib.photon_march_queue_group
-    f.argtypes = [ctypes.c_uint] * 4
-    f.restype = ctypes.c_uint
     size = lib.photon_march_queue_size
-    size.argtypes = [ctypes.c_uint] * 4
-    size.restype = ctypes.c_uint
-    lib.photon_march_queue_count.restype = ctypes.c_uint
-    lib.photon_march_queue_chunk.restype = ctypes.c_uint
     subs = lib.photon_march_queue_count() // 8
     assert subs == 4 and lib.photon_march_queue_chunk(2) == 16 and lib.photon_march_queue_chunk(1) == 128
     bad = 0xFFFFFFFF
@@ -146,10 +141,9 @@ def test_march_segments_plan():
     launches march whole."""
     import ctypes
     from photon_amd import build
-    lib = ctypes.CDLL(build.build_library(verbose=False))
+    from photon_amd.library import apply_signatures
+    lib = apply_signatures(ctypes.CDLL(build.build_library(verbose=False)))
     plan = lib.photon_march_segments_plan
-    plan.argtypes = [ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    plan.restype = ctypes.c_int
 
     def p(rays, depth, algo, interp, cus=256):
         h = ctypes.c_int(-1)
@@ -182,14 +176,12 @@ def march_plan(monkeypatch):
     the two environment variables of the planner unset."""
     import ctypes
     from photon_amd import build
-    from photon_amd.library import bind_march_launch_plan
+    from photon_amd.library import apply_signatures, bind_march_launch_plan
     monkeypatch.delenv("PHOTON_MARCH_SEGMENTS", raising=False)
     monkeypatch.delenv("PHOTON_MARCH_SEGMENT_SHAPE", raising=False)
-    lib = ctypes.CDLL(build.build_library(verbose=False))
+    lib = apply_signatures(ctypes.CDLL(build.build_library(verbose=False)))
     plan = bind_march_launch_plan(lib)
     old = lib.photon_march_segments_plan
-    old.argtypes = [ctypes.c_uint, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
-    old.restype = ctypes.c_int
 
     def segments_plan(rays, depth, algo, interp, cus):
         h = ctypes.c_int(-1)

@@ -1336,9 +1336,7 @@ def test_normal_range_division_and_sqrt_are_exact(photon):
     [2^-96, 2^96]: held here against numpy's float32 division and square root (correctly rounded by IEEE 754) on 3e6 operand
     pairs spread over that whole range, on the march's own neighbourhood (step / n, 1 / n, 1 / |T|), and on the specials
     (zeros, infinities, NaN), which v_div_fixup still handles."""
-    import ctypes
     f = photon.lib.photon_selftest_normal_range_math
-    f.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 5
     rng = np.random.default_rng(21)
 
     def run(a, b):

@@ -26,7 +26,6 @@ def test_block_cache_recycles_and_trims(photon, workdir):
     for _ in range(5):
         img = photon.render(call)
     assert first.any() and same(img, first)                      # recycled (unzeroed) blocks change nothing
-    photon.lib.photon_trim_caches.restype = None
     photon.lib.photon_trim_caches()
     assert same(photon.render(call), first)                      # and the next call simply allocates again
 

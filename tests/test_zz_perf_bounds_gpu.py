@@ -113,7 +113,6 @@ def test_block_cache_memory(photon, workdir):
         photon.render(call)
     b = used_mib()
     assert abs(b - a) < 1.0
-    photon.lib.photon_trim_caches.restype = None
     photon.lib.photon_trim_caches()
     c = used_mib()
     assert c < b - 30.0

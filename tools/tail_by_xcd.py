@@ -31,7 +31,6 @@ for _ in range(8):
 st = scene.stats_end()
 raw = (ctypes.c_ulonglong * (64 * 8))()
 f = lib.lib.photon_scene_march_profile_raw
-f.argtypes = [ctypes.c_void_p, ctypes.c_uint, ctypes.c_void_p]
 M = (1 << 64) - 1
 acc = np.zeros((8, 4))
 for launch in range(8):
