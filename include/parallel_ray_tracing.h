@@ -1002,6 +1002,52 @@ int photon_tomo_reconstruct_deflections(const double *d_g1, const double *d_g2, 
                                         long long n_rays, double lambda, double tol, int max_iter, double *d_f,
                                         photon_tomo_stats_t *stats, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 11: displacement uncertainty per vector from correlation statistics (Wieneke 2015): the a posteriori
+ * uncertainty (sigma_x, sigma_y) in pixels of section 5's estimator, from the converged image pair alone.  Host model:
+ * photon_amd/piv_uncertainty.py (uncertainty_model, f64); driver: PhotonLibrary.displacement_uncertainty.
+ *   d_im1, d_im2  device f32[height*width], row-major: a MATCHED pair -- both frames warped by the field whose
+ *             uncertainty is asked for (photon_piv_deform with scale -1/2 on frame 1 and +1/2 on frame 2), so that
+ *             what is left between them is noise.  The call does not warp.
+ *   win, step and the window grid (n_rows, n_cols, window k = i n_cols + j) are section 5's, at zero offset.
+ *   reach     K in [0, 4]: the neighbourhood over which the covariance of the pixel contributions is summed.
+ * All arithmetic is f64 on the f32 pixels.  Per window: a, b the win^2 pixels of im1, im2; ma, mb their means;
+ * A = a - ma, B = b - mb.  The window is flat when all pixels of a are equal or all pixels of b are equal (decided from
+ * the smallest and the largest pixel, as in section 5): flag 2, both sigma and all eight stats NaN.
+ * Axis x, e = one column, pixel set P = {(r, q): q <= win - 2} (axis y: rows and columns swap roles, e = one row,
+ * P = {(r, q): r <= win - 2}):
+ *   d(p)  = A(p) B(p + e) - A(p + e) B(p)                       (the two products are separate IEEE multiplications: identical
+ *                                                               frames give d = 0 exactly)
+ *   C1    = 1/2 sum_P [A(p) B(p + e) + A(p + e) B(p)]            the correlation at shift +-e, symmetrised
+ *   C0    = 1/2 sum_P [A(p) B(p) + A(p + e) B(p + e)]            the correlation at zero shift over the same pixels
+ *   S(D)  = sum d(p) d(p + D) over the p with p and p + D both in P
+ *   V     = S(0) + 2 sum_{D in H_K} S(D),  H_K = {(Dr, Dq): 0 <= Dr <= K, |Dq| <= K, Dr > 0 or Dq > 0}: S is symmetric
+ *           in D, so this is the sum over the full (2K + 1)^2 neighbourhood -- the variance of C(+e) - C(-e) with the
+ *           spatial covariance of its terms out to K pixels.
+ *   V < 0 or NaN:  V = S(0), flag 32.
+ *   s = sqrt(V), lo = C1 - s/2, hi = C1 + s/2.
+ *   lo > 0 and C0 > 0:  num = ln hi - ln lo,  den = (4 ln C0 - 2 ln lo) - 2 ln hi    (section 5's three-point Gaussian
+ *                       fit through (lo, C0, hi): the peak displaced by +-s/2)
+ *   otherwise:          num = hi - lo,        den = 4 (C0 - C1)                      (the parabolic fit)
+ *   sigma = num / den when den > 0; otherwise sigma = NaN, flag 16 (no maximum at zero shift: the pair is not matched).
+ * The mean-subtracted products and the fit are section 5's on purpose: sigma is the uncertainty of that estimator.
+ *   d_sigma   device f32[n][2] (sigma_x, sigma_y), each rounded once from f64
+ *   d_flags   device int[n], bits: 2 flat window, 16 no maximum at zero shift (either axis), 32 V < 0 replaced by S(0)
+ *             (either axis)
+ *   d_stats   device f64[n][2][4] or NULL: (C0, C1, S(0), V) of axis x, then of axis y; V as summed, before the
+ *             replacement of flag 32
+ * d_sigma == NULL: only *n_rows / *n_cols are written; nothing is launched.
+ * Refused (1, one stderr line, nothing written, no launch): win not 16 / 32 / 64, step < 1, reach outside [0, 4], an
+ * image smaller than one window, a null image pointer, d_sigma without d_flags.  Asynchronous on `stream`, no device
+ * scratch.  Every sum has a fixed order: two calls on the same inputs return the same bits.  The device sums V as
+ * sum_p d(p) (d(p) + 2 sum_{H_K} d(p + D)) and need not agree with the model to the last bit: tests hold the stats to the
+ * model within 1e-11 of the sums of the absolute terms.
+ * Known limits: correlation statistics see the noise of the pair only -- not bias, peak locking, or the truncation
+ * error of a field that varies inside a window; sigma underestimates the error where those dominate (low image noise,
+ * win 16): DESIGN.md section 4.3h. */
+int photon_piv_uncertainty(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int reach,
+                           float *d_sigma, int *d_flags, double *d_stats, int *n_rows, int *n_cols, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

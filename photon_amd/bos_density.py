@@ -9,6 +9,9 @@ on arrays, ``PhotonLibrary.integrate_gradient_ptr`` on raw device pointers).  Th
 * ``solve_direct``: a dense least-squares minimiser of the same energy for small grids, built from the edge list and not
   from the normal equations: an independent reference;
 * ``weights_from_correlation``: 0 for median-test outliers, flat windows and vectors that are not finite, 1 otherwise;
+* ``weights_from_uncertainty``: the same zeros, and w = median(sigma^2) / sigma^2 (capped) elsewhere, sigma the displacement
+  uncertainty per vector of section 11 (photon_amd.piv_uncertainty); ``gradient_uncertainty`` and
+  ``projected_density_uncertainty`` carry sigma through the physics and through section 6's minimiser to an error bar on phi;
 * the physics that turns a displacement field into the gradient of the projected density, and its truth:
   ``displacement_factor``, ``node_geometry``, ``gradients_from_displacements``, ``chief_ray_projection``;
 * ``reconstruct``: correlate an image pair on the device, weigh, convert, integrate.
@@ -217,6 +220,27 @@ def weights_from_correlation(vectors, flags, outliers) -> np.ndarray:
     return np.where(bad, 0.0, 1.0)
 
 
+def weights_from_uncertainty(sigma, flags, outliers, floor: float = 0.25) -> np.ndarray:
+    """Integration weights w = 1 / sigma^2, scaled to a median of 1.  sigma [n_rows, n_cols, 2] = (sigma_x, sigma_y) px
+    (``PhotonLibrary.displacement_uncertainty``), flags and outliers as weights_from_correlation takes them.  The weight is 0
+    wherever weights_from_correlation gives 0 (median-test outliers, flat windows) and where sigma is not finite.  On the
+    kept nodes, with s^2 = sigma_x^2 + sigma_y^2 and m^2 the median of s^2 over them, w = m^2 / max(s^2, (floor m)^2): the
+    median weight is 1, so the solver's `tol` keeps its meaning, and no node outweighs the median by more than
+    1 / floor^2 (a sigma of nearly 0 is an artefact of a window with hardly any noise in it, not 1000 times the
+    information).  Equal sigma everywhere reproduces weights_from_correlation."""
+    sg = np.asarray(sigma, np.float64)[..., :2]
+    floor = float(floor)
+    if not (np.isfinite(floor) and 0.0 < floor <= 1.0):
+        raise ValueError(f"floor must lie in (0, 1], not {floor}")
+    keep = weights_from_correlation(sg, flags, outliers) > 0
+    s2 = (sg * sg).sum(axis=-1)
+    w = np.zeros(s2.shape)
+    if keep.any():
+        m2 = float(np.median(s2[keep]))
+        w[keep] = m2 / np.maximum(s2[keep], floor * floor * m2) if m2 > 0 else 1.0
+    return w
+
+
 # ---- physics ------------------------------------------------------------------------------------------------------------
 def _magnification(call) -> float:
     return float(call.image_distance) / float(call.object_distance)
@@ -261,6 +285,59 @@ def gradients_from_displacements(disp_px, camera, factor: float):
     return sx * d[..., 0] / factor, sy * d[..., 1] / factor
 
 
+def gradient_uncertainty(sigma_px, camera, factor: float):
+    """Displacement uncertainties [..., 2] = (sigma_x, sigma_y) px -> (sigma_gx, sigma_gy): gradients_from_displacements'
+    linear map by absolute value (the axis flips of the splats change no standard deviation)."""
+    s = np.abs(np.asarray(sigma_px, np.float64))
+    return s[..., 0] / abs(float(factor)), s[..., 1] / abs(float(factor))
+
+
+def projected_density_uncertainty(sigma_gx, sigma_gy, w=None, fixed=None, hx=1.0, hy=1.0):
+    """The standard deviation of section 6's minimiser phi from those of its input gradients, by linear propagation: for
+    fixed weights phi = J_x g_x + J_y g_y + const, and with the nodes' errors independent
+    sigma_phi^2(k) = sum_j J_x[k, j]^2 sigma_gx[j]^2 + J_y[k, j]^2 sigma_gy[j]^2.  Arrays [ny, nx] as integrate_model takes
+    them (w None = 1, fixed None = the outer frame); a node whose sigma is not finite counts as invalid, like a gradient
+    that is not finite.  Returns sigma_phi [ny, nx]: 0 on the fixed nodes, NaN where phi is NaN.
+    Limits: J is built densely over the edge list like solve_direct (the pseudo-inverse of an edges x unknowns matrix): a few
+    thousand unknowns, host only.  The nodes are treated as independent although overlapping windows share pixels (at 50 %
+    overlap neighbouring vectors correlate, and the true error bar of a smooth phi is wider than this one); the weights are
+    taken as given, not as functions of the data; the uncertainty of the fixed values is not included."""
+    wh, _, wv, _, fixed, _ = edges(sigma_gx, sigma_gy, w, fixed, None, hx, hy)
+    sgx, sgy = np.asarray(sigma_gx, np.float64), np.asarray(sigma_gy, np.float64)
+    ny, nx = fixed.shape
+    solve = reachable(wh, wv, fixed)
+    s = solve.ravel()
+    k = np.arange(ny * nx).reshape(ny, nx)
+    nh = wh.size
+    a = np.concatenate([k[:, :-1].ravel(), k[:-1, :].ravel()])
+    b = np.concatenate([k[:, 1:].ravel(), k[1:, :].ravel()])
+    we = np.concatenate([wh.ravel(), wv.ravel()])
+    horizontal = np.arange(a.size) < nh
+    use = (we > 0) & (s[a] | s[b])
+    a, b, we, horizontal = a[use], b[use], we[use], horizontal[use]
+    n_unknown = int(s.sum())
+    out = np.where(fixed, 0.0, np.nan).ravel()
+    if n_unknown:
+        col = -np.ones(ny * nx, np.int64)
+        col[s] = np.arange(n_unknown)
+        D = np.zeros((a.size, n_unknown))
+        for sign, node in ((1.0, b), (-1.0, a)):
+            unk = s[node]
+            D[np.nonzero(unk)[0], col[node[unk]]] += sign
+        sq = np.sqrt(we)
+        M = np.linalg.pinv(D * sq[:, None]) * sq[None, :]           # phi = M t over the edges' targets t
+        var = np.zeros(n_unknown)
+        for sel, h, sg in ((horizontal, float(hx), sgx), (~horizontal, float(hy), sgy)):
+            # t_e = h (g_a + g_b) / 2: column j of J collects the edges that touch node j
+            J = np.zeros((n_unknown, ny * nx))
+            for node in (a[sel], b[sel]):
+                np.add.at(J.T, node, (0.5 * h * M[:, sel]).T)
+            touched = np.abs(J).sum(axis=0) > 0
+            var += (J[:, touched] ** 2) @ (sg.ravel()[touched] ** 2)
+        out[s] = np.sqrt(var)
+    return out.reshape(ny, nx)
+
+
 def chief_ray_projection(rho_fn, target_xy, object_distance: float, z_range, rho_0: float = RHO_0, samples: int = 2000):
     """The truth: P = int (rho - rho_0) ds along each node's chief ray, from its target-plane point (X_t, Y_t) at distance
     object_distance toward the lens centre, across z in z_range = (z0, z1) (midpoint rule, `samples` steps).
@@ -284,18 +361,24 @@ def gaussian_projection(r2, amplitude: float, sigma: float):
 
 
 def measured_gradients(vectors, flags, shape, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16,
-                       weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+                       weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, sigma=None):
     """What a correlation measures, before any integration: (gx, gy, w, target-plane nodes (X_t, Y_t), mid-plane nodes
     (X, Y), spacing h).  gx, gy [n_rows, n_cols]: int grad (rho - rho_0) ds along each node's chief ray, along the grid's
     columns and rows; w the weights (`weights`: "median" = weights_from_correlation after the normalised median test,
-    "unit" = 1 wherever the vector is finite)."""
+    "unit" = 1 wherever the vector is finite, "uncertainty" = weights_from_uncertainty with the same zeros as "median"
+    and `sigma` [n_rows, n_cols, 2], the vectors' uncertainty from ``PhotonLibrary.displacement_uncertainty``)."""
     from . import piv_correlation as pc
     if weights == "median":
         w = weights_from_correlation(vectors, flags, pc.normalized_median_test(vectors))
     elif weights == "unit":
         w = np.where(np.isfinite(np.asarray(vectors, np.float64)[..., :2]).all(axis=-1), 1.0, 0.0)
+    elif weights == "uncertainty":
+        if sigma is None:
+            raise ValueError("weights='uncertainty' needs sigma, the uncertainty of the vectors")
+        bad = weights_from_correlation(vectors, flags, pc.normalized_median_test(vectors)) == 0
+        w = weights_from_uncertainty(sigma, flags, bad)
     else:
-        raise ValueError(f"weights must be 'median' or 'unit', not {weights!r}")
+        raise ValueError(f"weights must be 'median', 'unit' or 'uncertainty', not {weights!r}")
     gx, gy = gradients_from_displacements(pc.sensor_displacements(vectors, call.camera), call.camera,
                                           displacement_factor(call, origin_z, extent_z, K, rho_0))
     target, mid, h = node_geometry(shape, win, step, call, origin_z, extent_z)
@@ -303,34 +386,44 @@ def measured_gradients(vectors, flags, shape, call, origin_z: float, extent_z: f
 
 
 def integrate_vectors(lib, vectors, flags, shape, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16,
-                      weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+                      weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, sigma=None):
     """Projected density from a correlation's vectors [n_rows, n_cols, >= 2] and flags on an image of `shape`: weights
     (`weights`: "median" = weights_from_correlation after the normalised median test, "unit" = 1 wherever the vector is
-    finite), gradients, integration on the device with the frame fixed at P = 0 (the frame must lie where the density is
-    ambient).  Returns (phi [n_rows, n_cols] kg/m^3 um, mid-plane nodes (X, Y), stats dict)."""
-    gx, gy, w, _, mid, h = measured_gradients(vectors, flags, shape, call, origin_z, extent_z, win, step, weights, K, rho_0)
+    finite, "uncertainty" = weights_from_uncertainty of `sigma`, the vectors' uncertainty), gradients, integration on the
+    device with the frame fixed at P = 0 (the frame must lie where the density is ambient).  Returns (phi [n_rows, n_cols]
+    kg/m^3 um, mid-plane nodes (X, Y), stats dict)."""
+    gx, gy, w, _, mid, h = measured_gradients(vectors, flags, shape, call, origin_z, extent_z, win, step, weights, K, rho_0, sigma)
     phi, stats = lib.integrate_gradient(gx, gy, w, hx=h, hy=h, tol=tol)
     return phi, mid, stats
 
 
+def _pair_uncertainty(lib, im1, im2, vectors, win, step, weights, reach):
+    """sigma of the vectors measured on the pair when the weights ask for it (None otherwise)."""
+    return lib.displacement_uncertainty(im1, im2, vectors, win=win, step=step, reach=reach)[0] if weights == "uncertainty" else None
+
+
 def reconstruct(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, passes: int = 2,
-                weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+                weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, reach: int = 2):
     """Projected density from a BOS image pair (im1 without, im2 through the volume; torch device tensors or numpy):
-    ``PhotonLibrary.correlate`` (`passes`), then integrate_vectors.  Returns (phi, mid-plane nodes (X, Y), stats)."""
+    ``PhotonLibrary.correlate`` (`passes`), with weights="uncertainty" ``PhotonLibrary.displacement_uncertainty`` of the
+    measured vectors on the same pair (`reach`), then integrate_vectors.  Returns (phi, mid-plane nodes (X, Y), stats)."""
     vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
-    return integrate_vectors(lib, vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step, weights, tol, K, rho_0)
+    sigma = _pair_uncertainty(lib, im1, im2, vectors, win, step, weights, reach)
+    return integrate_vectors(lib, vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step, weights, tol, K, rho_0,
+                             sigma)
 
 
 def deflection_data(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, passes: int = 2,
-                    weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+                    weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, reach: int = 2):
     """The deflections of a BOS image pair, for tomography without the per-view integral (``reconstruct`` up to, but
-    excluding, the integration): ``PhotonLibrary.correlate`` (`passes`), then measured_gradients.  Returns (g1, g2, w,
+    excluding, the integration): ``PhotonLibrary.correlate`` (`passes`), with weights="uncertainty"
+    ``PhotonLibrary.displacement_uncertainty`` (`reach`), then measured_gradients.  Returns (g1, g2, w,
     target-plane nodes (X_t, Y_t)), g1 = gx and g2 = gy [n_rows, n_cols]: the data of
     ``PhotonLibrary.tomo_reconstruct_deflections`` with the rays of tomography.view_rays and the vectors of
     tomography.view_frames at the same nodes."""
     vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
     gx, gy, w, target, _, _ = measured_gradients(vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step,
-                                                 weights, K, rho_0)
+                                                 weights, K, rho_0, _pair_uncertainty(lib, im1, im2, vectors, win, step, weights, reach))
     return gx, gy, w, target
 
 

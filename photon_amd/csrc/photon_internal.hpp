@@ -21,6 +21,7 @@
 //   photon_moments.hip       per-source sensor moments: the reduction of a launch's moments block into records
 //   photon_flow.hip          velocity fields on a grid, the PIV field advected through one
 //   photon_piv_deform.hip    image-deformation correlation: B-spline coefficients, warp, validate-and-update
+//   photon_piv_uncertainty.hip   displacement uncertainty per vector from correlation statistics
 #pragma once
 #include <hip/hip_runtime.h>
 

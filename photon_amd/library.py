@@ -5,8 +5,8 @@ Three layers, top to bottom of the file:
     loaded library.  The header is the source of truth; tests/test_abi.py holds the table against its prototypes.
   * ``PhotonLibrary``: one method per entry point -- marshalling only, raw device pointers in, return code checked -- and
     on top of those the pipelines that chain several calls on torch-allocated device buffers on the current stream
-    (``correlate``, ``correlate_deform``, ``correlation_predictor``, ``track_dots``, ``integrate_gradient``, the
-    tomography solvers).
+    (``correlate``, ``correlate_deform``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
+    ``integrate_gradient``, the tomography solvers).
   * ``Volume``, ``Sources``, ``Flow``, ``Scene``: the library's handles.
 All arithmetic is the HIP library's.  There is no Python or CPU fallback -- if the library is missing or a call fails,
 you get an exception.
@@ -168,6 +168,8 @@ def _signatures():
         "photon_tomo_deflect": (ci, [vp] + grid_frames + [vp, vp, vp]),
         "photon_tomo_deflect_adjoint": (ci, [vp, vp] + grid_frames + [vp, vp]),
         "photon_tomo_reconstruct_deflections": (ci, [vp, vp, vp, vp] + grid_frames + solve),
+        # section 11: displacement uncertainty from correlation statistics
+        "photon_piv_uncertainty": (ci, [vp, vp] + [ci] * 5 + [vp] * 3 + [P(ci), P(ci), vp]),
     }
 
 
@@ -520,6 +522,52 @@ class PhotonLibrary:
                               status.data_ptr(), eps, threshold, stream)
         out = torch.cat([field[cur], vec[..., 2:4]], dim=-1)
         return out.cpu().numpy(), status.cpu().numpy()
+
+    # ---- displacement uncertainty from correlation statistics (section 11) -------------------------------------------------
+    def piv_uncertainty(self, d_im1_ptr: int, d_im2_ptr: int, width: int, height: int, win: int, step: int, reach: int = 2,
+                        stats: bool = False, stream: int = 0):
+        """photon_piv_uncertainty on a matched pair of device f32 images (raw pointers, row-major height x width).  Returns
+        torch device tensors (sigma [n_rows, n_cols, 2] f32 = sigma_x, sigma_y in pixels; flags [n_rows, n_cols] int32; stats
+        [n_rows, n_cols, 2, 4] f64 = (C0, C1, S(0), V) per axis, or None), filled asynchronously on `stream`.  The
+        definition: include/parallel_ray_tracing.h, section 11 (photon_amd.piv_uncertainty: host model)."""
+        import torch
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        args = ("photon_piv_uncertainty", _vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(reach))
+        self._call(*args, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
+        r, c = rows.value, cols.value
+        dev, _ = _device_and_stream()
+        sigma = torch.empty((r, c, 2), dtype=torch.float32, device=dev)
+        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
+        st = torch.empty((r, c, 2, 4), dtype=torch.float64, device=dev) if stats else None
+        self._call(*args, _vp(sigma.data_ptr()), _vp(flags.data_ptr()), _vp(st.data_ptr()) if stats else None, None, None, _vp(stream))
+        return sigma, flags, st
+
+    def displacement_uncertainty(self, im1, im2, field, win: int = 32, step: int = 16, reach: int = 2, return_warped: bool = False):
+        """Uncertainty (sigma_x, sigma_y) in pixels of every vector of a displacement field on section 5's grid, whatever
+        measured it (``correlate``, ``correlate_deform``, window means of tracked dots): the B-spline coefficients of both
+        frames, frame 1 warped by -field / 2 and frame 2 by +field / 2 (photon_piv_deform), photon_piv_uncertainty on the
+        warped pair (model: photon_amd.piv_uncertainty.displacement_uncertainty_model).  im1, im2: torch device tensors or
+        numpy [height, width]; field [n_rows, n_cols, >= 2] (dx, dy first), numpy or a device tensor; a vector that is not
+        finite reads as (0, 0).  Returns numpy (sigma [n_rows, n_cols, 2] f32, flags [n_rows, n_cols] int32: bits 2, 16, 32
+        of section 11); with return_warped also the two warped images as torch device tensors.  Everything runs on the
+        current stream; the host waits once, for the result."""
+        import torch
+        from . import piv_correlation as pc
+        from . import piv_uncertainty as pu
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        pu.check_arguments((h, w), win, step, reach)
+        fld = torch.as_tensor(field).to(device=dev, dtype=torch.float32)
+        r, c = pc.grid_shape((h, w), win, step)
+        if fld.dim() != 3 or fld.shape[2] < 2 or tuple(fld.shape[:2]) != (r, c):
+            raise ValueError(f"field must be [{r}, {c}, >= 2]: the grid of a {h} x {w} image, win {win}, step {step}")
+        fld = (fld if fld.shape[2] in (2, 4) else fld[..., :2]).contiguous()
+        coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=dev), torch.empty((2, h, w), dtype=torch.float32, device=dev)
+        for k, (im, scale) in enumerate(((a, -0.5), (b, 0.5))):
+            self.bspline_coefficients(im.data_ptr(), w, h, coef[k].data_ptr(), stream)
+            self.piv_deform(coef[k].data_ptr(), w, h, fld.data_ptr(), int(fld.shape[2]), r, c, win, step, scale, warped[k].data_ptr(), stream)
+        sigma, flags, _ = self.piv_uncertainty(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, reach, stream=stream)
+        out = (sigma.cpu().numpy(), flags.cpu().numpy())
+        return (*out, warped[0], warped[1]) if return_warped else out
 
     # ---- dot tracking on the device (section 8) ---------------------------------------------------------------------------
     def dots_scratch_bytes(self, width: int, height: int, radius: Optional[float] = None, max1: int = 0, max2: int = 0) -> int:
