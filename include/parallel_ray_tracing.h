@@ -1048,6 +1048,69 @@ int photon_tomo_reconstruct_deflections(const double *d_g1, const double *d_g2, 
 int photon_piv_uncertainty(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int reach,
                            float *d_sigma, int *d_flags, double *d_stats, int *n_rows, int *n_cols, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 12: dense optical flow on an image pair (Horn & Schunck 1981; Brox et al. 2004; Atcheson et al. 2009 for BOS):
+ * one displacement vector per pixel where sections 5, 7 and 8 report one per window or dot.  The flow refines a predictor
+ * (a correlation's field) and has no image pyramid.  Host model: photon_amd/optical_flow.py; driver:
+ * PhotonLibrary.optical_flow.  Every call is asynchronous on `stream`, allocates nothing (scratch comes from the caller)
+ * and returns the same bits for the same inputs.  Inputs are finite f32; a pixel or a vector that is not finite is outside
+ * the contract, except where section 7b's rule is inherited.  A dense field is f32[height*width][2] = (dx, dy) per pixel,
+ * row-major.
+ *
+ * a. photon_piv_field_to_pixels.  d_dense = section 7b's dense displacement D of the grid field (d_field, field_stride,
+ *    n_rows, n_cols, win, step as section 7b takes them) at every pixel, in exactly the f32 operations of photon_piv_deform
+ *    (the same device function); a vector with a component that is not finite reads as (0, 0).
+ *    Refused: section 7b's rules for win, step, the image size (a side of more than 2^22 pixels included) and the grid,
+ *    field_stride not 2 or 4, a null pointer.
+ *
+ * b. photon_piv_deform_dense.  Section 7b's warp with D read per pixel from d_dense instead of interpolated:
+ *    s = clamp(scale D, -2^24, 2^24), the same taps, weights and order (one kernel template over where D comes from):
+ *    photon_piv_deform_dense of photon_piv_field_to_pixels(F) equals photon_piv_deform(F) bit for bit.
+ *    Refused: width or height < 1 or larger than 2^22, a scale that is not finite, a null pointer, d_out == d_coef.
+ *
+ * c. photon_optflow_terms.  d_w1, d_w2: a matched pair, frame 1 warped by -u0 / 2 and frame 2 by +u0 / 2; d_u0 the dense
+ *    field u0 they were warped by, or NULL for a zero field.  d_terms f32[height*width][4] = (Ix, Iy, c, w) per pixel
+ *    (row r, column q), every step one IEEE f32 operation in this order:
+ *      a = gain w1, b = gain w2, m = (a + b) 0.5
+ *      Ix = ((m(q-2) - m(q+2)) + 8 (m(q+1) - m(q-1))) / 12 along the row, Iy the same along the column, indices by
+ *           section 7's whole-sample mirror
+ *      It = b - a
+ *      c  = (It - Ix u0x) - Iy u0y
+ *      w  = 1 / ((alpha2 + Ix Ix) + Iy Iy)
+ *    Refused: width or height < 1, gain or alpha2 not finite or not > 0, a null d_w1, d_w2 or d_terms.
+ *
+ * d. photon_optflow_iterate.  `iterations` Jacobi sweeps of Horn-Schunck on the total field, starting from d_u.  Per
+ *    pixel, neighbour indices clamped to the image (Neumann boundary), all pixels updated from the previous sweep:
+ *      ub = ((u(q-1) + u(q+1)) + (u(r-1) + u(r+1))) 0.25, vb likewise
+ *      rho = ((Ix ub + Iy vb) + c) w
+ *      u' = ub - Ix rho, v' = vb - Iy rho
+ *    This relaxes the Euler-Lagrange equations of  sum (Ix du + Iy dv + It)^2 + alpha2 |grad (u0 + du)|^2  (du = u - u0;
+ *    alpha2 counted per 4-neighbour average).  The result is always in d_out; iterations = 0 copies d_u.  One launch
+ *    performs up to T = photon_optflow_iterations_per_launch() sweeps (a workgroup recomputes a halo of T pixels around
+ *    its tile; the halo clamps by image coordinates, so the bits are those of single sweeps); d_tmp f32[height*width][2]
+ *    is needed only when iterations > T and may be NULL otherwise.
+ *    Refused: width or height < 1, iterations < 0, a null d_terms, d_u or d_out, d_out == d_u, d_tmp equal to either,
+ *    iterations > T without d_tmp.
+ *
+ * e. photon_optflow_iterations_per_launch: T, a pure query (PHOTON_OPTFLOW_SWEEPS = 1 .. 8 overrides it for measurements).
+ * Every refusal: 1, one stderr line, nothing written, no launch.
+ *
+ * Driver (PhotonLibrary.optical_flow; optical_flow.optical_flow_model): the coefficients of both frames once; the
+ * predictor spread to pixels (a) -- None: one iteration of correlate_deform; gain = 1 / std(frame 1); per warp: (b) on
+ * frame 1 with scale -1/2 and on frame 2 with +1/2, (c) with the current field, (d).
+ * Known limits: quadratic penalties only (no robust norm: the field is smoothed across a discontinuity); no pyramid -- a
+ * predictor off by more than about a particle diameter is not recovered; the field refers to the mid-point frame, as in
+ * section 7.  DESIGN.md section 4.3i. */
+int photon_piv_field_to_pixels(const float *d_field, int field_stride, int n_rows, int n_cols, int win, int step, int width,
+                               int height, float *d_dense, void *stream);
+int photon_piv_deform_dense(const float *d_coef, int width, int height, const float *d_dense, float scale, float *d_out,
+                            void *stream);
+int photon_optflow_terms(const float *d_w1, const float *d_w2, int width, int height, const float *d_u0, float gain, float alpha2,
+                         float *d_terms, void *stream);
+int photon_optflow_iterate(const float *d_terms, const float *d_u, int width, int height, int iterations, float *d_out,
+                           float *d_tmp, void *stream);
+int photon_optflow_iterations_per_launch(void);
+
 #ifdef __cplusplus
 }
 #endif

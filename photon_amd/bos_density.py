@@ -14,7 +14,8 @@ on arrays, ``PhotonLibrary.integrate_gradient_ptr`` on raw device pointers).  Th
   ``projected_density_uncertainty`` carry sigma through the physics and through section 6's minimiser to an error bar on phi;
 * the physics that turns a displacement field into the gradient of the projected density, and its truth:
   ``displacement_factor``, ``node_geometry``, ``gradients_from_displacements``, ``chief_ray_projection``;
-* ``reconstruct``: correlate an image pair on the device, weigh, convert, integrate.
+* ``reconstruct``: correlate an image pair on the device, weigh, convert, integrate; ``reconstruct_tracked`` and
+  ``reconstruct_flow``: the same from tracked dots and from dense optical flow.
 
 Physics (the paraxial BOS relation photon states as epsilon = Delta pitch / (M Z_D), d(rho)/dx = epsilon n_0 / (K dz)).
 With P = int (rho - rho_0) ds (kg/m^3 um) along the chief ray and the gradient taken along world x, y in the volume's
@@ -442,3 +443,21 @@ def reconstruct_tracked(lib, im1, im2, call, origin_z: float, extent_z: float, w
     res = lib.track_dots(im1, im2, threshold, relative=relative, grid=(win, step, min_count, 0), **track)
     return integrate_vectors(lib, res["vectors"], res["flags"], tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step,
                              weights, tol, K, rho_0)
+
+
+def reconstruct_flow(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, alpha2: float = 5.0,
+                     warps: int = 3, iterations: int = 48, tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0):
+    """Projected density from a BOS image pair by dense optical flow: one iteration of ``PhotonLibrary.correlate_deform`` on
+    the (win, step) grid as the predictor, ``PhotonLibrary.optical_flow`` from it (`alpha2`, `warps`, `iterations`), the
+    dense field read at the window centres, then the integration of ``integrate_vectors``.  The weights are the
+    predictor's: 0 where its correlation is flat or not finite or fails the normalised median test -- the flow starts from
+    that vector and cannot be trusted to recover there -- 1 elsewhere.  Returns (phi, mid-plane nodes (X, Y), stats)."""
+    from . import piv_correlation as pc
+    pred, status = lib.correlate_deform(im1, im2, win=win, step=step, iterations=1)
+    _, grid = lib.optical_flow(im1, im2, predictor=pred[..., :2], win=win, step=step, alpha2=alpha2, warps=warps, iterations=iterations,
+                               return_grid=True)
+    w = weights_from_correlation(pred, status, pc.normalized_median_test(pred))
+    gx, gy, _, _, mid, h = measured_gradients(grid, status, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step, "unit", K,
+                                              rho_0)
+    phi, stats = lib.integrate_gradient(gx, gy, w, hx=h, hy=h, tol=tol)
+    return phi, mid, stats

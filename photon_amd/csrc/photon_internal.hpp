@@ -22,6 +22,7 @@
 //   photon_flow.hip          velocity fields on a grid, the PIV field advected through one
 //   photon_piv_deform.hip    image-deformation correlation: B-spline coefficients, warp, validate-and-update
 //   photon_piv_uncertainty.hip   displacement uncertainty per vector from correlation statistics
+//   photon_optflow.hip       dense optical flow: per-pixel warp (piv_warp.hpp, shared with photon_piv_deform.hip), data terms, fused Jacobi sweeps
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -5,7 +5,7 @@
 //
 //   bspline_coefficients_kernel   one workgroup per 32 x 64 tile: the tile and a 14-pixel mirrored halo in LDS, the
 //                                 29-tap FIR along the rows into a second LDS plane, then along the columns to memory
-//   deform_kernel                 one thread per output pixel: bilinear weights of the grid from integer arithmetic, 16
+//   deform_kernel (piv_warp.hpp)  one thread per output pixel: bilinear weights of the grid from integer arithmetic, 16
 //                                 coefficient taps gathered from global memory (the coefficient image of a 1024^2 frame
 //                                 is 4 MB: it stays in L2), one coalesced store
 //   validate_kernel               one workgroup per 16 x 16 nodes: the totals of a 22 x 22 neighbourhood in LDS, the
@@ -16,27 +16,12 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_warp.hpp"
 
 using namespace photon;
+using namespace photon::piv_warp;
 
 namespace {
-
-// whole-sample mirror of any index into [0, n): ... 2 1 | 0 1 2 ... n-2 n-1 | n-2 n-3 ...
-// An index within n - 1 of the image needs one reflection; the division is kept out of line for the others, so that the
-// compiler cannot flatten it into the common path (it was 2/3 of the warp's instructions).
-__device__ __noinline__ int mirror_far(int i, int n) {
-    if (n == 1) return 0;
-    const int period = 2 * (n - 1);
-    int m = i % period;
-    if (m < 0) m += period;
-    return m < n ? m : period - m;
-}
-__device__ __forceinline__ int mirror(int i, int n) {
-    int m = i < 0 ? -i : i;
-    m = m >= n ? 2 * (n - 1) - m : m;
-    if (__builtin_expect((unsigned)m >= (unsigned)n, 0)) m = mirror_far(i, n);
-    return m;
-}
 
 // =============================================================================================
 // a. coefficients
@@ -83,87 +68,7 @@ __global__ __launch_bounds__(kFirThreads) void bspline_coefficients_kernel(const
 // =============================================================================================
 // b. warp
 // =============================================================================================
-constexpr int kWarpX = 64, kWarpY = 4;
-constexpr float kMaxShift = 16777216.f;     // |scale D| is clamped to 2^24 pixels (section 7b)
-
-// node index and weight of the bilinear grid interpolation at pixel p: f = clamp((p - (win-1)/2) / step, 0, n - 1) from
-// the exact integers num = 2p - (win-1) and den = 2 step; i0 = floor(f) (at most n - 2 when n > 1), w = f - i0.  The
-// quotient comes from one f32 multiply by inv_den = 1 / den and is corrected by the exact remainder (num < 2^24).
-__device__ __forceinline__ void grid_weight(int p, int win, int step, float inv_den, int n, int &i0, int &i1, float &w) {
-    const int num = 2 * p - (win - 1), den = 2 * step;
-    if (num <= 0 || n == 1) {
-        i0 = i1 = 0;
-        w = 0.f;
-    } else if ((long long)num >= (long long)(n - 1) * den) {
-        i0 = i1 = n - 1;
-        w = 0.f;
-    } else {
-        int q = (int)((float)num * inv_den), r = num - q * den;
-        if (r < 0) {
-            q--;
-            r += den;
-        } else if (r >= den) {
-            q++;
-            r -= den;
-        }
-        i0 = q;
-        i1 = q + 1;
-        w = (float)r * inv_den;
-    }
-}
-
-__device__ __forceinline__ void node(const float *__restrict__ field, int stride, int k, float &dx, float &dy) {
-    dx = field[(size_t)k * stride];
-    dy = field[(size_t)k * stride + 1];
-    if (!(isfinite(dx) && isfinite(dy))) dx = dy = 0.f;
-}
-
-// cubic B-spline weights of the 4 taps floor(x) - 1 .. floor(x) + 2 at the fraction t
-__device__ __forceinline__ void bspline_weights(float t, float w[4]) {
-    const float u = 1.f - t, t2 = t * t, u2 = u * u;
-    w[0] = u2 * u * (1.f / 6.f);
-    w[1] = (4.f - 3.f * t2 * (2.f - t)) * (1.f / 6.f);
-    w[2] = (4.f - 3.f * u2 * (2.f - u)) * (1.f / 6.f);
-    w[3] = t2 * t * (1.f / 6.f);
-}
-
-__global__ __launch_bounds__(kWarpX *kWarpY) void deform_kernel(const float *__restrict__ coef, int W, int H,
-                                                                const float *__restrict__ field, int stride, int n_rows, int n_cols,
-                                                                int win, int step, float inv_den, float scale,
-                                                                float *__restrict__ out) {
-    const int q = blockIdx.x * kWarpX + threadIdx.x, r = blockIdx.y * kWarpY + threadIdx.y;
-    if (q >= W || r >= H) return;
-    int i0, i1, j0, j1;
-    float wy, wx;
-    grid_weight(r, win, step, inv_den, n_rows, i0, i1, wy);
-    grid_weight(q, win, step, inv_den, n_cols, j0, j1, wx);
-    float ax, ay, bx, by, cx, cy, ex, ey;
-    node(field, stride, i0 * n_cols + j0, ax, ay);
-    node(field, stride, i0 * n_cols + j1, bx, by);
-    node(field, stride, i1 * n_cols + j0, cx, cy);
-    node(field, stride, i1 * n_cols + j1, ex, ey);
-    const float tx = ax + wx * (bx - ax), ty = ay + wx * (by - ay);        // along the row of nodes i0, then i1, then between
-    const float ux = cx + wx * (ex - cx), uy = cy + wx * (ey - cy);
-    const float sx = fminf(fmaxf(scale * (tx + wy * (ux - tx)), -kMaxShift), kMaxShift);
-    const float sy = fminf(fmaxf(scale * (ty + wy * (uy - ty)), -kMaxShift), kMaxShift);
-    // the pixel index never enters a float: the fraction comes from the shift alone
-    const float fx = floorf(sx), fy = floorf(sy);
-    float wxs[4], wys[4];
-    bspline_weights(sx - fx, wxs);
-    bspline_weights(sy - fy, wys);
-    const int bx0 = q + (int)fx - 1, by0 = r + (int)fy - 1;
-    int xi[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) xi[t] = mirror(bx0 + t, W);
-    float acc = 0.f;
-#pragma unroll
-    for (int u = 0; u < 4; u++) {
-        const float *row = coef + (size_t)mirror(by0 + u, H) * W;
-        const float s = ((wxs[0] * row[xi[0]] + wxs[1] * row[xi[1]]) + wxs[2] * row[xi[2]]) + wxs[3] * row[xi[3]];
-        acc = acc + wys[u] * s;
-    }
-    out[(size_t)r * W + q] = acc;
-}
+// deform_kernel<GridField>: piv_warp.hpp, shared with the per-pixel warp of photon_optflow.hip
 
 // =============================================================================================
 // c. validate and update
@@ -330,15 +235,6 @@ __global__ __launch_bounds__(kValThreads) void validate_kernel(const float *__re
     }
 }
 
-// the argument rules the three entry points share with section 5; nullptr when the grid is fine
-const char *grid_error(int width, int height, int win, int step, int n_rows, int n_cols) {
-    if (win != 16 && win != 32 && win != 64) return "win must be 16, 32 or 64";
-    if (step < 1) return "step must be >= 1";
-    if (width < win || height < win) return "the image is smaller than one window";
-    if (n_rows != (height - win) / step + 1 || n_cols != (width - win) / step + 1) return "n_rows x n_cols is not the window grid of section 5";
-    return nullptr;
-}
-
 }  // namespace
 
 extern "C" int photon_piv_bspline_coefficients(const float *d_im, int width, int height, float *d_coef, void *stream_p) {
@@ -375,9 +271,9 @@ extern "C" int photon_piv_deform(const float *d_coef, int width, int height, con
                 step, width, height, n_rows, n_cols, field_stride, (double)scale);
         return 1;
     }
-    const dim3 grid((unsigned)((width + kWarpX - 1) / kWarpX), (unsigned)((height + kWarpY - 1) / kWarpY));
-    hipLaunchKernelGGL(deform_kernel, grid, dim3(kWarpX, kWarpY), 0, (hipStream_t)stream_p, d_coef, width, height, d_field, field_stride,
-                       n_rows, n_cols, win, step, 1.f / (float)(2 * step), scale, d_out);
+    const GridField D{d_field, field_stride, n_rows, n_cols, win, step, 1.f / (float)(2 * step)};
+    hipLaunchKernelGGL(deform_kernel<GridField>, warp_grid(width, height), dim3(kWarpX, kWarpY), 0, (hipStream_t)stream_p, d_coef, width, height, D,
+                       scale, d_out);
     PH_CHECK(hipGetLastError());
     return 0;
 }

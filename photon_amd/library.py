@@ -5,7 +5,7 @@ Three layers, top to bottom of the file:
     loaded library.  The header is the source of truth; tests/test_abi.py holds the table against its prototypes.
   * ``PhotonLibrary``: one method per entry point -- marshalling only, raw device pointers in, return code checked -- and
     on top of those the pipelines that chain several calls on torch-allocated device buffers on the current stream
-    (``correlate``, ``correlate_deform``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
+    (``correlate``, ``correlate_deform``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
     ``integrate_gradient``, the tomography solvers).
   * ``Volume``, ``Sources``, ``Flow``, ``Scene``: the library's handles.
 All arithmetic is the HIP library's.  There is no Python or CPU fallback -- if the library is missing or a call fails,
@@ -170,6 +170,12 @@ def _signatures():
         "photon_tomo_reconstruct_deflections": (ci, [vp, vp, vp, vp] + grid_frames + solve),
         # section 11: displacement uncertainty from correlation statistics
         "photon_piv_uncertainty": (ci, [vp, vp] + [ci] * 5 + [vp] * 3 + [P(ci), P(ci), vp]),
+        # section 12: dense optical flow
+        "photon_piv_field_to_pixels": (ci, [vp] + [ci] * 7 + [vp, vp]),
+        "photon_piv_deform_dense": (ci, [vp, ci, ci, vp, cf, vp, vp]),
+        "photon_optflow_terms": (ci, [vp, vp, ci, ci, vp, cf, cf, vp, vp]),
+        "photon_optflow_iterate": (ci, [vp, vp, ci, ci, ci, vp, vp, vp]),
+        "photon_optflow_iterations_per_launch": (ci, []),
     }
 
 
@@ -488,20 +494,15 @@ class PhotonLibrary:
                           stream)
         return vec, field, smoothed, status
 
-    def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
-                         residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0):
-        """Displacement field of an image pair by iterative image deformation (section 7; model:
-        photon_amd.piv_deformation.correlate_deform_model).  Pass 0 correlates the images with `radius` (None = win // 2);
-        every iteration warps both frames half-way by the validated, smoothed field, correlates the warped pair with
-        `residual_radius` and adds the residual.  Returns what ``correlate`` returns: numpy (vectors [n_rows, n_cols, 4] =
-        dx, dy of the last unsmoothed field, peak and ratio of the last correlation; status [n_rows, n_cols], section 5's
-        flags with bit 8 on replaced vectors).  Everything runs on the current stream; the host waits once, for the result."""
+    def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream):
+        """correlate_deform on the device images a, b, nothing copied back: (field [n_rows, n_cols, 2] of the last iteration,
+        vec [n_rows, n_cols, 4] of the last correlation, status [n_rows, n_cols]) as device tensors queued on `stream`."""
         import torch
         from . import piv_correlation as pc
         if int(iterations) < 0:
             raise ValueError(f"iterations must be >= 0, not {iterations}")
         radius = int(win) // 2 if radius is None else int(radius)
-        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        h, w = a.shape
         pc.check_arguments((h, w), win, step, radius)
         if int(iterations) > 0:
             pc.check_arguments((h, w), win, step, residual_radius)
@@ -520,7 +521,21 @@ class PhotonLibrary:
             cur ^= 1
             self.piv_validate(pred.data_ptr(), vec.data_ptr(), flg.data_ptr(), r, c, field[cur].data_ptr(), smoothed[cur].data_ptr(),
                               status.data_ptr(), eps, threshold, stream)
-        out = torch.cat([field[cur], vec[..., 2:4]], dim=-1)
+        return field[cur], vec, status
+
+    def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
+                         residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0):
+        """Displacement field of an image pair by iterative image deformation (section 7; model:
+        photon_amd.piv_deformation.correlate_deform_model).  Pass 0 correlates the images with `radius` (None = win // 2);
+        every iteration warps both frames half-way by the validated, smoothed field, correlates the warped pair with
+        `residual_radius` and adds the residual.  Returns what ``correlate`` returns: numpy (vectors [n_rows, n_cols, 4] =
+        dx, dy of the last unsmoothed field, peak and ratio of the last correlation; status [n_rows, n_cols], section 5's
+        flags with bit 8 on replaced vectors).  Everything runs on the current stream; the host waits once, for the result."""
+        import torch
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        field, vec, status = self._correlate_deform_device(a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev,
+                                                           stream)
+        out = torch.cat([field, vec[..., 2:4]], dim=-1)
         return out.cpu().numpy(), status.cpu().numpy()
 
     # ---- displacement uncertainty from correlation statistics (section 11) -------------------------------------------------
@@ -568,6 +583,77 @@ class PhotonLibrary:
         sigma, flags, _ = self.piv_uncertainty(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, reach, stream=stream)
         out = (sigma.cpu().numpy(), flags.cpu().numpy())
         return (*out, warped[0], warped[1]) if return_warped else out
+
+    # ---- dense optical flow on the device (section 12) --------------------------------------------------------------------
+    def field_to_pixels(self, d_field_ptr: int, field_stride: int, n_rows: int, n_cols: int, win: int, step: int, width: int, height: int,
+                        d_dense_ptr: int, stream: int = 0):
+        """photon_piv_field_to_pixels on raw device pointers: the grid's field at every pixel, f32 [height, width, 2]."""
+        self._call("photon_piv_field_to_pixels", _vp(d_field_ptr), int(field_stride), int(n_rows), int(n_cols), int(win), int(step), int(width),
+                   int(height), _vp(d_dense_ptr), _vp(stream))
+
+    def piv_deform_dense(self, d_coef_ptr: int, width: int, height: int, d_dense_ptr: int, scale: float, d_out_ptr: int, stream: int = 0):
+        """photon_piv_deform_dense on raw device pointers: the image of the coefficients warped by scale x a per-pixel field."""
+        self._call("photon_piv_deform_dense", _vp(d_coef_ptr), int(width), int(height), _vp(d_dense_ptr), float(scale), _vp(d_out_ptr),
+                   _vp(stream))
+
+    def optflow_terms(self, d_w1_ptr: int, d_w2_ptr: int, width: int, height: int, d_u0_ptr: int, gain: float, alpha2: float,
+                      d_terms_ptr: int, stream: int = 0):
+        """photon_optflow_terms on raw device pointers (d_u0_ptr: 0 = a zero field): (Ix, Iy, c, w) per pixel."""
+        self._call("photon_optflow_terms", _vp(d_w1_ptr), _vp(d_w2_ptr), int(width), int(height), _vp(d_u0_ptr), float(gain), float(alpha2),
+                   _vp(d_terms_ptr), _vp(stream))
+
+    def optflow_iterations_per_launch(self) -> int:
+        """T of photon_optflow_iterate: the sweeps one launch performs."""
+        return int(self.lib.photon_optflow_iterations_per_launch())
+
+    def optflow_iterate(self, d_terms_ptr: int, d_u_ptr: int, width: int, height: int, iterations: int, d_out_ptr: int,
+                        d_tmp_ptr: int = 0, stream: int = 0):
+        """photon_optflow_iterate on raw device pointers (d_tmp_ptr: 0 = NULL, accepted up to T iterations)."""
+        self._call("photon_optflow_iterate", _vp(d_terms_ptr), _vp(d_u_ptr), int(width), int(height), int(iterations), _vp(d_out_ptr),
+                   _vp(d_tmp_ptr), _vp(stream))
+
+    def optical_flow(self, im1, im2, predictor=None, win: int = 32, step: int = 16, alpha2: float = 5.0, warps: int = 3,
+                     iterations: int = 48, return_grid: bool = False):
+        """Dense displacement field of an image pair by optical flow (section 12; model:
+        photon_amd.optical_flow.optical_flow_model).  predictor: a vector grid [n_rows, n_cols, >= 2] of (win, step), numpy
+        or a device tensor, spread to the pixels on the device; or a dense field [height, width, 2]; or None: one iteration
+        of correlate_deform, kept on the device.  Per warp both frames are warped half-way by the current field, then the
+        data terms and `iterations` Jacobi sweeps.  Returns the field as numpy f32 [height, width, 2]; with return_grid also
+        the field at section 5's window centres [n_rows, n_cols, 2].  Everything runs on the current stream; the host waits
+        for the gain 1 / std(im1) (a scalar the terms take by value; the first kernels are queued before it) and for the
+        result."""
+        import torch
+        from . import optical_flow as of
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        of.check_driver_arguments(alpha2, warps, iterations)
+        inv_std = 1.0 / torch.std(a, correction=0)
+        if predictor is None:
+            predictor = self._correlate_deform_device(a, b, win, step, None, 1, 4, True, 0.1, 2.0, dev, stream)[0]
+        pred = torch.as_tensor(predictor).to(device=dev, dtype=torch.float32)
+        field = torch.empty((2, h, w, 2), dtype=torch.float32, device=dev)      # the current field and the next one
+        if of.predictor_shape(pred.shape, (h, w), win, step) == "grid":
+            pred = (pred if pred.shape[2] in (2, 4) else pred[..., :2]).contiguous()
+            self.field_to_pixels(pred.data_ptr(), int(pred.shape[2]), int(pred.shape[0]), int(pred.shape[1]), win, step, w, h,
+                                 field[0].data_ptr(), stream)
+        else:
+            field[0].copy_(pred)
+        coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=dev), torch.empty((2, h, w), dtype=torch.float32, device=dev)
+        terms = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
+        tmp = torch.empty((h, w, 2), dtype=torch.float32, device=dev) if int(iterations) > self.optflow_iterations_per_launch() else None
+        self.bspline_coefficients(a.data_ptr(), w, h, coef[0].data_ptr(), stream)
+        self.bspline_coefficients(b.data_ptr(), w, h, coef[1].data_ptr(), stream)
+        gain = float(inv_std)
+        cur = 0
+        for _ in range(int(warps)):
+            u = field[cur]
+            self.piv_deform_dense(coef[0].data_ptr(), w, h, u.data_ptr(), -0.5, warped[0].data_ptr(), stream)
+            self.piv_deform_dense(coef[1].data_ptr(), w, h, u.data_ptr(), 0.5, warped[1].data_ptr(), stream)
+            self.optflow_terms(warped[0].data_ptr(), warped[1].data_ptr(), w, h, u.data_ptr(), gain, alpha2, terms.data_ptr(), stream)
+            self.optflow_iterate(terms.data_ptr(), u.data_ptr(), w, h, iterations, field[cur ^ 1].data_ptr(),
+                                 tmp.data_ptr() if tmp is not None else 0, stream)
+            cur ^= 1
+        dense = field[cur].cpu().numpy()
+        return (dense, of.sample_at_window_centres(dense, win, step)) if return_grid else dense
 
     # ---- dot tracking on the device (section 8) ---------------------------------------------------------------------------
     def dots_scratch_bytes(self, width: int, height: int, radius: Optional[float] = None, max1: int = 0, max2: int = 0) -> int:

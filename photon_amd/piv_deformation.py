@@ -6,7 +6,8 @@ device pointers, ``PhotonLibrary.correlate_deform`` on arrays).  This module hol
 entry point, and the model of the driver:
 
 * ``bspline_coefficients_model``: the cubic B-spline coefficient image with whole-sample mirror boundaries;
-* ``dense_field`` and ``deform_model``: the grid's vectors interpolated to every pixel, and the image warped by them;
+* ``dense_field``, ``deform_model`` and ``deform_dense_model``: the grid's vectors interpolated to every pixel, and the image
+  warped by them or by any per-pixel field;
 * ``validate_model``: total, normalised median test, replacement, status and the smoothed predictor, in the operation
   order of section 7c (the device returns its f32 outputs bit for bit);
 * ``correlate_deform_model``: the driver on ``piv_correlation.correlate_model``.
@@ -85,12 +86,15 @@ def _bspline_weights(t):
     return np.stack([u * u * u, 4.0 - 3.0 * t * t * (2.0 - t), 4.0 - 3.0 * u * u * (2.0 - u), t * t * t]) / 6.0
 
 
-def deform_model(coef, field, win: int, step: int, scale: float) -> np.ndarray:
-    """Host model of photon_piv_deform in f64: out(r, q) = S(r + scale Dy, q + scale Dx), S the cubic B-spline of the
-    coefficient image `coef`, D = dense_field(field)."""
+def deform_dense_model(coef, dense, scale: float) -> np.ndarray:
+    """Host model of photon_piv_deform_dense in f64: out(r, q) = S(r + scale Dy, q + scale Dx), S the cubic B-spline of the
+    coefficient image `coef`, D = dense[r, q] = (Dx, Dy) given per pixel, [height, width, 2]."""
     c = np.asarray(coef, np.float64)
     h, w = c.shape
-    s = np.clip(float(scale) * dense_field(field, c.shape, win, step), -MAX_SHIFT, MAX_SHIFT)
+    d = np.asarray(dense, np.float64)
+    if d.shape != (h, w, 2):
+        raise ValueError(f"the dense field must be [{h}, {w}, 2], not {d.shape}")
+    s = np.clip(float(scale) * d, -MAX_SHIFT, MAX_SHIFT)
     fl = np.floor(s)
     wx, wy = _bspline_weights(s[..., 0] - fl[..., 0]), _bspline_weights(s[..., 1] - fl[..., 1])
     bx = np.arange(w)[None, :] + fl[..., 0].astype(np.int64) - 1
@@ -103,6 +107,11 @@ def deform_model(coef, field, win: int, step: int, scale: float) -> np.ndarray:
             row += wx[t] * c[yi, mirror_index(bx + t, w)]
         out += wy[u] * row
     return out
+
+
+def deform_model(coef, field, win: int, step: int, scale: float) -> np.ndarray:
+    """Host model of photon_piv_deform in f64: deform_dense_model with D = dense_field(field)."""
+    return deform_dense_model(coef, dense_field(field, np.shape(coef), win, step), scale)
 
 
 def _median_sorted(v, m):
