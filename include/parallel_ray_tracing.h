@@ -1111,6 +1111,67 @@ int photon_optflow_iterate(const float *d_terms, const float *d_u, int width, in
                            float *d_tmp, void *stream);
 int photon_optflow_iterations_per_launch(void);
 
+/* ------------------------------------------------------------------------------------
+ * Section 13: windowed FFT correlation of an image pair on the device: circular cross-correlation (mode 0) and robust
+ * phase correlation (mode 1; Eckstein & Vlachos 2009).  Where section 5 correlates amplitudes -- whatever does not move
+ * between the frames competes with the particles -- mode 1 keeps the phase of the cross spectrum only, weighted by the
+ * spectrum of a particle image; and the cost does not grow with the search radius.  Host models: photon_amd/piv_phase.py
+ * (correlate_phase_model_f32: this section operation by operation; correlate_phase_model: f64 on a library FFT).
+ *
+ * Grid, window numbering, d_offset, d_vectors [n][4] = dx, dy, peak, ratio, d_flags, the sign of a displacement and the
+ * size query with d_vectors == NULL are section 5's; d_planes is f32[n][(2R+1)^2] in section 5's layout, the central crop
+ * of the window's circular win x win plane.  photon_piv_validate, photon_piv_uncertainty, photon_piv_deform and every
+ * driver take the result as they take section 5's.
+ *   win 16, 32 or 64;  step >= 1;  radius R in [1, win/2 - 1] (a circular plane cannot tell +win/2 from -win/2)
+ *   mode 0 / 1;  window_sigma >= 0 (0: no weighting);  diameter >= 0: the e^-2 particle diameter d in pixels (0: W = 1)
+ *
+ * Definition.  a = im1 over the window, b(p) = im2(p + o) over the window moved by the offset; a pixel of im2 outside the
+ * image reads as the mean of the in-image ones (contributes 0) and sets flag 4.
+ *   a' = (a - mean a) g(row) g(col),  b' likewise,  g(p) = exp(-(p - (win-1)/2)^2 / (2 window_sigma^2))
+ *   A, B = the 2-D DFTs of a', b' (X(k) = sum_p x(p) exp(-2 pi i k p / win));  S = conj(A) B
+ *   mode 0:  P(s) = sum_k S(k) exp(+2 pi i k s / win),  Cn = P / (win^2 sqrt(sum a'^2 sum b'^2))   (|Cn| <= 1)
+ *   mode 1:  P(s) = sum_k W(k) S(k) / |S(k)| exp(+2 pi i k s / win),  Cn = P / sum_k W(k)         (1 for a pure shift)
+ *            W(kx, ky) = w(kx) w(ky),  w(k) = exp(-(d^2 / 16) (2 pi f / win)^2),  f = k below win/2 and k - win from there
+ *            on.  A bin with |S| = 0 contributes 0, and so does k = (0, 0) in every window: the means are subtracted, what
+ *            rounding leaves there has no phase.  sum W runs over the other bins: (sum_k w(k))^2 - 1.
+ * The plane holds Cn(s) for s in [-R, R]^2.  Integer peak with the row-major tie rule, the f64 three-point fit, the ratio
+ * and flags 1 and 2 are section 5's on that plane.  Flag 2 (every output NaN): all pixels of a equal, all in-image pixels
+ * of b equal or none -- decided from the smallest and the largest pixel -- or an f32 energy sum a'^2, sum b'^2 not above 0.
+ *
+ * The f32 order is part of the contract: the planes, peaks and ratios equal correlate_phase_model_f32's value for value
+ * (dx, dy up to the f64 logarithm).  Every operation below is one IEEE f32 operation, nothing fused:
+ *   sums       sum of win^2 values v = every row from its first column on (r = r + v), then the win row sums by halving:
+ *              r_i = r_i + r_(i+h) for i < h, h = win/2, win/4 ... 1.  An outside pixel of b adds 0.
+ *   means      mean a = sum a / win^2;  mean b = sum b / (number of in-image pixels)
+ *   weights    a' = ((a - mean a) g(row)) g(col);  b' the same, 0 for an outside pixel;  energies = sums of a' a', b' b'
+ *   forward    z = a' + i b'; radix-2 decimation in frequency along every row, then along every column, natural order in,
+ *              bit-reversed order out: for h = win/2 ... 1, for every block of 2h elements and j < h, with u = x(j),
+ *              v = x(j + h), t = twiddle(j win / (2h)):  x(j) = u + v,  x(j + h) = (u - v) t.
+ *              A product (c + i d)(t_r + i t_i) is (c t_r - d t_i) + i (c t_i + d t_r).
+ *   spectra    with Z- = Z(-k):  A_r = Z_r + Z-_r,  A_i = Z_i - Z-_i,  B_r = Z_i + Z-_i,  B_i = Z-_r - Z_r   (2 A, 2 B)
+ *              S_r = A_r B_r + A_i B_i,  S_i = A_r B_i - A_i B_r                                                (4 S)
+ *              mode 1:  m = sqrt(S_r S_r + S_i S_i);  q = (w(ky) w(kx)) / m;  T = (S_r q, S_i q), 0 where m is not > 0
+ *              or k = (0, 0);  mode 0: T = S
+ *   inverse    radix-2 decimation in time along every column, then along every row, bit-reversed in, natural out, with
+ *              t* = (t_r, -t_i): for h = 1 ... win/2:  x(j) = u + v t*,  x(j + h) = u - v t*.  P = the real part.
+ *   scale      in f64:  mode 0  inv = 1 / ((4 win^2) sqrt(energy_a energy_b));  mode 1  inv = 1 / ((sum_k w(k))^2 - 1), the
+ *              sum in the order of k;  Cn = (float)(P inv), peak likewise, ratio = (float)(P* / P2) as in section 5
+ * Tables: twiddle(k) = (cos, -sin)(2 pi k / win) for k < win/2, g and w are f32 values rounded once from f64
+ * (photon_det_sincos, photon_det_exp), filled on the host and handed to the kernel by value; the quarter turns are exactly
+ * (1, 0) and (0, -1).  photon_piv_phase_tables writes the library's own tables to HOST memory (twiddles f32[win/2][2],
+ * window f32[win], filter f32[win]) and launches nothing; it refuses a bad win, window_sigma or diameter and a null pointer.
+ *
+ * Refused (1, one stderr line, nothing written, no launch): section 5's list with R in [1, win/2 - 1], a mode other than
+ * 0 / 1, a window_sigma or diameter that is negative or not finite.  Asynchronous on `stream`, no device scratch; two calls
+ * on the same inputs return the same bits.
+ * Known limits: the plane is circular -- a displacement beyond win/2 - 1 aliases; pixels that enter the window only after
+ * the shift are not seen (section 5 enlarges the region instead), which the window weighting mitigates; images that are
+ * not finite are outside the contract.  DESIGN.md section 4.3j. */
+int photon_piv_correlate_phase(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int radius,
+                               const int *d_offset, int mode, float window_sigma, float diameter, float *d_vectors,
+                               int *d_flags, float *d_planes, int *n_rows, int *n_cols, void *stream);
+int photon_piv_phase_tables(int win, float window_sigma, float diameter, float *twiddles, float *window, float *filter);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_peak.hpp"
 
 using namespace photon;
 
@@ -50,18 +51,6 @@ __device__ __forceinline__ void block_sum2(float &a, float &b, float *red) {
     }
 }
 
-__device__ __forceinline__ float block_max(float v, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    const int nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    v = red[0];
-    for (int i = 1; i < nw; i++) v = fmaxf(v, red[i]);
-    return v;
-}
-
 // block_sum2 with a third value riding on the same two barriers (its wave totals sit in the argmax's index words)
 __device__ __forceinline__ void block_sum3(float &a, float &b, float &c, float *red) {
 #pragma unroll
@@ -86,46 +75,6 @@ __device__ __forceinline__ void block_sum3(float &a, float &b, float &c, float *
         b += red[16 + i];
         c += red[32 + i];
     }
-}
-
-// argmax with the tie rule: the larger value, then the smaller index
-__device__ __forceinline__ bool better(float v, int i, float bv, int bi) { return v > bv || (v == bv && i < bi); }
-
-__device__ __forceinline__ void block_argmax(float &bv, int &bi, float *red, int *redi) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float ov = __shfl_xor(bv, o, 64);
-        const int oi = __shfl_xor(bi, o, 64);
-        if (better(ov, oi, bv, bi)) {
-            bv = ov;
-            bi = oi;
-        }
-    }
-    const int nw = blockDim.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        red[threadIdx.x >> 6] = bv;
-        redi[threadIdx.x >> 6] = bi;
-    }
-    __syncthreads();
-    bv = red[0];
-    bi = redi[0];
-    for (int i = 1; i < nw; i++)
-        if (better(red[i], redi[i], bv, bi)) {
-            bv = red[i];
-            bi = redi[i];
-        }
-}
-
-// 3-point fit through (cm, c0, cp) in f64: Gaussian when all three are positive, parabolic otherwise; 0 for a flat triple
-__device__ __forceinline__ double subpixel(double cm, double c0, double cp) {
-    if (cm > 0.0 && c0 > 0.0 && cp > 0.0) {
-        const double lm = log(cm), l0 = log(c0), lp = log(cp);
-        const double den = 2.0 * (lm - 2.0 * l0 + lp);
-        return den != 0.0 ? (lm - lp) / den : 0.0;
-    }
-    const double den = 2.0 * (cm - 2.0 * c0 + cp);
-    return den != 0.0 ? (cm - cp) / den : 0.0;
 }
 
 // LDS layout (floats): a [WIN][WIN] | b [WIN + nSyp - 1][WIN + nSxp] | K partial planes [nSyp][nSxp] | reduction scratch.

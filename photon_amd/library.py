@@ -176,6 +176,9 @@ def _signatures():
         "photon_optflow_terms": (ci, [vp, vp, ci, ci, vp, cf, cf, vp, vp]),
         "photon_optflow_iterate": (ci, [vp, vp, ci, ci, ci, vp, vp, vp]),
         "photon_optflow_iterations_per_launch": (ci, []),
+        # section 13: FFT correlation (circular / phase)
+        "photon_piv_correlate_phase": (ci, [vp, vp] + [ci] * 5 + [vp, ci, cf, cf] + [vp] * 3 + [P(ci), P(ci), vp]),
+        "photon_piv_phase_tables": (ci, [ci, cf, cf, vp, vp, vp]),
     }
 
 
@@ -442,23 +445,73 @@ class PhotonLibrary:
                    None, _vp(stream))
         return vectors, flags, pl
 
-    def correlate(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1):
+    def piv_correlate_phase(self, d_im1_ptr: int, d_im2_ptr: int, width: int, height: int, win: int, step: int, radius: int,
+                            d_offset_ptr: int = 0, planes: bool = False, stream: int = 0, mode: int = 1, window_sigma: float = 0.0,
+                            diameter: float = 0.0):
+        """photon_piv_correlate_phase on raw device pointers: piv_correlate's arguments and results, by FFT -- mode 0 the
+        circular cross-correlation, mode 1 the phase correlation -- of windows weighted by a Gaussian of `window_sigma` px
+        (0: none), with the spectral filter for particles of e^-2 diameter `diameter` px (0: none).  The definition:
+        include/parallel_ray_tracing.h, section 13 (photon_amd.piv_phase: host models)."""
+        import torch
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        args = ("photon_piv_correlate_phase", _vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(radius))
+        how = (int(mode), float(window_sigma), float(diameter))
+        self._call(*args, None, *how, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
+        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
+        dev, _ = _device_and_stream()
+        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
+        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
+        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
+        self._call(*args, _vp(d_offset_ptr), *how, _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(pl.data_ptr()) if planes else None,
+                   None, None, _vp(stream))
+        return vectors, flags, pl
+
+    def piv_phase_tables(self, win: int, window_sigma: float, diameter: float):
+        """photon_piv_phase_tables: the library's own (twiddles f32 [win/2, 2], window f32 [win], filter f32 [win]) for
+        section 13, host arrays; needs no GPU."""
+        n = max(int(win), 2)
+        tw, g, w = np.zeros((n // 2, 2), np.float32), np.zeros(n, np.float32), np.zeros(n, np.float32)
+        self._call("photon_piv_phase_tables", int(win), float(window_sigma), float(diameter), _ptr(tw), _ptr(g), _ptr(w))
+        return tw, g, w
+
+    def _correlator(self, method: str, win: int, radius, window_sigma, diameter):
+        """What the drivers' method= selects: (a callable with piv_correlate's signature, the radius, the argument check).
+        "direct": section 5, radius None = win // 2.  "phase": section 13's mode 1 with window_sigma (None = win / 4) and
+        diameter bound, radius None or win // 2 = win // 2 - 1."""
+        from . import piv_correlation as pc
+        from . import piv_phase as pp
+        if method == "direct":
+            return self.piv_correlate, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
+        if method != "phase":
+            raise ValueError(f'method must be "direct" or "phase", not {method!r}')
+        sigma = int(win) / 4.0 if window_sigma is None else float(window_sigma)
+
+        def correlate(*args, **kwargs):
+            return self.piv_correlate_phase(*args, mode=pp.MODE_PHASE, window_sigma=sigma, diameter=float(diameter), **kwargs)
+
+        def check(shape, win, step, radius):
+            pp.check_arguments(shape, win, step, radius, pp.MODE_PHASE, sigma, diameter)
+        return correlate, pp.default_radius(win, radius), check
+
+    def correlate(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1,
+                  method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5):
         """Displacement field of an image pair (torch tensors on the device or numpy arrays, [height, width]): returns numpy
         (vectors [n_rows, n_cols, 4] = dx, dy, peak, ratio; flags [n_rows, n_cols]).  radius None = win // 2.  passes=2:
         pass 1, the normalised median test and the predictor on the host (photon_amd.piv_correlation), then pass 2 with
-        the integer window offsets."""
+        the integer window offsets.  method="phase": section 13's phase correlation instead of section 5's direct sums
+        (window_sigma None = win / 4; diameter: the e^-2 particle diameter; radius None or win // 2 = win // 2 - 1)."""
         import torch
         from . import piv_correlation as pc
         if int(passes) not in (1, 2):
             raise ValueError(f"passes must be 1 or 2, not {passes}")
-        radius = int(win) // 2 if radius is None else int(radius)
+        correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
-        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
+        vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
         vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         if int(passes) == 2:
             offsets = pc.predictor(vectors, flags, pc.normalized_median_test(vectors))
             d_off = torch.from_numpy(offsets).to(dev)
-            vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
+            vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
             vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         return vectors, flags
 
@@ -480,13 +533,14 @@ class PhotonLibrary:
         self._call("photon_piv_validate", _vp(d_pred_ptr), _vp(d_vectors_ptr), _vp(d_flags_ptr), int(n_rows), int(n_cols), float(eps),
                    float(threshold), _vp(d_field_ptr), _vp(d_smooth_ptr), _vp(d_status_ptr), _vp(stream))
 
-    def _correlate_validated(self, a, b, win, step, radius, eps, threshold, dev, stream, pairs=()):
-        """Pass 0 of correlate_deform, all of correlation_predictor: correlate the device images a, b, then validate with no
-        predictor.  Returns (vec, field, smoothed, status); field and smoothed are [*pairs, n_rows, n_cols, 2] and the
+    def _correlate_validated(self, correlate, a, b, win, step, radius, eps, threshold, dev, stream, pairs=()):
+        """Pass 0 of correlate_deform, all of correlation_predictor: correlate the device images a, b (`correlate`: what
+        _correlator returned), then validate with no predictor.  Returns (vec, field, smoothed, status); field and smoothed
+        are [*pairs, n_rows, n_cols, 2] and the
         validation fills their first [n_rows, n_cols, 2] (pairs=(2,): the ping-pong pairs of correlate_deform)."""
         import torch
         h, w = a.shape
-        vec, flg, _ = self.piv_correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
+        vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
         r, c = flg.shape
         field, smoothed = (torch.empty((*pairs, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))
         status = torch.empty((r, c), dtype=torch.int32, device=dev)
@@ -494,19 +548,19 @@ class PhotonLibrary:
                           stream)
         return vec, field, smoothed, status
 
-    def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream):
+    def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream,
+                                 method="direct", window_sigma=None, diameter=2.5):
         """correlate_deform on the device images a, b, nothing copied back: (field [n_rows, n_cols, 2] of the last iteration,
         vec [n_rows, n_cols, 4] of the last correlation, status [n_rows, n_cols]) as device tensors queued on `stream`."""
         import torch
-        from . import piv_correlation as pc
         if int(iterations) < 0:
             raise ValueError(f"iterations must be >= 0, not {iterations}")
-        radius = int(win) // 2 if radius is None else int(radius)
+        correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter)
         h, w = a.shape
-        pc.check_arguments((h, w), win, step, radius)
+        check((h, w), win, step, radius)
         if int(iterations) > 0:
-            pc.check_arguments((h, w), win, step, residual_radius)
-        vec, field, smoothed, status = self._correlate_validated(a, b, win, step, radius, eps, threshold, dev, stream, pairs=(2,))
+            check((h, w), win, step, residual_radius)
+        vec, field, smoothed, status = self._correlate_validated(correlate, a, b, win, step, radius, eps, threshold, dev, stream, pairs=(2,))
         r, c = status.shape
         cur = 0
         if int(iterations) > 0:
@@ -517,24 +571,26 @@ class PhotonLibrary:
             pred = (smoothed if smooth else field)[cur]
             self.piv_deform(coef[0].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, -0.5, warped[0].data_ptr(), stream)
             self.piv_deform(coef[1].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, 0.5, warped[1].data_ptr(), stream)
-            vec, flg, _ = self.piv_correlate(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, residual_radius, stream=stream)
+            vec, flg, _ = correlate(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, residual_radius, stream=stream)
             cur ^= 1
             self.piv_validate(pred.data_ptr(), vec.data_ptr(), flg.data_ptr(), r, c, field[cur].data_ptr(), smoothed[cur].data_ptr(),
                               status.data_ptr(), eps, threshold, stream)
         return field[cur], vec, status
 
     def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
-                         residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0):
+                         residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
+                         window_sigma: Optional[float] = None, diameter: float = 2.5):
         """Displacement field of an image pair by iterative image deformation (section 7; model:
         photon_amd.piv_deformation.correlate_deform_model).  Pass 0 correlates the images with `radius` (None = win // 2);
         every iteration warps both frames half-way by the validated, smoothed field, correlates the warped pair with
         `residual_radius` and adds the residual.  Returns what ``correlate`` returns: numpy (vectors [n_rows, n_cols, 4] =
         dx, dy of the last unsmoothed field, peak and ratio of the last correlation; status [n_rows, n_cols], section 5's
-        flags with bit 8 on replaced vectors).  Everything runs on the current stream; the host waits once, for the result."""
+        flags with bit 8 on replaced vectors).  Everything runs on the current stream; the host waits once, for the result.
+        method, window_sigma, diameter: the correlator of every pass, as ``correlate`` takes them."""
         import torch
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         field, vec, status = self._correlate_deform_device(a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev,
-                                                           stream)
+                                                           stream, method, window_sigma, diameter)
         out = torch.cat([field, vec[..., 2:4]], dim=-1)
         return out.cpu().numpy(), status.cpu().numpy()
 
@@ -697,16 +753,16 @@ class PhotonLibrary:
                    int(height), int(win), int(step), int(min_count), int(anchor), _vp(d_vectors_ptr), _vp(d_flags_ptr), _vp(stream))
 
     def correlation_predictor(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, eps: float = 0.1,
-                              threshold: float = 2.0):
+                              threshold: float = 2.0, method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5):
         """A predictor for track_dots from one pass of window correlation: photon_piv_correlate, then photon_piv_validate
         (median test, replacement, 3 x 3 smoothing) -- pass 0 of correlate_deform.  Returns the smoothed field as a torch
         device tensor [n_rows, n_cols, 2], queued on the current stream: hand it to track_dots as predictor=(field, win, step)
-        and a displacement larger than the spacing of the dots no longer pairs a dot with its neighbour."""
-        from . import piv_correlation as pc
-        radius = int(win) // 2 if radius is None else int(radius)
+        and a displacement larger than the spacing of the dots no longer pairs a dot with its neighbour.  method, window_sigma,
+        diameter: the correlator, as ``correlate`` takes them."""
+        correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
-        pc.check_arguments((h, w), win, step, radius)
-        return self._correlate_validated(a, b, win, step, radius, eps, threshold, dev, stream)[2]
+        check((h, w), win, step, radius)
+        return self._correlate_validated(correlate, a, b, win, step, radius, eps, threshold, dev, stream)[2]
 
     def track_dots(self, im1, im2, threshold: float, box_radius: int = 3, sigma_w: float = 1.0, iterations: int = 4,
                    background: float = 0.0, radius: float = 3.0, predictor=None, max_dots: Optional[int] = None, grid=None,

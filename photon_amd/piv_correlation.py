@@ -67,6 +67,41 @@ def _subpixel(cm, c0, cp):
         return np.where(den != 0.0, num / np.where(den != 0.0, den, 1.0), 0.0)
 
 
+def peak_outputs(C, R: int, ox, oy, norm, flat, outside, grid, planes: bool = False):
+    """What sections 5 and 13 report from the correlation planes C [n, 2R+1, 2R+1] of n = n_rows n_cols windows: the integer
+    peak with the row-major tie rule, the three-point fit, the ratio, the flags; norm [n] scales C to the normalised plane.
+    Returns (vectors [n_rows, n_cols, 4], flags [n_rows, n_cols] int32) and, with planes=True, the normalised planes."""
+    n_rows, n_cols = grid
+    n, nS = len(C), 2 * R + 1
+    k = np.arange(n)
+    Cf = C.reshape(n, nS * nS)
+    best = np.argmax(Cf, axis=1)                                   # the first maximum: the tie rule
+    py, px = best // nS, best % nS
+    peak_c = Cf[k, best]
+    sy_g, sx_g = np.meshgrid(np.arange(nS), np.arange(nS), indexing="ij")
+    far = np.maximum(np.abs(sy_g[None] - py[:, None, None]), np.abs(sx_g[None] - px[:, None, None])) >= 2
+    m2 = np.where(far, C, -np.inf).reshape(n, -1).max(axis=1)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(m2 > 0, peak_c / np.where(m2 > 0, m2, 1.0), np.inf)
+
+    edge_x, edge_y = (px == 0) | (px == nS - 1), (py == 0) | (py == nS - 1)
+    pxi, pyi = np.clip(px, 1, nS - 2), np.clip(py, 1, nS - 2)
+    dx = np.where(edge_x, 0.0, _subpixel(C[k, py, pxi - 1], C[k, py, pxi], C[k, py, pxi + 1]))
+    dy = np.where(edge_y, 0.0, _subpixel(C[k, pyi - 1, px], C[k, pyi, px], C[k, pyi + 1, px]))
+    with np.errstate(invalid="ignore"):                            # (a flat window: 0 * inf, NaN below anyway)
+        vectors = np.stack([ox + (px - R) + dx, oy + (py - R) + dy, peak_c * norm, ratio], axis=1)
+    flags = np.where(edge_x | edge_y, FLAG_EDGE_PEAK, 0) | np.where(outside, FLAG_OUTSIDE, 0)
+    flags = np.where(flat, FLAG_FLAT | np.where(outside, FLAG_OUTSIDE, 0), flags).astype(np.int32)
+    vectors[flat] = np.nan
+    out = (vectors.reshape(n_rows, n_cols, 4), flags.reshape(n_rows, n_cols))
+    if planes:
+        with np.errstate(invalid="ignore"):
+            Cn = C * norm[:, None, None]
+        Cn[flat] = np.nan
+        out = out + (Cn.reshape(n_rows, n_cols, nS, nS),)
+    return out
+
+
 def correlate_model(im1, im2, win: int, step: int, radius: int, offset=None, planes: bool = False):
     """Host model of photon_piv_correlate in f64.  im1, im2: [height, width]; offset: integer (ox, oy) per window,
     [n_rows, n_cols, 2] or [n][2], or None.  Returns (vectors [n_rows, n_cols, 4], flags [n_rows, n_cols] int32) and, with
@@ -113,34 +148,9 @@ def correlate_model(im1, im2, win: int, step: int, radius: int, offset=None, pla
             C[:, sy, sx] = np.einsum("nij,nij->n", a, b[:, sy:sy + win, sx:sx + win])
     flat = (ea == 0.0) | (eb == 0.0)
     outside = ~inside.all(axis=(1, 2))
-
-    Cf = C.reshape(n, nS * nS)
-    best = np.argmax(Cf, axis=1)                                   # the first maximum: the tie rule
-    py, px = best // nS, best % nS
-    peak_c = Cf[k, best]
-    sy_g, sx_g = np.meshgrid(np.arange(nS), np.arange(nS), indexing="ij")
-    far = np.maximum(np.abs(sy_g[None] - py[:, None, None]), np.abs(sx_g[None] - px[:, None, None])) >= 2
-    m2 = np.where(far, C, -np.inf).reshape(n, -1).max(axis=1)
     with np.errstate(divide="ignore", invalid="ignore"):
-        ratio = np.where(m2 > 0, peak_c / np.where(m2 > 0, m2, 1.0), np.inf)
         norm = 1.0 / np.sqrt(ea * eb)
-
-    edge_x, edge_y = (px == 0) | (px == nS - 1), (py == 0) | (py == nS - 1)
-    pxi, pyi = np.clip(px, 1, nS - 2), np.clip(py, 1, nS - 2)
-    dx = np.where(edge_x, 0.0, _subpixel(C[k, py, pxi - 1], C[k, py, pxi], C[k, py, pxi + 1]))
-    dy = np.where(edge_y, 0.0, _subpixel(C[k, pyi - 1, px], C[k, pyi, px], C[k, pyi + 1, px]))
-    with np.errstate(invalid="ignore"):                            # (a flat window: 0 * inf, NaN below anyway)
-        vectors = np.stack([ox + (px - R) + dx, oy + (py - R) + dy, peak_c * norm, ratio], axis=1)
-    flags = np.where(edge_x | edge_y, FLAG_EDGE_PEAK, 0) | np.where(outside, FLAG_OUTSIDE, 0)
-    flags = np.where(flat, FLAG_FLAT | np.where(outside, FLAG_OUTSIDE, 0), flags).astype(np.int32)
-    vectors[flat] = np.nan
-    out = (vectors.reshape(n_rows, n_cols, 4), flags.reshape(n_rows, n_cols))
-    if planes:
-        with np.errstate(invalid="ignore"):
-            Cn = C * norm[:, None, None]
-        Cn[flat] = np.nan
-        out = out + (Cn.reshape(n_rows, n_cols, nS, nS),)
-    return out
+    return peak_outputs(C, R, ox, oy, norm, flat, outside, (n_rows, n_cols), planes)
 
 
 def _neighbours(field):

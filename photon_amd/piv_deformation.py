@@ -166,26 +166,41 @@ def validate_model(pred, vectors, flags, eps: float = 0.1, threshold: float = 2.
 
 
 def correlate_deform_model(im1, im2, win: int = 32, step: int = 16, radius=None, iterations: int = 3, residual_radius: int = 4,
-                           smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, history: bool = False):
+                           smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, history: bool = False, method: str = "direct",
+                           window_sigma=None, diameter: float = 2.5):
     """Host model of PhotonLibrary.correlate_deform: returns (vectors [n_rows, n_cols, 4] = dx, dy of the last unsmoothed
     field, peak and ratio of the last correlation; status [n_rows, n_cols]); with history=True also the list of the
-    unsmoothed fields after pass 0 and after every iteration."""
+    unsmoothed fields after pass 0 and after every iteration.  method="phase": every pass correlates with
+    piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or win // 2 = win // 2 - 1)."""
     im1, im2 = np.asarray(im1, np.float64), np.asarray(im2, np.float64)
     if int(iterations) < 0:
         raise ValueError(f"iterations must be >= 0, not {iterations}")
-    radius = int(win) // 2 if radius is None else int(radius)
-    pc.check_arguments(im1.shape, win, step, radius)
+    if method == "direct":
+        correlate, check = pc.correlate_model, pc.check_arguments
+        radius = int(win) // 2 if radius is None else int(radius)
+    elif method == "phase":
+        from . import piv_phase as pp
+        how = dict(mode=pp.MODE_PHASE, window_sigma=int(win) / 4.0 if window_sigma is None else float(window_sigma), diameter=float(diameter))
+
+        def correlate(a, b, win, step, radius):
+            return pp.correlate_phase_model(a, b, win, step, radius, **how)
+
+        def check(shape, win, step, radius):
+            pp.check_arguments(shape, win, step, radius, **how)
+        radius = pp.default_radius(win, radius)
+    else:
+        raise ValueError(f'method must be "direct" or "phase", not {method!r}')
+    check(im1.shape, win, step, radius)
     if int(iterations) > 0:
-        pc.check_arguments(im1.shape, win, step, residual_radius)
-    vec, flg = pc.correlate_model(im1, im2, win, step, radius)
+        check(im1.shape, win, step, residual_radius)
+    vec, flg = correlate(im1, im2, win, step, radius)
     field, smoothed, status, _, _ = validate_model(None, vec, flg, eps, threshold)
     fields = [field]
     if int(iterations) > 0:
         c1, c2 = bspline_coefficients_model(im1), bspline_coefficients_model(im2)
     for _ in range(int(iterations)):
         pred = smoothed if smooth else field
-        vec, flg = pc.correlate_model(deform_model(c1, pred, win, step, -0.5), deform_model(c2, pred, win, step, 0.5), win, step,
-                                      int(residual_radius))
+        vec, flg = correlate(deform_model(c1, pred, win, step, -0.5), deform_model(c2, pred, win, step, 0.5), win, step, int(residual_radius))
         field, smoothed, status, _, _ = validate_model(pred, vec, flg, eps, threshold)
         fields.append(field)
     vectors = np.concatenate([field.astype(np.float64), vec[..., 2:4]], axis=-1)

@@ -15,9 +15,14 @@ FMA peak).  --deform adds iterative image deformation (PhotonLibrary.correlate_d
 figures after 1, 2 and 3 iterations against the same truth and windows (and against the truth that collects the particles
 by their position half-way between the frames, which is where a symmetric warp measures), and at 1024^2 the device-event
 times of the coefficients, one warp, one residual correlation at R 4 and one validate, and the wall time of the whole call
-beside correlate(passes=2).  Run it on a GPU box under a time limit of its own:
+beside correlate(passes=2).  --phase holds the FFT correlator (photon_piv_correlate_phase, header section 13: phase
+correlation, Gaussian window of win / 4, spectral filter for 2.5 px particles) next to photon_piv_correlate: the sample
+pair's error figures for one pass and for three deformation iterations with both methods, and at 1024^2 the device-event
+times of both kernels in the same run, alternating (win 32 / step 16 at R 4 and 15 | 16, win 64 / step 32 at R 4 and 31 | 32;
+the median of seven), and the wall time of correlate_deform with both methods.  Run it on a GPU box under a time limit of
+its own:
 
-    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate] [--deform]
+    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate] [--deform] [--phase]
 """
 import argparse
 import json
@@ -169,6 +174,56 @@ def deform_pair(lib, images, records, cam, rays, lit, row):
             row[f"deform_1024_w{win}_{k}_ms"] = round(v, 4)
 
 
+def phase_pair(lib, images, records, cam, rays, lit, row):
+    """--phase on the sample pair, then the 1024^2 timings; adds its figures to `row`."""
+    win, step = 32, 16
+    a, b = (torch.from_numpy(np.ascontiguousarray(im, np.float32)).cuda() for im in images)
+    m1 = deflections.dot_means(records[0], rays, 1, "arrived")
+    pos = pc.image_positions(deflections.to_pixels(m1["pos"], cam), cam)[lit]
+    d = pp.image_displacements(records[0], records[1], cam, rays)[lit]
+    flip = -1.0 if bool(cam.get("implement_diffraction", False)) else 1.0
+    truths = {"one_pass": pc.window_truth(pos, d, images[0].shape, win, step, min_count=5)[0],
+              "deform3": pc.window_truth(pos + 0.5 * d * np.array([flip, 1.0]), d, images[0].shape, win, step, min_count=5)[0]}
+    print("sample pair, |measured - truth| (one pass: frame-1 truth; 3 deformation iterations: half-way truth):")
+    for method in ("direct", "phase"):
+        results = {"one_pass": lib.correlate(a, b, win, step, method=method), "deform3": lib.correlate_deform(a, b, win, step, iterations=3, method=method)}
+        for name, (vec, status) in results.items():
+            ok = np.isfinite(truths[name]).all(axis=-1) & ((status & pc.FLAG_FLAT) == 0)
+            err = np.hypot(*(pc.sensor_displacements(vec, cam)[ok] - truths[name][ok]).T)
+            print(f"  {method:6s} {name:8s} {int(ok.sum())} windows: median {np.median(err):.4f} px, 95th percentile {np.percentile(err, 95):.4f} px, "
+                  f"{int((err > 1.0).sum())} beyond 1 px")
+            row[f"phase_{method}_{name}_median_err_px"] = float(np.median(err))
+            row[f"phase_{method}_{name}_p95_err_px"] = float(np.percentile(err, 95))
+    rng = np.random.default_rng(1)
+    n = 20_000
+    x, y = rng.uniform(-8, 1032, n), rng.uniform(-8, 1032, n)
+    big = [torch.from_numpy(pc.particle_image((1024, 1024), x + dx, y + dy).astype(np.float32)).cuda() for dx, dy in ((0, 0), (3.3, -2.6))]
+    h = w = 1024
+    p0, p1 = big[0].data_ptr(), big[1].data_ptr()
+    for win, step in ((32, 16), (64, 32)):
+        calls = {}
+        for R in (4, win // 2):
+            Rp = min(R, win // 2 - 1)
+            calls[f"direct_r{R}"] = lambda R=R: lib.piv_correlate(p0, p1, w, h, win, step, R)
+            calls[f"phase_r{Rp}"] = lambda Rp=Rp: lib.piv_correlate_phase(p0, p1, w, h, win, step, Rp, mode=1, window_sigma=win / 4.0, diameter=2.5)
+        times = {k: [] for k in calls}
+        for rep in range(10):                               # three warm-up rounds, then seven; one event pair per call
+            for k, fn in calls.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                if rep >= 3:
+                    times[k].append(e0.elapsed_time(e1))
+        ms = {k: float(np.median(v)) for k, v in times.items()}
+        ms.update(wall_ms({"correlate_deform_3_direct_wall": lambda: lib.correlate_deform(big[0], big[1], win, step, iterations=3),
+                           "correlate_deform_3_phase_wall": lambda: lib.correlate_deform(big[0], big[1], win, step, iterations=3, method="phase")}))
+        print(f"1024^2, win {win} step {step}: " + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items()))
+        for k, v in ms.items():
+            row[f"phase_1024_w{win}_{k}_ms"] = round(v, 4)
+
+
 def timed(fn, reps=3):
     out, best = None, 1e9
     for _ in range(reps):
@@ -189,6 +244,7 @@ def main():
     ap.add_argument("--bench-advect", action="store_true")
     ap.add_argument("--correlate", action="store_true")
     ap.add_argument("--deform", action="store_true")
+    ap.add_argument("--phase", action="store_true")
     args = ap.parse_args()
     lib = PhotonLibrary()
     lib.set_device(0)
@@ -268,13 +324,15 @@ def main():
         _, row["advect_1e6_16steps_128cubed_ms"] = timed(bench, 5)
         bflow.free()
         print(f"advection of 1e6 particles, 16 steps, 128^3 field: {row['advect_1e6_16steps_128cubed_ms']:.3f} ms")
-    if args.correlate or args.deform:
+    if args.correlate or args.deform or args.phase:
         sigma = BEAM_FWHM / (2.0 * math.sqrt(2.0 * math.log(2.0)))
         lit = np.exp(-w1[:, 2] ** 2 / (2.0 * sigma * sigma)) >= 0.1       # within 2.15 sigma of the sheet's centre plane
     if args.correlate:
         correlate_pair(lib, images, records, cam, rays, lit, row)
     if args.deform:
         deform_pair(lib, images, records, cam, rays, lit, row)
+    if args.phase:
+        phase_pair(lib, images, records, cam, rays, lit, row)
     print(json.dumps(row), flush=True)
     if not math.isfinite(row["p99_err_px"]):
         sys.exit(1)
