@@ -25,6 +25,7 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_peak.hpp"
 
 using namespace photon;
 
@@ -152,20 +153,6 @@ __global__ __launch_bounds__(256) void detect_write_kernel(const unsigned long l
 // =============================================================================================
 constexpr int kFitLanes = 16, kFitThreads = 256, kFitBox = 15;             // box_radius <= 7
 
-// section 5's 3-point fit, f64
-__device__ __forceinline__ double three_point(double cm, double c0, double cp) {
-    double num, den;
-    if (cm > 0.0 && c0 > 0.0 && cp > 0.0) {
-        const double lm = log(cm), l0 = log(c0), lp = log(cp);
-        num = lm - lp;
-        den = 2.0 * (lm - 2.0 * l0 + lp);
-    } else {
-        num = cm - cp;
-        den = 2.0 * (cm - 2.0 * c0 + cp);
-    }
-    return den != 0.0 ? num / den : 0.0;
-}
-
 __device__ __forceinline__ double fold16(double v) {
 #pragma unroll
     for (int d = kFitLanes / 2; d >= 1; d >>= 1) v = v + __shfl_xor(v, d, kFitLanes);
@@ -204,8 +191,8 @@ __global__ __launch_bounds__(kFitThreads) void fit_kernel(const float *__restric
     }
     // the 3-point start through the peak pixel: row R holds the x neighbours, column R of rows R - 1, R + 1 the y neighbours
     const double i0 = __shfl(i_mid, R, kFitLanes);
-    double dx = three_point(__shfl(i_left, R, kFitLanes), i0, __shfl(i_right, R, kFitLanes));
-    double dy = three_point(__shfl(i_mid, R - 1, kFitLanes), i0, __shfl(i_mid, R + 1, kFitLanes));
+    double dx = subpixel(__shfl(i_left, R, kFitLanes), i0, __shfl(i_right, R, kFitLanes));
+    double dy = subpixel(__shfl(i_mid, R - 1, kFitLanes), i0, __shfl(i_mid, R + 1, kFitLanes));
     int st = 0;
     if (q - R < 0 || q + R > W - 1 || r - R < 0 || r + R > H - 1) st |= 1;
 

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_grid.hpp"
 #include "piv_peak.hpp"
 
 using namespace photon;
@@ -24,58 +25,11 @@ namespace {
 constexpr int kTileX = 4;           // shifts per lane along x (one float4 of im2 per step)
 constexpr int kTileY = 4;           // shifts per lane along y
 constexpr int kMaxThreads = 512;
-constexpr int kRedWords = 64;       // block-reduction scratch: 16 floats x 2 + 16 ints (8 waves at most)
+constexpr int kRedWords = 64;       // block-reduction scratch, 8 waves at most: 5 floats a wave, or a float a wave and (from word 32) an int a wave
+
+static_assert(5 * (kMaxThreads / 64) <= kRedWords && 32 + kMaxThreads / 64 <= kRedWords, "the reduction scratch holds kRedWords words");
 
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-// Fixed-order block sums: a butterfly inside each wave (every lane ends with the same bits), then the wave totals in wave
-// order.  blockDim.x is a multiple of 64.
-__device__ __forceinline__ void block_sum2(float &a, float &b, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o, 64);
-        b += __shfl_xor(b, o, 64);
-    }
-    const int nw = blockDim.x >> 6, w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        red[w] = a;
-        red[16 + w] = b;
-    }
-    __syncthreads();
-    a = 0.f;
-    b = 0.f;
-    for (int i = 0; i < nw; i++) {
-        a += red[i];
-        b += red[16 + i];
-    }
-}
-
-// block_sum2 with a third value riding on the same two barriers (its wave totals sit in the argmax's index words)
-__device__ __forceinline__ void block_sum3(float &a, float &b, float &c, float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o, 64);
-        b += __shfl_xor(b, o, 64);
-        c += __shfl_xor(c, o, 64);
-    }
-    const int nw = blockDim.x >> 6, w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) {
-        red[w] = a;
-        red[16 + w] = b;
-        red[32 + w] = c;
-    }
-    __syncthreads();
-    a = 0.f;
-    b = 0.f;
-    c = 0.f;
-    for (int i = 0; i < nw; i++) {
-        a += red[i];
-        b += red[16 + i];
-        c += red[32 + i];
-    }
-}
 
 // LDS layout (floats): a [WIN][WIN] | b [WIN + nSyp - 1][WIN + nSxp] | K partial planes [nSyp][nSxp] | reduction scratch.
 // nSxp, nSyp: 2R + 1 rounded up to the tile; the shifts past 2R read zero padding and are dropped.
@@ -118,19 +72,20 @@ __global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float 
             dif_b += u != ref_b ? 1.f : 0.f;
         }
     }
-    block_sum2(sum_a, sum_b, red);
-    float cnt = cnt_b;
-    block_sum3(cnt, dif_a, dif_b, red);
-    const bool all_equal = dif_a == 0.f || dif_b == 0.f;        // all pixels of a equal, or all (or none) of b at zero shift
-    const float mean_a = sum_a / (float)(WIN * WIN);
-    const float mean_b = cnt > 0.f ? sum_b / cnt : 0.f;
+    const int n_waves = B >> 6;
+    float tot[5] = {sum_a, sum_b, cnt_b, dif_a, dif_b};
+    block_reduce(tot, red, n_waves, Sum());                   // 5 x 8 words: reaches into the argmax's index words, idle until the tail
+    const float cnt = tot[2];
+    const bool all_equal = tot[3] == 0.f || tot[4] == 0.f;  // all pixels of a equal, or all (or none) of b at zero shift
+    const float mean_a = tot[0] / (float)(WIN * WIN);
+    const float mean_b = cnt > 0.f ? tot[1] / cnt : 0.f;
 
     // ---- mean-subtracted a in place; the b region with zero padding; the two energies (b at zero shift)
-    float ea = 0.f, eb = 0.f;
+    float e[2] = {0.f, 0.f};            // a, b
     for (int i = tid; i < WIN * WIN; i += B) {
         const float v = sa[i] - mean_a;
         sa[i] = v;
-        ea = fmaf(v, v, ea);
+        e[0] = fmaf(v, v, e[0]);
     }
     const int span = WIN + 2 * R;
     for (int i = tid; i < rows * pitch; i += B) {
@@ -139,25 +94,17 @@ __global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float 
         if (ry < span && rx < span) {
             const int gy = wy0 + oy - R + ry, gx = wx0 + ox - R + rx;
             if (gy >= 0 && gy < H && gx >= 0 && gx < W) v = im2[(size_t)gy * W + gx] - mean_b;
-            if (ry >= R && ry < R + WIN && rx >= R && rx < R + WIN) eb = fmaf(v, v, eb);
+            if (ry >= R && ry < R + WIN && rx >= R && rx < R + WIN) e[1] = fmaf(v, v, e[1]);
         }
         sb[i] = v;
     }
-    block_sum2(ea, eb, red);           // (its barriers also publish sa and sb)
+    block_reduce(e, red, n_waves, Sum());       // (its barriers also publish sa and sb)
+    const float ea = e[0], eb = e[1];
 
     const bool outside = wy0 + oy - R < 0 || wx0 + ox - R < 0 || wy0 + oy + WIN - 1 + R >= H || wx0 + ox + WIN - 1 + R >= W;
     // flat window (block-uniform): by its pixels, or a contrast too small for the f32 energies (1 / sqrt(0) below)
     if (all_equal || !(ea > 0.f) || !(eb > 0.f)) {
-        const float qnan = __builtin_nanf("");
-        if (tid == 0) {
-            vectors[4 * (size_t)win_id + 0] = qnan;
-            vectors[4 * (size_t)win_id + 1] = qnan;
-            vectors[4 * (size_t)win_id + 2] = qnan;
-            vectors[4 * (size_t)win_id + 3] = qnan;
-            flags[win_id] = 2 | (outside ? 4 : 0);
-        }
-        if (planes)
-            for (int i = tid; i < nS2; i += B) planes[(size_t)win_id * nS2 + i] = qnan;
+        write_flat(win_id, nS2, outside, vectors, flags, planes);
         return;
     }
 
@@ -205,46 +152,17 @@ __global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float 
     }
     __syncthreads();
 
-    // ---- the plane (slices summed in order, into slice 0), its normalised copy, and the argmax
+    // ---- the plane (slices summed in order, into slice 0, as the tail's first pass meets each shift) and the peak read-out
     const double inv = 1.0 / sqrt((double)ea * (double)eb);
-    float bv = -INFINITY;
-    int bi = INT_MAX;
-    for (int i = tid; i < nS2; i += B) {
-        const int j = (i / nS) * nSxp + (i % nS);
+    auto sum_slices = [&](int sy, int sx) {
+        const int j = sy * nSxp + sx;
         float c = sp[j];
         for (int k = 1; k < K; k++) c += sp[k * P + j];
         sp[j] = c;
-        if (planes) planes[(size_t)win_id * nS2 + i] = (float)((double)c * inv);
-        if (better(c, i, bv, bi)) {
-            bv = c;
-            bi = i;
-        }
-    }
-    block_argmax(bv, bi, red, redi);            // (its barriers also publish the summed plane)
-    const int py = bi / nS, px = bi % nS;
-
-    // ---- the largest value at least 2 shifts away from the peak (Chebyshev distance)
-    float m2 = -INFINITY;
-    for (int i = tid; i < nS2; i += B) {
-        const int sy = i / nS, sx = i % nS;
-        if (max(abs(sy - py), abs(sx - px)) >= 2) m2 = fmaxf(m2, sp[sy * nSxp + sx]);
-    }
-    m2 = block_max(m2, red);
-
-    if (tid == 0) {
-        const float *row = sp + py * nSxp;
-        int f = outside ? 4 : 0;
-        double dx = 0.0, dy = 0.0;
-        if (px == 0 || px == nS - 1) f |= 1;
-        else dx = subpixel(row[px - 1], row[px], row[px + 1]);
-        if (py == 0 || py == nS - 1) f |= 1;
-        else dy = subpixel(row[px - nSxp], row[px], row[px + nSxp]);
-        vectors[4 * (size_t)win_id + 0] = (float)((double)(ox + px - R) + dx);
-        vectors[4 * (size_t)win_id + 1] = (float)((double)(oy + py - R) + dy);
-        vectors[4 * (size_t)win_id + 2] = (float)((double)bv * inv);
-        vectors[4 * (size_t)win_id + 3] = m2 > 0.f ? (float)((double)bv / (double)m2) : INFINITY;
-        flags[win_id] = f;
-    }
+        return c;
+    };
+    auto plane_at = [&](int sy, int sx) { return sp[sy * nSxp + sx]; };
+    peak_tail(sum_slices, plane_at, nS, R, ox, oy, inv, outside, win_id, vectors, flags, planes, red, redi);
 }
 
 // How the shift tiles of one window are spread over a workgroup: K row slices and B threads (a multiple of 64), chosen
@@ -279,16 +197,11 @@ Plan plan_for(int win, int R, size_t lds_limit) {
 template <int WIN>
 int launch(const float *im1, const float *im2, int W, int H, int step, int R, int n_rows, int n_cols, const int *offset,
            float *vectors, int *flags, float *planes, hipStream_t stream) {
-    int dev = 0, lds_limit = 0;
-    PH_CHECK(hipGetDevice(&dev));
-    PH_CHECK(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+    int lds_limit = 0;
+    PH_TRY(piv_grid::lds_limit(&lds_limit));
     const Plan p = plan_for(WIN, R, (size_t)lds_limit);
-    if (p.K == 0) {
-        fprintf(stderr, "photon: photon_piv_correlate: win %d, radius %d needs more LDS than the device's %d bytes\n", WIN, R, lds_limit);
-        return 1;
-    }
-    if (p.lds_bytes > 65536)
-        PH_CHECK(hipFuncSetAttribute((const void *)piv_correlate_kernel<WIN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)p.lds_bytes));
+    if (p.K == 0) return piv_grid::lds_refused("photon_piv_correlate", WIN, "radius", R, lds_limit);
+    PH_TRY(piv_grid::raise_lds(piv_correlate_kernel<WIN>, p.lds_bytes));
     hipLaunchKernelGGL(piv_correlate_kernel<WIN>, dim3((unsigned)(n_rows * n_cols)), dim3(p.threads), p.lds_bytes, stream, im1, im2, W, H,
                        step, R, n_cols, offset, p.K, p.nSxp, p.nSyp, vectors, flags, planes);
     PH_CHECK(hipGetLastError());
@@ -300,29 +213,20 @@ int launch(const float *im1, const float *im2, int W, int H, int step, int R, in
 extern "C" int photon_piv_correlate(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int radius,
                                     const int *d_offset, float *d_vectors, int *d_flags, float *d_planes, int *n_rows, int *n_cols,
                                     void *stream_p) {
-    const char *bad = nullptr;
-    if (win != 16 && win != 32 && win != 64) bad = "win must be 16, 32 or 64";
-    else if (radius < 1 || radius > win / 2) bad = "radius must lie in [1, win / 2]";
-    else if (step < 1) bad = "step must be >= 1";
-    else if (width < win || height < win) bad = "the image is smaller than one window";
-    else if (!d_im1 || !d_im2) bad = "null image pointer";
-    else if (d_vectors && !d_flags) bad = "d_vectors without d_flags";
+    const char *bad = piv_grid::win_error(win);
+    if (!bad && (radius < 1 || radius > win / 2)) bad = "radius must lie in [1, win / 2]";
+    if (!bad) bad = piv_grid::grid_error(width, height, win, step);
+    if (!bad && (!d_im1 || !d_im2)) bad = "null image pointer";
+    if (!bad && d_vectors && !d_flags) bad = "d_vectors without d_flags";
     if (bad) {
         fprintf(stderr, "photon: photon_piv_correlate: %s (win %d, step %d, radius %d, %d x %d image)\n", bad, win, step, radius, width, height);
         return 1;
     }
-    const int rows = (height - win) / step + 1, cols = (width - win) / step + 1;
-    if ((long long)rows * cols > INT_MAX) {
-        fprintf(stderr, "photon: photon_piv_correlate: %d x %d windows are too many for one call\n", rows, cols);
-        return 1;
-    }
-    if (n_rows) *n_rows = rows;
-    if (n_cols) *n_cols = cols;
+    int rows, cols;
+    PH_TRY(piv_grid::grid_size("photon_piv_correlate", width, height, win, step, rows, cols, n_rows, n_cols));
     if (!d_vectors) return 0;                   // the size query
     hipStream_t stream = (hipStream_t)stream_p;
-    switch (win) {
-    case 16: return launch<16>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, d_vectors, d_flags, d_planes, stream);
-    case 32: return launch<32>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, d_vectors, d_flags, d_planes, stream);
-    default: return launch<64>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, d_vectors, d_flags, d_planes, stream);
-    }
+    return piv_grid::dispatch_win(win, [&](auto WIN) {
+        return launch<WIN()>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, d_vectors, d_flags, d_planes, stream);
+    });
 }

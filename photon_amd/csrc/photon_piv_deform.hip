@@ -16,6 +16,7 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_grid.hpp"
 #include "piv_warp.hpp"
 
 using namespace photon;
@@ -258,7 +259,7 @@ extern "C" int photon_piv_bspline_coefficients(const float *d_im, int width, int
 
 extern "C" int photon_piv_deform(const float *d_coef, int width, int height, const float *d_field, int field_stride, int n_rows,
                                  int n_cols, int win, int step, float scale, float *d_out, void *stream_p) {
-    const char *bad = grid_error(width, height, win, step, n_rows, n_cols);
+    const char *bad = piv_grid::grid_error(width, height, win, step, n_rows, n_cols);
     if (!bad) {
         if (field_stride != 2 && field_stride != 4) bad = "field_stride must be 2 or 4";
         else if (width > (1 << 22) || height > (1 << 22)) bad = "the image is larger than 2^22 pixels a side";

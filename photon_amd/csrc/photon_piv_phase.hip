@@ -17,6 +17,7 @@
 
 #include "../../include/photon_det_math.h"
 #include "photon_internal.hpp"
+#include "piv_grid.hpp"
 #include "piv_peak.hpp"
 
 using namespace photon;
@@ -51,25 +52,6 @@ void fill_tables(int win, float window_sigma, float diameter, float *twiddles, f
         const double f = p < win / 2 ? p : p - win;
         const double u = 2.0 * PHOTON_PI * f / win;
         filter[p] = (float)photon_det_exp(-(d * d / 16.0) * (u * u));
-    }
-}
-
-// the largest of four values over the block, each in a fixed order; red holds 64 floats
-__device__ __forceinline__ void block_max4(float (&v)[4], float *red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1)
-#pragma unroll
-        for (int k = 0; k < 4; k++) v[k] = fmaxf(v[k], __shfl_xor(v[k], o, 64));
-    const int nw = blockDim.x >> 6, w = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 4; k++) red[16 * k + w] = v[k];
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        v[k] = red[16 * k];
-        for (int i = 1; i < nw; i++) v[k] = fmaxf(v[k], red[16 * k + i]);
     }
 }
 
@@ -117,13 +99,13 @@ __global__ __launch_bounds__(B) void piv_phase_kernel(const float *__restrict__ 
     __shared__ float2 z[N * PITCH];
     __shared__ float2 stw[N / 2];
     __shared__ float sg[N], sw[N];
-    __shared__ float red[68];           // 0..63: block_max4 and the tail's reductions; 64..67: the two sums, the two energies
+    __shared__ float red[68];           // 0..63: the block reductions (4 floats a wave at most); 64..67: the two sums, the two energies
     __shared__ int redi[16];
 
     const int win_id = blockIdx.x, tid = threadIdx.x;
     const int wy0 = (win_id / n_cols) * step, wx0 = (win_id % n_cols) * step;
     const int ox = offset ? offset[2 * win_id] : 0, oy = offset ? offset[2 * win_id + 1] : 0;
-    const int nS = 2 * R + 1, nS2 = nS * nS;
+    const int nS = 2 * R + 1;
 
     for (int i = tid; i < N / 2; i += B) stw[i] = make_float2(tab.twiddles[2 * i], tab.twiddles[2 * i + 1]);
     for (int i = tid; i < N; i += B) {
@@ -147,7 +129,7 @@ __global__ __launch_bounds__(B) void piv_phase_kernel(const float *__restrict__ 
         ext[1] = fmaxf(ext[1], -a);
         z[y * PITCH + x] = make_float2(a, b);
     }
-    block_max4(ext, red);               // (its barriers also publish z and the tables)
+    block_reduce(ext, red, B / 64, MaxF32());           // (its barriers also publish z and the tables)
     const int rows_in = count_inside((long long)wy0 + oy, N, H), cols_in = count_inside((long long)wx0 + ox, N, W);
     const float cnt = (float)(rows_in * cols_in);
     const bool outside = rows_in < N || cols_in < N;
@@ -206,16 +188,7 @@ __global__ __launch_bounds__(B) void piv_phase_kernel(const float *__restrict__ 
 
     // flat window (block-uniform): by its pixels, or a contrast too small for the f32 energies
     if (all_equal || !(ea > 0.f) || !(eb > 0.f)) {
-        const float qnan = __builtin_nanf("");
-        if (tid == 0) {
-            vectors[4 * (size_t)win_id + 0] = qnan;
-            vectors[4 * (size_t)win_id + 1] = qnan;
-            vectors[4 * (size_t)win_id + 2] = qnan;
-            vectors[4 * (size_t)win_id + 3] = qnan;
-            flags[win_id] = 2 | (outside ? 4 : 0);
-        }
-        if (planes)
-            for (int i = tid; i < nS2; i += B) planes[(size_t)win_id * nS2 + i] = qnan;
+        write_flat(win_id, nS * nS, outside, vectors, flags, planes);
         return;
     }
 
@@ -256,40 +229,7 @@ __global__ __launch_bounds__(B) void piv_phase_kernel(const float *__restrict__ 
     auto plane_at = [&](int sy, int sx) { return z[((sy - R) & (N - 1)) * PITCH + ((sx - R) & (N - 1))].x; };
 
     const double inv = mode == 1 ? inv_filter_sum : 1.0 / ((double)(4 * N * N) * sqrt((double)ea * (double)eb));
-    float bv = -INFINITY;
-    int bi = INT_MAX;
-    for (int i = tid; i < nS2; i += B) {
-        const float c = plane_at(i / nS, i % nS);
-        if (planes) planes[(size_t)win_id * nS2 + i] = (float)((double)c * inv);
-        if (better(c, i, bv, bi)) {
-            bv = c;
-            bi = i;
-        }
-    }
-    block_argmax(bv, bi, red, redi);
-    const int py = bi / nS, px = bi % nS;
-
-    // ---- the largest value at least 2 shifts away from the peak (Chebyshev distance)
-    float m2 = -INFINITY;
-    for (int i = tid; i < nS2; i += B) {
-        const int sy = i / nS, sx = i % nS;
-        if (max(abs(sy - py), abs(sx - px)) >= 2) m2 = fmaxf(m2, plane_at(sy, sx));
-    }
-    m2 = block_max(m2, red);
-
-    if (tid == 0) {
-        int f = outside ? 4 : 0;
-        double dx = 0.0, dy = 0.0;
-        if (px == 0 || px == nS - 1) f |= 1;
-        else dx = subpixel(plane_at(py, px - 1), plane_at(py, px), plane_at(py, px + 1));
-        if (py == 0 || py == nS - 1) f |= 1;
-        else dy = subpixel(plane_at(py - 1, px), plane_at(py, px), plane_at(py + 1, px));
-        vectors[4 * (size_t)win_id + 0] = (float)((double)(ox + px - R) + dx);
-        vectors[4 * (size_t)win_id + 1] = (float)((double)(oy + py - R) + dy);
-        vectors[4 * (size_t)win_id + 2] = (float)((double)bv * inv);
-        vectors[4 * (size_t)win_id + 3] = m2 > 0.f ? (float)((double)bv / (double)m2) : INFINITY;
-        flags[win_id] = f;
-    }
+    peak_tail(plane_at, plane_at, nS, R, ox, oy, inv, outside, win_id, vectors, flags, planes, red, redi);
 }
 
 template <int N, int B>
@@ -306,16 +246,18 @@ int launch(const float *im1, const float *im2, int W, int H, int step, int R, in
     return 0;
 }
 
-bool weight_ok(float v) { return std::isfinite(v) && v >= 0.f; }
+const char *weights_error(float window_sigma, float diameter) {
+    if (!(std::isfinite(window_sigma) && window_sigma >= 0.f)) return "window_sigma must be finite and >= 0";
+    if (!(std::isfinite(diameter) && diameter >= 0.f)) return "diameter must be finite and >= 0";
+    return nullptr;
+}
 
 }  // namespace
 
 extern "C" int photon_piv_phase_tables(int win, float window_sigma, float diameter, float *twiddles, float *window, float *filter) {
-    const char *bad = nullptr;
-    if (win != 16 && win != 32 && win != 64) bad = "win must be 16, 32 or 64";
-    else if (!weight_ok(window_sigma)) bad = "window_sigma must be finite and >= 0";
-    else if (!weight_ok(diameter)) bad = "diameter must be finite and >= 0";
-    else if (!twiddles || !window || !filter) bad = "null table pointer";
+    const char *bad = piv_grid::win_error(win);
+    if (!bad) bad = weights_error(window_sigma, diameter);
+    if (!bad && (!twiddles || !window || !filter)) bad = "null table pointer";
     if (bad) {
         fprintf(stderr, "photon: photon_piv_phase_tables: %s (win %d, window_sigma %g, diameter %g)\n", bad, win, (double)window_sigma,
                 (double)diameter);
@@ -328,36 +270,24 @@ extern "C" int photon_piv_phase_tables(int win, float window_sigma, float diamet
 extern "C" int photon_piv_correlate_phase(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int radius,
                                           const int *d_offset, int mode, float window_sigma, float diameter, float *d_vectors, int *d_flags,
                                           float *d_planes, int *n_rows, int *n_cols, void *stream_p) {
-    const char *bad = nullptr;
-    if (win != 16 && win != 32 && win != 64) bad = "win must be 16, 32 or 64";
-    else if (radius < 1 || radius > win / 2 - 1) bad = "radius must lie in [1, win / 2 - 1]";
-    else if (step < 1) bad = "step must be >= 1";
-    else if (width < win || height < win) bad = "the image is smaller than one window";
-    else if (mode != 0 && mode != 1) bad = "mode must be 0 or 1";
-    else if (!weight_ok(window_sigma)) bad = "window_sigma must be finite and >= 0";
-    else if (!weight_ok(diameter)) bad = "diameter must be finite and >= 0";
-    else if (!d_im1 || !d_im2) bad = "null image pointer";
-    else if (d_vectors && !d_flags) bad = "d_vectors without d_flags";
+    const char *bad = piv_grid::win_error(win);
+    if (!bad && (radius < 1 || radius > win / 2 - 1)) bad = "radius must lie in [1, win / 2 - 1]";
+    if (!bad) bad = piv_grid::grid_error(width, height, win, step);
+    if (!bad && mode != 0 && mode != 1) bad = "mode must be 0 or 1";
+    if (!bad) bad = weights_error(window_sigma, diameter);
+    if (!bad && (!d_im1 || !d_im2)) bad = "null image pointer";
+    if (!bad && d_vectors && !d_flags) bad = "d_vectors without d_flags";
     if (bad) {
         fprintf(stderr, "photon: photon_piv_correlate_phase: %s (win %d, step %d, radius %d, mode %d, window_sigma %g, diameter %g, %d x %d image)\n",
                 bad, win, step, radius, mode, (double)window_sigma, (double)diameter, width, height);
         return 1;
     }
-    const int rows = (height - win) / step + 1, cols = (width - win) / step + 1;
-    if ((long long)rows * cols > INT_MAX) {
-        fprintf(stderr, "photon: photon_piv_correlate_phase: %d x %d windows are too many for one call\n", rows, cols);
-        return 1;
-    }
-    if (n_rows) *n_rows = rows;
-    if (n_cols) *n_cols = cols;
+    int rows, cols;
+    PH_TRY(piv_grid::grid_size("photon_piv_correlate_phase", width, height, win, step, rows, cols, n_rows, n_cols));
     if (!d_vectors) return 0;                   // the size query
     hipStream_t stream = (hipStream_t)stream_p;
-    switch (win) {
-    case 16: return launch<16, 64>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, mode, window_sigma, diameter, d_vectors,
-                                   d_flags, d_planes, stream);
-    case 32: return launch<32, 256>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, mode, window_sigma, diameter, d_vectors,
-                                    d_flags, d_planes, stream);
-    default: return launch<64, 256>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, mode, window_sigma, diameter, d_vectors,
-                                    d_flags, d_planes, stream);
-    }
+    return piv_grid::dispatch_win(win, [&](auto N) {            // 64 threads at win 16, 256 above
+        return launch<N(), N() == 16 ? 64 : 256>(d_im1, d_im2, width, height, step, radius, rows, cols, d_offset, mode, window_sigma, diameter,
+                                                 d_vectors, d_flags, d_planes, stream);
+    });
 }

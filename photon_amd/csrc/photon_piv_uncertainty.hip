@@ -24,6 +24,7 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_grid.hpp"
 
 using namespace photon;
 
@@ -233,16 +234,7 @@ template <int WIN, int K>
 int launch(const float *im1, const float *im2, int W, int step, int n_rows, int n_cols, float *sigma, int *flags, double *stats,
            hipStream_t stream) {
     constexpr size_t bytes = Layout<WIN, K>::kBytes;
-    if (bytes > 65536) {
-        int dev = 0, lds_limit = 0;
-        PH_CHECK(hipGetDevice(&dev));
-        PH_CHECK(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
-        if (bytes > (size_t)lds_limit) {
-            fprintf(stderr, "photon: photon_piv_uncertainty: win %d, reach %d needs more LDS than the device's %d bytes\n", WIN, K, lds_limit);
-            return 1;
-        }
-        PH_CHECK(hipFuncSetAttribute((const void *)piv_uncertainty_kernel<WIN, K>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
-    }
+    PH_TRY(piv_grid::reserve_lds(piv_uncertainty_kernel<WIN, K>, bytes, "photon_piv_uncertainty", WIN, "reach", K));
     hipLaunchKernelGGL((piv_uncertainty_kernel<WIN, K>), dim3((unsigned)(n_rows * n_cols)), dim3(kThreads), bytes, stream, im1, im2, W, step,
                        n_cols, sigma, flags, stats);
     PH_CHECK(hipGetLastError());
@@ -265,29 +257,20 @@ int launch_reach(int reach, const float *im1, const float *im2, int W, int step,
 
 extern "C" int photon_piv_uncertainty(const float *d_im1, const float *d_im2, int width, int height, int win, int step, int reach,
                                       float *d_sigma, int *d_flags, double *d_stats, int *n_rows, int *n_cols, void *stream_p) {
-    const char *bad = nullptr;
-    if (win != 16 && win != 32 && win != 64) bad = "win must be 16, 32 or 64";
-    else if (reach < 0 || reach > kMaxReach) bad = "reach must lie in [0, 4]";
-    else if (step < 1) bad = "step must be >= 1";
-    else if (width < win || height < win) bad = "the image is smaller than one window";
-    else if (!d_im1 || !d_im2) bad = "null image pointer";
-    else if (d_sigma && !d_flags) bad = "d_sigma without d_flags";
+    const char *bad = piv_grid::win_error(win);
+    if (!bad && (reach < 0 || reach > kMaxReach)) bad = "reach must lie in [0, 4]";
+    if (!bad) bad = piv_grid::grid_error(width, height, win, step);
+    if (!bad && (!d_im1 || !d_im2)) bad = "null image pointer";
+    if (!bad && d_sigma && !d_flags) bad = "d_sigma without d_flags";
     if (bad) {
         fprintf(stderr, "photon: photon_piv_uncertainty: %s (win %d, step %d, reach %d, %d x %d image)\n", bad, win, step, reach, width, height);
         return 1;
     }
-    const int rows = (height - win) / step + 1, cols = (width - win) / step + 1;
-    if ((long long)rows * cols > INT_MAX) {
-        fprintf(stderr, "photon: photon_piv_uncertainty: %d x %d windows are too many for one call\n", rows, cols);
-        return 1;
-    }
-    if (n_rows) *n_rows = rows;
-    if (n_cols) *n_cols = cols;
+    int rows, cols;
+    PH_TRY(piv_grid::grid_size("photon_piv_uncertainty", width, height, win, step, rows, cols, n_rows, n_cols));
     if (!d_sigma) return 0;                     // the size query
     hipStream_t stream = (hipStream_t)stream_p;
-    switch (win) {
-    case 16: return launch_reach<16>(reach, d_im1, d_im2, width, step, rows, cols, d_sigma, d_flags, d_stats, stream);
-    case 32: return launch_reach<32>(reach, d_im1, d_im2, width, step, rows, cols, d_sigma, d_flags, d_stats, stream);
-    default: return launch_reach<64>(reach, d_im1, d_im2, width, step, rows, cols, d_sigma, d_flags, d_stats, stream);
-    }
+    return piv_grid::dispatch_win(win, [&](auto WIN) {
+        return launch_reach<WIN()>(reach, d_im1, d_im2, width, step, rows, cols, d_sigma, d_flags, d_stats, stream);
+    });
 }

@@ -136,14 +136,5 @@ inline dim3 warp_grid(int width, int height) {
     return dim3((unsigned)((width + kWarpX - 1) / kWarpX), (unsigned)((height + kWarpY - 1) / kWarpY));
 }
 
-// the argument rules the grid of section 7 shares with section 5; nullptr when the grid is fine
-inline const char *grid_error(int width, int height, int win, int step, int n_rows, int n_cols) {
-    if (win != 16 && win != 32 && win != 64) return "win must be 16, 32 or 64";
-    if (step < 1) return "step must be >= 1";
-    if (width < win || height < win) return "the image is smaller than one window";
-    if (n_rows != (height - win) / step + 1 || n_cols != (width - win) / step + 1) return "n_rows x n_cols is not the window grid of section 5";
-    return nullptr;
-}
-
 }  // namespace piv_warp
 }  // namespace photon

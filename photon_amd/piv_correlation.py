@@ -29,17 +29,28 @@ FLAG_FLAT = 2               # an energy is 0 (all pixels of a, or of b at zero s
 FLAG_OUTSIDE = 4            # a pixel of im2 the window needs lies outside the image (it reads as the window's mean)
 
 
-def check_arguments(shape, win: int, step: int, radius: int):
-    """The arguments photon_piv_correlate refuses, as a ValueError."""
-    h, w = shape
+def check_win(win: int):
     if int(win) not in WINDOW_SIZES:
         raise ValueError(f"win must be one of {WINDOW_SIZES}, not {win}")
-    if not 1 <= int(radius) <= int(win) // 2:
-        raise ValueError(f"radius must lie in [1, win / 2], not {radius}")
+
+
+def check_grid(shape, win: int, step: int):
+    """The (win, step) grids every window entry point refuses (sections 5, 11 and 13), as a ValueError.  An entry point with
+    a rule that depends on win alone (radius, reach) checks win, then that rule, then the grid, as the device does."""
+    h, w = shape
+    check_win(win)
     if int(step) < 1:
         raise ValueError(f"step must be >= 1, not {step}")
     if h < win or w < win:
         raise ValueError(f"a {h} x {w} image is smaller than one {win} x {win} window")
+
+
+def check_arguments(shape, win: int, step: int, radius: int):
+    """The arguments photon_piv_correlate refuses, as a ValueError."""
+    check_win(win)
+    if not 1 <= int(radius) <= int(win) // 2:
+        raise ValueError(f"radius must lie in [1, win / 2], not {radius}")
+    check_grid(shape, win, step)
 
 
 def grid_shape(shape, win: int, step: int):

@@ -27,15 +27,10 @@ MODE_CIRCULAR, MODE_PHASE = 0, 1
 
 def check_arguments(shape, win: int, step: int, radius: int, mode: int = MODE_PHASE, window_sigma: float = 0.0, diameter: float = 0.0):
     """The arguments photon_piv_correlate_phase refuses, as a ValueError."""
-    h, w = shape
-    if int(win) not in pc.WINDOW_SIZES:
-        raise ValueError(f"win must be one of {pc.WINDOW_SIZES}, not {win}")
+    pc.check_win(win)
     if not 1 <= int(radius) <= int(win) // 2 - 1:
         raise ValueError(f"radius must lie in [1, win / 2 - 1], not {radius}")
-    if int(step) < 1:
-        raise ValueError(f"step must be >= 1, not {step}")
-    if h < win or w < win:
-        raise ValueError(f"a {h} x {w} image is smaller than one {win} x {win} window")
+    pc.check_grid(shape, win, step)
     if int(mode) not in (MODE_CIRCULAR, MODE_PHASE):
         raise ValueError(f"mode must be 0 (circular correlation) or 1 (phase correlation), not {mode}")
     for name, v in (("window_sigma", window_sigma), ("diameter", diameter)):

@@ -29,15 +29,10 @@ MAX_REACH = 4
 
 def check_arguments(shape, win: int, step: int, reach: int):
     """The arguments photon_piv_uncertainty refuses, as a ValueError (null pointers aside)."""
-    h, w = shape
-    if int(win) not in pc.WINDOW_SIZES:
-        raise ValueError(f"win must be one of {pc.WINDOW_SIZES}, not {win}")
+    pc.check_win(win)
     if not 0 <= int(reach) <= MAX_REACH:
         raise ValueError(f"reach must lie in [0, {MAX_REACH}], not {reach}")
-    if int(step) < 1:
-        raise ValueError(f"step must be >= 1, not {step}")
-    if h < win or w < win:
-        raise ValueError(f"a {h} x {w} image is smaller than one {win} x {win} window")
+    pc.check_grid(shape, win, step)
 
 
 def half_neighbourhood(reach: int):

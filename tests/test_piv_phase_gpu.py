@@ -8,6 +8,7 @@ import pytest
 
 import piv_deformation_cases as dcs
 import piv_phase_cases as cs
+import piv_tail_cases
 from photon_amd import piv_correlation as pc
 from photon_amd import piv_deformation as pd
 from photon_amd import piv_phase as pp
@@ -34,24 +35,66 @@ def same_values(got, want):
 @pytest.mark.parametrize("index", range(len(cs.DEVICE_CASES)), ids=[cs.case_id(c) for c in cs.DEVICE_CASES])
 def test_device_equals_the_f32_model(photon, index):
     win, R, step, shape, _, with_off, mode, sigma, diameter = cs.DEVICE_CASES[index]
-    im1, im2, off, (want_v, want_f, want_p) = cs.device_case(index)
-    got_v, got_f, got_p = device_phase(photon, im1, im2, win, step, R, off, mode, sigma, diameter)
+    im1, im2, off, want = cs.device_case(index)
+    if with_off:
+        assert (want[1] & pc.FLAG_OUTSIDE).any()
+    assert not (want[1] & pc.FLAG_FLAT).any()
+    worst = assert_equals_the_f32_model(device_phase(photon, im1, im2, win, step, R, off, mode, sigma, diameter), want)
+    print(f"{cs.case_id(cs.DEVICE_CASES[index])}: {want[1].size} windows, largest |delta d| {worst:.3g} px")
+
+
+def assert_equals_the_f32_model(got, want):
+    """Flags, planes (NaN where the model has NaN), argmax, peak and ratio value for value; the subpixel part within 1e-5 px:
+    the f32 ulp at 31 px (1.9e-6) plus the device's f64 log against numpy's.  A window whose log-curvature lies below 1e-6
+    would be excluded (at most 1 % of the windows that are not flat) -- the cases have none (tests/test_piv_phase.py).
+    Returns the largest subpixel difference."""
+    (got_v, got_f, got_p), (want_v, want_f, want_p) = got, want
     assert got_v.shape == want_v.shape and got_p.shape == want_p.shape and got_p.dtype == want_p.dtype
     assert np.array_equal(got_f, want_f), np.argwhere(got_f != want_f)[:5]
-    if with_off:
-        assert (want_f & pc.FLAG_OUTSIDE).any()
-    assert not (want_f & pc.FLAG_FLAT).any()
     assert same_values(got_p, want_p), float(np.abs(got_p - want_p).max())
-    n = want_f.size
-    assert np.array_equal(np.argmax(got_p.reshape(n, -1), axis=1), np.argmax(want_p.reshape(n, -1), axis=1))
+    live = (want_f & pc.FLAG_FLAT) == 0
+    n = int(live.sum())
+    assert np.array_equal(np.argmax(got_p[live].reshape(n, -1), axis=1), np.argmax(want_p[live].reshape(n, -1), axis=1))
+    assert np.isnan(got_v[~live]).all()
     assert same_values(got_v[..., 2], want_v[..., 2]) and same_values(got_v[..., 3], want_v[..., 3])
-    # subpixel: the f32 ulp at 31 px (1.9e-6) plus the device's f64 log against numpy's; a window whose log-curvature lies
-    # below 1e-6 would be excluded (at most 1 % of them) -- the cases have none (tests/test_piv_phase.py)
-    keep = (pp.log_curvature(want_p) >= 1e-6).all(axis=-1)
+    keep = (pp.log_curvature(want_p[live]) >= 1e-6).all(axis=-1)
     assert keep.mean() >= 0.99
-    dv = np.abs(got_v[keep][:, :2].astype(np.float64) - want_v[keep][:, :2])
-    print(f"{cs.case_id(cs.DEVICE_CASES[index])}: {n} windows, largest |delta d| {dv.max():.3g} px")
+    dv = np.abs(got_v[live][keep][:, :2].astype(np.float64) - want_v[live][keep][:, :2])
     assert dv.max() <= 1e-5
+    return float(dv.max())
+
+
+NINE_FLAGS = {0: [[6, 1, 0], [0, 0, 4], [0, 4, 0]], 1: [[6, 1, 0], [0, 0, 4], [0, 4, 1]]}
+
+
+def nine_windows(mode):
+    """piv_tail_cases.nine_windows with section 13's second frame and offsets: flat + outside, a
+    peak on the plane's edge, outside alone and clean windows in one launch.  (im1, im2, offset, the f32 model's outputs)"""
+    im1, _, im2, off = piv_tail_cases.nine_windows()
+    want = pp.correlate_phase_model_f32(im1, im2, 16, 16, 4, offset=off, mode=mode, window_sigma=4.0, diameter=2.5, planes=True)
+    assert want[1].tolist() == NINE_FLAGS[mode]
+    return im1, im2, off, want
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_every_branch_of_the_peak_tail_in_nine_windows(photon, mode):
+    im1, im2, off, want = nine_windows(mode)
+    assert_equals_the_f32_model(device_phase(photon, im1, im2, 16, 16, 4, off, mode, 4.0, 2.5), want)
+
+
+@pytest.mark.parametrize("index", [1, 4, 8, "nine"])
+def test_without_planes_the_vectors_and_flags_are_the_same_bytes(photon, index):
+    """d_planes = NULL: the same vector and flag bytes, at win 16, 32 and 64 and on the nine windows with their flat one."""
+    if index == "nine":
+        im1, im2, off, _ = nine_windows(1)
+        args = (16, 16, 4, off, 1, 4.0, 2.5)
+    else:
+        win, R, step, _, _, _, mode, sigma, diameter = cs.DEVICE_CASES[index]
+        im1, im2, off, _ = cs.device_case(index)
+        args = (win, step, R, off, mode, sigma, diameter)
+    v1, f1, _ = device_phase(photon, im1, im2, *args, planes=True)
+    v0, f0, p0 = device_phase(photon, im1, im2, *args, planes=False)
+    assert p0 is None and v0.tobytes() == v1.tobytes() and f0.tobytes() == f1.tobytes()
 
 
 @pytest.mark.parametrize("kind", ["checkerboard", "stripes"])

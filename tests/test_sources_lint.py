@@ -62,3 +62,20 @@ def test_no_pool_malloc_or_pool_free_outside_the_pool():
     by hand is a block that leaks on the return path somebody forgot."""
     offenders = _calls_outside_the_pool(["pool_malloc", "pool_free"])
     assert not offenders, "pool_malloc / pool_free outside photon_pool.*:\n" + "\n".join(offenders)
+
+
+def test_the_build_knows_every_header():
+    """needs_build() and the per-object staleness test look at build.HEADERS alone: a header under csrc that the list does
+    not name can change without the library being rebuilt, and a GPU run then tests a stale one."""
+    from photon_amd import build
+    on_disk = {os.path.basename(p) for p in glob.glob(os.path.join(CSRC, "*.hpp"))}
+    listed = {os.path.basename(p) for p in build.HEADERS if os.path.dirname(p) == CSRC}
+    assert on_disk and on_disk == listed, sorted(on_disk ^ listed)
+
+
+def test_the_window_size_rule_is_stated_once():
+    """Every entry point on the (win, step) grid takes its argument rules from piv_grid.hpp: the win rule's message in a
+    second file is a second statement of the rule."""
+    holders = [os.path.basename(p) for p in sorted(glob.glob(os.path.join(CSRC, "*")))
+               if "win must be 16, 32 or 64" in open(p, encoding="utf-8").read()]
+    assert holders == ["piv_grid.hpp"], holders
