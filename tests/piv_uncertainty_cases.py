@@ -13,7 +13,7 @@ from photon_amd import piv_uncertainty as pu
 # more rows than columns and the reverse, every window size; each at every reach of REACHES
 GRIDS = [((64, 64), 16, 8), ((64, 64), 32, 8), ((64, 64), 64, 1), ((97, 130), 32, 16), ((130, 97), 16, 5), ((256, 256), 32, 16),
          ((256, 256), 64, 32)]
-REACHES = (0, 2, 4)
+REACHES = (0, 1, 2, 3, 4)                      # every reach the entry point accepts: odd ones pad the LDS rows to reach + 1
 CASES = [(shape, win, step, reach) for shape, win, step in GRIDS for reach in REACHES]
 NOISE = 0.03
 

@@ -17,7 +17,8 @@ from photon_amd import optical_flow as of
 from photon_amd import piv_correlation as pc
 from photon_amd import piv_deformation as pd
 from test_bos_density_gpu import BOUND_CORRELATED, blob_pairs, check  # noqa: F401  (blob_pairs: the fixture)
-from test_piv_deformation_gpu import device_coefficients, device_deform, image
+from test_piv_deformation_gpu import (FAR_SCALES, SMALL_SHAPES, TOL, device_coefficients, device_deform, exact_shift, far_dense_fields,
+                                      far_taps, image, random_image)
 
 pytestmark = pytest.mark.gpu
 
@@ -92,6 +93,29 @@ def test_dense_warp_equals_the_grid_warp_bit_for_bit(photon, shape, win, step):
             assert device_deform_dense(photon, coef, dense, scale).tobytes() == device_deform(photon, coef, field, win, step, scale).tobytes()
 
 
+@pytest.mark.parametrize("shape", SMALL_SHAPES + [(37, 53)], ids=lambda s: f"{s[0]}x{s[1]}")
+def test_dense_warp_far_from_the_image_matches_the_model(photon, shape):
+    """Sides from 1 pixel, shifts from a few pixels to beyond the clamp at 2^24: deform_kernel's clamp, and mirror_far for the
+    taps one reflection does not bring back, against the f64 model at the bar of the grid warp."""
+    im = random_image(shape, 7 * shape[0] + shape[1])
+    coef = pd.bspline_coefficients_model(im).astype(np.float32)             # both sides read the same f32 coefficients
+    zero = device_deform_dense(photon, coef, np.zeros((*shape, 2), np.float32), 1.0)
+    assert np.abs(zero - im).max() <= TOL * np.abs(im).max()
+    fields = far_dense_fields(shape, 11 * shape[0] + shape[1])
+    for scale in FAR_SCALES:
+        clamped = far = False
+        for dense in fields:
+            c, f = far_taps(exact_shift(dense, scale), shape)
+            clamped, far = clamped or c, far or f
+            want = pd.deform_dense_model(coef, dense, scale)
+            assert np.isfinite(want).all()
+            got = device_deform_dense(photon, coef, dense, scale)
+            err = float(np.abs(got - want).max() / np.abs(im).max())
+            print(f"dense warp {shape}, scale {scale}, |D| up to {np.abs(dense).max():.3g}: max |device - model| = {err:.2e} of max |im|")
+            assert (got != -77.0).all() and err <= TOL, (shape, scale, err)
+        assert clamped and far, (shape, scale)
+
+
 # ---- c: the data terms --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", oc.SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
 def test_terms_equal_the_model_bit_for_bit(photon, shape):
@@ -108,7 +132,17 @@ def sweep_shapes():
     ty, tx = tile_shape()
     big = (2 * ty + 3, 2 * tx + 9)              # sides of more than two tiles plus one pixel: nine workgroups, the last ones narrow
     assert max(big) <= 300
-    return oc.SHAPES + [big]
+    # one tile exactly, one tile plus a pixel down and less a pixel across, two tiles by two tiles plus a pixel
+    return oc.SHAPES + [big, (ty, tx), (ty + 1, tx - 1), (2 * ty, 2 * tx + 1)]
+
+
+def model_chain(terms, u, counts):
+    """{n: iterate_model(terms, u, n)} for the counts: one chain of model sweeps serves them all."""
+    model, done = {0: u}, 0
+    for n in sorted(set(counts) - {0}):
+        model[n] = of.iterate_model(terms, model[done], n - done)
+        done = n
+    return model
 
 
 @pytest.mark.parametrize("shape", sweep_shapes(), ids=lambda s: f"{s[0]}x{s[1]}")
@@ -117,16 +151,54 @@ def test_sweeps_equal_the_model_bit_for_bit(photon, shape):
     assert 1 <= T <= 64
     terms, u = oc.random_terms(shape, 31)
     counts = sorted({0, 1, T - 1, T, T + 1, 2 * T + 3})
-    model, done = {0: u}, 0
-    for n in counts[1:]:                        # one chain of model sweeps serves every count
-        model[n] = of.iterate_model(terms, model[done], n - done)
-        done = n
+    model = model_chain(terms, u, counts)
     for n in counts:
         got = device_iterate(photon, terms, u, n)
         assert got.tobytes() == model[n].tobytes(), (shape, n, float(np.abs(got - model[n]).max()))
         if n <= T:
             assert device_iterate(photon, terms, u, n, with_tmp=False).tobytes() == model[n].tobytes(), (shape, n)
     assert device_iterate(photon, terms, u, 0).tobytes() == u.tobytes()
+
+
+@pytest.mark.parametrize("shape", sweep_shapes(), ids=lambda s: f"{s[0]}x{s[1]}")
+def test_every_sweep_kernel_equals_the_model_bit_for_bit(photon, shape, monkeypatch):
+    """n = 0 .. T at the default T: count n is one launch of sweep_kernel<n>, so every instantiation (and with it every
+    thread arrangement: K = 3, 4 and 5 rows per thread) runs, with and without d_tmp."""
+    monkeypatch.delenv("PHOTON_OPTFLOW_SWEEPS", raising=False)
+    T = photon.optflow_iterations_per_launch()
+    assert T == 8                               # sweep_kernel<1 .. 8>: a new default changes what this test covers
+    terms, u = oc.random_terms(shape, 32)
+    model = model_chain(terms, u, range(T + 1))
+    for n in range(T + 1):
+        for with_tmp in (True, False):
+            got = device_iterate(photon, terms, u, n, with_tmp=with_tmp)
+            assert got.tobytes() == model[n].tobytes(), (shape, n, with_tmp, float(np.abs(got - model[n]).max()))
+
+
+@pytest.mark.parametrize("t", range(1, 8))
+def test_every_launch_size_equals_the_model_bit_for_bit(photon, monkeypatch, t):
+    """PHOTON_OPTFLOW_SWEEPS = t: 1 to 4 launches (both parities of the d_tmp / d_out alternation), with a remainder launch
+    of every size from 1 to t."""
+    monkeypatch.setenv("PHOTON_OPTFLOW_SWEEPS", str(t))
+    assert photon.optflow_iterations_per_launch() == t
+    counts = sorted({t, t + 1, 2 * t, 2 * t + 1, 3 * t + 2})
+    for shape in (sweep_shapes()[len(oc.SHAPES)], (3, 4)):
+        terms, u = oc.random_terms(shape, 33)
+        model = model_chain(terms, u, counts)
+        for n in counts:
+            got = device_iterate(photon, terms, u, n)
+            assert got.tobytes() == model[n].tobytes(), (t, shape, n, float(np.abs(got - model[n]).max()))
+        assert device_iterate(photon, terms, u, t, with_tmp=False).tobytes() == model[t].tobytes()
+
+
+@pytest.mark.parametrize("value", ["0", "9", "-1", "x"])
+def test_a_sweep_count_out_of_range_gives_the_default(photon, monkeypatch, value):
+    monkeypatch.delenv("PHOTON_OPTFLOW_SWEEPS", raising=False)
+    default = photon.optflow_iterations_per_launch()
+    monkeypatch.setenv("PHOTON_OPTFLOW_SWEEPS", value)
+    assert photon.optflow_iterations_per_launch() == default == 8
+    terms, u = oc.random_terms((37, 53), 34)    # the call reads the variable as the query does: `default` sweeps need no d_tmp
+    assert device_iterate(photon, terms, u, default, with_tmp=False).tobytes() == of.iterate_model(terms, u, default).tobytes()
 
 
 def test_identical_frames_keep_a_constant_field_on_the_device(photon):

@@ -76,6 +76,36 @@ def test_coefficients_match_the_model(photon, shape):
     assert err <= TOL
 
 
+# sides below the 14-pixel halo of the filter: a halo index is reflected more than once (mirror_far), a side of 1 has no period
+SMALL_SHAPES = [(1, 1), (1, 9), (9, 1), (3, 4), (14, 15), (15, 14), (2, 70)]
+# The first tap that needs a second reflection lies n pixels from the nearest pixel and weighs |z|^n = 0.268^n: only on sides
+# of 5 or less does a wrong second reflection move a coefficient by more than TOL.  The coefficient test adds these.
+TINY_SHAPES = [(4, 3), (5, 2), (2, 5)]
+
+
+def random_image(shape, seed):
+    """Plain random f32 in [0, 1): image() places no particle on the smallest shapes."""
+    return np.random.default_rng(seed).random(shape, dtype=np.float32)
+
+
+@pytest.mark.parametrize("shape", SMALL_SHAPES + TINY_SHAPES, ids=lambda s: f"{s[0]}x{s[1]}")
+def test_coefficients_of_small_images_match_the_model(photon, shape):
+    import torch
+    im = random_image(shape, 100 * shape[0] + shape[1])
+    want = pd.bspline_coefficients_model(im)
+    assert np.isfinite(want).all()
+    a = torch.from_numpy(im).cuda()
+    c = torch.full(shape, -77.0, dtype=torch.float32, device="cuda")
+    photon.bspline_coefficients(a.data_ptr(), shape[1], shape[0], c.data_ptr())
+    torch.cuda.synchronize()
+    got = c.cpu().numpy()
+    err = np.abs(got - want).max() / np.abs(im).max()
+    print(f"coefficients {shape[0]} x {shape[1]}: max |device - model| = {err:.2e} of max |im|")
+    assert (got != -77.0).all() and err <= TOL
+    if shape == (1, 1):
+        assert abs(float(got[0, 0]) - float(im[0, 0])) <= TOL * float(im[0, 0])       # every tap is the one pixel: the filter's gain, 1
+
+
 # ---- 5b. warp ------------------------------------------------------------------------------------------------------------
 def field_of(kind, n_rows, n_cols, stride, seed):
     rng = np.random.default_rng(seed)
@@ -126,6 +156,86 @@ def test_device_coefficients_and_zero_scale_return_the_image(photon):
     field = field_of("random", *pc.grid_shape(im.shape, 32, 16), 2, seed=1)
     got = device_deform(photon, device_coefficients(photon, im), field, 32, 16, 0.0)
     assert np.abs(got - im).max() <= TOL * np.abs(im).max()
+
+
+# ---- 5b, far from the image: the clamp of scale D to 2^24 pixels and tap indices that one reflection does not bring back ----
+FAR_SCALES = (1.0, -0.5)        # scale D is exact in f32 for every f32 D; 0.5 would be too, the existing WARPS hold it
+BEYOND = (3.0e7, -5.0e7)        # past the clamp at scale 1.0; at -0.5 the second one still is
+
+
+def exact_shift(d32, scale):
+    """scale D as the device forms it (f32) and as the model does (f64): the test's fields must make them the same number."""
+    assert d32.dtype == np.float32
+    s32, s64 = np.float32(scale) * d32, float(scale) * d32.astype(np.float64)
+    assert s32.dtype == np.float32 and np.array_equal(s32.astype(np.float64), s64)
+    return s64
+
+
+def far_taps(shift, shape):
+    """(clamped, far) of shifts [h, w, 2] = (x, y) per pixel: whether any shift meets the clamp's far side, and whether any of
+    the four tap indices per axis lies further than one reflection from the image (|i| > 2 (n - 1): piv_warp.hpp, mirror)."""
+    s = np.clip(shift, -pd.MAX_SHIFT, pd.MAX_SHIFT)
+    h, w = shape
+    far = False
+    for axis, n, at in ((0, w, np.arange(w)[None, :]), (1, h, np.arange(h)[:, None])):
+        first = at + np.floor(s[..., axis]).astype(np.int64) - 1
+        far = far or bool((np.abs(np.stack([first, first + 3])) > 2 * (n - 1)).any())
+    return bool((np.abs(shift) > pd.MAX_SHIFT).any()), far
+
+
+def far_dense_fields(shape, seed):
+    """Per-pixel fields f32 [k, h, w, 2] in multiples of 1/8 pixel, magnitudes cycling through a few pixels, a few image
+    widths, 1e3, 1e6 and the 64 pixels below 2^24, signs at random, plus the two entries of BEYOND; as many fields as it takes
+    to hold each of these at least twice (one, unless the image has fewer than 7 pixels)."""
+    h, w = shape
+    rng = np.random.default_rng(seed)
+    n = 2 * h * w
+    k = -(-14 // n)
+    top = [4.0, 3.0 * max(h, w), 1.0e3, 1.0e6, 2.0 ** 24]
+    low = [0.0, float(max(h, w)), 5.0e2, 5.0e5, 2.0 ** 24 - 64.0]
+    cls = np.arange(k * n) % 5
+    mag = np.round(8.0 * rng.uniform(np.take(low, cls), np.take(top, cls))) / 8.0
+    mag = np.where(cls == 4, np.minimum(np.floor(mag), 2.0 ** 24 - 1.0), mag)    # just under 2^24 an f32 is a whole number
+    d = mag * rng.choice([-1.0, 1.0], k * n)
+    d[0], d[-1] = BEYOND
+    d32 = d.astype(np.float32)
+    assert np.array_equal(d32.astype(np.float64), d)                             # every value is an f32
+    return d32.reshape(k, h, w, 2)
+
+
+FAR_GRID_CASES = [((64, 64), 16, 8), ((97, 130), 32, 16)]
+# constant fields (bilinear interpolation of equal nodes is exact: f32 and f64 agree on D).  2^24 - 0.5 is no f32 -- as one
+# it is 2^24, the clamp itself --, so 2^24 - 1 stands beside it: the largest shift with a fraction (at scale -0.5).
+FAR_GRID_VALUES = [(1000.25, -777.5), (2.0 ** 24 - 0.5, -(2.0 ** 24 - 0.5)), (2.0 ** 24 - 1.0, -(2.0 ** 24 - 1.0)), BEYOND]
+
+
+@pytest.mark.parametrize("shape,win,step", FAR_GRID_CASES, ids=lambda v: "x".join(map(str, v)) if isinstance(v, tuple) else str(v))
+def test_grid_warp_far_from_the_image_matches_the_model(photon, shape, win, step):
+    import torch
+    im = image(shape, win + step)
+    coef = pd.bspline_coefficients_model(im).astype(np.float32)
+    c = torch.from_numpy(coef).cuda()
+    n_rows, n_cols = pc.grid_shape(shape, win, step)
+    worst = 0.0
+    for value in FAR_GRID_VALUES:
+        for stride in (2, 4):
+            field = np.full((n_rows, n_cols, stride), 0.25, np.float32)
+            field[..., :2] = value
+            f = torch.from_numpy(field).cuda()
+            for scale in FAR_SCALES:
+                shift = np.broadcast_to(exact_shift(field[0, 0, :2], scale), (*shape, 2))
+                clamped, far = far_taps(shift, shape)
+                assert far and clamped == (value == BEYOND), (value, scale)
+                want = pd.deform_model(coef, field, win, step, scale)
+                assert np.isfinite(want).all()
+                out = torch.full(shape, -77.0, dtype=torch.float32, device="cuda")
+                photon.piv_deform(c.data_ptr(), shape[1], shape[0], f.data_ptr(), stride, n_rows, n_cols, win, step, scale, out.data_ptr())
+                torch.cuda.synchronize()
+                got = out.cpu().numpy()
+                err = float(np.abs(got - want).max() / np.abs(im).max())
+                worst = max(worst, err)
+                assert (got != -77.0).all() and err <= TOL, (value, stride, scale, err)
+    print(f"grid warp {shape} win {win} step {step}, shifts up to the clamp: max |device - model| = {worst:.2e} of max |im|")
 
 
 # ---- 5c. validate -------------------------------------------------------------------------------------------------------

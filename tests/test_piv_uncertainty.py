@@ -18,7 +18,7 @@ def test_identical_frames_give_zero_sigma():
         assert (sigma == 0.0).all() and (flags == 0).all()
 
 
-@pytest.mark.parametrize("case", uc.CASES[3:6] + uc.CASES[12:15], ids=uc.case_id)
+@pytest.mark.parametrize("case", uc.CASES[5:10] + uc.CASES[20:25], ids=uc.case_id)
 def test_swapping_the_frames_returns_identical_bits(case):
     shape, win, step, reach = case
     im1, im2 = uc.matched_pair(shape)
@@ -26,7 +26,7 @@ def test_swapping_the_frames_returns_identical_bits(case):
         assert got.tobytes() == want.tobytes()
 
 
-@pytest.mark.parametrize("case", uc.CASES[9:15], ids=uc.case_id)
+@pytest.mark.parametrize("case", uc.CASES[15:25], ids=uc.case_id)
 def test_transposing_the_images_swaps_the_axes(case):
     shape, win, step, reach = case
     im1, im2 = uc.matched_pair(shape)
@@ -74,6 +74,16 @@ def test_no_case_sits_on_a_branch(case):
     assert np.isfinite(sigma).all() and (sigma > 0).all()
     s2, f2 = pu.sigma_from_stats(stats)
     assert s2.tobytes() == sigma.tobytes() and np.array_equal(f2, flags)
+
+
+@pytest.mark.parametrize("case", uc.CASES, ids=uc.case_id)
+def test_the_sign_of_V_does_not_hang_on_rounding(case):
+    """The device's flags must equal the model's exactly, and bit 32 is the sign of V.  The device's V is held to the model's
+    within 1e-11 N T (test_piv_uncertainty_gpu.SUM_RTOL): every |V| lies 10^4 times further from zero, on either axis."""
+    _, _, stats, T = uc.model(case)
+    margin = np.abs(stats[..., 3]) / (uc.n_terms(case[3]) * T)            # [n_rows, n_cols, axis]
+    print(f"{uc.case_id(case)}: smallest |V| / (N T) = {margin.min():.2e}")
+    assert margin.min() >= 1e-7
 
 
 def test_negative_variances_occur_naturally():

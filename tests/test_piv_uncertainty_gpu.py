@@ -63,20 +63,36 @@ def test_two_calls_return_identical_bits_with_and_without_stats(photon):
 
 def test_identical_frames_give_zero_sigma(photon):
     im = uc.matched_pair((97, 130))[0]
-    for win, step, reach in ((16, 8, 4), (32, 16, 2), (64, 32, 0)):
+    odd = [(win, step, reach) for win, step in ((16, 8), (32, 16), (64, 32)) for reach in (1, 3)]       # every kernel of an odd reach
+    for win, step, reach in [(16, 8, 4), (32, 16, 2), (64, 32, 0)] + odd:
         sigma, flags, stats = device_uncertainty(photon, im, im, win, step, reach)
-        assert (sigma == 0.0).all() and (flags == 0).all() and (stats[..., 2:] == 0.0).all()
+        assert sigma.shape == (*pc.grid_shape(im.shape, win, step), 2), (win, step, reach)
+        assert (sigma == 0.0).all() and (flags == 0).all() and (stats[..., 2:] == 0.0).all(), (win, step, reach)
+
+
+def check_a_constant_window(photon, which, shape, win, step, reach):
+    """Window (1, 2) of the grid, and only that one, constant in frame `which`."""
+    ims = [im.copy() for im in uc.matched_pair(shape)]
+    ims[which][step:step + win, 2 * step:2 * step + win] = 0.37
+    sigma, flags, stats = device_uncertainty(photon, *ims, win, step, reach)
+    want_sigma, want_flags, _, _ = pu.uncertainty_model(*ims, win, step, reach)
+    assert flags[1, 2] == pu.FLAG_FLAT and np.isnan(sigma[1, 2]).all() and np.isnan(stats[1, 2]).all()
+    assert int((flags & pu.FLAG_FLAT).astype(bool).sum()) == 1
+    assert np.array_equal(flags, want_flags) and np.array_equal(np.isnan(sigma), np.isnan(want_sigma))
+    np.testing.assert_allclose(sigma, want_sigma, rtol=SIGMA_MODEL_RTOL)
 
 
 @pytest.mark.parametrize("which", [0, 1])
 def test_a_constant_window_is_flat(photon, which):
-    ims = [im.copy() for im in uc.matched_pair((64, 64))]
-    ims[which][8:24, 16:32] = 0.37                          # window (1, 2) of the 16 / 8 grid, and only that one
-    sigma, flags, stats = device_uncertainty(photon, *ims, 16, 8, 2)
-    want_sigma, want_flags, _, _ = pu.uncertainty_model(*ims, 16, 8, 2)
-    assert flags[1, 2] == pu.FLAG_FLAT and np.isnan(sigma[1, 2]).all() and np.isnan(stats[1, 2]).all()
-    assert np.array_equal(flags, want_flags) and np.array_equal(np.isnan(sigma), np.isnan(want_sigma))
-    np.testing.assert_allclose(sigma, want_sigma, rtol=SIGMA_MODEL_RTOL)
+    check_a_constant_window(photon, which, (64, 64), 16, 8, 2)
+
+
+@pytest.mark.parametrize("which", [0, 1])
+@pytest.mark.parametrize("reach", [1, 3])
+@pytest.mark.parametrize("shape,win,step", [((64, 64), 16, 8), ((64, 64), 32, 8), ((130, 192), 64, 32)],
+                         ids=["win16", "win32", "win64"])
+def test_a_constant_window_is_flat_at_an_odd_reach(photon, shape, win, step, reach, which):
+    check_a_constant_window(photon, which, shape, win, step, reach)
 
 
 def test_refusals_and_the_size_query_write_nothing(photon, capfd):

@@ -62,15 +62,31 @@ def through_volume(tmp_path_factory):
     return scenes.bos_scene(n_dots=5, points_per_dot=9, rays_per_source=150, density_grad_filename=nrrd, seed=3)
 
 
-@pytest.mark.parametrize("interp", [1, 2])
-@pytest.mark.parametrize("algorithm", [1, 2])
-def test_records_do_not_depend_on_the_launch_plan(photon, through_volume, monkeypatch, interp, algorithm):
+# 1 .. 64: both ends of every group size G = 1, 2, 4, ..., 64 of launch_moments; 65: a second ray in lane 0 of the full wave
+GROUP_EDGES = [1, 2, 3, 4, 5, 8, 9, 16, 17, 32, 33, 64, 65]
+
+
+@pytest.mark.parametrize("rps", GROUP_EDGES)
+def test_records_bit_exact_at_every_group_size(photon, tmp_path, rps):
+    """Image 1 of conftest.dump_pair_calls (a few dots, no volume, every ray dumped) at `rps` rays per source: scene creation
+    accepts every count from 1."""
+    c = scenes.bos_scene(n_dots=3, points_per_dot=8, rays_per_source=rps, seed=5)
+    c.simulate_density_gradients, c.ray_tracing_algorithm = False, 0
+    c.save_lightrays, c.num_lightrays_save = True, c.num_rays
+    for what in ("position", "direction"):
+        d = tmp_path / f"light-ray-{what}s"
+        d.mkdir()
+        setattr(c, f"lightray_{what}_save_path", str(d))
+    assert c.lightray_number_per_particle == rps and c.num_rays == c.num_sources * rps
+    _, rec = photon.render_moments(c)
+    assert rec.shape == (c.num_sources, 8) and rec[:, 0].sum() > 0
+    assert_records_equal(rec, dfl.moments_from_dumps(*read_dumps(c), rps), f"{rps} rays per source")
+
+
+def assert_launch_plan_changes_no_record(photon, call, algorithm, interp, base, k):
+    """Every ray order x skip on / off x segments 1, -1, 4, and the source range split at k in either order: the records of
+    photon_trace_moments must equal `base`."""
     import torch
-    call = through_volume
-    call.ray_tracing_algorithm = algorithm
-    monkeypatch.setenv("PHOTON_INTERP", "cubic" if interp == 2 else "linear")
-    base_img, base = photon.render_moments(call)
-    assert base[:, 0].sum() > 0
     vol = photon.volume_load_nrrd(call.density_grad_filename, interp)
     vol.set_weight_bits(8)                                  # what start_ray_tracing sets (PHOTON_TEX_WEIGHTS default)
     scene = photon.scene_create(call)
@@ -96,16 +112,38 @@ def test_records_do_not_depend_on_the_launch_plan(photon, through_volume, monkey
         scene.set_ray_order(2)
         scene.set_skip_doomed(True)
         scene.set_march_segments(-1)
-        k = 17
+        assert 0 < k < n
         assert_records_equal(trace((0, k), (k, n)), base, "split")
         assert_records_equal(trace((k, n), (0, k)), base, "split, reversed")
     finally:
         scene.free()
         vol.free()
+
+
+@pytest.mark.parametrize("interp", [1, 2])
+@pytest.mark.parametrize("algorithm", [1, 2])
+def test_records_do_not_depend_on_the_launch_plan(photon, through_volume, monkeypatch, interp, algorithm):
+    call = through_volume
+    call.ray_tracing_algorithm = algorithm
+    monkeypatch.setenv("PHOTON_INTERP", "cubic" if interp == 2 else "linear")
+    base_img, base = photon.render_moments(call)
+    assert base[:, 0].sum() > 0
+    assert_launch_plan_changes_no_record(photon, call, algorithm, interp, base, 17)
     monkeypatch.setenv("PHOTON_DEVICES", "0,0,0")
     img3, rec3 = photon.render_moments(call)
     assert_records_equal(rec3, base, "PHOTON_DEVICES=0,0,0")
     assert rel_l2(img3, base_img) <= 1e-6
+
+
+def test_records_of_a_small_group_do_not_depend_on_the_launch_plan(photon, through_volume, monkeypatch):
+    """12 rays per source through the volume: moments_kernel<16>, four sources to a wave, behind every launch plan."""
+    call = scenes.bos_scene(n_dots=5, points_per_dot=9, rays_per_source=12, density_grad_filename=through_volume.density_grad_filename,
+                            seed=3)
+    call.ray_tracing_algorithm = 2
+    monkeypatch.setenv("PHOTON_INTERP", "cubic")
+    _, base = photon.render_moments(call)
+    assert base[:, 0].sum() > 0
+    assert_launch_plan_changes_no_record(photon, call, 2, 2, base, 17)
 
 
 def test_culls_of_the_volume_free_path_change_no_record(photon, monkeypatch):
