@@ -1172,6 +1172,34 @@ int photon_piv_correlate_phase(const float *d_im1, const float *d_im2, int width
                                int *d_flags, float *d_planes, int *n_rows, int *n_cols, void *stream);
 int photon_piv_phase_tables(int win, float window_sigma, float diameter, float *twiddles, float *window, float *filter);
 
+/* ------------------------------------------------------------------------------------
+ * Section 14: ensemble correlation (sum of correlation; Meinhart, Wereley & Santiago 2000): one displacement field from
+ * n_pairs image pairs of one steady or periodic flow, a static BOS object or a seeding too sparse for single pairs.  The
+ * correlation planes and the energies of the pairs are summed per window before the peak is read.  Host model:
+ * photon_amd/piv_ensemble.py (correlate_ensemble_model, f64).
+ *   pair k    (d_im1 + k pair_stride, d_im2 + k pair_stride), each device f32[height*width] as in section 5;
+ *             pair_stride in floats, >= width height.  Two stacks [N][H][W]: stride H W.  A time series f0 .. fN in one
+ *             buffer: d_im2 = d_im1 + H W, stride H W (pairs f_k, f_k+1).  Frame-straddled pairs: stride 2 H W.
+ *   Grid, windows, d_offset (one integer predictor per window, shared by all pairs), d_flags and the layouts of
+ *   d_vectors and d_planes are section 5's.
+ * Per window: a_k, b_k, their means, C_k(s) and the energies ea_k, eb_k are section 5's for pair k, each pair
+ * mean-subtracted by its own window means.  Pair k contributes unless its window is flat by section 5's rule (all pixels
+ * of a_k equal, the in-image pixels of b_k at zero shift all equal or none, or an f32 energy not above 0).  Over the
+ * contributing pairs, in pair order:
+ *   C(s) = sum_k C_k(s),  Ea = sum_k ea_k,  Eb = sum_k eb_k,  Cn = C / sqrt(Ea Eb)
+ * The integer peak with the row-major tie rule, the f64 three-point fit, peak = Cn(s*), the ratio and flag 1 are section
+ * 5's on C.  Flag 4 is geometry, the same for all pairs.  No pair contributes: flag 2, every output of the window, its
+ * plane included, NaN.
+ *   d_count   device int[n], or NULL: the number of contributing pairs per window
+ * Order (f32): every sum has a fixed order, two calls on the same inputs return the same bits.  Within a pair the row
+ * slices of the plane are summed in section 5's order; the running totals start from the first contributing pair's
+ * values, not from 0, so n_pairs = 1 returns section 5's vectors, flags and planes bit for bit.
+ * d_vectors == NULL: the size query, as in section 5.  Refused (1, one stderr line, nothing written, no launch): section
+ * 5's list, n_pairs < 1, pair_stride < width height.  Asynchronous on `stream`, no device scratch.  DESIGN.md section 4.3m. */
+int photon_piv_correlate_ensemble(const float *d_im1, const float *d_im2, long long pair_stride, int n_pairs, int width,
+                                  int height, int win, int step, int radius, const int *d_offset, float *d_vectors,
+                                  int *d_flags, int *d_count, float *d_planes, int *n_rows, int *n_cols, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,7 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_direct.hpp"
 #include "piv_grid.hpp"
 #include "piv_peak.hpp"
 
@@ -22,14 +23,7 @@ using namespace photon;
 
 namespace {
 
-constexpr int kTileX = 4;           // shifts per lane along x (one float4 of im2 per step)
-constexpr int kTileY = 4;           // shifts per lane along y
-constexpr int kMaxThreads = 512;
-constexpr int kRedWords = 64;       // block-reduction scratch, 8 waves at most: 5 floats a wave, or a float a wave and (from word 32) an int a wave
-
-static_assert(5 * (kMaxThreads / 64) <= kRedWords && 32 + kMaxThreads / 64 <= kRedWords, "the reduction scratch holds kRedWords words");
-
-typedef float v4f __attribute__((ext_vector_type(4)));
+using namespace piv_direct;
 
 // LDS layout (floats): a [WIN][WIN] | b [WIN + nSyp - 1][WIN + nSxp] | K partial planes [nSyp][nSxp] | reduction scratch.
 // nSxp, nSyp: 2R + 1 rounded up to the tile; the shifts past 2R read zero padding and are dropped.
@@ -108,48 +102,8 @@ __global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float 
         return;
     }
 
-    // ---- the correlation: item = (row slice k, shift tile ty, shift tile tx)
-    const int ntx = nSxp / kTileX, nty = nSyp / kTileY, units = ntx * nty;
-    for (int item = tid; item < units * K; item += B) {
-        const int k = item / units, unit = item % units;
-        const int sy0 = (unit / ntx) * kTileY, sx0 = (unit % ntx) * kTileX;
-        const int y0 = (k * WIN) / K, y1 = ((k + 1) * WIN) / K;
-        float acc[kTileY][kTileX];
-#pragma unroll
-        for (int u = 0; u < kTileY; u++)
-#pragma unroll
-            for (int t = 0; t < kTileX; t++) acc[u][t] = 0.f;
-        for (int y = y0; y < y1; y++) {
-            const float *arow = sa + y * WIN;
-            const float *brow = sb + (y + sy0) * pitch + sx0;
-            v4f prev[kTileY];
-#pragma unroll
-            for (int u = 0; u < kTileY; u++) prev[u] = *reinterpret_cast<const v4f *>(brow + u * pitch);
-#pragma unroll
-            for (int x = 0; x < WIN; x += 4) {
-                const v4f av = *reinterpret_cast<const v4f *>(arow + x);
-#pragma unroll
-                for (int u = 0; u < kTileY; u++) {
-                    const v4f nxt = *reinterpret_cast<const v4f *>(brow + u * pitch + x + 4);
-                    const float s[8] = {prev[u].x, prev[u].y, prev[u].z, prev[u].w, nxt.x, nxt.y, nxt.z, nxt.w};
-#pragma unroll
-                    for (int t = 0; t < kTileX; t++) {
-                        float c = acc[u][t];
-                        c = fmaf(av.x, s[t + 0], c);
-                        c = fmaf(av.y, s[t + 1], c);
-                        c = fmaf(av.z, s[t + 2], c);
-                        c = fmaf(av.w, s[t + 3], c);
-                        acc[u][t] = c;
-                    }
-                    prev[u] = nxt;
-                }
-            }
-        }
-        float *out = sp + k * P + sy0 * nSxp + sx0;
-#pragma unroll
-        for (int u = 0; u < kTileY; u++)
-            *reinterpret_cast<v4f *>(out + u * nSxp) = v4f{acc[u][0], acc[u][1], acc[u][2], acc[u][3]};
-    }
+    // ---- the correlation: every lane's tile into its slice's partial plane
+    correlate_tiles<WIN>(sa, sb, sp, K, P, pitch, nSxp, nSyp);
     __syncthreads();
 
     // ---- the plane (slices summed in order, into slice 0, as the tail's first pass meets each shift) and the peak read-out
@@ -163,35 +117,6 @@ __global__ __launch_bounds__(kMaxThreads) void piv_correlate_kernel(const float 
     };
     auto plane_at = [&](int sy, int sx) { return sp[sy * nSxp + sx]; };
     peak_tail(sum_slices, plane_at, nS, R, ox, oy, inv, outside, win_id, vectors, flags, planes, red, redi);
-}
-
-// How the shift tiles of one window are spread over a workgroup: K row slices and B threads (a multiple of 64), chosen
-// to waste the fewest lane-rows (the lanes past the last item of a round idle) within the LDS the device allows.
-struct Plan {
-    int K, threads, nSxp, nSyp;
-    size_t lds_bytes;
-};
-
-Plan plan_for(int win, int R, size_t lds_limit) {
-    Plan best{0, 0, 0, 0, 0};
-    const int nS = 2 * R + 1;
-    const int nSxp = (nS + kTileX - 1) / kTileX * kTileX, nSyp = (nS + kTileY - 1) / kTileY * kTileY;
-    const int units = (nSxp / kTileX) * (nSyp / kTileY);
-    const size_t fixed = (size_t)win * win + (size_t)(win + nSyp - 1) * (win + nSxp) + kRedWords;
-    long long best_cost = LLONG_MAX;
-    for (int K = 1; K <= 8 && K <= win / 4; K++) {
-        const size_t bytes = 4 * (fixed + (size_t)K * nSxp * nSyp);
-        if (bytes > lds_limit) break;
-        const int items = units * K;
-        const int threads = std::min(kMaxThreads, (items + 63) / 64 * 64);
-        const long long rounds = (items + threads - 1) / threads;
-        const long long cost = rounds * threads * ((win + K - 1) / K);
-        if (cost < best_cost) {
-            best_cost = cost;
-            best = Plan{K, threads, nSxp, nSyp, bytes};
-        }
-    }
-    return best;
 }
 
 template <int WIN>

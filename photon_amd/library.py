@@ -179,6 +179,8 @@ def _signatures():
         # section 13: FFT correlation (circular / phase)
         "photon_piv_correlate_phase": (ci, [vp, vp] + [ci] * 5 + [vp, ci, cf, cf] + [vp] * 3 + [P(ci), P(ci), vp]),
         "photon_piv_phase_tables": (ci, [ci, cf, cf, vp, vp, vp]),
+        # section 14: ensemble correlation
+        "photon_piv_correlate_ensemble": (ci, [vp, vp, ll] + [ci] * 6 + [vp] * 5 + [P(ci), P(ci), vp]),
     }
 
 
@@ -514,6 +516,74 @@ class PhotonLibrary:
             vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
             vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         return vectors, flags
+
+    # ---- ensemble correlation: one field from many image pairs (section 14) ---------------------------------------------
+    def piv_correlate_ensemble(self, d_im1_ptr: int, d_im2_ptr: int, pair_stride: int, n_pairs: int, width: int, height: int, win: int,
+                               step: int, radius: int, d_offset_ptr: int = 0, planes: bool = False, stream: int = 0):
+        """photon_piv_correlate_ensemble on raw device pointers: pair k is (d_im1_ptr, d_im2_ptr) + k pair_stride floats, each
+        f32 [height, width]; the planes and energies of the pairs are summed per window before the peak is read.  Returns
+        torch device tensors (vectors [n_rows, n_cols, 4], flags [n_rows, n_cols] int32, count [n_rows, n_cols] int32 -- the
+        contributing pairs per window --, planes [n_rows, n_cols, 2R+1, 2R+1] or None) as piv_correlate does, filled
+        asynchronously on `stream`.  The definition: include/parallel_ray_tracing.h, section 14 (photon_amd.piv_ensemble:
+        host model)."""
+        import torch
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        args = ("photon_piv_correlate_ensemble", _vp(d_im1_ptr), _vp(d_im2_ptr), int(pair_stride), int(n_pairs), int(width), int(height),
+                int(win), int(step), int(radius))
+        self._call(*args, None, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
+        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
+        dev, _ = _device_and_stream()
+        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
+        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
+        count = torch.empty((r, c), dtype=torch.int32, device=dev)
+        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
+        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(count.data_ptr()),
+                   _vp(pl.data_ptr()) if planes else None, None, None, _vp(stream))
+        return vectors, flags, count, pl
+
+    def correlate_ensemble(self, frames1, frames2=None, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1):
+        """One displacement field from a stack of image pairs (torch tensors on the device or numpy arrays): frames1 and
+        frames2 [N, height, width] hold pair k as (frames1[k], frames2[k]); frames2 None: frames1 is a time series of N + 1
+        frames, pair k = (frames1[k], frames1[k + 1]).  Returns numpy (vectors [n_rows, n_cols, 4] = dx, dy, peak, ratio;
+        flags [n_rows, n_cols]; count [n_rows, n_cols], the pairs that contributed to each window).  radius None = win // 2.
+        passes=2: the ensemble pass, the normalised median test and the predictor on the host as ``correlate`` runs them,
+        then a second ensemble pass with the integer window offsets."""
+        import torch
+        from . import piv_correlation as pc
+        if int(passes) not in (1, 2):
+            raise ValueError(f"passes must be 1 or 2, not {passes}")
+        radius = int(win) // 2 if radius is None else int(radius)
+        dev, stream = _device_and_stream()
+
+        def stack(x):
+            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float32))
+            t = t.to(device=dev, dtype=torch.float32).contiguous()
+            if t.ndim != 3:
+                raise ValueError("a stack of frames must be [N, height, width]")
+            return t
+        a = stack(frames1)
+        if frames2 is None:
+            if a.shape[0] < 2:
+                raise ValueError("a time series needs at least two frames")
+            n, b_ptr = a.shape[0] - 1, a[1].data_ptr()
+        else:
+            b = stack(frames2)
+            if b.shape != a.shape:
+                raise ValueError("frames1 and frames2 must be two stacks of one shape")
+            n, b_ptr = a.shape[0], b.data_ptr()
+        h, w = int(a.shape[1]), int(a.shape[2])
+        pc.check_arguments((h, w), win, step, radius)
+        if n < 1:
+            raise ValueError("an ensemble needs at least one pair")
+        call = lambda off: self.piv_correlate_ensemble(a.data_ptr(), b_ptr, h * w, n, w, h, win, step, radius, off, stream=stream)  # noqa: E731
+        vec, flg, cnt, _ = call(0)
+        vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
+        if int(passes) == 2:
+            offsets = pc.predictor(vectors, flags, pc.normalized_median_test(vectors))
+            d_off = torch.from_numpy(offsets).to(dev)
+            vec, flg, cnt, _ = call(d_off.data_ptr())
+            vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
+        return vectors, flags, cnt.cpu().numpy()
 
     # ---- iterative image-deformation correlation on the device (section 7) ---------------------------------------------
     def bspline_coefficients(self, d_im_ptr: int, width: int, height: int, d_coef_ptr: int, stream: int = 0):

@@ -3,7 +3,8 @@
 The device form is photon_piv_correlate (include/parallel_ray_tracing.h, section 5; ``PhotonLibrary.piv_correlate`` on raw
 device pointers, ``PhotonLibrary.correlate`` on arrays).  This module holds
 
-* ``correlate_model``: its f64 host model -- the definition of section 5, vectorised over windows, one loop over shifts;
+* ``correlate_model``: its f64 host model -- the definition of section 5, vectorised over windows, one loop over shifts
+  (``raw_planes``: the unnormalised planes and the energies it reads the peak from);
 * ``normalized_median_test`` and ``predictor``: the outlier test of Westerweel & Scarano (2005) on the 3 x 3 neighbourhood
   and the integer window offsets a second pass takes from the first;
 * ``sensor_displacements``: the measured ``(dx, dy)`` -- along the image's columns and rows -- in the ``(x, y)`` pixel axes
@@ -113,13 +114,10 @@ def peak_outputs(C, R: int, ox, oy, norm, flat, outside, grid, planes: bool = Fa
     return out
 
 
-def correlate_model(im1, im2, win: int, step: int, radius: int, offset=None, planes: bool = False):
-    """Host model of photon_piv_correlate in f64.  im1, im2: [height, width]; offset: integer (ox, oy) per window,
-    [n_rows, n_cols, 2] or [n][2], or None.  Returns (vectors [n_rows, n_cols, 4], flags [n_rows, n_cols] int32) and, with
-    planes=True, the normalised planes [n_rows, n_cols, 2R+1, 2R+1] (row-major: sy, then sx) as a third item.
-    A window is flat where an f64 energy is 0, which for finite pixels is where all pixels of a, or all in-image pixels of b
-    at zero shift, are equal; the device decides that from the pixels' extremes and also calls flat a window whose f32
-    energies are not above 0, a contrast below f32 that this model still correlates."""
+def raw_planes(im1, im2, win: int, step: int, radius: int, offset=None):
+    """What section 5 defines for one pair before the peak is read, in f64: (C [n, 2R+1, 2R+1] the unnormalised planes,
+    ea [n], eb [n] the energies, ox [n], oy [n] the integer offsets, outside [n] bool, (n_rows, n_cols)).  correlate_model
+    reads the peak off these; piv_ensemble.correlate_ensemble_model sums them over pairs first."""
     im1 = np.asarray(im1, np.float64)
     im2 = np.asarray(im2, np.float64)
     if im1.ndim != 2 or im1.shape != im2.shape:
@@ -157,11 +155,21 @@ def correlate_model(im1, im2, win: int, step: int, radius: int, offset=None, pla
     for sy in range(nS):
         for sx in range(nS):
             C[:, sy, sx] = np.einsum("nij,nij->n", a, b[:, sy:sy + win, sx:sx + win])
+    return C, ea, eb, ox, oy, ~inside.all(axis=(1, 2)), (n_rows, n_cols)
+
+
+def correlate_model(im1, im2, win: int, step: int, radius: int, offset=None, planes: bool = False):
+    """Host model of photon_piv_correlate in f64.  im1, im2: [height, width]; offset: integer (ox, oy) per window,
+    [n_rows, n_cols, 2] or [n][2], or None.  Returns (vectors [n_rows, n_cols, 4], flags [n_rows, n_cols] int32) and, with
+    planes=True, the normalised planes [n_rows, n_cols, 2R+1, 2R+1] (row-major: sy, then sx) as a third item.
+    A window is flat where an f64 energy is 0, which for finite pixels is where all pixels of a, or all in-image pixels of b
+    at zero shift, are equal; the device decides that from the pixels' extremes and also calls flat a window whose f32
+    energies are not above 0, a contrast below f32 that this model still correlates."""
+    C, ea, eb, ox, oy, outside, grid = raw_planes(im1, im2, win, step, radius, offset)
     flat = (ea == 0.0) | (eb == 0.0)
-    outside = ~inside.all(axis=(1, 2))
     with np.errstate(divide="ignore", invalid="ignore"):
         norm = 1.0 / np.sqrt(ea * eb)
-    return peak_outputs(C, R, ox, oy, norm, flat, outside, (n_rows, n_cols), planes)
+    return peak_outputs(C, int(radius), ox, oy, norm, flat, outside, grid, planes)
 
 
 def _neighbours(field):
