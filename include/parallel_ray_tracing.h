@@ -1200,6 +1200,55 @@ int photon_piv_correlate_ensemble(const float *d_im1, const float *d_im2, long l
                                   int height, int win, int step, int radius, const int *d_offset, float *d_vectors,
                                   int *d_flags, int *d_count, float *d_planes, int *n_rows, int *n_cols, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 15: image pre-processing of a stack or a time series on the device, the step in front of sections 5, 7, 13 and
+ * 14: the background of the frames (what does not move: walls, reflections, the sensor's offset), and per frame the chain
+ * subtract, clamp, min-max filter (Westerweel 1993; Adrian & Westerweel 2011, section 9: local contrast normalisation
+ * against uneven illumination).  Host models: photon_amd/piv_preprocess.py (background_model, preprocess_model_f32: this
+ * section operation by operation; preprocess_model: f64).
+ *   frame k   d_frames + k frame_stride, device f32[height*width] as in section 5; frame_stride in floats, >= width height
+ *             (section 14's addressing: a stack, every other frame of a straddled series through 2 H W, a series in one buffer)
+ *   width, height in [1, 2^22]
+ * Below, max(a, b) is "a if a > b, else b", one comparison and no arithmetic; every other operation is one IEEE f32 (where
+ * said, f64) operation, nothing fused.
+ *
+ * photon_piv_background: d_out f32[height*width].
+ *   mode 0    the minimum: m = frame_0(p); for k = 1 .. n-1: m = frame_k(p) if frame_k(p) < m, else m.  Exact; the order
+ *             decides only the sign of a zero.
+ *   mode 1    the mean: s = (double)frame_0(p); s = s + (double)frame_k(p) in ascending k; d_out(p) = (float)(s / (double)n)
+ *   photon_piv_background_path returns 1 when the call with these pointers and this stride reads 16 bytes per lane (both
+ *   pointers 16-byte aligned, frame_stride a multiple of 4; the last width height mod 4 pixels one by one), 0 when it reads
+ *   pixel by pixel.  Both forms return the same bits.  Host arithmetic, nothing launched.
+ *   Refused (1, one stderr line, nothing written, no launch): a null pointer, n_frames < 1, frame_stride < width height,
+ *   a mode other than 0 / 1, a side outside [1, 2^22], d_out overlapping the span of the frames
+ *   [d_frames, d_frames + (n-1) frame_stride + width height).
+ *
+ * photon_piv_preprocess: frame k of the result at d_out + k out_stride, for all n_frames in one launch.  Per frame:
+ *   d         d = max(im - bg, 0) with the one plane d_background f32[height*width] for all frames; d_background NULL:
+ *             d = im, no clamp
+ *   radius 0  out = d.  d_out == d_frames with out_stride == frame_stride is allowed: in place.
+ *   radius r in [1, 8], with N(p) the (2r+1)^2 pixels around p that lie in the image, rows_in x cols_in of them:
+ *             mn(p), mx(p) = the smallest and the largest d over N(p)
+ *             lo(p) = (sum of mn over N(p)) / (float)(rows_in cols_in),  hi(p) likewise from mx
+ *             the sum:  every row of N(p) from +0 in ascending column (s = s + mn), then those row sums from +0 in
+ *             ascending row
+ *             out(p) = max(d - lo, 0) / max(hi - lo, floor)
+ *             floor > 0 is an absolute intensity: where the local contrast hi - lo is below it, the pixel is divided by
+ *             floor instead -- a region without particles keeps its noise small instead of being stretched to full scale.
+ * Pixels that are not finite are outside the contract: the results within 2r of one are unspecified, nothing faults.
+ * Refused (1, one stderr line, nothing written, no launch): a null d_frames or d_out, n_frames < 1, a stride < width
+ * height, a side outside [1, 2^22], radius outside [0, 8], radius > 0 with a floor that is not finite or not > 0, radius 0
+ * with a NULL background (nothing to do), d_out overlapping the span of the frames (but for the in-place form above) or
+ * the background.
+ * Both calls are asynchronous on `stream`, use no device scratch and return the same bits for the same inputs.
+ * DESIGN.md section 4.3n. */
+int photon_piv_background(const float *d_frames, long long frame_stride, int n_frames, int width, int height, int mode,
+                          float *d_out, void *stream);
+int photon_piv_background_path(const float *d_frames, long long frame_stride, const float *d_out);
+int photon_piv_preprocess(const float *d_frames, long long frame_stride, int n_frames, int width, int height,
+                          const float *d_background, int radius, float floor, float *d_out, long long out_stride,
+                          void *stream);
+
 #ifdef __cplusplus
 }
 #endif

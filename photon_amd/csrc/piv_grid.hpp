@@ -83,5 +83,13 @@ int reserve_lds(Kernel kernel, size_t bytes, const char *entry, int win, const c
     return raise_lds(kernel, bytes);
 }
 
+// the sides of an image without a window grid (section 15): pixel coordinates, moved by any halo of the library, stay far
+// inside an int.  (Below the launch helpers, whose error lines carry their line numbers.)
+inline const char *side_error(int width, int height) {
+    if (width < 1 || height < 1) return "width and height must be >= 1";
+    if (width > (1 << 22) || height > (1 << 22)) return "the image is larger than 2^22 pixels a side";
+    return nullptr;
+}
+
 }  // namespace piv_grid
 }  // namespace photon

@@ -5,7 +5,7 @@ Three layers, top to bottom of the file:
     loaded library.  The header is the source of truth; tests/test_abi.py holds the table against its prototypes.
   * ``PhotonLibrary``: one method per entry point -- marshalling only, raw device pointers in, return code checked -- and
     on top of those the pipelines that chain several calls on torch-allocated device buffers on the current stream
-    (``correlate``, ``correlate_deform``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
+    (``preprocess_series``, ``correlate``, ``correlate_deform``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
     ``integrate_gradient``, the tomography solvers).
   * ``Volume``, ``Sources``, ``Flow``, ``Scene``: the library's handles.
 All arithmetic is the HIP library's.  There is no Python or CPU fallback -- if the library is missing or a call fails,
@@ -181,6 +181,10 @@ def _signatures():
         "photon_piv_phase_tables": (ci, [ci, cf, cf, vp, vp, vp]),
         # section 14: ensemble correlation
         "photon_piv_correlate_ensemble": (ci, [vp, vp, ll] + [ci] * 6 + [vp] * 5 + [P(ci), P(ci), vp]),
+        # section 15: image pre-processing
+        "photon_piv_background": (ci, [vp, ll, ci, ci, ci, ci, vp, vp]),
+        "photon_piv_background_path": (ci, [vp, ll, vp]),
+        "photon_piv_preprocess": (ci, [vp, ll, ci, ci, ci, vp, ci, cf, vp, ll, vp]),
     }
 
 
@@ -584,6 +588,69 @@ class PhotonLibrary:
             vec, flg, cnt, _ = call(d_off.data_ptr())
             vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         return vectors, flags, cnt.cpu().numpy()
+
+    # ---- image pre-processing: background removal, min-max filter (section 15) -----------------------------------------
+    def piv_background(self, d_frames_ptr: int, frame_stride: int, n_frames: int, width: int, height: int, mode: int = 0, stream: int = 0):
+        """photon_piv_background on a raw device pointer: frame k is d_frames_ptr + k frame_stride floats, f32 [height, width].
+        Returns the per-pixel minimum (mode 0) or mean (mode 1) of the frames as a torch device tensor [height, width], filled
+        asynchronously on `stream`.  The definition: include/parallel_ray_tracing.h, section 15 (photon_amd.piv_preprocess:
+        host models)."""
+        import torch
+        dev, _ = _device_and_stream()
+        out = torch.empty((max(int(height), 0), max(int(width), 0)), dtype=torch.float32, device=dev)
+        self._call("photon_piv_background", _vp(d_frames_ptr), int(frame_stride), int(n_frames), int(width), int(height), int(mode),
+                   _vp(out.data_ptr()), _vp(stream))
+        return out
+
+    def piv_background_path(self, d_frames_ptr: int, frame_stride: int, d_out_ptr: int) -> int:
+        """1 when photon_piv_background reads these buffers 16 bytes per lane, 0 when pixel by pixel (the same bits)."""
+        return int(self.lib.photon_piv_background_path(_vp(d_frames_ptr), int(frame_stride), _vp(d_out_ptr)))
+
+    def piv_preprocess(self, d_frames_ptr: int, frame_stride: int, n_frames: int, width: int, height: int, d_background_ptr: int = 0,
+                       radius: int = 0, floor: float = 0.0, stream: int = 0):
+        """photon_piv_preprocess on raw device pointers: per frame max(frame - background, 0) (d_background_ptr 0: the frame
+        as it is), then the min-max filter of `radius` (0: none) with the absolute contrast floor `floor`.  Returns a new
+        torch device stack [n_frames, height, width], filled asynchronously on `stream`."""
+        import torch
+        dev, _ = _device_and_stream()
+        out = torch.empty((max(int(n_frames), 0), max(int(height), 0), max(int(width), 0)), dtype=torch.float32, device=dev)
+        self._call("photon_piv_preprocess", _vp(d_frames_ptr), int(frame_stride), int(n_frames), int(width), int(height),
+                   _vp(d_background_ptr), int(radius), float(floor), _vp(out.data_ptr()), int(width) * int(height), _vp(stream))
+        return out
+
+    def preprocess_series(self, frames1, frames2=None, background="min", minmax_radius: int = 0, floor: Optional[float] = None):
+        """Background removal and min-max filter of a stack or a time series (torch tensors on the device or numpy arrays,
+        [N, height, width]) on the current stream, no host wait inside.  background: "min" or "mean" of the stack itself, an
+        array or tensor [height, width], or None (no subtraction).  With frames2 each stack gets its own background (the two
+        exposures of a camera differ); a series in one buffer has one background over all its frames.  minmax_radius 0: no
+        filter; above 0 `floor` is required -- an absolute intensity just above the noise that remains after the
+        subtraction, which cannot be guessed from one image.  Returns the processed device stack, or the two stacks, that
+        ``correlate_ensemble`` takes as they are (``correlate`` and ``correlate_deform``: one frame of each)."""
+        import torch
+        from . import piv_preprocess as pp
+        dev, stream = _device_and_stream()
+        modes = {"min": pp.MODE_MIN, "mean": pp.MODE_MEAN}
+        if isinstance(background, str) and background not in modes:
+            raise ValueError(f'background must be "min", "mean", None or a [height, width] plane, not "{background}"')
+
+        def one(frames):
+            t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
+            t = t.to(device=dev, dtype=torch.float32).contiguous()
+            if t.ndim != 3:
+                raise ValueError("a stack of frames must be [N, height, width]")
+            n, h, w = (int(v) for v in t.shape)
+            pp.check_arguments((h, w), n, radius=minmax_radius, floor=floor, background=background is not None)
+            if background is None:
+                bg = None
+            elif isinstance(background, str):
+                bg = self.piv_background(t.data_ptr(), h * w, n, w, h, modes[background], stream=stream)
+            else:
+                bg = _on_device(background, torch.float32, dev)
+                if tuple(bg.shape) != (h, w):
+                    raise ValueError("the background must be one [height, width] plane")
+            return self.piv_preprocess(t.data_ptr(), h * w, n, w, h, bg.data_ptr() if bg is not None else 0, minmax_radius,
+                                       0.0 if floor is None else float(floor), stream=stream)
+        return one(frames1) if frames2 is None else (one(frames1), one(frames2))
 
     # ---- iterative image-deformation correlation on the device (section 7) ---------------------------------------------
     def bspline_coefficients(self, d_im_ptr: int, width: int, height: int, d_coef_ptr: int, stream: int = 0):
