@@ -1249,6 +1249,36 @@ int photon_piv_preprocess(const float *d_frames, long long frame_stride, int n_f
                           const float *d_background, int radius, float floor, float *d_out, long long out_stride,
                           void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 16: a vector field carried from one window grid to another on the same image -- the step between the levels of
+ * multigrid window refinement (64 -> 32 -> 16: large windows find the shift, small ones resolve its gradients).  Host
+ * models: photon_amd/piv_multigrid.py (regrid_model: this section operation by operation; regrid_model_f64).
+ *   d_src     device f32[src_rows*src_cols][src_stride], dx and dy first (src_stride 2: a field of section 7c; 4: d_vectors
+ *             of section 5), on the grid (src_win, src_step) of a width x height image
+ *   d_dst     device f32[dst_rows*dst_cols][2] on the grid (dst_win, dst_step) of the same image; NULL: the size query --
+ *             *dst_rows, *dst_cols (either may be NULL) are written and nothing is launched
+ * d_dst(k) = section 7b's D -- bilinear in the window-centre coordinates of the source grid, constant beyond its outermost
+ * centres, a source vector that is not finite read as (0, 0) -- at the centre of destination window k.  Per axis, with n
+ * source nodes, from exact integers (twice the distance from the first source centre; the half-pixel centres cancel):
+ *   num = (dst_win - src_win) + 2 k dst_step,  den = 2 src_step,  inv_den = 1.f / (float)den
+ *   num <= 0 or n = 1:  node 0, w = 0;   num >= (n - 1) den:  node n - 1, w = 0;
+ *   else  i0 = floor(num / den), i1 = i0 + 1, w = (float)(num - i0 den) inv_den   (i0 from (float)num inv_den, corrected by
+ *         the exact remainder: num < 2^24)
+ * and, every operation one IEEE f32 operation, nothing fused, for dx and dy alike:
+ *   t = a + wx (b - a),  u = c + wx (e - c),  d_dst = t + wy (u - t)      a, b = nodes (i0, j0), (i0, j1); c, e = (i1, j0), (i1, j1)
+ * This is the code photon_piv_deform and photon_piv_field_to_pixels run per pixel (there num = 2 p - (win - 1)), entered
+ * with a window centre.  The same grid returns the field (a non-finite vector as zeros); a constant field stays constant
+ * bit for bit.
+ * Refused (1, one stderr line, nothing written, no launch): a (win, step) that section 5 refuses for the image, src_rows x
+ * src_cols that is not the source grid, src_stride other than 2 or 4, a side above 2^22, a null d_src, d_dst == d_src.
+ * Asynchronous on `stream`, no device scratch; two calls on the same inputs return the same bits.
+ *
+ * Driver (PhotonLibrary.correlate_multigrid; piv_multigrid.correlate_multigrid_model): level 0 is correlate_deform at
+ * schedule[0]; every further level regrids the last (smoothed) field onto its grid as the predictor and runs its
+ * iterations of section 7 there.  DESIGN.md section 4.3o. */
+int photon_piv_regrid(const float *d_src, int src_stride, int src_rows, int src_cols, int src_win, int src_step, int width,
+                      int height, int dst_win, int dst_step, float *d_dst, int *dst_rows, int *dst_cols, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

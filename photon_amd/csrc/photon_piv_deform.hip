@@ -10,6 +10,8 @@
 //                                 is 4 MB: it stays in L2), one coalesced store
 //   validate_kernel               one workgroup per 16 x 16 nodes: the totals of a 22 x 22 neighbourhood in LDS, the
 //                                 median test on 20 x 20, the replaced field on 18 x 18, its binomial filter on 16 x 16
+//   regrid_kernel                 one thread per node of another window grid: the warp's bilinear weights at the node's
+//                                 window centre (section 16: what multigrid refinement carries from level to level)
 // No kernel needs device scratch, none writes what another workgroup reads, and every sum has a fixed order: two calls
 // on the same inputs return the same bits.
 #include <climits>
@@ -236,6 +238,19 @@ __global__ __launch_bounds__(kValThreads) void validate_kernel(const float *__re
     }
 }
 
+// =============================================================================================
+// d. regrid (section 16)
+// =============================================================================================
+// one thread per node of the destination grid: GridField at the node's window centre, one 8-byte store
+__global__ __launch_bounds__(kWarpX *kWarpY) void regrid_kernel(GridField D, int dst_win, int dst_step, int dst_rows, int dst_cols,
+                                                                float2 *__restrict__ dst) {
+    const int j = blockIdx.x * kWarpX + threadIdx.x, i = blockIdx.y * kWarpY + threadIdx.y;
+    if (j >= dst_cols || i >= dst_rows) return;
+    float dx, dy;
+    D.at_centre(i, j, dst_win, dst_step, dx, dy);
+    dst[(size_t)i * dst_cols + j] = make_float2(dx, dy);
+}
+
 }  // namespace
 
 extern "C" int photon_piv_bspline_coefficients(const float *d_im, int width, int height, float *d_coef, void *stream_p) {
@@ -295,6 +310,32 @@ extern "C" int photon_piv_validate(const float *d_pred, const float *d_vectors, 
     const dim3 grid((unsigned)((n_cols + kValTile - 1) / kValTile), (unsigned)((n_rows + kValTile - 1) / kValTile));
     hipLaunchKernelGGL(validate_kernel, grid, dim3(kValThreads), 0, (hipStream_t)stream_p, d_pred, d_vectors, d_flags, n_rows, n_cols, eps,
                        threshold * threshold, d_field, d_smooth, d_status);
+    PH_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int photon_piv_regrid(const float *d_src, int src_stride, int src_rows, int src_cols, int src_win, int src_step, int width,
+                                 int height, int dst_win, int dst_step, float *d_dst, int *dst_rows, int *dst_cols, void *stream_p) {
+    const char *bad = piv_grid::grid_error(width, height, src_win, src_step, src_rows, src_cols);
+    if (!bad) bad = piv_grid::grid_error(width, height, dst_win, dst_step);
+    if (!bad) {
+        if (src_stride != 2 && src_stride != 4) bad = "src_stride must be 2 or 4";
+        else if (width > (1 << 22) || height > (1 << 22)) bad = "the image is larger than 2^22 pixels a side";
+        else if ((long long)src_rows * src_cols > INT_MAX) bad = "more than INT_MAX source windows";
+        else if (!d_src) bad = "null d_src";
+        else if (d_dst == d_src) bad = "d_dst must not be d_src";
+    }
+    if (bad) {
+        fprintf(stderr, "photon: photon_piv_regrid: %s (%d x %d image, source win %d, step %d, %d x %d grid, stride %d; destination win %d, step %d)\n",
+                bad, width, height, src_win, src_step, src_rows, src_cols, src_stride, dst_win, dst_step);
+        return 1;
+    }
+    int rows, cols;
+    PH_TRY(piv_grid::grid_size("photon_piv_regrid", width, height, dst_win, dst_step, rows, cols, dst_rows, dst_cols));
+    if (!d_dst) return 0;                       // the size query
+    const GridField D{d_src, src_stride, src_rows, src_cols, src_win, src_step, 1.f / (float)(2 * src_step)};
+    hipLaunchKernelGGL(regrid_kernel, warp_grid(cols, rows), dim3(kWarpX, kWarpY), 0, (hipStream_t)stream_p, D, dst_win, dst_step, rows, cols,
+                       reinterpret_cast<float2 *>(d_dst));
     PH_CHECK(hipGetLastError());
     return 0;
 }

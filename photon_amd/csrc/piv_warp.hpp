@@ -30,11 +30,10 @@ static __device__ __forceinline__ int mirror(int i, int n) {
 constexpr int kWarpX = 64, kWarpY = 4;
 constexpr float kMaxShift = 16777216.f;     // |scale D| is clamped to 2^24 pixels (section 7b)
 
-// node index and weight of the bilinear grid interpolation at pixel p: f = clamp((p - (win-1)/2) / step, 0, n - 1) from
-// the exact integers num = 2p - (win-1) and den = 2 step; i0 = floor(f) (at most n - 2 when n > 1), w = f - i0.  The
-// quotient comes from one f32 multiply by inv_den = 1 / den and is corrected by the exact remainder (num < 2^24).
-static __device__ __forceinline__ void grid_weight(int p, int win, int step, float inv_den, int n, int &i0, int &i1, float &w) {
-    const int num = 2 * p - (win - 1), den = 2 * step;
+// node index and weight of the bilinear grid interpolation at a point that lies num / den nodes behind node 0, from the
+// exact integers num and den = 2 step: f = clamp(num / den, 0, n - 1), i0 = floor(f) (at most n - 2 when n > 1), w = f - i0.
+// The quotient comes from one f32 multiply by inv_den = 1 / den and is corrected by the exact remainder (num < 2^24).
+static __device__ __forceinline__ void grid_weight_num(int num, int den, float inv_den, int n, int &i0, int &i1, float &w) {
     if (num <= 0 || n == 1) {
         i0 = i1 = 0;
         w = 0.f;
@@ -56,6 +55,18 @@ static __device__ __forceinline__ void grid_weight(int p, int win, int step, flo
     }
 }
 
+// at pixel p: (p - (win-1)/2) / step, num = 2p - (win-1)
+static __device__ __forceinline__ void grid_weight(int p, int win, int step, float inv_den, int n, int &i0, int &i1, float &w) {
+    grid_weight_num(2 * p - (win - 1), 2 * step, inv_den, n, i0, i1, w);
+}
+
+// at the centre of window k of another grid (to_win, to_step) on the same image: the half-pixel centres cancel,
+// num = (to_win - win) + 2 k to_step (section 16)
+static __device__ __forceinline__ void grid_weight_centre(int k, int to_win, int to_step, int win, int step, float inv_den, int n, int &i0,
+                                                          int &i1, float &w) {
+    grid_weight_num((to_win - win) + 2 * k * to_step, 2 * step, inv_den, n, i0, i1, w);
+}
+
 static __device__ __forceinline__ void node(const float *__restrict__ field, int stride, int k, float &dx, float &dy) {
     dx = field[(size_t)k * stride];
     dy = field[(size_t)k * stride + 1];
@@ -67,11 +78,8 @@ struct GridField {
     const float *field;
     int stride, n_rows, n_cols, win, step;
     float inv_den;                          // 1 / (2 step)
-    __device__ __forceinline__ void operator()(int r, int q, int, float &dx, float &dy) const {
-        int i0, i1, j0, j1;
-        float wy, wx;
-        grid_weight(r, win, step, inv_den, n_rows, i0, i1, wy);
-        grid_weight(q, win, step, inv_den, n_cols, j0, j1, wx);
+    // the two-stage interpolation between the nodes (i0, i1) x (j0, j1)
+    __device__ __forceinline__ void lerp(int i0, int i1, float wy, int j0, int j1, float wx, float &dx, float &dy) const {
         float ax, ay, bx, by, cx, cy, ex, ey;
         node(field, stride, i0 * n_cols + j0, ax, ay);
         node(field, stride, i0 * n_cols + j1, bx, by);
@@ -81,6 +89,21 @@ struct GridField {
         const float ux = cx + wx * (ex - cx), uy = cy + wx * (ey - cy);
         dx = tx + wy * (ux - tx);
         dy = ty + wy * (uy - ty);
+    }
+    __device__ __forceinline__ void operator()(int r, int q, int, float &dx, float &dy) const {
+        int i0, i1, j0, j1;
+        float wy, wx;
+        grid_weight(r, win, step, inv_den, n_rows, i0, i1, wy);
+        grid_weight(q, win, step, inv_den, n_cols, j0, j1, wx);
+        lerp(i0, i1, wy, j0, j1, wx, dx, dy);
+    }
+    // D at the centre of window (i, j) of the grid (to_win, to_step)
+    __device__ __forceinline__ void at_centre(int i, int j, int to_win, int to_step, float &dx, float &dy) const {
+        int i0, i1, j0, j1;
+        float wy, wx;
+        grid_weight_centre(i, to_win, to_step, win, step, inv_den, n_rows, i0, i1, wy);
+        grid_weight_centre(j, to_win, to_step, win, step, inv_den, n_cols, j0, j1, wx);
+        lerp(i0, i1, wy, j0, j1, wx, dx, dy);
     }
 };
 

@@ -185,6 +185,8 @@ def _signatures():
         "photon_piv_background": (ci, [vp, ll, ci, ci, ci, ci, vp, vp]),
         "photon_piv_background_path": (ci, [vp, ll, vp]),
         "photon_piv_preprocess": (ci, [vp, ll, ci, ci, ci, vp, ci, cf, vp, ll, vp]),
+        # section 16: a field from one window grid to another
+        "photon_piv_regrid": (ci, [vp] + [ci] * 9 + [vp, P(ci), P(ci), vp]),
     }
 
 
@@ -670,49 +672,98 @@ class PhotonLibrary:
         self._call("photon_piv_validate", _vp(d_pred_ptr), _vp(d_vectors_ptr), _vp(d_flags_ptr), int(n_rows), int(n_cols), float(eps),
                    float(threshold), _vp(d_field_ptr), _vp(d_smooth_ptr), _vp(d_status_ptr), _vp(stream))
 
-    def _correlate_validated(self, correlate, a, b, win, step, radius, eps, threshold, dev, stream, pairs=()):
+    def piv_regrid(self, d_src_ptr: int, src_stride: int, src_rows: int, src_cols: int, src_win: int, src_step: int, width: int,
+                   height: int, dst_win: int, dst_step: int, stream: int = 0):
+        """photon_piv_regrid on raw device pointers: the field f32 [src_rows, src_cols, src_stride] of the grid (src_win,
+        src_step) at the window centres of the grid (dst_win, dst_step) of the same width x height image.  Returns a torch
+        device tensor [dst_rows, dst_cols, 2], filled asynchronously on `stream`.  The definition:
+        include/parallel_ray_tracing.h, section 16 (photon_amd.piv_multigrid: host models)."""
+        import torch
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        args = ("photon_piv_regrid", _vp(d_src_ptr), int(src_stride), int(src_rows), int(src_cols), int(src_win), int(src_step), int(width),
+                int(height), int(dst_win), int(dst_step))
+        self._call(*args, None, ctypes.byref(rows), ctypes.byref(cols), None)
+        dev, _ = _device_and_stream()
+        dst = torch.empty((rows.value, cols.value, 2), dtype=torch.float32, device=dev)
+        self._call(*args, _vp(dst.data_ptr()), None, None, _vp(stream))
+        return dst
+
+    def _correlate_validated(self, correlate, a, b, win, step, radius, eps, threshold, dev, stream):
         """Pass 0 of correlate_deform, all of correlation_predictor: correlate the device images a, b (`correlate`: what
-        _correlator returned), then validate with no predictor.  Returns (vec, field, smoothed, status); field and smoothed
-        are [*pairs, n_rows, n_cols, 2] and the
-        validation fills their first [n_rows, n_cols, 2] (pairs=(2,): the ping-pong pairs of correlate_deform)."""
+        _correlator returned), then validate with no predictor.  Returns (vec, field, smoothed, status), field and smoothed
+        [n_rows, n_cols, 2]."""
         import torch
         h, w = a.shape
         vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
         r, c = flg.shape
-        field, smoothed = (torch.empty((*pairs, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))
+        field, smoothed = (torch.empty((r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))
         status = torch.empty((r, c), dtype=torch.int32, device=dev)
         self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smoothed.data_ptr(), status.data_ptr(), eps, threshold,
                           stream)
         return vec, field, smoothed, status
 
-    def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream,
-                                 method="direct", window_sigma=None, diameter=2.5):
-        """correlate_deform on the device images a, b, nothing copied back: (field [n_rows, n_cols, 2] of the last iteration,
-        vec [n_rows, n_cols, 4] of the last correlation, status [n_rows, n_cols]) as device tensors queued on `stream`."""
+    def _deform_iterations(self, correlate, coef, warped, pred, win, step, iterations, residual_radius, smooth, eps, threshold, dev, stream):
+        """`iterations` >= 1 deformation iterations on the grid (win, step) from the predictor `pred` [n_rows, n_cols, 2]: warp
+        both frames (coef [2, h, w]: their coefficients; warped [2, h, w]: scratch) half-way, correlate with
+        `residual_radius`, validate with the predictor; the next predictor is the smoothed field, or the field itself.
+        Returns (vec, field, smoothed, status) of the last iteration."""
         import torch
-        if int(iterations) < 0:
-            raise ValueError(f"iterations must be >= 0, not {iterations}")
-        correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter)
-        h, w = a.shape
-        check((h, w), win, step, radius)
-        if int(iterations) > 0:
-            check((h, w), win, step, residual_radius)
-        vec, field, smoothed, status = self._correlate_validated(correlate, a, b, win, step, radius, eps, threshold, dev, stream, pairs=(2,))
-        r, c = status.shape
-        cur = 0
-        if int(iterations) > 0:
-            coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=dev), torch.empty((2, h, w), dtype=torch.float32, device=dev)
-            self.bspline_coefficients(a.data_ptr(), w, h, coef[0].data_ptr(), stream)
-            self.bspline_coefficients(b.data_ptr(), w, h, coef[1].data_ptr(), stream)
-        for _ in range(int(iterations)):
-            pred = (smoothed if smooth else field)[cur]
+        h, w = coef.shape[1:]
+        r, c = pred.shape[:2]
+        field, smoothed = (torch.empty((2, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))   # ping-pong: a predictor is no output
+        status = torch.empty((r, c), dtype=torch.int32, device=dev)
+        for k in range(int(iterations)):
+            cur = k & 1
             self.piv_deform(coef[0].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, -0.5, warped[0].data_ptr(), stream)
             self.piv_deform(coef[1].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, 0.5, warped[1].data_ptr(), stream)
             vec, flg, _ = correlate(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, residual_radius, stream=stream)
-            cur ^= 1
             self.piv_validate(pred.data_ptr(), vec.data_ptr(), flg.data_ptr(), r, c, field[cur].data_ptr(), smoothed[cur].data_ptr(),
                               status.data_ptr(), eps, threshold, stream)
-        return field[cur], vec, status
+            pred = (smoothed if smooth else field)[cur]
+        return vec, field[cur], smoothed[cur], status
+
+    def _deform_chain(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method, window_sigma,
+                      diameter):
+        """What correlate_deform (one level) and correlate_multigrid queue, arguments already checked: pass 0 and
+        iterations[0] deformation iterations at schedule[0]; per further level the last predictor regridded and iterations[l]
+        deformation iterations there.  The coefficients of both frames are computed once, before the first warp.  Returns
+        (field, vec, status) of the last level as device tensors queued on `stream`."""
+        import torch
+        h, w = a.shape
+        coef = warped = None
+        for level, ((win, step), n) in enumerate(zip(schedule, iterations)):
+            correlate, first_radius, _ = self._correlator(method, win, radius if level == 0 else None, window_sigma, diameter)
+            if level == 0:
+                vec, field, smoothed, status = self._correlate_validated(correlate, a, b, win, step, first_radius, eps, threshold, dev, stream)
+            else:
+                r, c = field.shape[:2]
+                field = smoothed = self.piv_regrid((smoothed if smooth else field).data_ptr(), 2, r, c, *schedule[level - 1], w, h, win, step,
+                                                   stream)
+            if int(n) > 0:
+                if coef is None:
+                    coef, warped = (torch.empty((2, h, w), dtype=torch.float32, device=dev) for _ in range(2))
+                    self.bspline_coefficients(a.data_ptr(), w, h, coef[0].data_ptr(), stream)
+                    self.bspline_coefficients(b.data_ptr(), w, h, coef[1].data_ptr(), stream)
+                vec, field, smoothed, status = self._deform_iterations(correlate, coef, warped, smoothed if smooth else field, win, step, n,
+                                                                       residual_radius, smooth, eps, threshold, dev, stream)
+        return field, vec, status
+
+    def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream,
+                                 method="direct", window_sigma=None, diameter=2.5):
+        """correlate_deform on the device images a, b, nothing copied back: (field [n_rows, n_cols, 2] of the last iteration,
+        vec [n_rows, n_cols, 4] of the last correlation, status [n_rows, n_cols]) as device tensors queued on `stream`: the
+        one-level schedule."""
+        return self._correlate_multigrid_device(a, b, ((win, step),), (iterations,), radius, residual_radius, smooth, eps, threshold, dev,
+                                                stream, method, window_sigma, diameter)
+
+    def _correlate_multigrid_device(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream,
+                                    method="direct", window_sigma=None, diameter=2.5):
+        """correlate_multigrid on the device images a, b, nothing copied back: (field, vec, status) of the last level's grid as
+        device tensors queued on `stream`.  Every refusal is raised before anything is queued."""
+        from . import piv_multigrid as pm
+        schedule, iterations = pm.check_schedule(tuple(a.shape), schedule, iterations, radius, residual_radius, method, window_sigma, diameter)
+        return self._deform_chain(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method,
+                                  window_sigma, diameter)
 
     def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
                          residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
@@ -728,6 +779,26 @@ class PhotonLibrary:
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         field, vec, status = self._correlate_deform_device(a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev,
                                                            stream, method, window_sigma, diameter)
+        out = torch.cat([field, vec[..., 2:4]], dim=-1)
+        return out.cpu().numpy(), status.cpu().numpy()
+
+    def correlate_multigrid(self, im1, im2, schedule=((64, 32), (32, 16), (16, 8)), iterations=(1, 1, 2), radius: Optional[int] = None,
+                            residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
+                            window_sigma: Optional[float] = None, diameter: float = 2.5):
+        """Displacement field of an image pair by multigrid window refinement (section 16; model:
+        photon_amd.piv_multigrid.correlate_multigrid_model): large windows find the shift, small ones resolve its gradients,
+        in one call.  schedule: the (win, step) of every level, any valid pairs; iterations: the deformation iterations per
+        level (>= 0 on level 0, >= 1 after).  Level 0 is ``correlate_deform`` at schedule[0] with `radius`; every further
+        level takes the previous level's smoothed field (smooth=False: the field itself), regridded to its window centres,
+        as the predictor and iterates on its own grid with `residual_radius`.  A one-level schedule is ``correlate_deform``
+        bit for bit.  Returns what ``correlate_deform`` returns, on the last level's grid: hand it to
+        ``displacement_uncertainty`` or ``optical_flow(predictor=...)`` with the last (win, step).  method, window_sigma
+        (None = win / 4 of each level), diameter: the correlator of every pass.  Everything runs on the current stream; the
+        host waits once, for the result."""
+        import torch
+        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        field, vec, status = self._correlate_multigrid_device(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold,
+                                                              dev, stream, method, window_sigma, diameter)
         out = torch.cat([field, vec[..., 2:4]], dim=-1)
         return out.cpu().numpy(), status.cpu().numpy()
 

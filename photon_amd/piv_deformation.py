@@ -165,6 +165,26 @@ def validate_model(pred, vectors, flags, eps: float = 0.1, threshold: float = 2.
     return out.astype(np.float32), smooth.astype(np.float32), status, outliers, score
 
 
+def model_correlator(method: str, win: int, radius, window_sigma, diameter):
+    """What method= selects in the models of the drivers, as PhotonLibrary._correlator does on the device: (correlate(im1, im2,
+    win, step, radius) -> (vectors, flags), the radius, check(shape, win, step, radius)).  "direct": piv_correlation's model,
+    radius None = win // 2.  "phase": piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or
+    win // 2 = win // 2 - 1)."""
+    if method == "direct":
+        return pc.correlate_model, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
+    if method != "phase":
+        raise ValueError(f'method must be "direct" or "phase", not {method!r}')
+    from . import piv_phase as pp
+    how = dict(mode=pp.MODE_PHASE, window_sigma=int(win) / 4.0 if window_sigma is None else float(window_sigma), diameter=float(diameter))
+
+    def correlate(a, b, win, step, radius):
+        return pp.correlate_phase_model(a, b, win, step, radius, **how)
+
+    def check(shape, win, step, radius):
+        pp.check_arguments(shape, win, step, radius, **how)
+    return correlate, pp.default_radius(win, radius), check
+
+
 def correlate_deform_model(im1, im2, win: int = 32, step: int = 16, radius=None, iterations: int = 3, residual_radius: int = 4,
                            smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, history: bool = False, method: str = "direct",
                            window_sigma=None, diameter: float = 2.5):
@@ -175,21 +195,7 @@ def correlate_deform_model(im1, im2, win: int = 32, step: int = 16, radius=None,
     im1, im2 = np.asarray(im1, np.float64), np.asarray(im2, np.float64)
     if int(iterations) < 0:
         raise ValueError(f"iterations must be >= 0, not {iterations}")
-    if method == "direct":
-        correlate, check = pc.correlate_model, pc.check_arguments
-        radius = int(win) // 2 if radius is None else int(radius)
-    elif method == "phase":
-        from . import piv_phase as pp
-        how = dict(mode=pp.MODE_PHASE, window_sigma=int(win) / 4.0 if window_sigma is None else float(window_sigma), diameter=float(diameter))
-
-        def correlate(a, b, win, step, radius):
-            return pp.correlate_phase_model(a, b, win, step, radius, **how)
-
-        def check(shape, win, step, radius):
-            pp.check_arguments(shape, win, step, radius, **how)
-        radius = pp.default_radius(win, radius)
-    else:
-        raise ValueError(f'method must be "direct" or "phase", not {method!r}')
+    correlate, radius, check = model_correlator(method, win, radius, window_sigma, diameter)
     check(im1.shape, win, step, radius)
     if int(iterations) > 0:
         check(im1.shape, win, step, residual_radius)

@@ -19,10 +19,13 @@ beside correlate(passes=2).  --phase holds the FFT correlator (photon_piv_correl
 correlation, Gaussian window of win / 4, spectral filter for 2.5 px particles) next to photon_piv_correlate: the sample
 pair's error figures for one pass and for three deformation iterations with both methods, and at 1024^2 the device-event
 times of both kernels in the same run, alternating (win 32 / step 16 at R 4 and 15 | 16, win 64 / step 32 at R 4 and 31 | 32;
-the median of seven), and the wall time of correlate_deform with both methods.  Run it on a GPU box under a time limit of
-its own:
+the median of seven), and the wall time of correlate_deform with both methods.  --multigrid times multigrid window
+refinement (PhotonLibrary.correlate_multigrid, header section 16: 64 / 32 -> 32 / 16 -> 16 / 8, iterations 1, 1, 2) on the
+sample pair next to correlate_deform at the final grid's 16 / 8 with three iterations: device events around the queued
+chains (nothing copied back), alternating, the median of seven; per level the difference between the chains that stop
+there; and the time of one photon_piv_regrid per grid change.  Run it on a GPU box under a time limit of its own:
 
-    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate] [--deform] [--phase]
+    timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate] [--deform] [--phase] [--multigrid]
 """
 import argparse
 import json
@@ -224,6 +227,44 @@ def phase_pair(lib, images, records, cam, rays, lit, row):
             row[f"phase_1024_w{win}_{k}_ms"] = round(v, 4)
 
 
+def multigrid_pair(lib, images, row):
+    """--multigrid on the sample pair; adds its figures to `row`."""
+    from photon_amd import piv_multigrid as pm
+    schedule, iterations = pm.DEFAULT_SCHEDULE, pm.DEFAULT_ITERATIONS
+    a, b = (torch.from_numpy(np.ascontiguousarray(im, np.float32)).cuda() for im in images)
+    h, w = a.shape
+    dev, stream = a.device, torch.cuda.current_stream().cuda_stream
+    win, step = schedule[-1]
+    calls = {f"multigrid_to_level{n - 1}": lambda n=n: lib._correlate_multigrid_device(a, b, schedule[:n], iterations[:n], None, 4, True, 0.1,
+                                                                                          2.0, dev, stream)
+             for n in range(1, len(schedule) + 1)}
+    calls["correlate_deform_3"] = lambda: lib._correlate_deform_device(a, b, win, step, None, 3, 4, True, 0.1, 2.0, dev, stream)
+    for k, (src, dst) in enumerate(zip(schedule, schedule[1:])):
+        r, c = pc.grid_shape((h, w), *src)
+        fld = torch.zeros((r, c, 2), device="cuda")
+        calls[f"regrid_{k}_to_{k + 1}"] = lambda fld=fld, r=r, c=c, src=src, dst=dst: lib.piv_regrid(fld.data_ptr(), 2, r, c, *src, w, h, *dst)
+    times = {k: [] for k in calls}
+    for rep in range(10):                                   # three warm-up rounds, then seven; one event pair per call
+        for k, fn in calls.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            if rep >= 3:
+                times[k].append(e0.elapsed_time(e1))
+    ms = {k: float(np.median(v)) for k, v in times.items()}
+    last = 0.0
+    for n in range(len(schedule)):
+        ms[f"level{n}"] = ms[f"multigrid_to_level{n}"] - last
+        last = ms[f"multigrid_to_level{n}"]
+    ms["multigrid"] = last
+    print(f"{h} x {w} sample pair, schedule {schedule}, iterations {iterations}, final grid {pc.grid_shape((h, w), win, step)}: "
+          + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items() if not k.startswith("multigrid_to")))
+    for k, v in ms.items():
+        row[f"multigrid_{k}_ms"] = round(v, 4)
+
+
 def timed(fn, reps=3):
     out, best = None, 1e9
     for _ in range(reps):
@@ -245,6 +286,7 @@ def main():
     ap.add_argument("--correlate", action="store_true")
     ap.add_argument("--deform", action="store_true")
     ap.add_argument("--phase", action="store_true")
+    ap.add_argument("--multigrid", action="store_true")
     args = ap.parse_args()
     lib = PhotonLibrary()
     lib.set_device(0)
@@ -333,6 +375,8 @@ def main():
         deform_pair(lib, images, records, cam, rays, lit, row)
     if args.phase:
         phase_pair(lib, images, records, cam, rays, lit, row)
+    if args.multigrid:
+        multigrid_pair(lib, images, row)
     print(json.dumps(row), flush=True)
     if not math.isfinite(row["p99_err_px"]):
         sys.exit(1)
