@@ -1279,6 +1279,37 @@ int photon_piv_preprocess(const float *d_frames, long long frame_stride, int n_f
 int photon_piv_regrid(const float *d_src, int src_stride, int src_rows, int src_cols, int src_win, int src_step, int width,
                       int height, int dst_win, int dst_step, float *d_dst, int *dst_rows, int *dst_cols, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 17: section 5 with excluded pixels -- a model, a wall, a nozzle lip, the region outside the laser sheet or the
+ * dot pattern.  Host model: photon_amd/piv_mask.py (correlate_masked_model, f64).  Everything section 5 says about the
+ * grid, the offsets, the peak, the subpixel fit, the ratio, bits 1 / 2 / 4, the size query and asynchrony holds here.
+ *   d_mask1, d_mask2  device u8[height*width] in image coordinates, nonzero = the pixel is excluded; either may be NULL
+ *             (nothing excluded), and they may be one pointer
+ *   min_valid in [1, win^2]: the fewest valid pixels a window may keep
+ * A pixel of a is valid when mask1 is 0 there; a pixel of b when it lies in the image and mask2 is 0 at its own position
+ * (offset and shift applied).  n_a = the valid pixels of a, n_b = the valid pixels of b in the zero-shift window.
+ *   mean a over the valid pixels of a, mean b over the valid pixels of the zero-shift window; an invalid pixel of either
+ *   contributes 0 after the mean is subtracted (section 5's rule for pixels outside the image, extended); the energies run
+ *   over valid pixels; the flat rule (bit 2) reads the extremes of the valid pixels.  The value of an invalid pixel is
+ *   never used in arithmetic: NaN or inf under a mask changes no output bit.
+ *   d_valid   device int[n][2] = (n_a, n_b), or NULL
+ *   d_flags   section 5's bits, and
+ *             16 masked out: n_a < min_valid or n_b < min_valid.  Vector and plane NaN as for a flat window; bit 4 is still
+ *                reported, bit 2 is not set.
+ *             32 partially masked: not masked out, and a pixel with a nonzero mask lies in a's window (mask1) or in the
+ *                in-image part of b's search region (mask2).
+ * A window without bit 16 or 32 returns section 5's bits exactly (vectors, flags, planes): with NULL masks, with all-zero
+ * masks, with masks that are nonzero only where the window does not look.  A window with bit 32 normalises by the overlap:
+ *   N(s)  = the number of p with a(p) valid and b(p + s) valid (the correlation of the two 0/1 validity planes)
+ *   C'(s) = (float)((double)C(s) (double)n_a / (double)N(s)) where 2 N(s) >= n_a, else 0 (shifts that keep few pairs are
+ *           not amplified into peaks; N = 0 included)
+ * and peak, ratio, fit and d_planes are read from C', with section 5's 1 / sqrt(energy a energy b).
+ * Refused as in section 5, and: min_valid outside [1, win^2], d_valid without d_vectors.  Two calls on the same inputs
+ * return the same bits.  DESIGN.md section 4.3p. */
+int photon_piv_correlate_masked(const float *d_im1, const float *d_im2, const unsigned char *d_mask1, const unsigned char *d_mask2,
+                                int width, int height, int win, int step, int radius, int min_valid, const int *d_offset,
+                                float *d_vectors, int *d_flags, int *d_valid, float *d_planes, int *n_rows, int *n_cols, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

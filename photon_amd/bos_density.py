@@ -404,25 +404,27 @@ def _pair_uncertainty(lib, im1, im2, vectors, win, step, weights, reach):
 
 
 def reconstruct(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, passes: int = 2,
-                weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, reach: int = 2):
+                weights: str = "median", tol: float = 1e-8, K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, reach: int = 2, mask=None):
     """Projected density from a BOS image pair (im1 without, im2 through the volume; torch device tensors or numpy):
     ``PhotonLibrary.correlate`` (`passes`), with weights="uncertainty" ``PhotonLibrary.displacement_uncertainty`` of the
-    measured vectors on the same pair (`reach`), then integrate_vectors.  Returns (phi, mid-plane nodes (X, Y), stats)."""
-    vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
+    measured vectors on the same pair (`reach`), then integrate_vectors.  Returns (phi, mid-plane nodes (X, Y), stats).
+    mask: pixels outside the dot pattern or behind a model, as ``PhotonLibrary.correlate`` takes them; a masked-out window's
+    NaN vector gets weight 0, and a node without a live edge stays NaN."""
+    vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes, **({} if mask is None else {"mask": mask}))
     sigma = _pair_uncertainty(lib, im1, im2, vectors, win, step, weights, reach)
     return integrate_vectors(lib, vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step, weights, tol, K, rho_0,
                              sigma)
 
 
 def deflection_data(lib, im1, im2, call, origin_z: float, extent_z: float, win: int = 32, step: int = 16, passes: int = 2,
-                    weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, reach: int = 2):
+                    weights: str = "median", K: float = K_GLADSTONE_DALE, rho_0: float = RHO_0, reach: int = 2, mask=None):
     """The deflections of a BOS image pair, for tomography without the per-view integral (``reconstruct`` up to, but
     excluding, the integration): ``PhotonLibrary.correlate`` (`passes`), with weights="uncertainty"
     ``PhotonLibrary.displacement_uncertainty`` (`reach`), then measured_gradients.  Returns (g1, g2, w,
     target-plane nodes (X_t, Y_t)), g1 = gx and g2 = gy [n_rows, n_cols]: the data of
     ``PhotonLibrary.tomo_reconstruct_deflections`` with the rays of tomography.view_rays and the vectors of
-    tomography.view_frames at the same nodes."""
-    vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes)
+    tomography.view_frames at the same nodes.  mask: as ``reconstruct`` takes it (weight 0 on masked-out nodes)."""
+    vectors, flags = lib.correlate(im1, im2, win=win, step=step, passes=passes, **({} if mask is None else {"mask": mask}))
     gx, gy, w, target, _, _ = measured_gradients(vectors, flags, tuple(int(v) for v in im1.shape), call, origin_z, extent_z, win, step,
                                                  weights, K, rho_0, _pair_uncertainty(lib, im1, im2, vectors, win, step, weights, reach))
     return gx, gy, w, target

@@ -187,6 +187,8 @@ def _signatures():
         "photon_piv_preprocess": (ci, [vp, ll, ci, ci, ci, vp, ci, cf, vp, ll, vp]),
         # section 16: a field from one window grid to another
         "photon_piv_regrid": (ci, [vp] + [ci] * 9 + [vp, P(ci), P(ci), vp]),
+        # section 17: direct correlation with excluded pixels
+        "photon_piv_correlate_masked": (ci, [vp] * 4 + [ci] * 6 + [vp] * 5 + [P(ci), P(ci), vp]),
     }
 
 
@@ -263,6 +265,28 @@ def _image_pair(im1, im2):
     if a.dim() != 2 or a.shape != b.shape:
         raise ValueError("im1 and im2 must be two 2-d images of one shape")
     return (dev, stream, a, b, *a.shape)
+
+
+def _mask_pair(mask, shape, dev):
+    """The drivers' mask= (piv_mask.mask_pair: one plane, or a tuple or list of two) as two contiguous u8 device tensors
+    [h, w], 1 = excluded; one tensor twice for one plane."""
+    import torch
+    pair = tuple(mask) if isinstance(mask, (tuple, list)) and len(mask) == 2 else (mask,)
+    out = tuple((torch.as_tensor(m if torch.is_tensor(m) else np.asarray(m) != 0).to(device=dev) != 0).to(torch.uint8).contiguous()
+                for m in pair)
+    for m in out:
+        if tuple(m.shape) != tuple(int(v) for v in shape):
+            raise ValueError(f"a mask of shape {tuple(m.shape)} does not cover a {shape[0]} x {shape[1]} image")
+    return out[0], out[-1]
+
+
+def _replace_masked(im, m):
+    """piv_mask.replace_masked on the device, queued on the current stream: the frame with its masked pixels at the mean of
+    the unmasked ones."""
+    import torch
+    hidden = m != 0
+    free = torch.where(hidden, torch.zeros((), dtype=im.dtype, device=im.device), im)
+    return torch.where(hidden, free.sum() / (im.numel() - hidden.sum()).clamp(min=1), im).contiguous()
 
 
 def bind_march_launch_plan(lib):
@@ -482,12 +506,48 @@ class PhotonLibrary:
         self._call("photon_piv_phase_tables", int(win), float(window_sigma), float(diameter), _ptr(tw), _ptr(g), _ptr(w))
         return tw, g, w
 
-    def _correlator(self, method: str, win: int, radius, window_sigma, diameter):
+    def piv_correlate_masked(self, d_im1_ptr: int, d_im2_ptr: int, d_mask1_ptr: int, d_mask2_ptr: int, width: int, height: int, win: int,
+                             step: int, radius: int, min_valid: int = 1, d_offset_ptr: int = 0, planes: bool = False, valid: bool = True,
+                             stream: int = 0):
+        """photon_piv_correlate_masked on raw device pointers: piv_correlate's arguments and results with two u8 masks
+        [height, width] (nonzero = excluded; 0 = NULL, nothing excluded; they may be one pointer) and the fewest valid pixels
+        a window may keep.  Returns (vectors, flags, planes or None, valid int32 [n_rows, n_cols, 2] = (n_a, n_b) or None),
+        filled asynchronously on `stream`; flags carry bit 16 (masked out: every output NaN) and bit 32 (partially masked:
+        the overlap-normalised plane).  The definition: include/parallel_ray_tracing.h, section 17 (photon_amd.piv_mask:
+        host model)."""
+        import torch
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        args = ("photon_piv_correlate_masked", _vp(d_im1_ptr), _vp(d_im2_ptr), _vp(d_mask1_ptr), _vp(d_mask2_ptr), int(width), int(height),
+                int(win), int(step), int(radius), int(min_valid))
+        self._call(*args, None, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
+        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
+        dev, _ = _device_and_stream()
+        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
+        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
+        val = torch.empty((r, c, 2), dtype=torch.int32, device=dev) if valid else None
+        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
+        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(val.data_ptr()) if valid else None,
+                   _vp(pl.data_ptr()) if planes else None, None, None, _vp(stream))
+        return vectors, flags, pl, val
+
+    def _correlator(self, method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5):
         """What the drivers' method= selects: (a callable with piv_correlate's signature, the radius, the argument check).
         "direct": section 5, radius None = win // 2.  "phase": section 13's mode 1 with window_sigma (None = win / 4) and
-        diameter bound, radius None or win // 2 = win // 2 - 1."""
+        diameter bound, radius None or win // 2 = win // 2 - 1.  mask (what _mask_pair returned): section 17 with the two
+        masks and min_valid = ceil(min_valid_fraction win^2) bound, "direct" alone; None: what it returns without."""
         from . import piv_correlation as pc
         from . import piv_phase as pp
+        if mask is not None:
+            from . import piv_mask
+            piv_mask.check_method(method, mask)
+            if method == "direct":
+                m1, m2 = mask
+                min_valid = piv_mask.min_valid_for(win, min_valid_fraction)
+
+                def correlate_masked(d_im1_ptr, d_im2_ptr, width, height, win, step, radius, d_offset_ptr=0, planes=False, stream=0):
+                    return self.piv_correlate_masked(d_im1_ptr, d_im2_ptr, m1.data_ptr(), m2.data_ptr(), width, height, win, step, radius,
+                                                     min_valid, d_offset_ptr, planes, False, stream)[:3]
+                return correlate_masked, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
         if method == "direct":
             return self.piv_correlate, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
         if method != "phase":
@@ -502,18 +562,28 @@ class PhotonLibrary:
         return correlate, pp.default_radius(win, radius), check
 
     def correlate(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1,
-                  method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5):
+                  method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None,
+                  min_valid_fraction: float = 0.5, fill_masked: bool = False):
         """Displacement field of an image pair (torch tensors on the device or numpy arrays, [height, width]): returns numpy
         (vectors [n_rows, n_cols, 4] = dx, dy, peak, ratio; flags [n_rows, n_cols]).  radius None = win // 2.  passes=2:
         pass 1, the normalised median test and the predictor on the host (photon_amd.piv_correlation), then pass 2 with
         the integer window offsets.  method="phase": section 13's phase correlation instead of section 5's direct sums
-        (window_sigma None = win / 4; diameter: the e^-2 particle diameter; radius None or win // 2 = win // 2 - 1)."""
+        (window_sigma None = win / 4; diameter: the e^-2 particle diameter; radius None or win // 2 = win // 2 - 1).
+        mask: pixels to leave out (a bool / u8 array or device tensor [height, width], nonzero = excluded, or a tuple of two
+        for the two frames): section 17 instead of section 5, "direct" alone.  A window that keeps fewer than
+        min_valid_fraction of its pixels in either frame is masked out (flag 16, NaN vector); fill_masked=True gives those
+        nodes the median of their finite 3 x 3 neighbours instead (photon_amd.piv_mask.fill_masked).  A partially masked
+        window (flag 32) measures its free pixels: its vector sits at their centroid (piv_mask.window_valid)."""
         import torch
         from . import piv_correlation as pc
         if int(passes) not in (1, 2):
             raise ValueError(f"passes must be 1 or 2, not {passes}")
+        from . import piv_mask
+        piv_mask.check_method(method, mask)
         correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
+        if mask is not None:
+            correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter, _mask_pair(mask, (h, w), dev), min_valid_fraction)
         vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
         vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
         if int(passes) == 2:
@@ -521,6 +591,8 @@ class PhotonLibrary:
             d_off = torch.from_numpy(offsets).to(dev)
             vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
             vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
+        if mask is not None and fill_masked:
+            vectors = piv_mask.fill_masked(vectors, flags, True).astype(np.float32)
         return vectors, flags
 
     # ---- ensemble correlation: one field from many image pairs (section 14) ---------------------------------------------
@@ -723,16 +795,21 @@ class PhotonLibrary:
         return vec, field[cur], smoothed[cur], status
 
     def _deform_chain(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method, window_sigma,
-                      diameter):
+                      diameter, mask=None, min_valid_fraction=0.5):
         """What correlate_deform (one level) and correlate_multigrid queue, arguments already checked: pass 0 and
         iterations[0] deformation iterations at schedule[0]; per further level the last predictor regridded and iterations[l]
         deformation iterations there.  The coefficients of both frames are computed once, before the first warp.  Returns
-        (field, vec, status) of the last level as device tensors queued on `stream`."""
+        (field, vec, status) of the last level as device tensors queued on `stream`.  mask (what _mask_pair returned): every
+        correlation is section 17's under the mask in unwarped image coordinates, each level with min_valid from its own
+        win, and each frame's masked pixels are at that frame's unmasked mean before the coefficients (no host wait)."""
         import torch
         h, w = a.shape
         coef = warped = None
+        if mask is not None:
+            a, b = _replace_masked(a, mask[0]), _replace_masked(b, mask[1])
         for level, ((win, step), n) in enumerate(zip(schedule, iterations)):
-            correlate, first_radius, _ = self._correlator(method, win, radius if level == 0 else None, window_sigma, diameter)
+            correlate, first_radius, _ = self._correlator(method, win, radius if level == 0 else None, window_sigma, diameter, mask,
+                                                          min_valid_fraction)
             if level == 0:
                 vec, field, smoothed, status = self._correlate_validated(correlate, a, b, win, step, first_radius, eps, threshold, dev, stream)
             else:
@@ -749,42 +826,66 @@ class PhotonLibrary:
         return field, vec, status
 
     def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream,
-                                 method="direct", window_sigma=None, diameter=2.5):
+                                 method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5):
         """correlate_deform on the device images a, b, nothing copied back: (field [n_rows, n_cols, 2] of the last iteration,
         vec [n_rows, n_cols, 4] of the last correlation, status [n_rows, n_cols]) as device tensors queued on `stream`: the
         one-level schedule."""
         return self._correlate_multigrid_device(a, b, ((win, step),), (iterations,), radius, residual_radius, smooth, eps, threshold, dev,
-                                                stream, method, window_sigma, diameter)
+                                                stream, method, window_sigma, diameter, mask, min_valid_fraction)
 
     def _correlate_multigrid_device(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream,
-                                    method="direct", window_sigma=None, diameter=2.5):
+                                    method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5):
         """correlate_multigrid on the device images a, b, nothing copied back: (field, vec, status) of the last level's grid as
-        device tensors queued on `stream`.  Every refusal is raised before anything is queued."""
+        device tensors queued on `stream`.  Every refusal is raised before anything is queued.  mask: the drivers' mask=, or
+        None."""
+        from . import piv_mask
         from . import piv_multigrid as pm
         schedule, iterations = pm.check_schedule(tuple(a.shape), schedule, iterations, radius, residual_radius, method, window_sigma, diameter)
+        if mask is not None:
+            piv_mask.check_method(method, mask)
+            for win, _ in schedule:
+                piv_mask.min_valid_for(win, min_valid_fraction)
+            mask = _mask_pair(mask, tuple(a.shape), dev)
         return self._deform_chain(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method,
-                                  window_sigma, diameter)
+                                  window_sigma, diameter, mask, min_valid_fraction)
+
+    @staticmethod
+    def _masked_result(field, vec, status, masked: bool, fill_masked: bool):
+        """What the deformation drivers copy back, [n_rows, n_cols, 4] on the device: dx, dy of the field, peak and ratio of the
+        last correlation; under a mask with fill_masked=False, NaN where status has bit 16 (piv_mask.fill_masked)."""
+        import torch
+        out = torch.cat([field, vec[..., 2:4]], dim=-1)
+        if masked and not fill_masked:
+            out = torch.where(((status & 16) != 0)[..., None], torch.full((), float("nan"), dtype=out.dtype, device=out.device), out)
+        return out
 
     def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
                          residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
-                         window_sigma: Optional[float] = None, diameter: float = 2.5):
+                         window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None, min_valid_fraction: float = 0.5,
+                         fill_masked: bool = False):
         """Displacement field of an image pair by iterative image deformation (section 7; model:
         photon_amd.piv_deformation.correlate_deform_model).  Pass 0 correlates the images with `radius` (None = win // 2);
         every iteration warps both frames half-way by the validated, smoothed field, correlates the warped pair with
         `residual_radius` and adds the residual.  Returns what ``correlate`` returns: numpy (vectors [n_rows, n_cols, 4] =
         dx, dy of the last unsmoothed field, peak and ratio of the last correlation; status [n_rows, n_cols], section 5's
         flags with bit 8 on replaced vectors).  Everything runs on the current stream; the host waits once, for the result.
-        method, window_sigma, diameter: the correlator of every pass, as ``correlate`` takes them."""
-        import torch
+        method, window_sigma, diameter: the correlator of every pass, as ``correlate`` takes them.
+        mask, min_valid_fraction: as ``correlate`` takes them, for every pass.  The mask stays in unwarped image coordinates
+        on every iteration (it does not follow the warp), and each frame's masked pixels are set to that frame's unmasked
+        mean before the B-spline coefficients, so that a bright body does not ring into the warped free pixels.  Inside the
+        loop a masked-out node (status 16 | 8) holds its neighbours' median, a smooth predictor across the hole;
+        fill_masked=False returns NaN (dx, dy, peak, ratio) there, True the medians, for callers that pass the field on to
+        ``displacement_uncertainty`` or ``optical_flow(predictor=...)``."""
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         field, vec, status = self._correlate_deform_device(a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev,
-                                                           stream, method, window_sigma, diameter)
-        out = torch.cat([field, vec[..., 2:4]], dim=-1)
+                                                           stream, method, window_sigma, diameter, mask, min_valid_fraction)
+        out = self._masked_result(field, vec, status, mask is not None, fill_masked)
         return out.cpu().numpy(), status.cpu().numpy()
 
     def correlate_multigrid(self, im1, im2, schedule=((64, 32), (32, 16), (16, 8)), iterations=(1, 1, 2), radius: Optional[int] = None,
                             residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
-                            window_sigma: Optional[float] = None, diameter: float = 2.5):
+                            window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None, min_valid_fraction: float = 0.5,
+                            fill_masked: bool = False):
         """Displacement field of an image pair by multigrid window refinement (section 16; model:
         photon_amd.piv_multigrid.correlate_multigrid_model): large windows find the shift, small ones resolve its gradients,
         in one call.  schedule: the (win, step) of every level, any valid pairs; iterations: the deformation iterations per
@@ -794,12 +895,12 @@ class PhotonLibrary:
         bit for bit.  Returns what ``correlate_deform`` returns, on the last level's grid: hand it to
         ``displacement_uncertainty`` or ``optical_flow(predictor=...)`` with the last (win, step).  method, window_sigma
         (None = win / 4 of each level), diameter: the correlator of every pass.  Everything runs on the current stream; the
-        host waits once, for the result."""
-        import torch
+        host waits once, for the result.  mask, min_valid_fraction, fill_masked: as ``correlate_deform`` takes them; every
+        level takes its min_valid from its own win."""
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         field, vec, status = self._correlate_multigrid_device(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold,
-                                                              dev, stream, method, window_sigma, diameter)
-        out = torch.cat([field, vec[..., 2:4]], dim=-1)
+                                                              dev, stream, method, window_sigma, diameter, mask, min_valid_fraction)
+        out = self._masked_result(field, vec, status, mask is not None, fill_masked)
         return out.cpu().numpy(), status.cpu().numpy()
 
     # ---- displacement uncertainty from correlation statistics (section 11) -------------------------------------------------
@@ -961,16 +1062,28 @@ class PhotonLibrary:
                    int(height), int(win), int(step), int(min_count), int(anchor), _vp(d_vectors_ptr), _vp(d_flags_ptr), _vp(stream))
 
     def correlation_predictor(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, eps: float = 0.1,
-                              threshold: float = 2.0, method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5):
+                              threshold: float = 2.0, method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5,
+                              mask=None, min_valid_fraction: float = 0.5, fill_masked: bool = False):
         """A predictor for track_dots from one pass of window correlation: photon_piv_correlate, then photon_piv_validate
         (median test, replacement, 3 x 3 smoothing) -- pass 0 of correlate_deform.  Returns the smoothed field as a torch
         device tensor [n_rows, n_cols, 2], queued on the current stream: hand it to track_dots as predictor=(field, win, step)
         and a displacement larger than the spacing of the dots no longer pairs a dot with its neighbour.  method, window_sigma,
-        diameter: the correlator, as ``correlate`` takes them."""
+        diameter: the correlator, as ``correlate`` takes them.  mask, min_valid_fraction: as ``correlate`` takes them.  The
+        smoothed field carries the neighbours' median across masked-out nodes; as in the other drivers fill_masked=False
+        returns NaN there (set on the device, nothing waits), and a caller who hands the field on as a predictor wants
+        fill_masked=True: a node that is not finite reads as (0, 0) in every warp."""
+        from . import piv_mask
+        piv_mask.check_method(method, mask)
         correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         check((h, w), win, step, radius)
-        return self._correlate_validated(correlate, a, b, win, step, radius, eps, threshold, dev, stream)[2]
+        if mask is not None:
+            correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter, _mask_pair(mask, (h, w), dev), min_valid_fraction)
+        _, _, smoothed, status = self._correlate_validated(correlate, a, b, win, step, radius, eps, threshold, dev, stream)
+        if mask is not None and not fill_masked:
+            import torch
+            smoothed = torch.where(((status & 16) != 0)[..., None], torch.full((), float("nan"), dtype=smoothed.dtype, device=dev), smoothed)
+        return smoothed
 
     def track_dots(self, im1, im2, threshold: float, box_radius: int = 3, sigma_w: float = 1.0, iterations: int = 4,
                    background: float = 0.0, radius: float = 3.0, predictor=None, max_dots: Optional[int] = None, grid=None,

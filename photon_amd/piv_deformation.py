@@ -165,11 +165,22 @@ def validate_model(pred, vectors, flags, eps: float = 0.1, threshold: float = 2.
     return out.astype(np.float32), smooth.astype(np.float32), status, outliers, score
 
 
-def model_correlator(method: str, win: int, radius, window_sigma, diameter):
+def model_correlator(method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5):
     """What method= selects in the models of the drivers, as PhotonLibrary._correlator does on the device: (correlate(im1, im2,
     win, step, radius) -> (vectors, flags), the radius, check(shape, win, step, radius)).  "direct": piv_correlation's model,
     radius None = win // 2.  "phase": piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or
-    win // 2 = win // 2 - 1)."""
+    win // 2 = win // 2 - 1).  mask (a plane, or a pair of them for the two frames): piv_mask.correlate_masked_model with
+    min_valid = ceil(min_valid_fraction win^2), "direct" alone."""
+    if mask is not None:
+        from . import piv_mask
+        piv_mask.check_method(method, mask)
+        if method == "direct":
+            min_valid = piv_mask.min_valid_for(win, min_valid_fraction)
+
+            def correlate_masked(a, b, win, step, radius):
+                m1, m2 = piv_mask.mask_pair(mask, np.shape(a))
+                return piv_mask.correlate_masked_model(a, b, m1, m2, win, step, radius, min_valid)
+            return correlate_masked, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
     if method == "direct":
         return pc.correlate_model, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
     if method != "phase":
@@ -187,18 +198,26 @@ def model_correlator(method: str, win: int, radius, window_sigma, diameter):
 
 def correlate_deform_model(im1, im2, win: int = 32, step: int = 16, radius=None, iterations: int = 3, residual_radius: int = 4,
                            smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, history: bool = False, method: str = "direct",
-                           window_sigma=None, diameter: float = 2.5):
+                           window_sigma=None, diameter: float = 2.5, mask=None, min_valid_fraction: float = 0.5,
+                           fill_masked: bool = False):
     """Host model of PhotonLibrary.correlate_deform: returns (vectors [n_rows, n_cols, 4] = dx, dy of the last unsmoothed
     field, peak and ratio of the last correlation; status [n_rows, n_cols]); with history=True also the list of the
     unsmoothed fields after pass 0 and after every iteration.  method="phase": every pass correlates with
-    piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or win // 2 = win // 2 - 1)."""
+    piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or win // 2 = win // 2 - 1).
+    mask, min_valid_fraction, fill_masked: as the driver takes them -- every pass correlates with
+    piv_mask.correlate_masked_model under the mask in unwarped image coordinates, each frame's masked pixels are at that
+    frame's unmasked mean before the coefficients, and piv_mask.fill_masked decides what masked-out nodes return."""
     im1, im2 = np.asarray(im1, np.float64), np.asarray(im2, np.float64)
     if int(iterations) < 0:
         raise ValueError(f"iterations must be >= 0, not {iterations}")
-    correlate, radius, check = model_correlator(method, win, radius, window_sigma, diameter)
+    correlate, radius, check = model_correlator(method, win, radius, window_sigma, diameter, mask, min_valid_fraction)
     check(im1.shape, win, step, radius)
     if int(iterations) > 0:
         check(im1.shape, win, step, residual_radius)
+    if mask is not None:
+        from . import piv_mask
+        m1, m2 = piv_mask.mask_pair(mask, im1.shape)
+        im1, im2 = piv_mask.replace_masked(im1, m1), piv_mask.replace_masked(im2, m2)
     vec, flg = correlate(im1, im2, win, step, radius)
     field, smoothed, status, _, _ = validate_model(None, vec, flg, eps, threshold)
     fields = [field]
@@ -210,4 +229,6 @@ def correlate_deform_model(im1, im2, win: int = 32, step: int = 16, radius=None,
         field, smoothed, status, _, _ = validate_model(pred, vec, flg, eps, threshold)
         fields.append(field)
     vectors = np.concatenate([field.astype(np.float64), vec[..., 2:4]], axis=-1)
+    if mask is not None:
+        vectors = piv_mask.fill_masked(vectors, status, fill_masked)
     return (vectors, status, fields) if history else (vectors, status)

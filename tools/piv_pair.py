@@ -265,6 +265,43 @@ def multigrid_pair(lib, images, row):
         row[f"multigrid_{k}_ms"] = round(v, 4)
 
 
+def mask_pair(lib, row):
+    """--mask: photon_piv_correlate_masked next to photon_piv_correlate on phase_pair's 1024^2 pair, under an all-zero mask
+    (every window clear), a disc over about 10 % of the frame, and a sparse dot lattice that touches every window (every
+    window takes the normalised path); adds the medians to `row`."""
+    rng = np.random.default_rng(1)
+    n = 20_000
+    x, y = rng.uniform(-8, 1032, n), rng.uniform(-8, 1032, n)
+    big = [torch.from_numpy(pc.particle_image((1024, 1024), x + dx, y + dy).astype(np.float32)).cuda() for dx, dy in ((0, 0), (3.3, -2.6))]
+    h = w = 1024
+    yy, xx = np.mgrid[:h, :w]
+    masks = {"zeros": np.zeros((h, w), bool), "disc": np.hypot(xx - 600.0, yy - 450.0) <= 183.0, "lattice": (yy % 12 == 5) & (xx % 12 == 5)}
+    d_masks = {k: torch.from_numpy(m.astype(np.uint8)).cuda() for k, m in masks.items()}
+    p0, p1 = big[0].data_ptr(), big[1].data_ptr()
+    for win, step in ((32, 16), (64, 32), (16, 8)):
+        for R in (4, win // 2):
+            calls = {"plain": lambda: lib.piv_correlate(p0, p1, w, h, win, step, R)}
+            for k, m in d_masks.items():
+                calls[k] = lambda m=m: lib.piv_correlate_masked(p0, p1, m.data_ptr(), m.data_ptr(), w, h, win, step, R, win * win // 2)
+            times = {k: [] for k in calls}
+            for rep in range(10):                           # three warm-up rounds, then seven; one event pair per call
+                for k, fn in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    if rep >= 3:
+                        times[k].append(e0.elapsed_time(e1))
+            ms = {k: float(np.median(v)) for k, v in times.items()}
+            flg = {k: calls[k]()[1].cpu().numpy() for k in d_masks}
+            share = {k: (float(((f & 32) != 0).mean()), float(((f & 16) != 0).mean())) for k, f in flg.items()}
+            print(f"1024^2, win {win} step {step} R {R}: " + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items()) + "; partial / masked out: "
+                  + ", ".join(f"{k} {100 * a:.0f} % / {100 * b:.0f} %" for k, (a, b) in share.items()))
+            for k, v in ms.items():
+                row[f"mask_1024_w{win}_r{R}_{k}_ms"] = round(v, 4)
+
+
 def timed(fn, reps=3):
     out, best = None, 1e9
     for _ in range(reps):
@@ -287,6 +324,7 @@ def main():
     ap.add_argument("--deform", action="store_true")
     ap.add_argument("--phase", action="store_true")
     ap.add_argument("--multigrid", action="store_true")
+    ap.add_argument("--mask", action="store_true")
     args = ap.parse_args()
     lib = PhotonLibrary()
     lib.set_device(0)
@@ -377,6 +415,8 @@ def main():
         phase_pair(lib, images, records, cam, rays, lit, row)
     if args.multigrid:
         multigrid_pair(lib, images, row)
+    if args.mask:
+        mask_pair(lib, row)
     print(json.dumps(row), flush=True)
     if not math.isfinite(row["p99_err_px"]):
         sys.exit(1)
