@@ -65,7 +65,30 @@ def dense_case() -> DeflectionCase:
     return view_frames_of(tc.dense_case())
 
 
-CASES = {"random": random_case, "views": views_case, "large": large_case, "dense": dense_case}
+@functools.lru_cache(maxsize=None)
+def coarse_case(n: int) -> DeflectionCase:
+    return view_frames_of(tc.coarse_case(n))
+
+
+# "coarse2" .. "coarse4": runs of up to 64, 52 and 34 adjacent lanes in one voxel (test_tomography.py holds the lengths)
+CASES = {"random": random_case, "views": views_case, "large": large_case, "dense": dense_case,
+         "coarse2": functools.partial(coarse_case, 2), "coarse3": functools.partial(coarse_case, 3),
+         "coarse4": functools.partial(coarse_case, 4)}
+
+
+@functools.lru_cache(maxsize=None)
+def runs_case() -> DeflectionCase:
+    """The exact family of tomography_cases.runs_case for section 10: its rays with vectors whose entries are multiples of
+    1/4 in [-2, 2], and two whole-number ray vectors y1, y2 that are 0 together in the rays of tc.RUNS_DEAD.  Every weight is
+    a multiple of 2^-7, so D^T y is exact in f64 in any order of addition."""
+    base = tc.runs_case()
+    rng = np.random.default_rng(43)
+    t1, t2 = (rng.integers(-8, 9, (base.n_rays, 3)) / 4.0 for _ in range(2))
+    c = DeflectionCase(base, t1, t2)
+    c.y1, c.y2 = tc.whole_numbers(rng, base.n_rays), tc.whole_numbers(rng, base.n_rays)
+    c.y1[list(tc.RUNS_DEAD)] = c.y2[list(tc.RUNS_DEAD)] = 0.0
+    c.live = (c.y1 != 0.0) | (c.y2 != 0.0)
+    return c
 
 
 def random_problem(c: DeflectionCase):

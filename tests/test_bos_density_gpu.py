@@ -42,7 +42,7 @@ def test_device_matches_the_host_model(photon, case):
     want, ws = bd.integrate_model(**c, hx=hx, hy=hy, tol=0.0, max_iter=max_iter)
     got, gs = photon.integrate_gradient(**c, hx=hx, hy=hy, tol=0.0, max_iter=max_iter)
     assert np.array_equal(np.isnan(got), np.isnan(want))
-    for k in ("iterations", "unknowns", "unreachable"):
+    for k in ("iterations", "converged", "unknowns", "unreachable"):
         assert gs[k] == ws[k], (k, gs, ws)
     err = float(np.nanmax(np.abs(got - want))) / scale(want) if np.isfinite(want).any() else 0.0
     print(f"{name}: {gs['unknowns']} unknowns, {gs['unreachable']} unreachable, {gs['iterations']} iterations, "

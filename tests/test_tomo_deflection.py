@@ -65,6 +65,27 @@ def test_adjoint_identity_in_the_model():
                                   v0 + tm.deflect_adjoint_model(y1, y2, *c.grid, *c.rays, taps=c.taps))
 
 
+def test_runs_adjoint_is_exact_in_any_order_on_the_projectors_lane_layout():
+    """D^T y of the "runs" family in rational arithmetic over the model's taps (two weights each) is the model's f64 result,
+    and no order of addition could round; its runs of lanes are those of section 9's family, whose layout test_tomography.py
+    checks item by item."""
+    from fractions import Fraction
+    c = dc.runs_case()
+    for a, top in ((c.y1, 8), (c.y2, 8), (4 * c.t1, 8), (4 * c.t2, 8)):
+        assert (a == np.round(a)).all() and np.abs(a).max() <= top
+    exact, any_order = tc.exact_adjoint(c.taps, (c.y1, c.y2))
+    model = tm.deflect_adjoint_model(c.y1, c.y2, *c.grid, *c.rays, taps=c.taps).ravel()
+    assert all(Fraction(float(m)) == e for m, e in zip(model, exact))
+    assert any_order
+    assert (model != 0).sum() > 100
+    base = tc.runs_case()
+    assert (c.taps.ray == base.taps.ray).all() and (c.taps.voxel == base.taps.voxel).all() and (c.live == base.live).all()
+    assert all((a == b).all() for a, b in zip(tc.lane_runs(c, c.live), tc.lane_runs(base, base.live)))
+    hist = tc.lane_run_histogram(c, c.live)
+    assert len(hist) - 1 == 64 and all(hist[n] > 0 for n in range(2, 8)) and hist[48] == 0
+    assert hist[8:16].sum() > 0 and hist[16:32].sum() > 0 and hist[32:64].sum() > 0
+
+
 def test_hand_set_vectors():
     c = dc.random_case()
     f = tc.random_field(c.case, seed=17)

@@ -46,24 +46,29 @@ def ray_pointers(s):
     return [t.data_ptr() for t in s["rays"]]
 
 
-def deflect(photon, s, f):
+def deflect(photon, s, f, stream=None):
+    """stream: a torch.cuda.Stream to run on (None = the null stream)."""
     import torch
     c = s["case"]
     g1 = torch.full((c.n_rays,), 7.0, dtype=torch.float64, device="cuda")
     g2 = torch.full((c.n_rays,), 7.0, dtype=torch.float64, device="cuda")
     df = dev(f)
-    photon.tomo_deflect(df.data_ptr(), *c.grid, *ray_pointers(s), c.n_rays, g1.data_ptr(), g2.data_ptr())
-    torch.cuda.synchronize()
+    torch.cuda.synchronize()                                    # the inputs are there before another stream reads them
+    photon.tomo_deflect(df.data_ptr(), *c.grid, *ray_pointers(s), c.n_rays, g1.data_ptr(), g2.data_ptr(),
+                        stream=0 if stream is None else stream.cuda_stream)
+    (torch.cuda if stream is None else stream).synchronize()
     return g1.cpu().numpy(), g2.cpu().numpy()
 
 
-def deflect_adjoint(photon, s, y1, y2, v0=None):
+def deflect_adjoint(photon, s, y1, y2, v0=None, stream=None):
     import torch
     c = s["case"]
     v = torch.zeros(c.shape, dtype=torch.float64, device="cuda") if v0 is None else dev(v0)
     d1, d2 = dev(y1), dev(y2)                                   # both alive until the call has run
-    photon.tomo_deflect_adjoint(d1.data_ptr(), d2.data_ptr(), *c.grid, *ray_pointers(s), c.n_rays, v.data_ptr())
     torch.cuda.synchronize()
+    photon.tomo_deflect_adjoint(d1.data_ptr(), d2.data_ptr(), *c.grid, *ray_pointers(s), c.n_rays, v.data_ptr(),
+                                stream=0 if stream is None else stream.cuda_stream)
+    (torch.cuda if stream is None else stream).synchronize()
     return v.cpu().numpy()
 
 
@@ -139,6 +144,53 @@ def test_central_difference_of_the_device_projector_is_the_operator(photon, on_d
         assert err <= 1e-10
 
 
+# ---- "runs": the adjoint's lane merge in exact arithmetic ------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def runs():
+    """dc.runs_case on the device with the model's D^T y: every sum is exact (test_tomo_deflection.py proves it in rational
+    arithmetic), so the device owes the model's bits in whatever order its lanes merge and its atomics land."""
+    c = dc.runs_case()
+    return dict(case=c, rays=[dev(a) for a in c.rays], DTy=tm.deflect_adjoint_model(c.y1, c.y2, *c.grid, *c.rays, taps=c.taps))
+
+
+@pytest.fixture(scope="module")
+def side_stream():
+    import torch
+    return torch.cuda.Stream()
+
+
+def test_runs_deflect_adjoint_is_the_model_bit_for_bit(photon, runs):
+    c = runs["case"]
+    got = deflect_adjoint(photon, runs, c.y1, c.y2)
+    print(f"runs: {int((got != runs['DTy']).sum())} of {got.size} voxels differ, {int((runs['DTy'] != 0).sum())} are not 0")
+    assert np.array_equal(got, runs["DTy"])
+
+
+def test_runs_deflect_adjoint_adds_into_whole_numbers_bit_for_bit(photon, runs):
+    c = runs["case"]
+    v0 = tc.whole_numbers(np.random.default_rng(6), c.shape, top=100)
+    got = deflect_adjoint(photon, runs, c.y1, c.y2, v0)
+    assert np.array_equal(got, v0 + runs["DTy"])
+    assert not np.array_equal(got, runs["DTy"])
+
+
+def test_runs_deflect_is_the_model_bit_for_bit(photon, runs):
+    c = runs["case"]
+    f = np.random.default_rng(17).normal(size=c.shape)
+    got, want = deflect(photon, runs, f), tm.deflect_model(f, c.spacing, c.origin, *c.rays, taps=c.taps)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
+def test_runs_on_a_side_stream(photon, runs, side_stream):
+    """The `stream` argument of photon_tomo_deflect and photon_tomo_deflect_adjoint: the same bits from a stream of the
+    caller's."""
+    c = runs["case"]
+    assert np.array_equal(deflect_adjoint(photon, runs, c.y1, c.y2, stream=side_stream), runs["DTy"])
+    f = np.random.default_rng(17).normal(size=c.shape)
+    got, want = deflect(photon, runs, f, stream=side_stream), tm.deflect_model(f, c.spacing, c.origin, *c.rays, taps=c.taps)
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])
+
+
 # ---- the solver -------------------------------------------------------------------------------------------------------------
 def both(photon, c, g1, g2, **kw):
     want, ws = tm.reconstruct_deflections_model(g1, g2, *c.grid, *c.rays, taps=c.taps, **kw)
@@ -146,41 +198,143 @@ def both(photon, c, g1, g2, **kw):
     return got, gs, want, ws
 
 
+def assert_statistics(gs, ws, residual_rtol=None):
+    """The device's stats against the model's: the whole numbers equal, the residual within residual_rtol (None =
+    RESIDUAL_RTOL) of the model's."""
+    print(f"stats device {gs}, model {ws}")
+    for k in ("iterations", "converged", "unknowns", "rays_used"):
+        assert gs[k] == ws[k], (k, gs, ws)
+    assert abs(gs["residual"] - ws["residual"]) <= (RESIDUAL_RTOL if residual_rtol is None else residual_rtol) * ws["residual"], (gs, ws)
+
+
 # CG amplifies the adjoint's summation-order noise, and the deflection problem is worse conditioned than section 9's: with the
 # model's tap order permuted in the adjoint the "random" solutions spread by 7.6e-15 of max |f| after 8 iterations at lambda
 # 0.05 (3.9e-8 after 20), and by 2.8e-12 after 20 iterations at lambda 50 (1.5e-15 after 8).  (a) keeps 130 x the first
-# spread, (b) 350 x the second.
-@pytest.mark.parametrize("label,lam,iterations,rtol", [("a", 0.05, 8, 1e-12), ("b", 50.0, 20, 1e-9)])
+# spread, (b) 350 x the second.  The counts (c) to (g) are there for the statistics, as section 9's are: odd and even, at a
+# check, between checks and none; the model's residuals after 0, 1, 7, 8, 9 and 17 iterations at lambda 50 are 1, 0.4645,
+# 0.02681, 0.01899, 0.01341 and 7.07e-4, and under a permuted tap order they moved by at most 1.5e-15 of themselves (20
+# iterations; lambda 0.05, 8 iterations: 9.4e-16): RESIDUAL_RTOL keeps 650 x.  The solutions moved by at most 1.6e-15 of max
+# |f| up to 9 iterations and by 3.4e-13 after 17: (g) keeps 300 x.
+RESIDUAL_RTOL = 1e-12
+
+
+@pytest.mark.parametrize("label,lam,iterations,rtol", [("a", 0.05, 8, 1e-12), ("b", 50.0, 20, 1e-9), ("c", 50.0, 0, 1e-12),
+                                                       ("d", 50.0, 1, 1e-12), ("e", 50.0, 7, 1e-12), ("f", 50.0, 9, 1e-12),
+                                                       ("g", 50.0, 17, 1e-10)])
 def test_fixed_iteration_parity(photon, label, lam, iterations, rtol):
     c = dc.random_case()
     g1, g2, w, support = dc.random_problem(c)
     got, gs, want, ws = both(photon, c, g1, g2, w=w, support=support, lam=lam, tol=0.0, max_iter=iterations)
-    err = float(np.abs(got - want).max() / np.abs(want).max())
+    err = float(np.abs(got - want).max() / max(np.abs(want).max(), 1e-300))
     print(f"({label}) lambda {lam}, {iterations} iterations: max |device - model| / max |f| = {err:.2e}; residual device "
           f"{gs['residual']:.3e}, model {ws['residual']:.3e}")
-    for k in ("iterations", "unknowns", "rays_used"):
-        assert gs[k] == ws[k], (k, gs, ws)
-    assert gs["iterations"] == iterations and gs["unknowns"] == int(support.sum())
+    assert_statistics(gs, ws)
+    assert gs["iterations"] == iterations and gs["unknowns"] == int(support.sum()) and gs["converged"] == 0
     assert (got[support == 0] == 0).all()
     assert err <= rtol
+    if iterations == 0:
+        assert (got == 0).all() and gs["residual"] == 1.0
 
 
 def test_fixed_iteration_parity_with_dense_rays(photon):
     """The solver where the adjoint merges lanes.  With the model's tap order permuted the "dense" solution moved by 1.9e-15 of
-    max |f| after 8 iterations at lambda 50 (2.5e-15 at lambda 1): the operators' bound keeps 500 x."""
+    max |f| after 8 iterations at lambda 50 (2.5e-15 at lambda 1): the operators' bound keeps 500 x; its residual moved by
+    6.8e-16 of itself."""
     c = dc.dense_case()
-    rng = np.random.default_rng(9)
     g1, g2 = dc.blob_deflections(c)
-    w = rng.uniform(0.2, 2.0, g1.shape)
-    w[rng.random(g1.shape) < 0.1] = 0.0
     support = tc.sphere_support(c.case)
-    got, gs, want, ws = both(photon, c, g1, g2, w=w, support=support, lam=50.0, tol=0.0, max_iter=8)
+    got, gs, want, ws = both(photon, c, g1, g2, w=tc.ray_weights(c.n_rays), support=support, lam=50.0, tol=0.0, max_iter=8)
     err = float(np.abs(got - want).max() / np.abs(want).max())
     print(f"dense, lambda 50, 8 iterations: max |device - model| / max |f| = {err:.2e}")
-    for k in ("iterations", "unknowns", "rays_used"):
-        assert gs[k] == ws[k], (k, gs, ws)
+    assert_statistics(gs, ws)
     assert (got[support == 0] == 0).all()
     assert err <= OPERATOR_RTOL
+
+
+# The dense rays on 2^3, 3^3 and 4^3: every voxel and 2 iterations, as in section 9's test of the same name.  With the model's
+# tap order permuted (8 permutations) the solution after 2 iterations moved by at most 1.9e-14 of max |f| and the residual by
+# 8.3e-14 of itself: both bounds keep 120 x.
+COARSE_RTOL = 1e-11
+
+
+@pytest.mark.parametrize("name", ["coarse2", "coarse3", "coarse4"])
+def test_fixed_iteration_parity_with_whole_waves_in_one_voxel(photon, name):
+    c = dc.CASES[name]()
+    g1, g2 = dc.blob_deflections(c)
+    got, gs, want, ws = both(photon, c, g1, g2, w=tc.ray_weights(c.n_rays), lam=50.0, tol=0.0, max_iter=2)
+    err = float(np.abs(got - want).max() / np.abs(want).max())
+    print(f"{name}, lambda 50, 2 iterations: max |device - model| / max |f| = {err:.2e}")
+    assert_statistics(gs, ws, COARSE_RTOL)
+    assert gs["iterations"] == 2 and gs["unknowns"] == c.taps.n_voxels
+    assert err <= COARSE_RTOL
+
+
+# ---- the capped grid: more voxels than kMaxBlocks * kThreads = 262 144 (section 9's test of the same name) -----------------------
+# With the model's tap order permuted the solutions moved by at most 7.5e-16 of max |f| and the residuals by 1.7e-16; on every
+# voxel, where the second trip of the element-wise kernels counts (the solution there reaches 0.41 of max |f|), by 1.1e-15 and
+# 6.2e-16.
+@pytest.mark.parametrize("n,iterations,sphere", [(65, 3, True), (64, 2, True), (65, 3, False)], ids=["65-sphere", "64-sphere", "65-every-voxel"])
+def test_fixed_iteration_parity_on_a_capped_grid(photon, n, iterations, sphere):
+    c = dc.view_frames_of(tc.view_case(n, 24, 4), k_views=4)
+    g1, g2 = dc.blob_deflections(c)
+    support = tc.sphere_support(c.case) if sphere else np.ones(c.shape, np.uint8)
+    got, gs, want, ws = both(photon, c, g1, g2, w=tc.ray_weights(c.n_rays), support=support, lam=50.0, tol=0.0, max_iter=iterations)
+    err = float(np.abs(got - want).max() / np.abs(want).max())
+    print(f"{n}^3, {'sphere' if sphere else 'every voxel'}, lambda 50, {iterations} iterations: max |device - model| / max |f| = {err:.2e}")
+    assert_statistics(gs, ws)
+    assert gs["iterations"] == iterations and gs["unknowns"] == int(support.sum()) and gs["converged"] == 0
+    assert (got[support == 0] == 0).all()
+    assert err <= OPERATOR_RTOL
+
+
+# ---- where the solver stops, and what it reports then ------------------------------------------------------------------------
+@pytest.mark.parametrize("stop,before", [(8, 7), (16, 8)])
+def test_tolerance_stops_at_a_check_before_the_limit(photon, stop, before):
+    """tol between the model's residuals after `before` and after `stop` iterations (their geometric mean), max_iter = stop +
+    1: the check after `stop` iterations ends the run, one iteration before the limit would (section 9's test of the same
+    name).  After 16 iterations the solution moves by 1.5e-13 of max |f| under a permuted tap order: the bound of (g)."""
+    c = dc.random_case()
+    g1, g2, w, support = dc.random_problem(c)
+    kw = dict(w=w, support=support, lam=50.0)
+    r = [tm.reconstruct_deflections_model(g1, g2, *c.grid, *c.rays, taps=c.taps, tol=0.0, max_iter=k, **kw)[1]["residual"]
+         for k in (before, stop)]
+    tol = float(np.sqrt(r[0] * r[1]))
+    assert r[1] < tol < r[0]
+    got, gs, want, ws = both(photon, c, g1, g2, tol=tol, max_iter=stop + 1, **kw)
+    assert_statistics(gs, ws)
+    assert gs["iterations"] == stop and gs["converged"] == 1
+    assert np.abs(got - want).max() <= (OPERATOR_RTOL if stop == 8 else 1e-10) * np.abs(want).max()
+
+
+def test_an_empty_support_needs_no_iteration(photon):
+    c = dc.random_case()
+    g1, g2, w, _ = dc.random_problem(c)
+    got, gs, want, ws = both(photon, c, g1, g2, w=w, support=np.zeros(c.shape, np.uint8), lam=50.0, tol=0.0, max_iter=9)
+    assert_statistics(gs, ws)
+    assert gs["iterations"] == 0 and gs["unknowns"] == 0 and gs["converged"] == 1 and gs["residual"] == 0.0
+    assert (got == 0).all() and (want == 0).all()
+
+
+def test_pointer_form_on_a_side_stream(photon, side_stream):
+    """tomo_reconstruct_deflections_ptr on device tensors and a stream of the caller's against the array form and the model."""
+    import torch
+    c = dc.random_case()
+    g1, g2, w, support = dc.random_problem(c)
+    kw = dict(lam=50.0, tol=0.0, max_iter=9)
+    _, array_stats, want, ws = both(photon, c, g1, g2, w=w, support=support, **kw)
+    d1, d2, dw, ds = dev(g1), dev(g2), dev(w), dev(support)
+    rays = [dev(a) for a in c.rays]
+    f = torch.full(c.shape, 7.0, dtype=torch.float64, device="cuda")
+    torch.cuda.synchronize()
+    gs = photon.tomo_reconstruct_deflections_ptr(d1.data_ptr(), d2.data_ptr(), *c.grid, *(t.data_ptr() for t in rays), c.n_rays,
+                                                 f.data_ptr(), d_w_ptr=dw.data_ptr(), d_support_ptr=ds.data_ptr(),
+                                                 stream=side_stream.cuda_stream, **kw)
+    got = f.cpu().numpy()                                       # the call has synchronised its stream
+    for k in ("iterations", "converged", "unknowns", "rays_used"):
+        assert gs[k] == array_stats[k], (k, gs, array_stats)
+    assert_statistics(gs, ws)
+    assert (got[support == 0] == 0).all()
+    assert np.abs(got - want).max() <= OPERATOR_RTOL * np.abs(want).max()
 
 
 def test_converged_parity(photon):

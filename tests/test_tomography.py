@@ -63,12 +63,73 @@ def test_a_constant_field_integrates_to_the_chord_length():
 def test_dense_case_has_long_runs_of_lanes_in_one_voxel():
     """The device's adjoint sums runs of adjacent lanes that add to one voxel by a shift-and-add with steps 1, 2, 4, ...: a
     step of distance d changes a value only in a run longer than d.  The other cases never get past two lanes; the "dense"
-    case must keep runs of at least 5 (steps 1, 2 and 4), or the GPU tests stop covering them."""
+    case must keep runs of at least 5 (steps 1, 2 and 4), and the same rays on 2^3, 3^3 and 4^3 a whole wave, 40 and 24 lanes
+    (every step up to 32), or the GPU tests stop covering them."""
     runs = {name: tc.longest_lane_run(case()) for name, case in (("random", tc.random_case), ("views", tc.views_case),
                                                                   ("dense", tc.dense_case))}
+    runs.update({f"coarse{n}": tc.longest_lane_run(tc.coarse_case(n)) for n in (2, 3, 4)})
     print(f"longest run of adjacent lanes in one voxel: {runs}")
     assert runs["dense"] >= 5
     assert runs["random"] <= 2 and runs["views"] <= 2
+    assert runs["coarse2"] == 64 and runs["coarse3"] >= 40 and runs["coarse4"] >= 24
+
+
+# ---- "runs": the exact family of the adjoint's lane merge ------------------------------------------------------------------------
+def test_runs_adjoint_is_exact_in_any_order():
+    """A^T y of the "runs" family in rational arithmetic over the model's taps is the model's f64 result, and no order of
+    addition could round: the GPU test asks the device for these bits."""
+    from fractions import Fraction
+    c = tc.runs_case()
+    assert (c.y == np.round(c.y)).all() and np.abs(c.y).max() <= 8
+    exact, any_order = tc.exact_adjoint(c.taps, (c.y,))
+    model = tm.backproject_model(c.y, *c.grid, c.origins, c.dirs, taps=c.taps).ravel()
+    assert all(Fraction(float(m)) == e for m, e in zip(model, exact))
+    assert any_order
+    assert (model != 0).sum() > 100
+
+
+def test_runs_lane_layout():
+    """Every lane layout the device's merge has to get right is in the family: the run-length histogram and the runs wave by
+    wave (ray r is lane r % 64 of wave r // 64; a ray with y = 0 is a dead lane)."""
+    c = tc.runs_case()
+    wave, first, length = tc.lane_runs(c, c.live)
+    hist = tc.lane_run_histogram(c, c.live)
+    print(f"run lengths present: {np.flatnonzero(hist).tolist()}")
+
+    def runs_of(k):
+        return set(zip(first[wave == k].tolist(), length[wave == k].tolist()))
+
+    def voxel_of(ray):                                          # the ray's first tap
+        return int(c.taps.voxel[np.flatnonzero(c.taps.ray == ray)[0]])
+
+    assert len(hist) - 1 == 64 and runs_of(0) == {(0, 64)}                                  # a whole wave in one cell
+    assert all(hist[n] > 0 for n in range(2, 8))
+    assert hist[8:16].sum() > 0 and hist[16:32].sum() > 0 and hist[32:64].sum() > 0
+    assert runs_of(1) == {(0, 1), (1, 2), (3, 3), (6, 4), (10, 5), (15, 6), (21, 7), (28, 8), (36, 12), (48, 16)}
+    # the lanes of a run cross their cell at different points: 16 of them in wave 0, and as many different first weights
+    in_cell = (c.origins[:64, :2] - c.origin[:2]) / c.spacing[:2] - (3, 2)
+    assert len({tuple(p) for p in in_cell}) == 16 and (in_cell >= 0).all() and (in_cell < 1).all() and (in_cell == 0).any()
+    first_tap = np.array([c.taps.weights[0][np.flatnonzero(c.taps.ray == r)[0]] for r in range(64)])
+    assert len(set(first_tap.tolist())) >= 8 and len(set((first_tap * c.y[:64]).tolist())) >= 16
+    # A B A B: the same voxel in every second lane, never in the next one
+    assert runs_of(2) == {(lane, 1) for lane in range(64)}
+    assert voxel_of(128) == voxel_of(130) != voxel_of(129) == voxel_of(131)
+    # runs cut by lanes beside the grid (5, 17, 18) and by lanes with y = 0 (9, 30)
+    assert runs_of(3) == {(0, 5), (6, 3), (10, 7), (19, 11), (31, 9), (40, 24)}
+    assert (c.taps.planes[[197, 209, 210]] == 0).all() and (c.y[list(tc.RUNS_DEAD)] == 0).all()
+    assert (c.taps.planes[list(tc.RUNS_DEAD)] == 4).all() and int((~c.live).sum()) == 2
+    # 48 lanes of one cell across a wave boundary: 24 + 24
+    assert len({voxel_of(r) for r in range(3 * 64 + 40, 4 * 64 + 24)}) == 1
+    assert (40, 24) in runs_of(3) and runs_of(4) == {(0, 24), (24, 33), (57, 7)} and hist[48] == 0
+    # rays along x: all 8 planes; a wave of both kinds walks 8 planes, its z lanes 4
+    e = np.abs(c.dirs)
+    assert (e[5 * 64:6 * 64].argmax(axis=1) == 0).all() and (c.taps.planes[5 * 64:6 * 64] == 8).all()
+    assert runs_of(5) == {(0, 40), (40, 14), (54, 10)}
+    mixed = e[6 * 64:7 * 64].argmax(axis=1)
+    assert set(mixed.tolist()) == {0, 2} and (c.taps.planes[6 * 64:7 * 64] == np.where(mixed == 0, 8, 4)).all()
+    assert runs_of(6) == {(0, 20), (20, 26), (46, 18)}
+    # a last wave of 17 lanes in the second block of 256
+    assert c.n_rays == tc.RUNS_N == 465 and c.n_rays % 64 == 17 and c.n_rays % 256 != 0 and runs_of(7) == {(0, 17)}
 
 
 @pytest.mark.parametrize("name", ["random", "views"])

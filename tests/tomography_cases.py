@@ -126,9 +126,104 @@ def dense_case() -> Case:
     return view_case(16, 64)
 
 
-def longest_lane_run(case: Case, wave: int = 64) -> int:
-    """The longest run of adjacent lanes that add to one voxel in one step of the device's adjoint: ray r is lane r % wave of
-    wave r // wave, and a step is one tap (0 .. 3) of one plane kappa.  A lane whose plane does not count breaks a run."""
+@functools.lru_cache(maxsize=None)
+def coarse_case(n: int) -> Case:
+    """The dense rays on a grid of n^3, n = 2, 3, 4: up to a whole wave of adjacent lanes in one voxel, with the weights of
+    ordinary rotated views."""
+    return view_case(n, 64)
+
+
+# ---- "runs": exact arithmetic, every lane layout of the adjoint's merge --------------------------------------------------------
+# Rays parallel to a grid axis on a grid whose spacings and origin are powers of two or small integers, through points at
+# quarter fractions of a cell: every weight is a multiple of 2^-5 (section 10: 2^-7) below 8, y holds whole numbers, and so
+# every product and every partial sum of A^T y is exact in f64 -- the result has the same bits in any order of addition.
+RUNS_GRID = ((8, 8, 4), (2.0, 4.0, 0.5), (-8.0, 16.0, 1.0))
+RUNS_Z, RUNS_X, RUNS_X_BACK = (0.0, 0.0, 3.0), (5.0, 0.0, 0.0), (-5.0, 0.0, 0.0)      # directions of exact length
+RUNS_OUTSIDE = -3                                           # a cell index beside the grid: the ray misses
+# (direction, cell, lanes) in ray order; cell = the indices of the ray's cell along the two in-plane axes (x, y for a ray
+# along z; y, z for one along x).  Ray r is lane r % 64 of wave r // 64.
+RUNS_LAYOUT = (
+    # wave 0: one cell, a run of 64
+    (RUNS_Z, (3, 2), 64),
+    # wave 1: runs of 1 .. 8, 12 and 16
+    (RUNS_Z, (0, 0), 1), (RUNS_Z, (1, 3), 2), (RUNS_Z, (2, 6), 3), (RUNS_Z, (3, 2), 4), (RUNS_Z, (4, 5), 5), (RUNS_Z, (5, 1), 6),
+    (RUNS_Z, (6, 4), 7), (RUNS_Z, (0, 5), 8), (RUNS_Z, (1, 1), 12), (RUNS_Z, (2, 4), 16),
+    # wave 2: two cells in turn, A B A B ...: equal voxels that are never adjacent
+    *(((RUNS_Z, (1, 1), 1), (RUNS_Z, (4, 3), 1)) * 32),
+    # wave 3: 40 lanes of one cell with lanes 5, 17, 18 beside the grid (and y = 0 in lanes 9 and 30: RUNS_DEAD), then the
+    # first half of a run of 48 that the wave boundary cuts into 24 + 24
+    (RUNS_Z, (5, 4), 5), (RUNS_Z, (RUNS_OUTSIDE, 4), 1), (RUNS_Z, (5, 4), 11), (RUNS_Z, (RUNS_OUTSIDE, 4), 2), (RUNS_Z, (5, 4), 21),
+    (RUNS_Z, (0, 6), 24),
+    # wave 4: its second half, then runs of 33 and 7
+    (RUNS_Z, (0, 6), 24), (RUNS_Z, (6, 0), 33), (RUNS_Z, (2, 5), 7),
+    # wave 5: rays along x, runs of 40, 14 and 10 through all 8 planes
+    (RUNS_X, (3, 1), 40), (RUNS_X, (6, 2), 14), (RUNS_X, (0, 0), 10),
+    # wave 6: rays along z and along x in one wave: it walks max(nx, nz) = 8 planes, the z lanes only the first 4
+    (RUNS_Z, (4, 4), 20), (RUNS_X_BACK, (2, 0), 26), (RUNS_Z, (4, 4), 18),
+    # wave 7: 17 lanes, the other 47 have no ray
+    (RUNS_Z, (6, 6), 17),
+)
+RUNS_DEAD = (3 * 64 + 9, 3 * 64 + 30)                       # rays whose y is 0: the device takes them for dead lanes
+RUNS_N = 465
+
+
+class RunsCase(Case):
+    """A Case with the whole-number ray vector y of the exact family, and which of its rays the device's adjoint walks."""
+
+    def __init__(self, *args, y):
+        super().__init__(*args)
+        self.y = np.ascontiguousarray(y, np.float64)
+        self.live = self.y != 0.0
+
+
+def whole_numbers(rng, size, top: int = 8) -> np.ndarray:
+    """Whole numbers in [-top, top] without 0, as f64."""
+    v = rng.integers(1, top + 1, size).astype(np.float64)
+    return np.where(rng.random(size) < 0.5, -v, v)
+
+
+@functools.lru_cache(maxsize=None)
+def runs_case() -> RunsCase:
+    dims, spacing, origin = RUNS_GRID
+    quarter = (0.0, 0.25, 0.5, 0.75)
+    o, d = [], []
+    for direction, cell, lanes in RUNS_LAYOUT:
+        a = int(np.flatnonzero(direction)[0])
+        b, c = [k for k in range(3) if k != a]
+        for _ in range(lanes):
+            r = len(o)                                          # the fractions turn with the ray: the lanes of a run differ
+            p = [0.0, 0.0, 0.0]
+            p[a] = origin[a] - 4.0 * spacing[a] if direction[a] > 0 else origin[a] + (dims[a] + 3.0) * spacing[a]
+            p[b] = origin[b] + (cell[0] + quarter[r % 4]) * spacing[b]
+            p[c] = origin[c] + (cell[1] + quarter[(r // 4 + r // 16) % 4]) * spacing[c]
+            o.append(p)
+            d.append(direction)
+    y = whole_numbers(np.random.default_rng(41), len(o))
+    y[list(RUNS_DEAD)] = 0.0
+    return RunsCase(dims, spacing, origin, o, d, y=y)
+
+
+def exact_adjoint(taps, ys):
+    """sum over the taps of weight * y per voxel in rational arithmetic (one Fraction per voxel), and whether every sum of
+    the model is safe from rounding in any order: all products are multiples of one power of two 2^-q, and the sum of their
+    magnitudes per voxel stays below 2^(53 - q).  Returns (list of Fraction, bool)."""
+    from fractions import Fraction
+    total = [Fraction(0)] * taps.n_voxels
+    size = [Fraction(0)] * taps.n_voxels
+    q = 0
+    for i in range(taps.ray.size):
+        parts = [Fraction(float(w[i])) * Fraction(float(y[taps.ray[i]])) for w, y in zip(taps.weights, ys)]     # a float is dyadic
+        q = max([q] + [p.denominator.bit_length() - 1 for p in parts])
+        total[taps.voxel[i]] += sum(parts)
+        size[taps.voxel[i]] += sum(abs(p) for p in parts)
+    return total, max(size) * 2 ** q < 2 ** 53
+
+
+def lane_runs(case, live=None, wave: int = 64):
+    """Every run of adjacent lanes that add to one voxel in one step of the device's adjoint, as (wave, first lane, length),
+    three arrays: ray r is lane r % wave of wave r // wave, and a step is one tap (0 .. 3) of one plane kappa.  A lane whose
+    plane does not count breaks a run, and so does a ray that is not `live` (a mask over the rays: the device skips a ray
+    whose y are all 0)."""
     t = case.taps
     with np.errstate(invalid="ignore"):
         e = case.dirs / np.linalg.norm(case.dirs, axis=1, keepdims=True)
@@ -138,13 +233,26 @@ def longest_lane_run(case: Case, wave: int = 64) -> int:
     a = axis[t.ray]
     kappa = (t.voxel // stride[a]) % extent[a]
     tap = np.arange(t.ray.size) % 4
-    order = np.lexsort((t.ray % wave, tap, kappa, t.ray // wave))
-    key = np.stack([t.ray // wave, kappa, tap, t.voxel], axis=1)[order]
-    lane = (t.ray % wave)[order]
+    keep = np.ones(t.ray.size, bool) if live is None else np.asarray(live, bool)[t.ray]
+    ray, kappa, tap, voxel = t.ray[keep], kappa[keep], tap[keep], t.voxel[keep]
+    if ray.size == 0:
+        return (np.zeros(0, np.int64),) * 3
+    order = np.lexsort((ray % wave, tap, kappa, ray // wave))
+    key = np.stack([ray // wave, kappa, tap, voxel], axis=1)[order]
+    lane = (ray % wave)[order]
     joined = (key[1:] == key[:-1]).all(axis=1) & (lane[1:] == lane[:-1] + 1)
-    # lengths of the stretches of True in `joined`, plus one
-    edges = np.flatnonzero(np.diff(np.concatenate([[0], joined.astype(np.int8), [0]])))
-    return int((edges[1::2] - edges[::2]).max()) + 1 if edges.size else 1
+    first = np.concatenate([[True], ~joined])
+    return key[first, 0], lane[first], np.bincount(np.cumsum(first) - 1)
+
+
+def lane_run_histogram(case, live=None, wave: int = 64) -> np.ndarray:
+    """np.bincount of the lengths of lane_runs: entry n counts the runs of exactly n lanes."""
+    return np.bincount(lane_runs(case, live, wave)[2])
+
+
+def longest_lane_run(case, wave: int = 64) -> int:
+    """The longest run of adjacent lanes that add to one voxel in one step of the device's adjoint (lane_runs)."""
+    return max(len(lane_run_histogram(case, wave=wave)) - 1, 1)
 
 
 def blob_field(case: Case, centre=None) -> np.ndarray:
@@ -162,6 +270,14 @@ def blob_projection(case: Case, centre=None) -> np.ndarray:
 def sphere_support(case: Case, radius: float = 11000.0) -> np.ndarray:
     x, y, z = case.nodes()
     return ((x * x + y * y + z * z) <= radius * radius).astype(np.uint8)
+
+
+def ray_weights(n_rays: int) -> np.ndarray:
+    """Random weights in [0.2, 2) with 10 % of them 0, for the solver tests on the views of a blob."""
+    rng = np.random.default_rng(9)
+    w = rng.uniform(0.2, 2.0, n_rays)
+    w[rng.random(n_rays) < 0.1] = 0.0
+    return w
 
 
 def rel_l2(a, b) -> float:
