@@ -1310,6 +1310,40 @@ int photon_piv_correlate_masked(const float *d_im1, const float *d_im2, const un
                                 int width, int height, int win, int step, int radius, int min_valid, const int *d_offset,
                                 float *d_vectors, int *d_flags, int *d_valid, float *d_planes, int *n_rows, int *n_cols, void *stream);
 
+/* ------------------------------------------------------------------------------------
+ * Section 18: section 5 with a weight per window pixel -- a Gaussian window in place of the top hat, whose frequency
+ * response sinc(win / lambda) is negative for displacement wavelengths below the window size.  Host model:
+ * photon_amd/piv_weighting.py (correlate_weighted_model, f64).  Everything section 5 says about the grid, the offsets, the
+ * peak, the subpixel fit, the ratio, bits 1 and 4, the outputs and their layouts, the size query and asynchrony holds here.
+ *   d_weight  device f32[win*win], row-major in window coordinates: row y, column x of frame 1's window; one table for
+ *             all windows.  The kernel reads W = w where w > 0 and 0 otherwise: negative and NaN entries count as 0.
+ *             +inf is outside the contract (the sums become inf or NaN and the window comes back flat or NaN).
+ * The weight rides on frame 1's window.  With a, b, o and s as in section 5 and every sum over the win^2 pixels p:
+ *   mean a = sum W a / sum W;  mean b = sum W b / sum W over the in-image pixels of the zero-shift window (0 where their
+ *   weights sum to 0); pixels of im2 outside the image read as mean b (contribute 0)
+ *   C(s)  = sum_p W(p) (a(p) - mean a)(b(p + s) - mean b)
+ *   Cn    = C / sqrt(ea eb),  ea = sum W (a - mean a)^2,  eb = sum W (b - mean b)^2 at zero shift
+ * Flat (bit 2, every output of the window NaN): sum W = 0; all pixels of a with W > 0 equal; the in-image pixels of b at
+ * zero shift with W > 0 all equal, or none; an f32 energy not above 0.  As in section 5 this is decided from the pixels,
+ * not from the means: (w a) / w need not return a.  A pixel under a weight of 0 is still multiplied by it: the images
+ * are finite, as section 5 expects them.
+ * With every weight 1.0f the call returns section 5's vectors, flags and planes bit for bit (fmaf(1, v, s) is s + v, 1 d
+ * is d, sum W is win^2 exactly, and the staging pass keeps section 5's lane order).  A table scaled by a power of two
+ * returns the same planes, peaks and ratios bit for bit.
+ * Section 13's window_sigma multiplies both frames by a Gaussian; the product weight on a pair of pixels is then a
+ * Gaussian of window_sigma / sqrt(2): the table that weights a pair alike here has sigma = window_sigma / sqrt(2).
+ * Refused (1, one stderr line, nothing written, no launch): section 5's list, and a null d_weight.  f32 sums in a fixed
+ * order: two calls on the same inputs return the same bits.  DESIGN.md section 4.3q.
+ *
+ * photon_piv_window_weights fills a host table f32[win*win] for it (needs no GPU): kind 0 uniform (1.0f; param unused),
+ * kind 1 Gaussian, exp(-(cy^2 + cx^2) / (2 sigma^2)) with c = index - (win - 1) / 2 and sigma = param pixels, evaluated in
+ * f64 and rounded once.  Refused (1, one stderr line, nothing written): win not 16 / 32 / 64, another kind, a sigma that is
+ * not finite and > 0, a null pointer. */
+int photon_piv_correlate_weighted(const float *d_im1, const float *d_im2, const float *d_weight, int width, int height, int win,
+                                  int step, int radius, const int *d_offset, float *d_vectors, int *d_flags, float *d_planes,
+                                  int *n_rows, int *n_cols, void *stream);
+int photon_piv_window_weights(int win, int kind, float param, float *weights);
+
 #ifdef __cplusplus
 }
 #endif

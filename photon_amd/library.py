@@ -189,6 +189,9 @@ def _signatures():
         "photon_piv_regrid": (ci, [vp] + [ci] * 9 + [vp, P(ci), P(ci), vp]),
         # section 17: direct correlation with excluded pixels
         "photon_piv_correlate_masked": (ci, [vp] * 4 + [ci] * 6 + [vp] * 5 + [P(ci), P(ci), vp]),
+        # section 18: direct correlation with a weight per window pixel
+        "photon_piv_correlate_weighted": (ci, [vp] * 3 + [ci] * 5 + [vp] * 4 + [P(ci), P(ci), vp]),
+        "photon_piv_window_weights": (ci, [ci, ci, cf, vp]),
     }
 
 
@@ -278,6 +281,20 @@ def _mask_pair(mask, shape, dev):
         if tuple(m.shape) != tuple(int(v) for v in shape):
             raise ValueError(f"a mask of shape {tuple(m.shape)} does not cover a {shape[0]} x {shape[1]} image")
     return out[0], out[-1]
+
+
+def _weight_tables(weighting, wins, dev):
+    """The drivers' weighting= (piv_weighting.resolve: None, "gaussian", ("gaussian", sigma) or an array [win, win]) for the
+    window sizes `wins`: None, or one contiguous f32 device tensor [win, win] per entry of `wins`.  Every refusal is
+    raised before the first table is copied."""
+    import torch
+    from . import piv_weighting as pw
+    if weighting is None:
+        return None
+    if torch.is_tensor(weighting):
+        weighting = weighting.detach().cpu().numpy()
+    tables = [pw.resolve(weighting, win) for win in wins]
+    return [torch.from_numpy(t).to(device=dev).contiguous() for t in tables]
 
 
 def _replace_masked(im, m):
@@ -530,13 +547,56 @@ class PhotonLibrary:
                    _vp(pl.data_ptr()) if planes else None, None, None, _vp(stream))
         return vectors, flags, pl, val
 
-    def _correlator(self, method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5):
+    def piv_correlate_weighted(self, d_im1_ptr: int, d_im2_ptr: int, d_weight_ptr: int, width: int, height: int, win: int, step: int,
+                               radius: int, d_offset_ptr: int = 0, planes: bool = False, stream: int = 0):
+        """photon_piv_correlate_weighted on raw device pointers: piv_correlate's arguments and results with a device f32 table
+        [win, win] of weights on frame 1's window (row y, column x; entries that are not above 0 count as 0), one table for all
+        windows.  A table of ones returns piv_correlate's bits.  The definition: include/parallel_ray_tracing.h, section 18
+        (photon_amd.piv_weighting: host model and tables)."""
+        import torch
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        args = ("photon_piv_correlate_weighted", _vp(d_im1_ptr), _vp(d_im2_ptr), _vp(d_weight_ptr), int(width), int(height), int(win),
+                int(step), int(radius))
+        self._call(*args, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
+        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
+        dev, _ = _device_and_stream()
+        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
+        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
+        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
+        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(pl.data_ptr()) if planes else None, None,
+                   None, _vp(stream))
+        return vectors, flags, pl
+
+    def piv_window_weights(self, win: int, kind: str = "gaussian", sigma: Optional[float] = None) -> np.ndarray:
+        """photon_piv_window_weights: the library's own table f32 [win, win] for section 18 ("uniform", or "gaussian" with
+        sigma pixels, None = win / 4), a host array; needs no GPU.  photon_amd.piv_weighting.window_weights is the same
+        table."""
+        from . import piv_weighting as pw
+        if kind not in pw.KINDS:
+            raise ValueError(f'kind must be "uniform" or "gaussian", not {kind!r}')
+        n = max(int(win), 1)
+        out = np.zeros((n, n), np.float32)
+        self._call("photon_piv_window_weights", int(win), pw.KINDS[kind], float(pw.default_sigma(win) if sigma is None else sigma), _ptr(out))
+        return out
+
+    def _correlator(self, method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5,
+                    weighting=None):
         """What the drivers' method= selects: (a callable with piv_correlate's signature, the radius, the argument check).
         "direct": section 5, radius None = win // 2.  "phase": section 13's mode 1 with window_sigma (None = win / 4) and
         diameter bound, radius None or win // 2 = win // 2 - 1.  mask (what _mask_pair returned): section 17 with the two
-        masks and min_valid = ceil(min_valid_fraction win^2) bound, "direct" alone; None: what it returns without."""
+        masks and min_valid = ceil(min_valid_fraction win^2) bound, "direct" alone; None: what it returns without.
+        weighting (a device f32 table [win, win], what _weight_table returned): section 18 with the table bound, "direct"
+        without a mask alone; None: what it returns without."""
         from . import piv_correlation as pc
         from . import piv_phase as pp
+        if weighting is not None:
+            from . import piv_weighting as pw
+            pw.check_method(method, weighting, mask)
+            if method == "direct":
+                def correlate_weighted(d_im1_ptr, d_im2_ptr, width, height, win, step, radius, d_offset_ptr=0, planes=False, stream=0):
+                    return self.piv_correlate_weighted(d_im1_ptr, d_im2_ptr, weighting.data_ptr(), width, height, win, step, radius,
+                                                       d_offset_ptr, planes, stream)
+                return correlate_weighted, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
         if mask is not None:
             from . import piv_mask
             piv_mask.check_method(method, mask)
@@ -563,7 +623,7 @@ class PhotonLibrary:
 
     def correlate(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1,
                   method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None,
-                  min_valid_fraction: float = 0.5, fill_masked: bool = False):
+                  min_valid_fraction: float = 0.5, fill_masked: bool = False, weighting=None):
         """Displacement field of an image pair (torch tensors on the device or numpy arrays, [height, width]): returns numpy
         (vectors [n_rows, n_cols, 4] = dx, dy, peak, ratio; flags [n_rows, n_cols]).  radius None = win // 2.  passes=2:
         pass 1, the normalised median test and the predictor on the host (photon_amd.piv_correlation), then pass 2 with
@@ -573,14 +633,22 @@ class PhotonLibrary:
         for the two frames): section 17 instead of section 5, "direct" alone.  A window that keeps fewer than
         min_valid_fraction of its pixels in either frame is masked out (flag 16, NaN vector); fill_masked=True gives those
         nodes the median of their finite 3 x 3 neighbours instead (photon_amd.piv_mask.fill_masked).  A partially masked
-        window (flag 32) measures its free pixels: its vector sits at their centroid (piv_mask.window_valid)."""
+        window (flag 32) measures its free pixels: its vector sits at their centroid (piv_mask.window_valid).
+        weighting: a weight per window pixel on frame 1's window, section 18 instead of section 5: "gaussian" (sigma = win /
+        4), ("gaussian", sigma), or an array [win, win] of finite weights >= 0 (photon_amd.piv_weighting); "direct" without a
+        mask alone.  A Gaussian window keeps the response to displacement wavelengths below the window size positive."""
         import torch
         from . import piv_correlation as pc
         if int(passes) not in (1, 2):
             raise ValueError(f"passes must be 1 or 2, not {passes}")
         from . import piv_mask
+        from . import piv_weighting
         piv_mask.check_method(method, mask)
+        piv_weighting.check_method(method, weighting, mask)
         correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter)
+        if weighting is not None:
+            table, = _weight_tables(weighting, (win,), _device_and_stream()[0])
+            correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter, weighting=table)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         if mask is not None:
             correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter, _mask_pair(mask, (h, w), dev), min_valid_fraction)
@@ -795,13 +863,15 @@ class PhotonLibrary:
         return vec, field[cur], smoothed[cur], status
 
     def _deform_chain(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method, window_sigma,
-                      diameter, mask=None, min_valid_fraction=0.5):
+                      diameter, mask=None, min_valid_fraction=0.5, weighting=None):
         """What correlate_deform (one level) and correlate_multigrid queue, arguments already checked: pass 0 and
         iterations[0] deformation iterations at schedule[0]; per further level the last predictor regridded and iterations[l]
         deformation iterations there.  The coefficients of both frames are computed once, before the first warp.  Returns
         (field, vec, status) of the last level as device tensors queued on `stream`.  mask (what _mask_pair returned): every
         correlation is section 17's under the mask in unwarped image coordinates, each level with min_valid from its own
-        win, and each frame's masked pixels are at that frame's unmasked mean before the coefficients (no host wait)."""
+        win, and each frame's masked pixels are at that frame's unmasked mean before the coefficients (no host wait).
+        weighting (what _weight_tables returned for the schedule's wins): every correlation of level l is section 18's with
+        table l."""
         import torch
         h, w = a.shape
         coef = warped = None
@@ -809,7 +879,7 @@ class PhotonLibrary:
             a, b = _replace_masked(a, mask[0]), _replace_masked(b, mask[1])
         for level, ((win, step), n) in enumerate(zip(schedule, iterations)):
             correlate, first_radius, _ = self._correlator(method, win, radius if level == 0 else None, window_sigma, diameter, mask,
-                                                          min_valid_fraction)
+                                                          min_valid_fraction, None if weighting is None else weighting[level])
             if level == 0:
                 vec, field, smoothed, status = self._correlate_validated(correlate, a, b, win, step, first_radius, eps, threshold, dev, stream)
             else:
@@ -826,28 +896,32 @@ class PhotonLibrary:
         return field, vec, status
 
     def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream,
-                                 method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5):
+                                 method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5, weighting=None):
         """correlate_deform on the device images a, b, nothing copied back: (field [n_rows, n_cols, 2] of the last iteration,
         vec [n_rows, n_cols, 4] of the last correlation, status [n_rows, n_cols]) as device tensors queued on `stream`: the
         one-level schedule."""
         return self._correlate_multigrid_device(a, b, ((win, step),), (iterations,), radius, residual_radius, smooth, eps, threshold, dev,
-                                                stream, method, window_sigma, diameter, mask, min_valid_fraction)
+                                                stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
 
     def _correlate_multigrid_device(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream,
-                                    method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5):
+                                    method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5, weighting=None):
         """correlate_multigrid on the device images a, b, nothing copied back: (field, vec, status) of the last level's grid as
         device tensors queued on `stream`.  Every refusal is raised before anything is queued.  mask: the drivers' mask=, or
-        None."""
+        None.  weighting: the drivers' weighting=, or None; the string forms make one table per level's win, an array has to
+        be [win, win] for every level's win."""
         from . import piv_mask
         from . import piv_multigrid as pm
+        from . import piv_weighting
         schedule, iterations = pm.check_schedule(tuple(a.shape), schedule, iterations, radius, residual_radius, method, window_sigma, diameter)
+        piv_weighting.check_method(method, weighting, mask)
+        weighting = _weight_tables(weighting, [win for win, _ in schedule], dev)
         if mask is not None:
             piv_mask.check_method(method, mask)
             for win, _ in schedule:
                 piv_mask.min_valid_for(win, min_valid_fraction)
             mask = _mask_pair(mask, tuple(a.shape), dev)
         return self._deform_chain(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method,
-                                  window_sigma, diameter, mask, min_valid_fraction)
+                                  window_sigma, diameter, mask, min_valid_fraction, weighting)
 
     @staticmethod
     def _masked_result(field, vec, status, masked: bool, fill_masked: bool):
@@ -862,7 +936,7 @@ class PhotonLibrary:
     def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
                          residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
                          window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None, min_valid_fraction: float = 0.5,
-                         fill_masked: bool = False):
+                         fill_masked: bool = False, weighting=None):
         """Displacement field of an image pair by iterative image deformation (section 7; model:
         photon_amd.piv_deformation.correlate_deform_model).  Pass 0 correlates the images with `radius` (None = win // 2);
         every iteration warps both frames half-way by the validated, smoothed field, correlates the warped pair with
@@ -875,17 +949,19 @@ class PhotonLibrary:
         mean before the B-spline coefficients, so that a bright body does not ring into the warped free pixels.  Inside the
         loop a masked-out node (status 16 | 8) holds its neighbours' median, a smooth predictor across the hole;
         fill_masked=False returns NaN (dx, dy, peak, ratio) there, True the medians, for callers that pass the field on to
-        ``displacement_uncertainty`` or ``optical_flow(predictor=...)``."""
+        ``displacement_uncertainty`` or ``optical_flow(predictor=...)``.
+        weighting: as ``correlate`` takes it, for every pass: with a top-hat window the loop amplifies the wrong-signed
+        response to wavelengths below the window size, with a Gaussian window it converges towards the true amplitude."""
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         field, vec, status = self._correlate_deform_device(a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev,
-                                                           stream, method, window_sigma, diameter, mask, min_valid_fraction)
+                                                           stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
         out = self._masked_result(field, vec, status, mask is not None, fill_masked)
         return out.cpu().numpy(), status.cpu().numpy()
 
     def correlate_multigrid(self, im1, im2, schedule=((64, 32), (32, 16), (16, 8)), iterations=(1, 1, 2), radius: Optional[int] = None,
                             residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
                             window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None, min_valid_fraction: float = 0.5,
-                            fill_masked: bool = False):
+                            fill_masked: bool = False, weighting=None):
         """Displacement field of an image pair by multigrid window refinement (section 16; model:
         photon_amd.piv_multigrid.correlate_multigrid_model): large windows find the shift, small ones resolve its gradients,
         in one call.  schedule: the (win, step) of every level, any valid pairs; iterations: the deformation iterations per
@@ -896,10 +972,12 @@ class PhotonLibrary:
         ``displacement_uncertainty`` or ``optical_flow(predictor=...)`` with the last (win, step).  method, window_sigma
         (None = win / 4 of each level), diameter: the correlator of every pass.  Everything runs on the current stream; the
         host waits once, for the result.  mask, min_valid_fraction, fill_masked: as ``correlate_deform`` takes them; every
-        level takes its min_valid from its own win."""
+        level takes its min_valid from its own win.  weighting: as ``correlate`` takes it; "gaussian" and ("gaussian", sigma)
+        make one table per level's win (sigma None = win / 4 of each level), an array is accepted only when every level has
+        its win."""
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         field, vec, status = self._correlate_multigrid_device(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold,
-                                                              dev, stream, method, window_sigma, diameter, mask, min_valid_fraction)
+                                                              dev, stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
         out = self._masked_result(field, vec, status, mask is not None, fill_masked)
         return out.cpu().numpy(), status.cpu().numpy()
 
@@ -1063,7 +1141,7 @@ class PhotonLibrary:
 
     def correlation_predictor(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, eps: float = 0.1,
                               threshold: float = 2.0, method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5,
-                              mask=None, min_valid_fraction: float = 0.5, fill_masked: bool = False):
+                              mask=None, min_valid_fraction: float = 0.5, fill_masked: bool = False, weighting=None):
         """A predictor for track_dots from one pass of window correlation: photon_piv_correlate, then photon_piv_validate
         (median test, replacement, 3 x 3 smoothing) -- pass 0 of correlate_deform.  Returns the smoothed field as a torch
         device tensor [n_rows, n_cols, 2], queued on the current stream: hand it to track_dots as predictor=(field, win, step)
@@ -1071,10 +1149,15 @@ class PhotonLibrary:
         diameter: the correlator, as ``correlate`` takes them.  mask, min_valid_fraction: as ``correlate`` takes them.  The
         smoothed field carries the neighbours' median across masked-out nodes; as in the other drivers fill_masked=False
         returns NaN there (set on the device, nothing waits), and a caller who hands the field on as a predictor wants
-        fill_masked=True: a node that is not finite reads as (0, 0) in every warp."""
+        fill_masked=True: a node that is not finite reads as (0, 0) in every warp.  weighting: as ``correlate`` takes it."""
         from . import piv_mask
+        from . import piv_weighting
         piv_mask.check_method(method, mask)
+        piv_weighting.check_method(method, weighting, mask)
         correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter)
+        if weighting is not None:
+            table, = _weight_tables(weighting, (win,), _device_and_stream()[0])
+            correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter, weighting=table)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         check((h, w), win, step, radius)
         if mask is not None:

@@ -165,12 +165,23 @@ def validate_model(pred, vectors, flags, eps: float = 0.1, threshold: float = 2.
     return out.astype(np.float32), smooth.astype(np.float32), status, outliers, score
 
 
-def model_correlator(method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5):
+def model_correlator(method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5,
+                     weighting=None):
     """What method= selects in the models of the drivers, as PhotonLibrary._correlator does on the device: (correlate(im1, im2,
     win, step, radius) -> (vectors, flags), the radius, check(shape, win, step, radius)).  "direct": piv_correlation's model,
     radius None = win // 2.  "phase": piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or
     win // 2 = win // 2 - 1).  mask (a plane, or a pair of them for the two frames): piv_mask.correlate_masked_model with
-    min_valid = ceil(min_valid_fraction win^2), "direct" alone."""
+    min_valid = ceil(min_valid_fraction win^2), "direct" alone.  weighting (the drivers' weighting=):
+    piv_weighting.correlate_weighted_model with the table piv_weighting.resolve makes of it for `win`, "direct" without a
+    mask alone."""
+    if weighting is not None:
+        from . import piv_weighting
+        piv_weighting.check_method(method, weighting, mask)
+        table = piv_weighting.resolve(weighting, win)
+
+        def correlate_weighted(a, b, win, step, radius):
+            return piv_weighting.correlate_weighted_model(a, b, table, win, step, radius)
+        return correlate_weighted, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
     if mask is not None:
         from . import piv_mask
         piv_mask.check_method(method, mask)
@@ -199,18 +210,19 @@ def model_correlator(method: str, win: int, radius, window_sigma, diameter, mask
 def correlate_deform_model(im1, im2, win: int = 32, step: int = 16, radius=None, iterations: int = 3, residual_radius: int = 4,
                            smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, history: bool = False, method: str = "direct",
                            window_sigma=None, diameter: float = 2.5, mask=None, min_valid_fraction: float = 0.5,
-                           fill_masked: bool = False):
+                           fill_masked: bool = False, weighting=None):
     """Host model of PhotonLibrary.correlate_deform: returns (vectors [n_rows, n_cols, 4] = dx, dy of the last unsmoothed
     field, peak and ratio of the last correlation; status [n_rows, n_cols]); with history=True also the list of the
     unsmoothed fields after pass 0 and after every iteration.  method="phase": every pass correlates with
     piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or win // 2 = win // 2 - 1).
     mask, min_valid_fraction, fill_masked: as the driver takes them -- every pass correlates with
     piv_mask.correlate_masked_model under the mask in unwarped image coordinates, each frame's masked pixels are at that
-    frame's unmasked mean before the coefficients, and piv_mask.fill_masked decides what masked-out nodes return."""
+    frame's unmasked mean before the coefficients, and piv_mask.fill_masked decides what masked-out nodes return.
+    weighting: as the driver takes it -- every pass correlates with piv_weighting.correlate_weighted_model."""
     im1, im2 = np.asarray(im1, np.float64), np.asarray(im2, np.float64)
     if int(iterations) < 0:
         raise ValueError(f"iterations must be >= 0, not {iterations}")
-    correlate, radius, check = model_correlator(method, win, radius, window_sigma, diameter, mask, min_valid_fraction)
+    correlate, radius, check = model_correlator(method, win, radius, window_sigma, diameter, mask, min_valid_fraction, weighting)
     check(im1.shape, win, step, radius)
     if int(iterations) > 0:
         check(im1.shape, win, step, residual_radius)

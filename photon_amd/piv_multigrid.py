@@ -130,7 +130,7 @@ def check_schedule(shape, schedule, iterations, radius, residual_radius, method,
 def correlate_multigrid_model(im1, im2, schedule=DEFAULT_SCHEDULE, iterations=DEFAULT_ITERATIONS, radius=None, residual_radius: int = 4,
                               smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct", window_sigma=None,
                               diameter: float = 2.5, history: bool = False, mask=None, min_valid_fraction: float = 0.5,
-                              fill_masked: bool = False):
+                              fill_masked: bool = False, weighting=None):
     """Host model of PhotonLibrary.correlate_multigrid.  Level 0 is correlate_deform_model at schedule[0] with `radius` and
     iterations[0] iterations; level l > 0 takes regrid_model of the previous level's smoothed field (smooth=False: of the
     field itself) as its predictor and runs iterations[l] >= 1 deformation iterations on its own grid with
@@ -138,9 +138,15 @@ def correlate_multigrid_model(im1, im2, schedule=DEFAULT_SCHEDULE, iterations=DE
     Returns (vectors [n_rows, n_cols, 4] = dx, dy of the last unsmoothed field, peak and ratio of the last correlation;
     status [n_rows, n_cols]) on the last level's grid; with history=True also the list of the unsmoothed fields after pass
     0 and after every iteration of every level, each on its level's grid.  mask, min_valid_fraction, fill_masked: as
-    correlate_deform_model takes them; every level takes min_valid from its own win."""
+    correlate_deform_model takes them; every level takes min_valid from its own win.  weighting: as the driver takes it;
+    the string forms make one table per level's win, an array has to be [win, win] for every level's win."""
     im1, im2 = np.asarray(im1, np.float64), np.asarray(im2, np.float64)
     schedule, iterations = check_schedule(im1.shape, schedule, iterations, radius, residual_radius, method, window_sigma, diameter)
+    if weighting is not None:
+        from . import piv_weighting
+        piv_weighting.check_method(method, weighting, mask)
+        for win, _ in schedule:
+            piv_weighting.resolve(weighting, win)
     if mask is not None:
         from . import piv_mask
         piv_mask.check_method(method, mask)
@@ -149,7 +155,7 @@ def correlate_multigrid_model(im1, im2, schedule=DEFAULT_SCHEDULE, iterations=DE
     fields, coef = [], None
     for level, ((win, step), n) in enumerate(zip(schedule, iterations)):
         correlate, first_radius, _ = pd.model_correlator(method, win, radius if level == 0 else None, window_sigma, diameter, mask,
-                                                         min_valid_fraction)
+                                                         min_valid_fraction, weighting)
         if level == 0:
             vec, flg = correlate(im1, im2, win, step, first_radius)
             field, smoothed, status, _, _ = pd.validate_model(None, vec, flg, eps, threshold)

@@ -23,9 +23,14 @@ the median of seven), and the wall time of correlate_deform with both methods.  
 refinement (PhotonLibrary.correlate_multigrid, header section 16: 64 / 32 -> 32 / 16 -> 16 / 8, iterations 1, 1, 2) on the
 sample pair next to correlate_deform at the final grid's 16 / 8 with three iterations: device events around the queued
 chains (nothing copied back), alternating, the median of seven; per level the difference between the chains that stop
-there; and the time of one photon_piv_regrid per grid change.  Run it on a GPU box under a time limit of its own:
+there; and the time of one photon_piv_regrid per grid change.  --weighting times the weighted direct correlator
+(photon_piv_correlate_weighted, header section 18, Gaussian table of win / 4) next to photon_piv_correlate at 1024^2 and
+prints the response table of DESIGN.md section 4.3q from the device: the amplitude correlate_deform recovers of
+dy = sin(2 pi x / lambda) at lambda 24 and 40 px with a top-hat and with a Gaussian window, after pass 0 and after six
+iterations.  Run it on a GPU box under a time limit of its own:
 
     timeout -k 10 600 python tools/piv_pair.py [--tiff DIR] [--bench-advect] [--correlate] [--deform] [--phase] [--multigrid]
+                                               [--mask] [--weighting]
 """
 import argparse
 import json
@@ -302,6 +307,51 @@ def mask_pair(lib, row):
                 row[f"mask_1024_w{win}_r{R}_{k}_ms"] = round(v, 4)
 
 
+def weighting_pair(lib, row):
+    """--weighting: photon_piv_correlate_weighted (Gaussian table, sigma = win / 4) next to photon_piv_correlate on
+    mask_pair's 1024^2 pair, alternating, section 5 twice a round (its difference from itself is the run's resolution); then
+    the response study of tests/piv_weighting_cases.py through correlate_deform, seeds 1 to 4.  Adds both to `row`."""
+    import piv_weighting_cases as wc
+    from photon_amd import piv_weighting as pw
+    rng = np.random.default_rng(1)
+    n = 20_000
+    x, y = rng.uniform(-8, 1032, n), rng.uniform(-8, 1032, n)
+    big = [torch.from_numpy(pc.particle_image((1024, 1024), x + dx, y + dy).astype(np.float32)).cuda() for dx, dy in ((0, 0), (3.3, -2.6))]
+    h = w = 1024
+    p0, p1 = big[0].data_ptr(), big[1].data_ptr()
+    for win, step in ((32, 16), (64, 32), (16, 8)):
+        table = torch.from_numpy(pw.window_weights(win)).cuda()
+        for R in sorted({4, win // 4, win // 2}):
+            calls = {"plain": lambda: lib.piv_correlate(p0, p1, w, h, win, step, R),
+                     "weighted": lambda: lib.piv_correlate_weighted(p0, p1, table.data_ptr(), w, h, win, step, R),
+                     "plain_again": lambda: lib.piv_correlate(p0, p1, w, h, win, step, R)}
+            times = {k: [] for k in calls}
+            for rep in range(10):                           # three warm-up rounds, then seven; one event pair per call
+                for k, fn in calls.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    e1.synchronize()
+                    if rep >= 3:
+                        times[k].append(e0.elapsed_time(e1))
+            ms = {k: float(np.median(v)) for k, v in times.items()}
+            print(f"1024^2, win {win} step {step} R {R}: " + ", ".join(f"{k} {v:.4f} ms" for k, v in ms.items())
+                  + f"; weighted / plain {ms['weighted'] / ms['plain']:.4f}, plain again / plain {ms['plain_again'] / ms['plain']:.4f}")
+            for k, v in ms.items():
+                row[f"weighting_1024_w{win}_r{R}_{k}_ms"] = round(v, 4)
+    print("response to dy = sin(2 pi x / lambda), win 32, step 8, six iterations, seeds 1-4 (pass 0 | after 6):")
+    for lam in wc.WAVELENGTHS:
+        for name, weighting in (("uniform", None), ("gaussian", "gaussian")):
+            first, last = [], []
+            for seed in (1, 2, 3, 4):
+                im1, im2 = (np.array(c) for c in wc.response_pair(lam, seed))
+                first.append(wc.amplitude(lib.correlate_deform(im1, im2, **wc.R_ARGS, iterations=0, weighting=weighting)[0], lam))
+                last.append(wc.amplitude(lib.correlate_deform(im1, im2, **wc.R_ARGS, iterations=wc.R_ITERATIONS, weighting=weighting)[0], lam))
+            print(f"  lambda {lam}, {name}: {min(first):+.3f} ... {max(first):+.3f} | {min(last):+.3f} ... {max(last):+.3f}")
+            row[f"weighting_response_l{lam}_{name}"] = [round(min(first), 4), round(max(first), 4), round(min(last), 4), round(max(last), 4)]
+
+
 def timed(fn, reps=3):
     out, best = None, 1e9
     for _ in range(reps):
@@ -325,6 +375,7 @@ def main():
     ap.add_argument("--phase", action="store_true")
     ap.add_argument("--multigrid", action="store_true")
     ap.add_argument("--mask", action="store_true")
+    ap.add_argument("--weighting", action="store_true")
     args = ap.parse_args()
     lib = PhotonLibrary()
     lib.set_device(0)
@@ -417,6 +468,8 @@ def main():
         multigrid_pair(lib, images, row)
     if args.mask:
         mask_pair(lib, row)
+    if args.weighting:
+        weighting_pair(lib, row)
     print(json.dumps(row), flush=True)
     if not math.isfinite(row["p99_err_px"]):
         sys.exit(1)
