@@ -215,7 +215,7 @@ static bool parse_nrrd(const char *path, std::vector<float> &rho, int dims[3], d
             if (!(f >> rho[i])) { why = "payload shorter than sizes"; return false; }
     } else {
         // gzip: the compressed bytes are in the file; deflate's best ratio is ~1032 : 1, so sizes a file cannot hold are refused
-        // before the allocation, and the stream is never inflated beyond what the sizes ask for
+        // before the allocation, and the stream is never inflated beyond what the sizes ask for (but for the 64-byte probe below)
         if (in_file < 18 || count * sizeof(float) / 1032ull > in_file) { why = "payload shorter than sizes"; return false; }
         std::vector<unsigned char> z((size_t)in_file);
         f.read(reinterpret_cast<char *>(z.data()), (std::streamsize)z.size());
@@ -238,8 +238,27 @@ static bool parse_nrrd(const char *path, std::vector<float> &rho, int dims[3], d
             zr = inflate(&zs, Z_NO_FLUSH);
             got += room - zs.avail_out;
         }
+        // the sizes' worth of bytes is out, so the stream has to end here: inflate once more into a scratch buffer, which takes the
+        // trailer (gzip: CRC32 and ISIZE, zlib: Adler-32).  A payload that inflates further, fails its check or length, stops
+        // short of its trailer or is followed by anything else is refused.
+        unsigned char scratch[64];
+        bool longer = false;
+        while (zr == Z_OK && got == want && !longer) {
+            if (zs.avail_in == 0) {
+                const unsigned long long piece = std::min<unsigned long long>(z.size() - fed, 1ull << 30);
+                if (piece == 0) break;
+                zs.next_in = z.data() + fed; zs.avail_in = (uInt)piece; fed += piece;
+            }
+            zs.next_out = scratch; zs.avail_out = (uInt)sizeof scratch;
+            zr = inflate(&zs, Z_NO_FLUSH);
+            longer = zs.avail_out != sizeof scratch;
+        }
+        const bool input_left = zs.avail_in != 0 || fed != z.size();
         inflateEnd(&zs);
         if ((zr != Z_OK && zr != Z_STREAM_END) || got != want) { why = "compressed payload is damaged or shorter than sizes"; return false; }
+        if (longer) { why = "compressed payload inflates to more than sizes"; return false; }
+        if (zr != Z_STREAM_END) { why = "compressed payload ends before its trailer"; return false; }
+        if (input_left) { why = "bytes after the end of the compressed payload"; return false; }
     }
     if (endian == "big" && !is_ascii) {
         unsigned *u = reinterpret_cast<unsigned *>(rho.data());

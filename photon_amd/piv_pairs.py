@@ -71,8 +71,11 @@ def _store(X, Y, Z, ud, z_object, beam_fwhm, irradiance_constant, diameter_cdf) 
     else:
         cdf = np.asarray(diameter_cdf, np.float64)
         dia = np.minimum(np.searchsorted(cdf, ud, side="right"), cdf.size - 1).astype(np.int32)   # first d with ud < cdf[d]
-    with np.errstate(over="ignore", invalid="ignore"):
-        radiance = coef * np.exp(-1.0 * (Z * Z / two_sigma2))
+    with np.errstate(over="ignore", under="ignore", invalid="ignore"):
+        arg = -1.0 * (Z * Z / two_sigma2)
+        # photon_det_exp returns 0 below -708 (include/photon_det_math.h), where numpy's exp still has 3e-308 .. 5e-324: a
+        # particle more than 37.6 sigma off the sheet
+        radiance = coef * np.where(arg < -708.0, 0.0, np.exp(arg))
     return dict(x=X.astype(np.float32), y=Y.astype(np.float32), z=(Z + float(z_object)).astype(np.float32),
                 radiance=radiance, diameter_index=dia, world=np.stack([X, Y, Z], 1))
 

@@ -1322,6 +1322,12 @@ def test_nrrd_payload_encodings(photon, oracle, tmp_path):
            "sizes_lie": header("gzip", "little").replace(f"sizes: {n[2]} {n[1]} {n[0]}".encode(), b"sizes: 60000 60000 60000") + gz,
            "ascii_short": header("ascii", "little") + b"1.0 2.0 3.0\n", "unknown": header("bzip2", "little") + little,
            "endian": header("raw", "middle") + little}
+    # payloads that hold the sizes' worth of the right bytes and lie behind them: a flipped CRC32, a changed ISIZE, a stream that
+    # inflates 400 bytes further, 16 bytes of junk after the stream (generator_cases.lying_gzip_payloads)
+    from generator_cases import lying_gzip_payloads
+    lies = lying_gzip_payloads(little)
+    assert len(lies) == 4
+    bad.update({name: header("gzip", "little") + payload for name, payload in lies.items()})
     for name, blob in bad.items():
         path = tmp_path / f"bad_{name}.nrrd"
         path.write_bytes(blob)
