@@ -8,7 +8,7 @@
 // (exact size match, per device); the cache holds at most PHOTON_POOL_MAX_MB (default 4096; 0 = off), evicting its largest
 // blocks first; photon_trim_caches() empties it, and so does any allocation of this library that finds the device out of
 // memory (device_malloc).  Recycled memory is not zeroed -- neither is hipMalloc'd memory: every buffer that needs a
-// defined start is cleared where it is allocated or used.
+// defined start is cleared where it is allocated or used.  Held by tests/test_dirty_memory_gpu.py (solvers on recycled blocks).
 #include "photon_pool.hpp"
 
 #include <cstdio>
