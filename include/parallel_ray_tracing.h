@@ -1067,6 +1067,13 @@ int photon_piv_uncertainty(const float *d_im1, const float *d_im2, int width, in
  *    s = clamp(scale D, -2^24, 2^24), the same taps, weights and order (one kernel template over where D comes from):
  *    photon_piv_deform_dense of photon_piv_field_to_pixels(F) equals photon_piv_deform(F) bit for bit.
  *    Refused: width or height < 1 or larger than 2^22, a scale that is not finite, a null pointer, d_out == d_coef.
+ *    Limit at a pedestal: the warp sums 16 f32 taps of coefficients as large as the image, so its error grows with the
+ *    pedestal and not with the signal.  Frames in camera counts with a pedestal of 61000 under a signal of 4000 counts
+ *    (uint16) move the flow of the optical-flow driver by 3.7e-5 px against the f64 model (measured on an MI355X; 4e-7 px
+ *    at a pedestal of 64), where frames of amplitude 1 stay within 3e-5 px, and the sigma of the uncertainty driver (section
+ *    11 behind this warp and section 7b's) by 1.2e-4 of itself against its f64 model (1e-6 at a pedestal of 64), where the
+ *    kernel alone stays within 1e-5.  A caller who needs more subtracts the pedestal
+ *    first (section 15); the flow does not depend on a constant.  tests/test_driver_inputs_gpu.py holds the figure.
  *
  * c. photon_optflow_terms.  d_w1, d_w2: a matched pair, frame 1 warped by -u0 / 2 and frame 2 by +u0 / 2; d_u0 the dense
  *    field u0 they were warped by, or NULL for a zero field.  d_terms f32[height*width][4] = (Ix, Iy, c, w) per pixel

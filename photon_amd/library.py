@@ -247,10 +247,65 @@ def _piv_args(seed, n, box_min, box_max, z_object, beam_fwhm, irradiance_constan
             float(irradiance_constant), None if cdf is None else _ptr(cdf), 0 if cdf is None else int(cdf.size))
 
 
-def _on_device(a, dtype, dev):
-    """a (a numpy array or a torch tensor; None stays None) as a contiguous torch tensor of `dtype` on `dev`."""
+def _checked(x, name: str, ndim=None):
+    """The first half of the drivers' ingest rule (PhotonLibrary's docstring), on the host alone: `x` as the caller's torch
+    tensor or as a base-class numpy array (np.asarray: memmaps, lists, scalars' sequences), or the refusal that names
+    the argument -- TypeError for a dtype that is not real numeric or bool (complex, object, strings), ValueError for
+    what numpy cannot make an array of and for a number of dimensions other than `ndim` (None: any).  Nothing is copied,
+    allocated or launched; None stays None."""
+    import sys
+    if x is None:
+        return None
+    torch = sys.modules.get("torch")
+    if torch is not None and isinstance(x, torch.Tensor):
+        if x.is_complex():
+            raise TypeError(f"{name} must hold real numbers, not {x.dtype}")
+        a = x
+    else:
+        try:
+            a = np.asarray(x)
+        except ValueError as e:
+            raise ValueError(f"{name} is not an array: {e}") from e
+        if a.dtype.kind not in "biuf":
+            raise TypeError(f"{name} must hold real numbers, not dtype {a.dtype}")
+    if ndim is not None and a.ndim != int(ndim):
+        raise ValueError(f"{name} must have {int(ndim)} dimensions, not {a.ndim} (shape {tuple(a.shape)})")
+    return a
+
+
+def _on_device(x, dtype, dev, name: str = "array", ndim=None, nonzero: bool = False):
+    """The drivers' ingest rule (PhotonLibrary's docstring), the one way a caller's array reaches the device: `x` (what
+    _checked accepts; None stays None) as a contiguous torch tensor of the torch dtype `dtype` on `dev` that holds
+    np.asarray(x).astype(dtype) in C order -- numpy's conversion, made on the host for whatever lives there; a device
+    tensor is converted where it is, by the same round-to-nearest.  nonzero: the value is (x != 0) instead, the masks'
+    reading.  A tensor that is already of `dtype`, contiguous and on `dev` is returned as it is, uncopied (nonzero: never);
+    no driver writes to what this returns.  The caller's object is never written and no warning is raised: a read-only
+    or foreign-endian array is copied on the host first."""
     import torch
-    return None if a is None else torch.as_tensor(a).to(device=dev, dtype=dtype).contiguous()
+    a = _checked(x, name, ndim)
+    if a is None:
+        return None
+    dev = torch.device(dev)
+    if isinstance(a, torch.Tensor):
+        a = a.detach()
+        if a.device.type != "cpu":
+            if nonzero:
+                return (a.to(device=dev) != 0).to(dtype).contiguous()
+            if a.dtype == dtype and a.device == dev and a.is_contiguous():
+                return a
+            return a.to(device=dev, dtype=dtype).contiguous()
+        if dev.type == "cpu" and a.dtype == dtype and a.is_contiguous() and not nonzero:
+            return a
+        if a.dtype == torch.bfloat16:
+            a = a.to(torch.float32)                     # numpy has no bfloat16; every bfloat16 is an f32
+        a = a.numpy()                                   # strides and all; converted below as numpy does
+    if nonzero:
+        a = a != 0
+    targets = {torch.float32: np.float32, torch.float64: np.float64, torch.uint8: np.uint8}       # what the drivers ask for
+    c = np.ascontiguousarray(a, dtype=targets[dtype])   # native byte order, C order, positive strides
+    if not c.flags.writeable:
+        c = c.copy()            # torch warns about tensors over read-only memory
+    return torch.from_numpy(c).to(device=dev)
 
 
 def _device_and_stream():
@@ -260,13 +315,37 @@ def _device_and_stream():
     return dev, torch.cuda.current_stream(dev).cuda_stream
 
 
-def _image_pair(im1, im2):
-    """(dev, stream, a, b, h, w): the two images as contiguous f32 device tensors [h, w] on the current device."""
+def _checked_mask(mask, shape):
+    """The drivers' mask= (piv_mask.mask_pair: one plane, or a tuple or list of two) checked on the host against the image
+    shape (height, width): the tuple of its one or two planes as _checked returns them.  None stays None."""
+    if mask is None:
+        return None
+    two = isinstance(mask, (tuple, list)) and len(mask) == 2
+    pair = tuple(_checked(m, "mask", 2) for m in (mask if two else (mask,)))
+    for m in pair:
+        if tuple(m.shape) != tuple(int(v) for v in shape):
+            raise ValueError(f"a mask of shape {tuple(m.shape)} does not cover a {shape[0]} x {shape[1]} image")
+    return pair
+
+
+def _checked_pair(im1, im2, mask=None):
+    """Every refusal of an image pair and its mask=, on the host, before anything is allocated or queued: (a, b, mask) as
+    _checked and _checked_mask return them."""
+    a, b = _checked(im1, "im1", 2), _checked(im2, "im2", 2)
+    if a is None or b is None:
+        raise TypeError("im1 and im2 must be two images, not None")
+    if tuple(a.shape) != tuple(b.shape):
+        raise ValueError(f"im1 and im2 must be two 2-d images of one shape, not {tuple(a.shape)} and {tuple(b.shape)}")
+    return a, b, _checked_mask(mask, a.shape)
+
+
+def _image_pair(im1, im2, mask=None):
+    """(dev, stream, a, b, h, w): the two images as contiguous f32 device tensors [h, w] on the current device.  mask: the
+    driver's mask=, checked here with the images (_checked_pair) and brought over later, by _mask_pair."""
     import torch
+    a, b, _ = _checked_pair(im1, im2, mask)
     dev, stream = _device_and_stream()
-    a, b = (torch.as_tensor(x).to(device=dev, dtype=torch.float32).contiguous() for x in (im1, im2))
-    if a.dim() != 2 or a.shape != b.shape:
-        raise ValueError("im1 and im2 must be two 2-d images of one shape")
+    a, b = _on_device(a, torch.float32, dev, "im1", 2), _on_device(b, torch.float32, dev, "im2", 2)
     return (dev, stream, a, b, *a.shape)
 
 
@@ -274,13 +353,18 @@ def _mask_pair(mask, shape, dev):
     """The drivers' mask= (piv_mask.mask_pair: one plane, or a tuple or list of two) as two contiguous u8 device tensors
     [h, w], 1 = excluded; one tensor twice for one plane."""
     import torch
-    pair = tuple(mask) if isinstance(mask, (tuple, list)) and len(mask) == 2 else (mask,)
-    out = tuple((torch.as_tensor(m if torch.is_tensor(m) else np.asarray(m) != 0).to(device=dev) != 0).to(torch.uint8).contiguous()
-                for m in pair)
-    for m in out:
-        if tuple(m.shape) != tuple(int(v) for v in shape):
-            raise ValueError(f"a mask of shape {tuple(m.shape)} does not cover a {shape[0]} x {shape[1]} image")
+    out = tuple(_on_device(m, torch.uint8, dev, "mask", 2, nonzero=True) for m in _checked_mask(mask, shape))
     return out[0], out[-1]
+
+
+def _checked_weighting(weighting):
+    """The drivers' weighting= on the host: the named forms as they are, an array [win, win] as a numpy array that _checked
+    passed (a device tensor is copied back: piv_weighting.check_weights reads every weight before any table is made)."""
+    if weighting is None or isinstance(weighting, str) or (isinstance(weighting, (tuple, list)) and len(weighting) == 2
+                                                           and isinstance(weighting[0], str)):
+        return weighting
+    a = _checked(weighting, "weighting", 2)
+    return a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
 
 
 def _weight_tables(weighting, wins, dev):
@@ -291,10 +375,8 @@ def _weight_tables(weighting, wins, dev):
     from . import piv_weighting as pw
     if weighting is None:
         return None
-    if torch.is_tensor(weighting):
-        weighting = weighting.detach().cpu().numpy()
-    tables = [pw.resolve(weighting, win) for win in wins]
-    return [torch.from_numpy(t).to(device=dev).contiguous() for t in tables]
+    tables = [pw.resolve(_checked_weighting(weighting), win) for win in wins]
+    return [_on_device(t, torch.float32, dev, "weighting", 2) for t in tables]
 
 
 def _replace_masked(im, m):
@@ -353,6 +435,25 @@ def mapped_hip_runtimes():
 
 
 class PhotonLibrary:
+    """The loaded library: one method per entry point (raw device pointers) and the drivers that chain them.
+
+    The ingest rule -- how every driver takes an array argument (images, stacks, masks, weights, fields, predictors,
+    gradients, solver data, rays), through _on_device alone:
+      * accepted: a numpy array or whatever np.asarray takes (a memmap, nested lists), of any real numeric or bool dtype, any
+        byte order, any strides (views, crops, Fortran order, np.flipud / np.rot90 / a[::-1]), writable or read-only; a torch
+        tensor on any device, of any real dtype, with any strides;
+      * the value: the device tensor holds np.asarray(x).astype(target) -- numpy's conversion, round to nearest -- in C order,
+        target f32 for images, stacks, fields and weights, f64 for gradients, solver data and rays; a mask (mask=, fixed=,
+        support=) holds x != 0.  Integer frames (uint8 / uint16 camera counts) are taken as they are, no scaling.  No warning
+        is raised and the caller's array is never written;
+      * refused: complex, object and string dtypes with a TypeError, what numpy makes no array of and a wrong number of
+        dimensions with a ValueError; the message names the argument, and the refusal -- like that of two images of
+        different shapes or a mask of another shape -- comes before anything is allocated or queued on the device;
+      * device tensors: one that is already of the target dtype, contiguous and on the current device is used in place,
+        uncopied, so work queued on the current stream that fills it is waited for by the driver's kernels and by nothing
+        else; every other tensor is converted on its device, on the current stream.  No driver writes to an input, and no
+        result shares storage with one."""
+
     def __init__(self, path: Optional[str] = None, build: bool = True):
         if path is None:
             path = os.environ.get("PHOTON_LIBRARY")
@@ -645,6 +746,8 @@ class PhotonLibrary:
         from . import piv_weighting
         piv_mask.check_method(method, mask)
         piv_weighting.check_method(method, weighting, mask)
+        im1, im2, _ = _checked_pair(im1, im2, mask)
+        weighting = _checked_weighting(weighting)
         correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter)
         if weighting is not None:
             table, = _weight_tables(weighting, (win,), _device_and_stream()[0])
@@ -699,23 +802,19 @@ class PhotonLibrary:
         if int(passes) not in (1, 2):
             raise ValueError(f"passes must be 1 or 2, not {passes}")
         radius = int(win) // 2 if radius is None else int(radius)
+        frames1, frames2 = _checked(frames1, "frames1", 3), _checked(frames2, "frames2", 3)      # [N, height, width]
+        if frames1 is None:
+            raise TypeError("frames1 must be a stack of frames, not None")
+        if frames2 is not None and tuple(frames2.shape) != tuple(frames1.shape):
+            raise ValueError("frames1 and frames2 must be two stacks of one shape")
         dev, stream = _device_and_stream()
-
-        def stack(x):
-            t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(x, np.float32))
-            t = t.to(device=dev, dtype=torch.float32).contiguous()
-            if t.ndim != 3:
-                raise ValueError("a stack of frames must be [N, height, width]")
-            return t
-        a = stack(frames1)
+        a = _on_device(frames1, torch.float32, dev, "frames1", 3)
         if frames2 is None:
             if a.shape[0] < 2:
                 raise ValueError("a time series needs at least two frames")
             n, b_ptr = a.shape[0] - 1, a[1].data_ptr()
         else:
-            b = stack(frames2)
-            if b.shape != a.shape:
-                raise ValueError("frames1 and frames2 must be two stacks of one shape")
+            b = _on_device(frames2, torch.float32, dev, "frames2", 3)
             n, b_ptr = a.shape[0], b.data_ptr()
         h, w = int(a.shape[1]), int(a.shape[2])
         pc.check_arguments((h, w), win, step, radius)
@@ -770,16 +869,21 @@ class PhotonLibrary:
         ``correlate_ensemble`` takes as they are (``correlate`` and ``correlate_deform``: one frame of each)."""
         import torch
         from . import piv_preprocess as pp
-        dev, stream = _device_and_stream()
         modes = {"min": pp.MODE_MIN, "mean": pp.MODE_MEAN}
         if isinstance(background, str) and background not in modes:
             raise ValueError(f'background must be "min", "mean", None or a [height, width] plane, not "{background}"')
+        frames1, frames2 = _checked(frames1, "frames1", 3), _checked(frames2, "frames2", 3)      # [N, height, width]
+        if frames1 is None:
+            raise TypeError("frames1 must be a stack of frames, not None")
+        if background is not None and not isinstance(background, str):
+            background = _checked(background, "background", 2)
+            for frames in (frames1, frames2):
+                if frames is not None and tuple(background.shape) != tuple(frames.shape[1:]):
+                    raise ValueError("the background must be one [height, width] plane")
+        dev, stream = _device_and_stream()
 
-        def one(frames):
-            t = frames if isinstance(frames, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(frames, np.float32))
-            t = t.to(device=dev, dtype=torch.float32).contiguous()
-            if t.ndim != 3:
-                raise ValueError("a stack of frames must be [N, height, width]")
+        def one(frames, name):
+            t = _on_device(frames, torch.float32, dev, name, 3)
             n, h, w = (int(v) for v in t.shape)
             pp.check_arguments((h, w), n, radius=minmax_radius, floor=floor, background=background is not None)
             if background is None:
@@ -787,12 +891,10 @@ class PhotonLibrary:
             elif isinstance(background, str):
                 bg = self.piv_background(t.data_ptr(), h * w, n, w, h, modes[background], stream=stream)
             else:
-                bg = _on_device(background, torch.float32, dev)
-                if tuple(bg.shape) != (h, w):
-                    raise ValueError("the background must be one [height, width] plane")
+                bg = _on_device(background, torch.float32, dev, "background", 2)
             return self.piv_preprocess(t.data_ptr(), h * w, n, w, h, bg.data_ptr() if bg is not None else 0, minmax_radius,
                                        0.0 if floor is None else float(floor), stream=stream)
-        return one(frames1) if frames2 is None else (one(frames1), one(frames2))
+        return one(frames1, "frames1") if frames2 is None else (one(frames1, "frames1"), one(frames2, "frames2"))
 
     # ---- iterative image-deformation correlation on the device (section 7) ---------------------------------------------
     def bspline_coefficients(self, d_im_ptr: int, width: int, height: int, d_coef_ptr: int, stream: int = 0):
@@ -952,7 +1054,8 @@ class PhotonLibrary:
         ``displacement_uncertainty`` or ``optical_flow(predictor=...)``.
         weighting: as ``correlate`` takes it, for every pass: with a top-hat window the loop amplifies the wrong-signed
         response to wavelengths below the window size, with a Gaussian window it converges towards the true amplitude."""
-        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        weighting = _checked_weighting(weighting)
+        dev, stream, a, b, h, w = _image_pair(im1, im2, mask)
         field, vec, status = self._correlate_deform_device(a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev,
                                                            stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
         out = self._masked_result(field, vec, status, mask is not None, fill_masked)
@@ -975,7 +1078,8 @@ class PhotonLibrary:
         level takes its min_valid from its own win.  weighting: as ``correlate`` takes it; "gaussian" and ("gaussian", sigma)
         make one table per level's win (sigma None = win / 4 of each level), an array is accepted only when every level has
         its win."""
-        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        weighting = _checked_weighting(weighting)
+        dev, stream, a, b, h, w = _image_pair(im1, im2, mask)
         field, vec, status = self._correlate_multigrid_device(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold,
                                                               dev, stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
         out = self._masked_result(field, vec, status, mask is not None, fill_masked)
@@ -1012,9 +1116,10 @@ class PhotonLibrary:
         import torch
         from . import piv_correlation as pc
         from . import piv_uncertainty as pu
+        field = _checked(field, "field", 3)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         pu.check_arguments((h, w), win, step, reach)
-        fld = torch.as_tensor(field).to(device=dev, dtype=torch.float32)
+        fld = _on_device(field, torch.float32, dev, "field", 3)
         r, c = pc.grid_shape((h, w), win, step)
         if fld.dim() != 3 or fld.shape[2] < 2 or tuple(fld.shape[:2]) != (r, c):
             raise ValueError(f"field must be [{r}, {c}, >= 2]: the grid of a {h} x {w} image, win {win}, step {step}")
@@ -1067,12 +1172,13 @@ class PhotonLibrary:
         result."""
         import torch
         from . import optical_flow as of
+        predictor = _checked(predictor, "predictor", 3)
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         of.check_driver_arguments(alpha2, warps, iterations)
         inv_std = 1.0 / torch.std(a, correction=0)
         if predictor is None:
             predictor = self._correlate_deform_device(a, b, win, step, None, 1, 4, True, 0.1, 2.0, dev, stream)[0]
-        pred = torch.as_tensor(predictor).to(device=dev, dtype=torch.float32)
+        pred = _on_device(predictor, torch.float32, dev, "predictor", 3)
         field = torch.empty((2, h, w, 2), dtype=torch.float32, device=dev)      # the current field and the next one
         if of.predictor_shape(pred.shape, (h, w), win, step) == "grid":
             pred = (pred if pred.shape[2] in (2, 4) else pred[..., :2]).contiguous()
@@ -1154,6 +1260,8 @@ class PhotonLibrary:
         from . import piv_weighting
         piv_mask.check_method(method, mask)
         piv_weighting.check_method(method, weighting, mask)
+        im1, im2, _ = _checked_pair(im1, im2, mask)
+        weighting = _checked_weighting(weighting)
         correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter)
         if weighting is not None:
             table, = _weight_tables(weighting, (win,), _device_and_stream()[0])
@@ -1183,6 +1291,8 @@ class PhotonLibrary:
         import torch
         from . import dot_tracking as dt
         from . import piv_correlation as pc
+        if predictor is not None:
+            predictor = (_checked(predictor[0], "the predictor field", 3), *predictor[1:])
         dev, stream, a, b, h, w = _image_pair(im1, im2)
         cap = dt.default_max_dots((h, w)) if max_dots is None else int(max_dots)
         det_bytes = self.dots_scratch_bytes(w, h)
@@ -1206,8 +1316,8 @@ class PhotonLibrary:
         field_args = {}
         if predictor is not None:
             field, pwin, pstep = predictor
-            fld = torch.as_tensor(field).to(device=dev, dtype=torch.float32).contiguous()
-            if fld.dim() != 3 or fld.shape[2] not in (2, 4):
+            fld = _on_device(field, torch.float32, dev, "the predictor field", 3)
+            if fld.shape[2] not in (2, 4):
                 raise ValueError("the predictor field must be [n_rows, n_cols, 2 or 4]")
             field_args = dict(d_field_ptr=fld.data_ptr(), field_stride=int(fld.shape[2]), n_rows=int(fld.shape[0]), n_cols=int(fld.shape[1]),
                               win=int(pwin), step=int(pstep))
@@ -1256,16 +1366,17 @@ class PhotonLibrary:
         unknown nodes that reach no fixed node.  max_iter None = 20 max(nx, ny)."""
         import torch
         from . import bos_density
-        dev, stream = _device_and_stream()
-        tgx, tgy = _on_device(gx, torch.float64, dev), _on_device(gy, torch.float64, dev)
-        if tgx.dim() != 2 or tgx.shape != tgy.shape:
+        gx, gy, w, fixed, value = (_checked(a, name, 2) for a, name in ((gx, "gx"), (gy, "gy"), (w, "w"), (fixed, "fixed"), (value, "value")))
+        if gx is None or gy is None or tuple(gx.shape) != tuple(gy.shape):
             raise ValueError("gx and gy must be two 2-d arrays of one shape")
+        for name, t in (("w", w), ("fixed", fixed), ("value", value)):
+            if t is not None and tuple(t.shape) != tuple(gx.shape):
+                raise ValueError(f"{name} must have the shape of gx, {tuple(gx.shape)}")
+        dev, stream = _device_and_stream()
+        tgx, tgy = _on_device(gx, torch.float64, dev, "gx", 2), _on_device(gy, torch.float64, dev, "gy", 2)
         ny, nx = tgx.shape
-        tw, tv = _on_device(w, torch.float64, dev), _on_device(value, torch.float64, dev)
-        tf = None if fixed is None else _on_device(torch.as_tensor(fixed) != 0, torch.uint8, dev)
-        for name, t in (("w", tw), ("fixed", tf), ("value", tv)):
-            if t is not None and t.shape != tgx.shape:
-                raise ValueError(f"{name} must have the shape of gx, {tuple(tgx.shape)}")
+        tw, tv = _on_device(w, torch.float64, dev, "w", 2), _on_device(value, torch.float64, dev, "value", 2)
+        tf = _on_device(fixed, torch.uint8, dev, "fixed", 2, nonzero=True)
         bos_density.check_arguments(nx, ny, hx, hy, tol, bos_density.default_max_iter(nx, ny) if max_iter is None else max_iter)
         phi = torch.empty((ny, nx), dtype=torch.float64, device=dev)
         stats = self.integrate_gradient_ptr(tgx.data_ptr(), tgy.data_ptr(), nx, ny, phi.data_ptr(),
@@ -1312,17 +1423,25 @@ class PhotonLibrary:
         of three values per ray (origins and dirs, and t1, t2); the names are the message's."""
         import torch
         from . import tomography
-        dev, stream = _device_and_stream()
         nx, ny, nz = (int(n) for n in dims)
-        rays = [_on_device(a, torch.float64, dev).reshape(-1, 3) for a in rays]
-        data = [_on_device(a, torch.float64, dev).reshape(-1) for a in data]
-        tw = _on_device(w, torch.float64, dev)
-        n_rays = data[0].numel()
-        if any(a.shape != (n_rays, 3) for a in rays) or any(a.numel() != n_rays for a in data) or (tw is not None and tw.numel() != n_rays):
+        data_names, rays_names = names.split(", "), ray_names.replace(" and ", ", ").split(", ")      # the messages' names, one per array
+        assert len(data_names) == len(data) and len(rays_names) == len(rays), (names, ray_names)
+        rays = [_checked(a, name) for a, name in zip(rays, rays_names)]
+        data = [_checked(a, name) for a, name in zip(data, data_names)]
+        w, support = _checked(w, "w"), _checked(support, "support", 3)
+        if any(a is None for a in (*rays, *data)):
+            raise TypeError(f"{names}, {ray_names} must be arrays, not None")
+        n_rays = int(np.prod(data[0].shape))
+        if any(int(np.prod(a.shape)) != 3 * n_rays for a in rays) or any(int(np.prod(a.shape)) != n_rays for a in data) \
+                or (w is not None and int(np.prod(w.shape)) != n_rays):
             raise ValueError(f"{names} and w hold one value per ray, {ray_names} three")
-        ts = None if support is None else _on_device(torch.as_tensor(support) != 0, torch.uint8, dev)
-        if ts is not None and tuple(ts.shape) != (nz, ny, nx):
+        if support is not None and tuple(support.shape) != (nz, ny, nx):
             raise ValueError(f"support must be [nz, ny, nx] = {(nz, ny, nx)}")
+        dev, stream = _device_and_stream()
+        rays = [_on_device(a, torch.float64, dev, name).reshape(-1, 3) for a, name in zip(rays, rays_names)]
+        data = [_on_device(a, torch.float64, dev, name).reshape(-1) for a, name in zip(data, data_names)]
+        tw = _on_device(w, torch.float64, dev, "w")
+        ts = _on_device(support, torch.uint8, dev, "support", 3, nonzero=True)
         max_iter = tomography.DEFAULT_MAX_ITER if max_iter is None else int(max_iter)
         tomography.check_arguments(dims, _f64x3(spacing, scalar_ok=True), origin, n_rays, lam, tol, max_iter)
         f = torch.empty((nz, ny, nx), dtype=torch.float64, device=dev)
