@@ -611,6 +611,28 @@ int photon_selftest_normal_range_math(int n, const float *a, const float *b, flo
  * keys, the library's own stable radix sort: photon_amd/csrc/photon_sort.hip); tests hold it against numpy's stable argsort. */
 int photon_selftest_morton_order(const float *x, const float *y, long long n_total, long long first, long long n, int *perm_out);
 
+/* Test hook: make device allocations of the library fail, without memory pressure.  Every block of the library is asked
+ * for in one place; a REQUEST is one such asking (a block of the cache, or a block outside it), numbered per process.
+ * Requests number first .. first + count - 1, counted from this call (1 = the next one), fail: count = 1 one request,
+ * LLONG_MAX "the device stays full" until disarmed; first = 0 disarms.  first_attempt_only = 0: the request returns
+ * hipErrorOutOfMemory, the runtime is not called and no cached block is handed out.  first_attempt_only = 1: the request
+ * passes the cache by and only its first hipMalloc is replaced by hipErrorOutOfMemory -- the library then empties its block
+ * cache and asks the runtime again, for real.  Disarmed the hook costs one atomic increment per request.  Thread safe.
+ * Returns 0, or 1 for first < 0 or count < 1 (message on stderr). */
+int photon_selftest_fail_alloc(long long first, long long count, int first_attempt_only);
+
+/* Test hook: the allocation counters of this process.  outstanding: blocks handed out and not yet given back, of the cache
+ * and outside it alike; idle: what the block cache holds. */
+typedef struct photon_alloc_stats {
+    long long requests;                 /* requests so far */
+    long long injected_failures;        /* requests photon_selftest_fail_alloc made fail (either mode) */
+    long long oom_retries;              /* times an allocation found the device full, emptied the cache and asked again */
+    long long retry_blocks_returned;    /* cached blocks those retries handed back to the runtime */
+    long long idle_blocks, idle_bytes;
+    long long outstanding_blocks, outstanding_bytes;
+} photon_alloc_stats_t;
+int photon_selftest_alloc_stats(photon_alloc_stats_t *out);
+
 /* Device-to-device float4 streaming copy of `bytes` bytes, `reps` times: read + write rate in GB/s -- the HBM rate a
  * trivial kernel reaches on this GPU, which bench.py prints next to the 8 TB/s specification. */
 int photon_measure_copy_gbs(size_t bytes, int reps, double *gbs_out);

@@ -383,7 +383,8 @@ int render_on_one_device(const CallArgs &a, const CallSettings &cs, float *image
     photon_volume *vol = nullptr;                                       // the device's cached volume: not the call's to free
     const long long num_particles = a.lsp->num_particles;
     if (const int rc = setup_scene(a, cs, 0, num_particles, nullptr, &scene.p, &vol, &t.scene)) {
-        if (!scene.p) fprintf(stderr, "photon: scene upload failed; image left untouched\n");     // (a volume says why itself)
+        // (a volume says why itself, but not what becomes of the image)
+        fprintf(stderr, "photon: %s failed; image left untouched\n", scene.p ? "the density volume" : "scene upload");
         return rc;
     }
     t.volume = Clock::now();

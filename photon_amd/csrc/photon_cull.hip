@@ -279,8 +279,13 @@ int photon::ensure_live_sources(photon_scene *s) {
     const size_t ns = (size_t)s->dev.num_sources;
     if (!s->source_cull.ok || ns == 0) return 0;
     DeviceScope on_scene_device(s->device);
+    // The cull only saves work: without room for it every source is launched, and the trace is as right as with it.
+    const auto skipped = [] {
+        fprintf(stderr, "photon: no device memory for the source cull: it is skipped and every source is launched\n");
+        return 0;
+    };
     PoolBuffer<unsigned char> d_off;
-    PH_CHECK(d_off.alloc(ns));
+    if (d_off.alloc(ns) != hipSuccess) return skipped();
     hipLaunchKernelGGL(source_cull_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, nullptr, s->source_cull, s->dev.sx, s->dev.sy, s->dev.sz,
                        (long long)ns, d_off.p);
     std::vector<unsigned char> off(ns);
@@ -293,9 +298,11 @@ int photon::ensure_live_sources(photon_scene *s) {
         if (!off[i]) keep.push_back((int)i);
     if (keep.size() == ns) return 0;
     if (keep.empty()) keep.push_back(0);                                // a launch of zero rays is nobody's friend
-    int *d_keep = nullptr;
-    PH_TRY(scene_block(s, keep.size() * sizeof(int), &d_keep));
+    PoolBuffer<char> list;                                              // the scene's once it is filled
+    if (list.alloc(keep.size() * sizeof(int)) != hipSuccess) return skipped();
+    int *d_keep = reinterpret_cast<int *>(list.p);
     PH_CHECK(hipMemcpy(d_keep, keep.data(), keep.size() * sizeof(int), hipMemcpyHostToDevice));
+    s->allocs.push_back(std::move(list));
     s->d_live_sources = d_keep;
     s->live_sources = std::move(keep);
     s->live_sources_known = true;

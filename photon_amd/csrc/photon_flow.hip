@@ -152,6 +152,10 @@ int photon_sources_piv_advected(uint64_t seed, long long n, const double box_min
         fprintf(stderr, "photon: photon_sources_piv_advected: bad arguments\n");
         return 1;
     }
+    const auto alloc_failed = [](const char *what) {
+        fprintf(stderr, "photon: photon_sources_piv_advected: device allocation failed (%s)\n", what);
+        return 3;
+    };
     return guarded("photon_sources_piv_advected", [&]() -> int {
         std::unique_ptr<photon_sources> src;
         PH_TRY(sources_alloc(n, &src));
@@ -168,13 +172,13 @@ int photon_sources_piv_advected(uint64_t seed, long long n, const double box_min
         DeviceBuffer<double> d_cdf, d_world;
         DeviceBuffer<float4> d_partial;
         if (n_diameters > 0) {
-            if (d_cdf.alloc((size_t)n_diameters) != hipSuccess) return 3;
+            if (d_cdf.alloc((size_t)n_diameters) != hipSuccess) return alloc_failed("diameter table");
             if (hipMemcpy(d_cdf.p, diameter_cdf, n_diameters * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
         }
         std::vector<float4> partial(blocks);
         if (n) {
-            if (d_partial.alloc(blocks) != hipSuccess) return 3;
-            if (world_xyz && d_world.alloc((size_t)n * 3) != hipSuccess) return 3;
+            if (d_partial.alloc(blocks) != hipSuccess) return alloc_failed("extent partials");
+            if (world_xyz && d_world.alloc((size_t)n * 3) != hipSuccess) return alloc_failed("world positions");
             hipLaunchKernelGGL(sources_piv_advected_kernel, dim3(blocks), dim3(kBlock), 0, 0, (unsigned long long)seed, n, f, d_cdf.p,
                                g, h, run_steps, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p, d_world.p, d_partial.p);
             if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;

@@ -11,6 +11,10 @@
 // defined start is cleared where it is allocated or used.  Held by tests/test_dirty_memory_gpu.py (solvers on recycled blocks).
 #include "photon_pool.hpp"
 
+#include "../../include/parallel_ray_tracing.h"
+
+#include <atomic>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -29,7 +33,8 @@ struct DevicePool {
     std::mutex lock;
     std::multimap<PoolKey, void *> idle;        // ordered by (device, size): a device's largest block is the last of its run
     std::map<void *, PoolKey> live;
-    size_t idle_bytes = 0;
+    std::map<void *, size_t> direct;            // blocks of device_malloc that are not the cache's, until device_free
+    size_t idle_bytes = 0, live_bytes = 0, direct_bytes = 0;
 };
 DevicePool &device_pool() { static DevicePool *p = new DevicePool; return *p; }      // never destroyed: the runtime may be gone by then
 size_t pool_cap_bytes() {
@@ -49,9 +54,40 @@ std::multimap<PoolKey, void *>::iterator largest_idle(DevicePool &p) {
     return best;
 }
 
-}  // namespace
+// ---------------------------------------------------------------------------------------------
+// failure injection (photon_selftest_fail_alloc): a REQUEST is one pool_malloc, or one device_malloc that does not come from
+// pool_malloc.  Requests are numbered per process; those whose number lies in [fail_first, fail_last] fail.  Disarmed
+// (fail_first = 0) a request pays the increment and one relaxed load.  All of it is atomics: it may be armed while the
+// worker threads of a PHOTON_DEVICES call allocate.
+// ---------------------------------------------------------------------------------------------
+std::atomic<long long> g_requests{0}, g_injected{0}, g_retries{0}, g_retry_blocks{0};
+std::atomic<long long> g_fail_first{0}, g_fail_last{0};
+std::atomic<int> g_fail_first_attempt_only{0};
 
-void pool_trim(size_t keep_bytes) {                              // caller holds no lock
+enum class Inject { none, whole_request, first_attempt };
+Inject next_request() {
+    const long long n = g_requests.fetch_add(1, std::memory_order_relaxed) + 1;
+    const long long first = g_fail_first.load(std::memory_order_relaxed);
+    if (first == 0 || n < first || n > g_fail_last.load(std::memory_order_relaxed)) return Inject::none;
+    g_injected.fetch_add(1, std::memory_order_relaxed);
+    return g_fail_first_attempt_only.load(std::memory_order_relaxed) ? Inject::first_attempt : Inject::whole_request;
+}
+
+size_t trim(size_t keep_bytes);
+
+// hipMalloc, and once more after the cache has been emptied when the device is out of memory
+hipError_t malloc_with_retry(void **out, size_t bytes, bool fail_first_attempt) {
+    hipError_t e = fail_first_attempt ? hipErrorOutOfMemory : hipMalloc(out, bytes ? bytes : 1);
+    if (e == hipErrorOutOfMemory) {
+        if (!fail_first_attempt) (void)hipGetLastError();
+        g_retries.fetch_add(1, std::memory_order_relaxed);
+        g_retry_blocks.fetch_add((long long)trim(0), std::memory_order_relaxed);
+        e = hipMalloc(out, bytes ? bytes : 1);
+    }
+    return e;
+}
+
+size_t trim(size_t keep_bytes) {                                 // caller holds no lock; returns the blocks handed back
     DevicePool &p = device_pool();
     std::vector<void *> victims;
     {
@@ -64,16 +100,35 @@ void pool_trim(size_t keep_bytes) {                              // caller holds
         }
     }
     for (void *v : victims) (void)hipFree(v);                   // outside the lock: hipFree synchronises the device
+    return victims.size();
 }
 
+}  // namespace
+
+void pool_trim(size_t keep_bytes) { (void)trim(keep_bytes); }
+
 hipError_t device_malloc(void **out, size_t bytes) {
-    hipError_t e = hipMalloc(out, bytes ? bytes : 1);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        pool_trim(0);
-        e = hipMalloc(out, bytes ? bytes : 1);
+    const Inject inject = next_request();
+    if (inject == Inject::whole_request) { *out = nullptr; return hipErrorOutOfMemory; }
+    const hipError_t e = malloc_with_retry(out, bytes, inject == Inject::first_attempt);
+    if (e == hipSuccess) {
+        DevicePool &p = device_pool();
+        std::lock_guard<std::mutex> g(p.lock);
+        p.direct[*out] = bytes ? bytes : 1;
+        p.direct_bytes += bytes ? bytes : 1;
     }
     return e;
+}
+
+void device_free(void *ptr) {
+    if (!ptr) return;
+    {
+        DevicePool &p = device_pool();
+        std::lock_guard<std::mutex> g(p.lock);
+        auto it = p.direct.find(ptr);
+        if (it != p.direct.end()) { p.direct_bytes -= it->second; p.direct.erase(it); }
+    }
+    (void)hipFree(ptr);                                         // waits for the device by itself
 }
 
 hipError_t device_zero(void *p, size_t bytes) {
@@ -87,7 +142,9 @@ hipError_t pool_malloc(void **out, size_t bytes) {
     int device = 0;
     (void)hipGetDevice(&device);
     DevicePool &p = device_pool();
-    {
+    const Inject inject = next_request();
+    if (inject == Inject::whole_request) { *out = nullptr; return hipErrorOutOfMemory; }
+    if (inject == Inject::none) {                               // first_attempt: past the cache, to the allocation that "fails"
         std::lock_guard<std::mutex> g(p.lock);
         auto it = p.idle.find(PoolKey{device, bytes});
         if (it != p.idle.end()) {
@@ -95,11 +152,12 @@ hipError_t pool_malloc(void **out, size_t bytes) {
             p.idle.erase(it);
             p.idle_bytes -= bytes;
             p.live[*out] = PoolKey{device, bytes};
+            p.live_bytes += bytes;
             return hipSuccess;
         }
     }
-    const hipError_t e = device_malloc(out, bytes);
-    if (e == hipSuccess) { std::lock_guard<std::mutex> g(p.lock); p.live[*out] = PoolKey{device, bytes}; }
+    const hipError_t e = malloc_with_retry(out, bytes, inject == Inject::first_attempt);
+    if (e == hipSuccess) { std::lock_guard<std::mutex> g(p.lock); p.live[*out] = PoolKey{device, bytes}; p.live_bytes += bytes; }
     return e;
 }
 
@@ -113,6 +171,7 @@ void pool_free(void *ptr) {
         if (it != p.live.end()) {
             const PoolKey k = it->second;
             p.live.erase(it);
+            p.live_bytes -= k.bytes;
             if (k.bytes <= pool_cap_bytes()) { p.idle.emplace(k, ptr); p.idle_bytes += k.bytes; keep = true; }
         }
         over = p.idle_bytes > pool_cap_bytes();                 // decided under the lock
@@ -158,3 +217,34 @@ bool peer_access(int dev, int peer) {
 }  // namespace photon
 
 extern "C" void photon_trim_caches(void) { photon::pool_trim(0); }
+
+extern "C" int photon_selftest_fail_alloc(long long first, long long count, int first_attempt_only) {
+    using namespace photon;
+    if (first < 0 || (first > 0 && count < 1)) {
+        fprintf(stderr, "photon: photon_selftest_fail_alloc: bad arguments\n");
+        return 1;
+    }
+    g_fail_first.store(0, std::memory_order_relaxed);           // disarmed while the range changes
+    if (first == 0) return 0;
+    const long long from = g_requests.load(std::memory_order_relaxed) + first;
+    g_fail_last.store(count - 1 > LLONG_MAX - from ? LLONG_MAX : from + count - 1, std::memory_order_relaxed);
+    g_fail_first_attempt_only.store(first_attempt_only != 0, std::memory_order_relaxed);
+    g_fail_first.store(from, std::memory_order_relaxed);
+    return 0;
+}
+
+extern "C" int photon_selftest_alloc_stats(photon_alloc_stats_t *out) {
+    using namespace photon;
+    if (!out) return 1;
+    out->requests = g_requests.load(std::memory_order_relaxed);
+    out->injected_failures = g_injected.load(std::memory_order_relaxed);
+    out->oom_retries = g_retries.load(std::memory_order_relaxed);
+    out->retry_blocks_returned = g_retry_blocks.load(std::memory_order_relaxed);
+    DevicePool &p = device_pool();
+    std::lock_guard<std::mutex> g(p.lock);
+    out->idle_blocks = (long long)p.idle.size();
+    out->idle_bytes = (long long)p.idle_bytes;
+    out->outstanding_blocks = (long long)(p.live.size() + p.direct.size());
+    out->outstanding_bytes = (long long)(p.live_bytes + p.direct_bytes);
+    return 0;
+}

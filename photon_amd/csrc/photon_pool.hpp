@@ -19,6 +19,8 @@ void pool_trim(size_t keep_bytes);
 // on hipErrorOutOfMemory the cache is emptied and the call repeated once -- what the cache holds must never be the
 // reason another allocation of this library fails.
 hipError_t device_malloc(void **out, size_t bytes);
+// give such a block back to the runtime (hipFree waits for the device by itself)
+void device_free(void *ptr);
 
 // Zero `bytes` at `p` on the current device, COMPLETE when the call returns.  hipMemset is not: it queues a fill kernel on
 // the null stream and returns (measured: 9 us, with the fill still 200 ms away behind a full chip), and work launched
@@ -32,7 +34,7 @@ hipError_t device_zero(void *p, size_t bytes);
 // go of the old block and takes one of exactly n elements (one element for n = 0: a valid address); reserve(n) keeps a block
 // that already holds n.  Neither waits for the device: whoever regrows a block that kernels may still use waits first
 // (photon_internal.hpp, scene_reserve).
-// An allocation outside the cache (hipFree waits for the device by itself):
+// An allocation outside the cache (device_free waits for the device by itself):
 template <typename T>
 struct DeviceBuffer {
     T *p = nullptr;
@@ -41,7 +43,7 @@ struct DeviceBuffer {
     DeviceBuffer(DeviceBuffer &&o) noexcept : p(o.p), n(o.n) { o.p = nullptr; o.n = 0; }
     DeviceBuffer &operator=(DeviceBuffer &&o) noexcept { if (this != &o) { reset(); p = o.p; n = o.n; o.p = nullptr; o.n = 0; } return *this; }
     ~DeviceBuffer() { reset(); }
-    void reset() { if (p) (void)hipFree(p); p = nullptr; n = 0; }
+    void reset() { device_free(p); p = nullptr; n = 0; }
     hipError_t alloc(size_t count) {
         reset();
         const hipError_t e = device_malloc((void **)&p, (count ? count : 1) * sizeof(T));

@@ -184,23 +184,28 @@ int photon_sources_bos(const double *dot_x, const double *dot_y, int n_dots, con
         fprintf(stderr, "photon: photon_sources_bos: bad arguments\n");
         return 1;
     }
-    const long long n = (long long)n_dots * n_tmpl;
-    std::unique_ptr<photon_sources> src;
-    PH_TRY(sources_alloc(n, &src));
-    DeviceBuffer<double> d_in;                                          // dot_x | dot_y | tmpl_x | tmpl_y
-    if (d_in.alloc(2 * (size_t)n_dots + 2 * (size_t)n_tmpl) != hipSuccess) return 3;
-    double *d_dx = d_in.p, *d_dy = d_dx + n_dots, *d_tx = d_dx + 2 * (size_t)n_dots, *d_ty = d_tx + n_tmpl;
-    if ((n_dots && (hipMemcpy(d_dx, dot_x, n_dots * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(d_dy, dot_y, n_dots * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)) ||
-        hipMemcpy(d_tx, tmpl_x, n_tmpl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_ty, tmpl_y, n_tmpl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
-    if (n) {
-        hipLaunchKernelGGL(sources_bos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_dx, d_dy, (long long)n_dots,
-                           d_tx, d_ty, n_tmpl, z, radiance, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;
-    }
-    *out = src.release();
-    return 0;
+    return guarded("photon_sources_bos", [&]() -> int {
+        const long long n = (long long)n_dots * n_tmpl;
+        std::unique_ptr<photon_sources> src;
+        PH_TRY(sources_alloc(n, &src));
+        DeviceBuffer<double> d_in;                                          // dot_x | dot_y | tmpl_x | tmpl_y
+        if (d_in.alloc(2 * (size_t)n_dots + 2 * (size_t)n_tmpl) != hipSuccess) {
+            fprintf(stderr, "photon: photon_sources_bos: device allocation failed (dots and template)\n");
+            return 3;
+        }
+        double *d_dx = d_in.p, *d_dy = d_dx + n_dots, *d_tx = d_dx + 2 * (size_t)n_dots, *d_ty = d_tx + n_tmpl;
+        if ((n_dots && (hipMemcpy(d_dx, dot_x, n_dots * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+                        hipMemcpy(d_dy, dot_y, n_dots * sizeof(double), hipMemcpyHostToDevice) != hipSuccess)) ||
+            hipMemcpy(d_tx, tmpl_x, n_tmpl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess ||
+            hipMemcpy(d_ty, tmpl_y, n_tmpl * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
+        if (n) {
+            hipLaunchKernelGGL(sources_bos_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, d_dx, d_dy, (long long)n_dots,
+                               d_tx, d_ty, n_tmpl, z, radiance, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p);
+            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;
+        }
+        *out = src.release();
+        return 0;
+    });
 }
 
 int photon_sources_piv(uint64_t seed, long long n, const double box_min[3], const double box_max[3], double z_object,
@@ -211,25 +216,30 @@ int photon_sources_piv(uint64_t seed, long long n, const double box_min[3], cons
         fprintf(stderr, "photon: photon_sources_piv: bad arguments\n");
         return 1;
     }
-    std::unique_ptr<photon_sources> src;
-    PH_TRY(sources_alloc(n, &src));
-    const PivFieldDev f = piv_field_setup(box_min, box_max, z_object, beam_fwhm, irradiance_constant, n_diameters);
-    DeviceBuffer<double> d_cdf;
-    if (n_diameters > 0) {
-        if (d_cdf.alloc((size_t)n_diameters) != hipSuccess) return 3;
-        if (hipMemcpy(d_cdf.p, diameter_cdf, n_diameters * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
-    }
-    if (n) {
-        hipLaunchKernelGGL(sources_piv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (unsigned long long)seed, n, f,
-                           d_cdf.p, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p);
-        if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;
-    }
-    {   // the box the particles were drawn from (sources_piv_kernel: X, Y uniform in the box, z = Z + z_object)
-        const double ax = std::max(fabs(box_min[0]), fabs(box_max[0])), ay = std::max(fabs(box_min[1]), fabs(box_max[1]));
-        sources_set_extent(src.get(), ax, ay, std::min(box_min[2], box_max[2]) + z_object, std::max(box_min[2], box_max[2]) + z_object);
-    }
-    *out = src.release();
-    return 0;
+    return guarded("photon_sources_piv", [&]() -> int {
+        std::unique_ptr<photon_sources> src;
+        PH_TRY(sources_alloc(n, &src));
+        const PivFieldDev f = piv_field_setup(box_min, box_max, z_object, beam_fwhm, irradiance_constant, n_diameters);
+        DeviceBuffer<double> d_cdf;
+        if (n_diameters > 0) {
+            if (d_cdf.alloc((size_t)n_diameters) != hipSuccess) {
+                fprintf(stderr, "photon: photon_sources_piv: device allocation failed (diameter table)\n");
+                return 3;
+            }
+            if (hipMemcpy(d_cdf.p, diameter_cdf, n_diameters * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) return 4;
+        }
+        if (n) {
+            hipLaunchKernelGGL(sources_piv_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, (unsigned long long)seed, n, f,
+                               d_cdf.p, src->x.p, src->y.p, src->z.p, src->radiance.p, src->diameter_index.p);
+            if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) return 4;
+        }
+        {   // the box the particles were drawn from (sources_piv_kernel: X, Y uniform in the box, z = Z + z_object)
+            const double ax = std::max(fabs(box_min[0]), fabs(box_max[0])), ay = std::max(fabs(box_min[1]), fabs(box_max[1]));
+            sources_set_extent(src.get(), ax, ay, std::min(box_min[2], box_max[2]) + z_object, std::max(box_min[2], box_max[2]) + z_object);
+        }
+        *out = src.release();
+        return 0;
+    });
 }
 
 long long photon_sources_count(const photon_sources_t *src) { return src ? src->n : -1; }
@@ -319,6 +329,7 @@ static int scene_create_impl(float lens_pitch, float image_distance, const scatt
     const size_t ns = (size_t)n_sources;
     d.num_sources = (int)ns;
     if (generated) {                                    // already in HBM: device-to-device, no host arrays
+        s->launched = true;                             // copies in flight: a failure below must not hand their blocks to the cache unwaited
         PH_TRY(copy_device<float>(s, generated->x.p, ns, &d.sx));
         PH_TRY(copy_device<float>(s, generated->y.p, ns, &d.sy));
         PH_TRY(copy_device<float>(s, generated->z.p, ns, &d.sz));

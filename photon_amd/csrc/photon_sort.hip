@@ -222,7 +222,10 @@ extern "C" int photon_selftest_morton_order(const float *x, const float *y, long
     photon_sort_scratch sc;
     if (dx.alloc((size_t)n_total) != hipSuccess || dy.alloc((size_t)n_total) != hipSuccess || dp.alloc((size_t)n) != hipSuccess ||
         hipMemcpy(dx.p, x, (size_t)n_total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(dy.p, y, (size_t)n_total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) return 1;
+        hipMemcpy(dy.p, y, (size_t)n_total * sizeof(float), hipMemcpyHostToDevice) != hipSuccess) {
+        fprintf(stderr, "photon: photon_selftest_morton_order: device allocation or upload failed\n");
+        return 1;
+    }
     int rc = photon_morton_order(dx.p, dy.p, (int)first, n, dp.p, nullptr, &sc);
     if (!rc) rc = hipMemcpy(perm_out, dp.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess ? 0 : 1;      // waits for the null stream
     (void)hipDeviceSynchronize();

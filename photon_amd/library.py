@@ -54,6 +54,11 @@ class photon_tomo_stats_t(_Stats):
                 ("rays_used", ctypes.c_longlong), ("residual", ctypes.c_double)]
 
 
+class photon_alloc_stats_t(_Stats):
+    _fields_ = [(n, ctypes.c_longlong) for n in ("requests", "injected_failures", "oom_retries", "retry_blocks_returned", "idle_blocks",
+                                                 "idle_bytes", "outstanding_blocks", "outstanding_bytes")]
+
+
 class photon_march_profile_t(ctypes.Structure):
     _fields_ = [("struct_size", ctypes.c_uint32), ("launches", ctypes.c_uint32), ("waves", ctypes.c_uint32),
                 ("span_ms", ctypes.c_float), ("start_mean_ms", ctypes.c_float), ("start_max_ms", ctypes.c_float),
@@ -144,6 +149,8 @@ def _signatures():
         "photon_measure_copy_gbs": (ci, [sz, ci, P(cd)]),
         "photon_selftest_normal_range_math": (ci, [ci] + [vp] * 5),
         "photon_selftest_morton_order": (ci, [vp, vp, ll, ll, ll, vp]),
+        "photon_selftest_fail_alloc": (ci, [ll, ll, ci]),
+        "photon_selftest_alloc_stats": (ci, [P(photon_alloc_stats_t)]),
         # section 5: image-pair cross-correlation on the device
         "photon_piv_correlate": (ci, [vp, vp] + [ci] * 5 + [vp] * 4 + [P(ci), P(ci), vp]),
         # section 6: gradient-field integration on the device
@@ -505,6 +512,16 @@ class PhotonLibrary:
         r2 = np.empty(n, np.float32)
         self._call("photon_rand_table", n, _ptr(r1), _ptr(r2))
         return r1, r2
+
+    def fail_alloc(self, first: int, count: int = 1, first_attempt_only: bool = False):
+        """photon_selftest_fail_alloc: device allocation requests first .. first + count - 1 from now fail (0 disarms)."""
+        self._call("photon_selftest_fail_alloc", int(first), int(count), int(bool(first_attempt_only)))
+
+    def alloc_stats(self) -> dict:
+        """photon_selftest_alloc_stats: requests, injected failures, retries, cached and outstanding blocks of this process."""
+        st = photon_alloc_stats_t()
+        self._call("photon_selftest_alloc_stats", ctypes.byref(st))
+        return st.as_dict()
 
     def morton_order(self, x, y, first: int = 0, n: Optional[int] = None):
         """photon_selftest_morton_order: the spatial order of sources first .. first + n - 1, as the device computes it."""

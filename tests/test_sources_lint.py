@@ -38,10 +38,10 @@ def test_no_host_side_device_to_device_hipmemcpy():
     assert not offenders, "host-asynchronous device-to-device hipMemcpy on the null stream:\n" + "\n".join(offenders)
 
 
-def _calls_outside_the_pool(names):
+def _calls_outside_the_pool(names, pool=("photon_pool.hip", "photon_pool.hpp")):
     offenders = []
     for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))):
-        if os.path.basename(path) in ("photon_pool.hip", "photon_pool.hpp"):
+        if os.path.basename(path) in pool:
             continue
         for no, code in code_lines(path):
             if re.search(r"\b(" + "|".join(names) + r")\s*\(", code):
@@ -57,11 +57,43 @@ def test_no_hipmalloc_or_hipfree_outside_the_pool():
     assert not offenders, "raw hipMalloc / hipFree outside photon_pool.*:\n" + "\n".join(offenders)
 
 
+def test_hipmalloc_and_hipfree_are_in_photon_pool_hip_alone():
+    """The header's owners release through device_free and pool_free: every block that is handed out or given back passes the
+    counters of photon_selftest_alloc_stats (outstanding blocks) and the failure hook of photon_selftest_fail_alloc, which
+    tests/test_alloc_failures_gpu.py relies on."""
+    offenders = _calls_outside_the_pool(["hipMalloc", "hipFree"], pool=("photon_pool.hip",))
+    assert not offenders, "raw hipMalloc / hipFree outside photon_pool.hip:\n" + "\n".join(offenders)
+
+
 def test_no_pool_malloc_or_pool_free_outside_the_pool():
     """The same for blocks of the cache: pool_malloc and pool_free are PoolBuffer's business.  A block that somebody frees
     by hand is a block that leaks on the return path somebody forgot."""
     offenders = _calls_outside_the_pool(["pool_malloc", "pool_free"])
     assert not offenders, "pool_malloc / pool_free outside photon_pool.*:\n" + "\n".join(offenders)
+
+
+ALLOCATION_SITE = r"\.alloc\(|\.reserve\(|\bscene_reserve\(|\bscene_block\(|\bdevice_malloc\("
+
+
+def test_every_allocation_site_is_in_the_table_of_failed_allocations():
+    """DESIGN.md section 4.3v lists, site by site, the case of tests/alloc_failure_cases.py that fails every allocation of the
+    library (and the few lines the same search finds that are no device allocation).  Per source file the table's rows
+    (their `n` column) add up to what the search finds: a new allocation site without a row fails here, and its row asks
+    for a case."""
+    found = {}
+    for path in sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))):
+        n = sum(len(re.findall(ALLOCATION_SITE, code)) for _, code in code_lines(path))
+        if n:
+            found[os.path.basename(path)] = n
+    design = open(os.path.join(os.path.dirname(os.path.dirname(CSRC)), "DESIGN.md"), encoding="utf-8").read()
+    section = design.split("### 4.3v ", 1)[1].split("\n### ", 1)[0]
+    listed, cases = {}, set()
+    for row in re.findall(r"^\| `(photon_\w+\.h(?:ip|pp))` \| ([^|]+) \| (\d+) \| ([^|]+) \|$", section, flags=re.M):
+        listed[row[0]] = listed.get(row[0], 0) + int(row[2])
+        cases.update(re.findall(r"`(\w+)`", row[3]))
+    assert found == listed, {f: (found.get(f), listed.get(f)) for f in set(found) | set(listed) if found.get(f) != listed.get(f)}
+    import alloc_failure_cases as afc
+    assert cases and cases <= set(afc.CASES), sorted(cases - set(afc.CASES))
 
 
 def test_the_build_knows_every_header():
