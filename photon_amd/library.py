@@ -15,7 +15,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 
@@ -315,10 +315,16 @@ def _on_device(x, dtype, dev, name: str = "array", ndim=None, nonzero: bool = Fa
     return torch.from_numpy(c).to(device=dev)
 
 
+def _current_device():
+    """torch's current device: where every wrapper that allocates its own outputs puts them."""
+    import torch
+    return torch.device("cuda", torch.cuda.current_device())
+
+
 def _device_and_stream():
     """torch's current device and the raw handle of its current stream: where every pipeline allocates and runs."""
     import torch
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _current_device()
     return dev, torch.cuda.current_stream(dev).cuda_stream
 
 
@@ -346,11 +352,17 @@ def _checked_pair(im1, im2, mask=None):
     return a, b, _checked_mask(mask, a.shape)
 
 
-def _image_pair(im1, im2, mask=None):
-    """(dev, stream, a, b, h, w): the two images as contiguous f32 device tensors [h, w] on the current device.  mask: the
-    driver's mask=, checked here with the images (_checked_pair) and brought over later, by _mask_pair."""
+def _image_pair(im1, im2):
+    """(dev, stream, a, b, h, w): the two images, checked (_checked_pair), as contiguous f32 device tensors [h, w] on the
+    current device."""
+    a, b, _ = _checked_pair(im1, im2)
+    return _pair_on_device(a, b)
+
+
+def _pair_on_device(a, b):
+    """_image_pair's device half, for the two images as _checked_pair returned them: the drivers with a mask= or a
+    weighting= raise their other refusals between the two."""
     import torch
-    a, b, _ = _checked_pair(im1, im2, mask)
     dev, stream = _device_and_stream()
     a, b = _on_device(a, torch.float32, dev, "im1", 2), _on_device(b, torch.float32, dev, "im2", 2)
     return (dev, stream, a, b, *a.shape)
@@ -374,16 +386,41 @@ def _checked_weighting(weighting):
     return a if isinstance(a, np.ndarray) else a.detach().cpu().numpy()
 
 
-def _weight_tables(weighting, wins, dev):
-    """The drivers' weighting= (piv_weighting.resolve: None, "gaussian", ("gaussian", sigma) or an array [win, win]) for the
-    window sizes `wins`: None, or one contiguous f32 device tensor [win, win] per entry of `wins`.  Every refusal is
-    raised before the first table is copied."""
+def _weight_tables(tables, dev):
+    """The drivers' weighting= on the device: `tables` {win: f32 table [win, win]}, what piv_weighting.resolve made of it for
+    every window size (_Correlator), as {win: contiguous f32 device tensor [win, win]}; None stays None."""
     import torch
-    from . import piv_weighting as pw
-    if weighting is None:
-        return None
-    tables = [pw.resolve(_checked_weighting(weighting), win) for win in wins]
-    return [_on_device(t, torch.float32, dev, "weighting", 2) for t in tables]
+    return None if tables is None else {win: _on_device(t, torch.float32, dev, "weighting", 2) for win, t in tables.items()}
+
+
+def _nan_where_masked_out(x, status):
+    """The device tensor x [n_rows, n_cols, k] with NaN where status [n_rows, n_cols] has bit 16, the masked-out nodes
+    (piv_mask.fill_masked); queued on the current stream, nothing waits."""
+    import torch
+    return torch.where(((status & 16) != 0)[..., None], torch.full((), float("nan"), dtype=x.dtype, device=x.device), x)
+
+
+def _checked_passes(passes) -> int:
+    if int(passes) not in (1, 2):
+        raise ValueError(f"passes must be 1 or 2, not {passes}")
+    return int(passes)
+
+
+def _two_passes(correlate, passes: int, dev):
+    """What correlate and correlate_ensemble share behind their first pass.  correlate(d_offset_ptr) -> (vec, flg, ...), device
+    tensors: pass 1 without offsets; passes == 2: the normalised median test and the predictor on the host
+    (photon_amd.piv_correlation), then pass 2 with the integer window offsets.  Returns (vectors, flags, what the last pass
+    returned), the first two as numpy."""
+    import torch
+    from . import piv_correlation as pc
+    out = correlate(0)
+    vectors, flags = out[0].cpu().numpy(), out[1].cpu().numpy()
+    if passes == 2:
+        offsets = pc.predictor(vectors, flags, pc.normalized_median_test(vectors))
+        d_off = torch.from_numpy(offsets).to(dev)
+        out = correlate(d_off.data_ptr())
+        vectors, flags = out[0].cpu().numpy(), out[1].cpu().numpy()
+    return vectors, flags, out
 
 
 def _replace_masked(im, m):
@@ -393,6 +430,89 @@ def _replace_masked(im, m):
     hidden = m != 0
     free = torch.where(hidden, torch.zeros((), dtype=im.dtype, device=im.device), im)
     return torch.where(hidden, free.sum() / (im.numel() - hidden.sum()).clamp(min=1), im).contiguous()
+
+
+class _DeformSettings(NamedTuple):
+    """What the deformation chain takes besides its correlator: pass 0's radius (None: the correlator's default), the
+    iterations' radius, whether the smoothed field is the next predictor, and photon_piv_validate's eps and threshold.
+    The defaults are the drivers'."""
+    radius: Optional[int] = None
+    residual_radius: int = 4
+    smooth: bool = True
+    eps: float = 0.1
+    threshold: float = 2.0
+
+
+class _Correlator:
+    """What the drivers' method=, window_sigma=, diameter=, mask=, min_valid_fraction= and weighting= select, for the window
+    sizes `wins` a driver will correlate with, resolved in two steps.
+    The host step, the constructor, raises every refusal and touches no device: mask= and weighting= need "direct" and
+    exclude each other (piv_mask.check_method, piv_weighting.check_method), weighting= is one of piv_weighting.resolve's
+    forms with a table for every win, method is "direct" or "phase", min_valid_fraction lies in (0, 1].  The mask's planes
+    are checked with the images, by _checked_pair, before.
+    The device step, on_device, brings the masks (_mask_pair) and one weight table per win (_weight_tables) over and binds
+    the library.  After it, at(win, radius) answers with (a callable with piv_correlate's signature, the radius, the
+    argument check): "direct" is section 5, radius None = win // 2; with a mask section 17 with the two masks and
+    min_valid = ceil(min_valid_fraction win^2) bound; with weighting section 18 with win's table bound; "phase" is
+    section 13's mode 1 with window_sigma (None = win / 4) and diameter bound, radius None or win // 2 = win // 2 - 1."""
+
+    def __init__(self, wins, method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None,
+                 min_valid_fraction: float = 0.5, weighting=None):
+        from . import piv_mask
+        from . import piv_weighting as pw
+        piv_mask.check_method(method, mask)
+        pw.check_method(method, weighting, mask)
+        weighting = _checked_weighting(weighting)
+        if method not in ("direct", "phase"):
+            raise ValueError(f'method must be "direct" or "phase", not {method!r}')
+        self.method, self.window_sigma, self.diameter, self.mask = method, window_sigma, diameter, mask
+        self.min_valid = None if mask is None else {int(win): piv_mask.min_valid_for(win, min_valid_fraction) for win in wins}
+        self.tables = None if weighting is None else {int(win): pw.resolve(weighting, win) for win in wins}
+        self.lib = None
+
+    def on_device(self, lib, shape, dev):
+        """The device step for images of `shape` on `dev`; returns the correlator."""
+        self.lib = lib
+        if self.mask is not None:
+            self.mask = _mask_pair(self.mask, shape, dev)
+        self.tables = _weight_tables(self.tables, dev)
+        return self
+
+    def at(self, win: int, radius=None):
+        lib = self.lib
+        if self.method == "phase":
+            from . import piv_phase as pp
+            sigma, diameter = int(win) / 4.0 if self.window_sigma is None else float(self.window_sigma), self.diameter
+
+            def correlate(*args, **kwargs):
+                return lib.piv_correlate_phase(*args, mode=pp.MODE_PHASE, window_sigma=sigma, diameter=float(diameter), **kwargs)
+
+            def check(shape, win, step, radius):
+                pp.check_arguments(shape, win, step, radius, pp.MODE_PHASE, sigma, diameter)
+            return correlate, pp.default_radius(win, radius), check
+        correlate = lib.piv_correlate
+        if self.tables is not None:
+            table = self.tables[int(win)]
+
+            def correlate(d_im1_ptr, d_im2_ptr, width, height, win, step, radius, d_offset_ptr=0, planes=False, stream=0):
+                return lib.piv_correlate_weighted(d_im1_ptr, d_im2_ptr, table.data_ptr(), width, height, win, step, radius, d_offset_ptr,
+                                                  planes, stream)
+        elif self.mask is not None:
+            (m1, m2), min_valid = self.mask, self.min_valid[int(win)]
+
+            def correlate(d_im1_ptr, d_im2_ptr, width, height, win, step, radius, d_offset_ptr=0, planes=False, stream=0):
+                return lib.piv_correlate_masked(d_im1_ptr, d_im2_ptr, m1.data_ptr(), m2.data_ptr(), width, height, win, step, radius,
+                                                min_valid, d_offset_ptr, planes, False, stream)[:3]
+        from . import piv_correlation as pc
+        return correlate, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
+
+
+# the outputs of the window correlators as _grid_call takes them
+_VECTORS, _FLAGS = ((4,), "float32", True), ((), "int32", True)
+
+
+def _planes(radius: int, asked: bool):
+    return (2 * int(radius) + 1,) * 2, "float32", asked
 
 
 def bind_march_launch_plan(lib):
@@ -501,6 +621,21 @@ class PhotonLibrary:
         """One call of an entry point that returns 0 or an error code."""
         self._check(getattr(self.lib, entry)(*args), entry)
 
+    def _grid_call(self, entry: str, head, outputs, stream: int, offset=(), after_offset=()):
+        """An entry point that sizes its own window grid: the query with NULL outputs for (n_rows, n_cols), the outputs allocated
+        on the current device, then the launch on `stream`.  head: the arguments before d_offset; offset: (d_offset_ptr,), NULL
+        in the query, or () for an entry without one; after_offset: the arguments between it and the outputs.  outputs: per
+        output of the entry, in its order, (the shape after [n_rows, n_cols], the torch dtype's name, whether the caller asked
+        for it).  Returns the tuple of device tensors, None where not asked for, filled asynchronously."""
+        import torch
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        self._call(entry, *head, *[None] * len(offset), *after_offset, *[None] * len(outputs), ctypes.byref(rows), ctypes.byref(cols), None)
+        dev, grid = _current_device(), (rows.value, cols.value)
+        made = [torch.empty(grid + shape, dtype=getattr(torch, dtype), device=dev) if asked else None for shape, dtype, asked in outputs]
+        pointers = [None if t is None else _vp(t.data_ptr()) for t in made]
+        self._call(entry, *head, *[_vp(p) for p in offset], *after_offset, *pointers, None, None, _vp(stream))
+        return tuple(made)
+
     def version(self) -> str:
         return self.lib.photon_version().decode()
 
@@ -599,18 +734,8 @@ class PhotonLibrary:
         int32 [n][2] integer offsets, or 0.  Returns torch device tensors (vectors [n_rows, n_cols, 4] = dx, dy, peak,
         ratio; flags [n_rows, n_cols] int32; planes [n_rows, n_cols, 2R+1, 2R+1] or None), filled asynchronously on
         `stream`.  The definition: include/parallel_ray_tracing.h, section 5 (photon_amd.piv_correlation: host model)."""
-        import torch
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = ("photon_piv_correlate", _vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(radius))
-        self._call(*args, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
-        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
-        dev, _ = _device_and_stream()
-        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
-        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
-        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
-        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(pl.data_ptr()) if planes else None, None,
-                   None, _vp(stream))
-        return vectors, flags, pl
+        head = (_vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(radius))
+        return self._grid_call("photon_piv_correlate", head, (_VECTORS, _FLAGS, _planes(radius, planes)), stream, (d_offset_ptr,))
 
     def piv_correlate_phase(self, d_im1_ptr: int, d_im2_ptr: int, width: int, height: int, win: int, step: int, radius: int,
                             d_offset_ptr: int = 0, planes: bool = False, stream: int = 0, mode: int = 1, window_sigma: float = 0.0,
@@ -619,19 +744,9 @@ class PhotonLibrary:
         circular cross-correlation, mode 1 the phase correlation -- of windows weighted by a Gaussian of `window_sigma` px
         (0: none), with the spectral filter for particles of e^-2 diameter `diameter` px (0: none).  The definition:
         include/parallel_ray_tracing.h, section 13 (photon_amd.piv_phase: host models)."""
-        import torch
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = ("photon_piv_correlate_phase", _vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(radius))
-        how = (int(mode), float(window_sigma), float(diameter))
-        self._call(*args, None, *how, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
-        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
-        dev, _ = _device_and_stream()
-        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
-        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
-        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
-        self._call(*args, _vp(d_offset_ptr), *how, _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(pl.data_ptr()) if planes else None,
-                   None, None, _vp(stream))
-        return vectors, flags, pl
+        head = (_vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(radius))
+        return self._grid_call("photon_piv_correlate_phase", head, (_VECTORS, _FLAGS, _planes(radius, planes)), stream, (d_offset_ptr,),
+                               after_offset=(int(mode), float(window_sigma), float(diameter)))
 
     def piv_phase_tables(self, win: int, window_sigma: float, diameter: float):
         """photon_piv_phase_tables: the library's own (twiddles f32 [win/2, 2], window f32 [win], filter f32 [win]) for
@@ -650,19 +765,10 @@ class PhotonLibrary:
         filled asynchronously on `stream`; flags carry bit 16 (masked out: every output NaN) and bit 32 (partially masked:
         the overlap-normalised plane).  The definition: include/parallel_ray_tracing.h, section 17 (photon_amd.piv_mask:
         host model)."""
-        import torch
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = ("photon_piv_correlate_masked", _vp(d_im1_ptr), _vp(d_im2_ptr), _vp(d_mask1_ptr), _vp(d_mask2_ptr), int(width), int(height),
-                int(win), int(step), int(radius), int(min_valid))
-        self._call(*args, None, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
-        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
-        dev, _ = _device_and_stream()
-        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
-        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
-        val = torch.empty((r, c, 2), dtype=torch.int32, device=dev) if valid else None
-        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
-        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(val.data_ptr()) if valid else None,
-                   _vp(pl.data_ptr()) if planes else None, None, None, _vp(stream))
+        head = (_vp(d_im1_ptr), _vp(d_im2_ptr), _vp(d_mask1_ptr), _vp(d_mask2_ptr), int(width), int(height), int(win), int(step), int(radius),
+                int(min_valid))
+        outputs = (_VECTORS, _FLAGS, ((2,), "int32", valid), _planes(radius, planes))
+        vectors, flags, val, pl = self._grid_call("photon_piv_correlate_masked", head, outputs, stream, (d_offset_ptr,))
         return vectors, flags, pl, val
 
     def piv_correlate_weighted(self, d_im1_ptr: int, d_im2_ptr: int, d_weight_ptr: int, width: int, height: int, win: int, step: int,
@@ -671,19 +777,8 @@ class PhotonLibrary:
         [win, win] of weights on frame 1's window (row y, column x; entries that are not above 0 count as 0), one table for all
         windows.  A table of ones returns piv_correlate's bits.  The definition: include/parallel_ray_tracing.h, section 18
         (photon_amd.piv_weighting: host model and tables)."""
-        import torch
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = ("photon_piv_correlate_weighted", _vp(d_im1_ptr), _vp(d_im2_ptr), _vp(d_weight_ptr), int(width), int(height), int(win),
-                int(step), int(radius))
-        self._call(*args, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
-        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
-        dev, _ = _device_and_stream()
-        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
-        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
-        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
-        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(pl.data_ptr()) if planes else None, None,
-                   None, _vp(stream))
-        return vectors, flags, pl
+        head = (_vp(d_im1_ptr), _vp(d_im2_ptr), _vp(d_weight_ptr), int(width), int(height), int(win), int(step), int(radius))
+        return self._grid_call("photon_piv_correlate_weighted", head, (_VECTORS, _FLAGS, _planes(radius, planes)), stream, (d_offset_ptr,))
 
     def piv_window_weights(self, win: int, kind: str = "gaussian", sigma: Optional[float] = None) -> np.ndarray:
         """photon_piv_window_weights: the library's own table f32 [win, win] for section 18 ("uniform", or "gaussian" with
@@ -696,48 +791,6 @@ class PhotonLibrary:
         out = np.zeros((n, n), np.float32)
         self._call("photon_piv_window_weights", int(win), pw.KINDS[kind], float(pw.default_sigma(win) if sigma is None else sigma), _ptr(out))
         return out
-
-    def _correlator(self, method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5,
-                    weighting=None):
-        """What the drivers' method= selects: (a callable with piv_correlate's signature, the radius, the argument check).
-        "direct": section 5, radius None = win // 2.  "phase": section 13's mode 1 with window_sigma (None = win / 4) and
-        diameter bound, radius None or win // 2 = win // 2 - 1.  mask (what _mask_pair returned): section 17 with the two
-        masks and min_valid = ceil(min_valid_fraction win^2) bound, "direct" alone; None: what it returns without.
-        weighting (a device f32 table [win, win], what _weight_table returned): section 18 with the table bound, "direct"
-        without a mask alone; None: what it returns without."""
-        from . import piv_correlation as pc
-        from . import piv_phase as pp
-        if weighting is not None:
-            from . import piv_weighting as pw
-            pw.check_method(method, weighting, mask)
-            if method == "direct":
-                def correlate_weighted(d_im1_ptr, d_im2_ptr, width, height, win, step, radius, d_offset_ptr=0, planes=False, stream=0):
-                    return self.piv_correlate_weighted(d_im1_ptr, d_im2_ptr, weighting.data_ptr(), width, height, win, step, radius,
-                                                       d_offset_ptr, planes, stream)
-                return correlate_weighted, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
-        if mask is not None:
-            from . import piv_mask
-            piv_mask.check_method(method, mask)
-            if method == "direct":
-                m1, m2 = mask
-                min_valid = piv_mask.min_valid_for(win, min_valid_fraction)
-
-                def correlate_masked(d_im1_ptr, d_im2_ptr, width, height, win, step, radius, d_offset_ptr=0, planes=False, stream=0):
-                    return self.piv_correlate_masked(d_im1_ptr, d_im2_ptr, m1.data_ptr(), m2.data_ptr(), width, height, win, step, radius,
-                                                     min_valid, d_offset_ptr, planes, False, stream)[:3]
-                return correlate_masked, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
-        if method == "direct":
-            return self.piv_correlate, (int(win) // 2 if radius is None else int(radius)), pc.check_arguments
-        if method != "phase":
-            raise ValueError(f'method must be "direct" or "phase", not {method!r}')
-        sigma = int(win) / 4.0 if window_sigma is None else float(window_sigma)
-
-        def correlate(*args, **kwargs):
-            return self.piv_correlate_phase(*args, mode=pp.MODE_PHASE, window_sigma=sigma, diameter=float(diameter), **kwargs)
-
-        def check(shape, win, step, radius):
-            pp.check_arguments(shape, win, step, radius, pp.MODE_PHASE, sigma, diameter)
-        return correlate, pp.default_radius(win, radius), check
 
     def correlate(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1,
                   method: str = "direct", window_sigma: Optional[float] = None, diameter: float = 2.5, mask=None,
@@ -755,31 +808,16 @@ class PhotonLibrary:
         weighting: a weight per window pixel on frame 1's window, section 18 instead of section 5: "gaussian" (sigma = win /
         4), ("gaussian", sigma), or an array [win, win] of finite weights >= 0 (photon_amd.piv_weighting); "direct" without a
         mask alone.  A Gaussian window keeps the response to displacement wavelengths below the window size positive."""
-        import torch
-        from . import piv_correlation as pc
-        if int(passes) not in (1, 2):
-            raise ValueError(f"passes must be 1 or 2, not {passes}")
-        from . import piv_mask
-        from . import piv_weighting
-        piv_mask.check_method(method, mask)
-        piv_weighting.check_method(method, weighting, mask)
+        passes = _checked_passes(passes)
         im1, im2, _ = _checked_pair(im1, im2, mask)
-        weighting = _checked_weighting(weighting)
-        correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter)
-        if weighting is not None:
-            table, = _weight_tables(weighting, (win,), _device_and_stream()[0])
-            correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter, weighting=table)
-        dev, stream, a, b, h, w = _image_pair(im1, im2)
-        if mask is not None:
-            correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter, _mask_pair(mask, (h, w), dev), min_valid_fraction)
-        vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
-        vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
-        if int(passes) == 2:
-            offsets = pc.predictor(vectors, flags, pc.normalized_median_test(vectors))
-            d_off = torch.from_numpy(offsets).to(dev)
-            vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, d_off.data_ptr(), stream=stream)
-            vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
+        correlator = _Correlator((win,), method, window_sigma=window_sigma, diameter=diameter, mask=mask,
+                                 min_valid_fraction=min_valid_fraction, weighting=weighting)
+        dev, stream, a, b, h, w = _pair_on_device(im1, im2)
+        correlate, radius, _ = correlator.on_device(self, (h, w), dev).at(win, radius)
+        vectors, flags, _ = _two_passes(lambda off: correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, off, stream=stream),
+                                        passes, dev)
         if mask is not None and fill_masked:
+            from . import piv_mask
             vectors = piv_mask.fill_masked(vectors, flags, True).astype(np.float32)
         return vectors, flags
 
@@ -792,20 +830,9 @@ class PhotonLibrary:
         contributing pairs per window --, planes [n_rows, n_cols, 2R+1, 2R+1] or None) as piv_correlate does, filled
         asynchronously on `stream`.  The definition: include/parallel_ray_tracing.h, section 14 (photon_amd.piv_ensemble:
         host model)."""
-        import torch
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = ("photon_piv_correlate_ensemble", _vp(d_im1_ptr), _vp(d_im2_ptr), int(pair_stride), int(n_pairs), int(width), int(height),
-                int(win), int(step), int(radius))
-        self._call(*args, None, None, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
-        r, c, ns = rows.value, cols.value, 2 * int(radius) + 1
-        dev, _ = _device_and_stream()
-        vectors = torch.empty((r, c, 4), dtype=torch.float32, device=dev)
-        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
-        count = torch.empty((r, c), dtype=torch.int32, device=dev)
-        pl = torch.empty((r, c, ns, ns), dtype=torch.float32, device=dev) if planes else None
-        self._call(*args, _vp(d_offset_ptr), _vp(vectors.data_ptr()), _vp(flags.data_ptr()), _vp(count.data_ptr()),
-                   _vp(pl.data_ptr()) if planes else None, None, None, _vp(stream))
-        return vectors, flags, count, pl
+        head = (_vp(d_im1_ptr), _vp(d_im2_ptr), int(pair_stride), int(n_pairs), int(width), int(height), int(win), int(step), int(radius))
+        outputs = (_VECTORS, _FLAGS, ((), "int32", True), _planes(radius, planes))
+        return self._grid_call("photon_piv_correlate_ensemble", head, outputs, stream, (d_offset_ptr,))
 
     def correlate_ensemble(self, frames1, frames2=None, win: int = 32, step: int = 16, radius: Optional[int] = None, passes: int = 1):
         """One displacement field from a stack of image pairs (torch tensors on the device or numpy arrays): frames1 and
@@ -816,8 +843,7 @@ class PhotonLibrary:
         then a second ensemble pass with the integer window offsets."""
         import torch
         from . import piv_correlation as pc
-        if int(passes) not in (1, 2):
-            raise ValueError(f"passes must be 1 or 2, not {passes}")
+        passes = _checked_passes(passes)
         radius = int(win) // 2 if radius is None else int(radius)
         frames1, frames2 = _checked(frames1, "frames1", 3), _checked(frames2, "frames2", 3)      # [N, height, width]
         if frames1 is None:
@@ -837,14 +863,8 @@ class PhotonLibrary:
         pc.check_arguments((h, w), win, step, radius)
         if n < 1:
             raise ValueError("an ensemble needs at least one pair")
-        call = lambda off: self.piv_correlate_ensemble(a.data_ptr(), b_ptr, h * w, n, w, h, win, step, radius, off, stream=stream)  # noqa: E731
-        vec, flg, cnt, _ = call(0)
-        vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
-        if int(passes) == 2:
-            offsets = pc.predictor(vectors, flags, pc.normalized_median_test(vectors))
-            d_off = torch.from_numpy(offsets).to(dev)
-            vec, flg, cnt, _ = call(d_off.data_ptr())
-            vectors, flags = vec.cpu().numpy(), flg.cpu().numpy()
+        vectors, flags, (_, _, cnt, _) = _two_passes(
+            lambda off: self.piv_correlate_ensemble(a.data_ptr(), b_ptr, h * w, n, w, h, win, step, radius, off, stream=stream), passes, dev)
         return vectors, flags, cnt.cpu().numpy()
 
     # ---- image pre-processing: background removal, min-max filter (section 15) -----------------------------------------
@@ -937,120 +957,77 @@ class PhotonLibrary:
         src_step) at the window centres of the grid (dst_win, dst_step) of the same width x height image.  Returns a torch
         device tensor [dst_rows, dst_cols, 2], filled asynchronously on `stream`.  The definition:
         include/parallel_ray_tracing.h, section 16 (photon_amd.piv_multigrid: host models)."""
-        import torch
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = ("photon_piv_regrid", _vp(d_src_ptr), int(src_stride), int(src_rows), int(src_cols), int(src_win), int(src_step), int(width),
-                int(height), int(dst_win), int(dst_step))
-        self._call(*args, None, ctypes.byref(rows), ctypes.byref(cols), None)
-        dev, _ = _device_and_stream()
-        dst = torch.empty((rows.value, cols.value, 2), dtype=torch.float32, device=dev)
-        self._call(*args, _vp(dst.data_ptr()), None, None, _vp(stream))
-        return dst
+        head = (_vp(d_src_ptr), int(src_stride), int(src_rows), int(src_cols), int(src_win), int(src_step), int(width), int(height), int(dst_win),
+                int(dst_step))
+        return self._grid_call("photon_piv_regrid", head, (((2,), "float32", True),), stream)[0]
 
-    def _correlate_validated(self, correlate, a, b, win, step, radius, eps, threshold, dev, stream):
-        """Pass 0 of correlate_deform, all of correlation_predictor: correlate the device images a, b (`correlate`: what
-        _correlator returned), then validate with no predictor.  Returns (vec, field, smoothed, status), field and smoothed
-        [n_rows, n_cols, 2]."""
+    def _correlate_validated(self, correlate, a, b, grid, radius: int, settings: _DeformSettings, stream: int):
+        """Pass 0 of the deformation chain, all of correlation_predictor: correlate the device images a, b on the grid (win,
+        step) with `correlate` (what _Correlator.at returned) and `radius`, then validate with no predictor (settings: eps and
+        threshold).  Returns (vec, field, smoothed, status), field and smoothed [n_rows, n_cols, 2]."""
         import torch
         h, w = a.shape
-        vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, win, step, radius, stream=stream)
+        vec, flg, _ = correlate(a.data_ptr(), b.data_ptr(), w, h, *grid, radius, stream=stream)
         r, c = flg.shape
-        field, smoothed = (torch.empty((r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))
-        status = torch.empty((r, c), dtype=torch.int32, device=dev)
-        self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smoothed.data_ptr(), status.data_ptr(), eps, threshold,
-                          stream)
+        field, smoothed = (torch.empty((r, c, 2), dtype=torch.float32, device=a.device) for _ in range(2))
+        status = torch.empty((r, c), dtype=torch.int32, device=a.device)
+        self.piv_validate(0, vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smoothed.data_ptr(), status.data_ptr(),
+                          eps=settings.eps, threshold=settings.threshold, stream=stream)
         return vec, field, smoothed, status
 
-    def _deform_iterations(self, correlate, coef, warped, pred, win, step, iterations, residual_radius, smooth, eps, threshold, dev, stream):
-        """`iterations` >= 1 deformation iterations on the grid (win, step) from the predictor `pred` [n_rows, n_cols, 2]: warp
-        both frames (coef [2, h, w]: their coefficients; warped [2, h, w]: scratch) half-way, correlate with
-        `residual_radius`, validate with the predictor; the next predictor is the smoothed field, or the field itself.
-        Returns (vec, field, smoothed, status) of the last iteration."""
-        import torch
-        h, w = coef.shape[1:]
-        r, c = pred.shape[:2]
-        field, smoothed = (torch.empty((2, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))   # ping-pong: a predictor is no output
-        status = torch.empty((r, c), dtype=torch.int32, device=dev)
-        for k in range(int(iterations)):
-            cur = k & 1
-            self.piv_deform(coef[0].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, -0.5, warped[0].data_ptr(), stream)
-            self.piv_deform(coef[1].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, 0.5, warped[1].data_ptr(), stream)
-            vec, flg, _ = correlate(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, residual_radius, stream=stream)
-            self.piv_validate(pred.data_ptr(), vec.data_ptr(), flg.data_ptr(), r, c, field[cur].data_ptr(), smoothed[cur].data_ptr(),
-                              status.data_ptr(), eps, threshold, stream)
-            pred = (smoothed if smooth else field)[cur]
-        return vec, field[cur], smoothed[cur], status
-
-    def _deform_chain(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method, window_sigma,
-                      diameter, mask=None, min_valid_fraction=0.5, weighting=None):
-        """What correlate_deform (one level) and correlate_multigrid queue, arguments already checked: pass 0 and
-        iterations[0] deformation iterations at schedule[0]; per further level the last predictor regridded and iterations[l]
-        deformation iterations there.  The coefficients of both frames are computed once, before the first warp.  Returns
-        (field, vec, status) of the last level as device tensors queued on `stream`.  mask (what _mask_pair returned): every
-        correlation is section 17's under the mask in unwarped image coordinates, each level with min_valid from its own
-        win, and each frame's masked pixels are at that frame's unmasked mean before the coefficients (no host wait).
-        weighting (what _weight_tables returned for the schedule's wins): every correlation of level l is section 18's with
-        table l."""
+    def _frame_coefficients(self, a, b, stream: int):
+        """(coef, warped), two device tensors [2, h, w]: the B-spline coefficients of the frames a and b, queued on `stream`, and
+        the scratch their warps go to."""
         import torch
         h, w = a.shape
+        coef, warped = (torch.empty((2, h, w), dtype=torch.float32, device=a.device) for _ in range(2))
+        self.bspline_coefficients(a.data_ptr(), w, h, coef[0].data_ptr(), stream)
+        self.bspline_coefficients(b.data_ptr(), w, h, coef[1].data_ptr(), stream)
+        return coef, warped
+
+    def _deform_chain(self, a, b, schedule, iterations, correlator: _Correlator, settings: _DeformSettings = _DeformSettings()):
+        """What correlate_deform (a one-level schedule), correlate_multigrid and optical_flow's default predictor queue on the
+        device images a, b, nothing copied back.  schedule, iterations: what piv_multigrid.check_schedule returned;
+        correlator: after its device step.  Pass 0 (settings.radius) and iterations[0] deformation iterations at schedule[0];
+        per further level the last predictor regridded and iterations[l] deformation iterations there.  An iteration warps
+        both frames half-way by the predictor, correlates with settings.residual_radius and validates with the predictor;
+        the next predictor is the smoothed field, or with smooth=False the field itself.  The coefficients of both frames
+        are computed once, before the first warp.  Returns (field [n_rows, n_cols, 2], vec [n_rows, n_cols, 4] of the last
+        correlation, status [n_rows, n_cols]) of the last level as device tensors queued on the current stream.  Under a mask
+        every correlation is section 17's in unwarped image coordinates, each level with min_valid from its own win, and
+        each frame's masked pixels are at that frame's unmasked mean before the coefficients (no host wait); with weighting
+        every correlation of a level is section 18's with the table of its win."""
+        import torch
+        dev, stream = _device_and_stream()
+        h, w = a.shape
         coef = warped = None
-        if mask is not None:
-            a, b = _replace_masked(a, mask[0]), _replace_masked(b, mask[1])
+        if correlator.mask is not None:
+            a, b = _replace_masked(a, correlator.mask[0]), _replace_masked(b, correlator.mask[1])
         for level, ((win, step), n) in enumerate(zip(schedule, iterations)):
-            correlate, first_radius, _ = self._correlator(method, win, radius if level == 0 else None, window_sigma, diameter, mask,
-                                                          min_valid_fraction, None if weighting is None else weighting[level])
+            correlate, first_radius, _ = correlator.at(win, settings.radius if level == 0 else None)
             if level == 0:
-                vec, field, smoothed, status = self._correlate_validated(correlate, a, b, win, step, first_radius, eps, threshold, dev, stream)
+                vec, field, smoothed, status = self._correlate_validated(correlate, a, b, (win, step), first_radius, settings, stream)
             else:
                 r, c = field.shape[:2]
-                field = smoothed = self.piv_regrid((smoothed if smooth else field).data_ptr(), 2, r, c, *schedule[level - 1], w, h, win, step,
-                                                   stream)
-            if int(n) > 0:
-                if coef is None:
-                    coef, warped = (torch.empty((2, h, w), dtype=torch.float32, device=dev) for _ in range(2))
-                    self.bspline_coefficients(a.data_ptr(), w, h, coef[0].data_ptr(), stream)
-                    self.bspline_coefficients(b.data_ptr(), w, h, coef[1].data_ptr(), stream)
-                vec, field, smoothed, status = self._deform_iterations(correlate, coef, warped, smoothed if smooth else field, win, step, n,
-                                                                       residual_radius, smooth, eps, threshold, dev, stream)
+                field = smoothed = self.piv_regrid((smoothed if settings.smooth else field).data_ptr(), 2, r, c, *schedule[level - 1], w, h,
+                                                   win, step, stream)
+            if n == 0:
+                continue
+            if coef is None:
+                coef, warped = self._frame_coefficients(a, b, stream)
+            pred = smoothed if settings.smooth else field
+            r, c = pred.shape[:2]
+            fields, smooths = (torch.empty((2, r, c, 2), dtype=torch.float32, device=dev) for _ in range(2))   # ping-pong: a predictor is no output
+            status = torch.empty((r, c), dtype=torch.int32, device=dev)
+            for k in range(n):
+                field, smoothed = fields[k & 1], smooths[k & 1]
+                self.piv_deform(coef[0].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, -0.5, warped[0].data_ptr(), stream)
+                self.piv_deform(coef[1].data_ptr(), w, h, pred.data_ptr(), 2, r, c, win, step, 0.5, warped[1].data_ptr(), stream)
+                vec, flg, _ = correlate(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, settings.residual_radius, stream=stream)
+                self.piv_validate(pred.data_ptr(), vec.data_ptr(), flg.data_ptr(), r, c, field.data_ptr(), smoothed.data_ptr(),
+                                  status.data_ptr(), eps=settings.eps, threshold=settings.threshold, stream=stream)
+                pred = smoothed if settings.smooth else field
         return field, vec, status
-
-    def _correlate_deform_device(self, a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev, stream,
-                                 method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5, weighting=None):
-        """correlate_deform on the device images a, b, nothing copied back: (field [n_rows, n_cols, 2] of the last iteration,
-        vec [n_rows, n_cols, 4] of the last correlation, status [n_rows, n_cols]) as device tensors queued on `stream`: the
-        one-level schedule."""
-        return self._correlate_multigrid_device(a, b, ((win, step),), (iterations,), radius, residual_radius, smooth, eps, threshold, dev,
-                                                stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
-
-    def _correlate_multigrid_device(self, a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream,
-                                    method="direct", window_sigma=None, diameter=2.5, mask=None, min_valid_fraction=0.5, weighting=None):
-        """correlate_multigrid on the device images a, b, nothing copied back: (field, vec, status) of the last level's grid as
-        device tensors queued on `stream`.  Every refusal is raised before anything is queued.  mask: the drivers' mask=, or
-        None.  weighting: the drivers' weighting=, or None; the string forms make one table per level's win, an array has to
-        be [win, win] for every level's win."""
-        from . import piv_mask
-        from . import piv_multigrid as pm
-        from . import piv_weighting
-        schedule, iterations = pm.check_schedule(tuple(a.shape), schedule, iterations, radius, residual_radius, method, window_sigma, diameter)
-        piv_weighting.check_method(method, weighting, mask)
-        weighting = _weight_tables(weighting, [win for win, _ in schedule], dev)
-        if mask is not None:
-            piv_mask.check_method(method, mask)
-            for win, _ in schedule:
-                piv_mask.min_valid_for(win, min_valid_fraction)
-            mask = _mask_pair(mask, tuple(a.shape), dev)
-        return self._deform_chain(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold, dev, stream, method,
-                                  window_sigma, diameter, mask, min_valid_fraction, weighting)
-
-    @staticmethod
-    def _masked_result(field, vec, status, masked: bool, fill_masked: bool):
-        """What the deformation drivers copy back, [n_rows, n_cols, 4] on the device: dx, dy of the field, peak and ratio of the
-        last correlation; under a mask with fill_masked=False, NaN where status has bit 16 (piv_mask.fill_masked)."""
-        import torch
-        out = torch.cat([field, vec[..., 2:4]], dim=-1)
-        if masked and not fill_masked:
-            out = torch.where(((status & 16) != 0)[..., None], torch.full((), float("nan"), dtype=out.dtype, device=out.device), out)
-        return out
 
     def correlate_deform(self, im1, im2, win: int = 32, step: int = 16, radius: Optional[int] = None, iterations: int = 3,
                          residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
@@ -1071,12 +1048,9 @@ class PhotonLibrary:
         ``displacement_uncertainty`` or ``optical_flow(predictor=...)``.
         weighting: as ``correlate`` takes it, for every pass: with a top-hat window the loop amplifies the wrong-signed
         response to wavelengths below the window size, with a Gaussian window it converges towards the true amplitude."""
-        weighting = _checked_weighting(weighting)
-        dev, stream, a, b, h, w = _image_pair(im1, im2, mask)
-        field, vec, status = self._correlate_deform_device(a, b, win, step, radius, iterations, residual_radius, smooth, eps, threshold, dev,
-                                                           stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
-        out = self._masked_result(field, vec, status, mask is not None, fill_masked)
-        return out.cpu().numpy(), status.cpu().numpy()
+        return self.correlate_multigrid(im1, im2, ((win, step),), (iterations,), radius=radius, residual_radius=residual_radius, smooth=smooth,
+                                        eps=eps, threshold=threshold, method=method, window_sigma=window_sigma, diameter=diameter, mask=mask,
+                                        min_valid_fraction=min_valid_fraction, fill_masked=fill_masked, weighting=weighting)
 
     def correlate_multigrid(self, im1, im2, schedule=((64, 32), (32, 16), (16, 8)), iterations=(1, 1, 2), radius: Optional[int] = None,
                             residual_radius: int = 4, smooth: bool = True, eps: float = 0.1, threshold: float = 2.0, method: str = "direct",
@@ -1095,11 +1069,18 @@ class PhotonLibrary:
         level takes its min_valid from its own win.  weighting: as ``correlate`` takes it; "gaussian" and ("gaussian", sigma)
         make one table per level's win (sigma None = win / 4 of each level), an array is accepted only when every level has
         its win."""
-        weighting = _checked_weighting(weighting)
-        dev, stream, a, b, h, w = _image_pair(im1, im2, mask)
-        field, vec, status = self._correlate_multigrid_device(a, b, schedule, iterations, radius, residual_radius, smooth, eps, threshold,
-                                                              dev, stream, method, window_sigma, diameter, mask, min_valid_fraction, weighting)
-        out = self._masked_result(field, vec, status, mask is not None, fill_masked)
+        import torch
+        from . import piv_multigrid as pm
+        im1, im2, _ = _checked_pair(im1, im2, mask)
+        schedule, iterations = pm.check_schedule(tuple(im1.shape), schedule, iterations, radius, residual_radius, method, window_sigma, diameter)
+        correlator = _Correlator([win for win, _ in schedule], method, window_sigma=window_sigma, diameter=diameter, mask=mask,
+                                 min_valid_fraction=min_valid_fraction, weighting=weighting)
+        dev, _, a, b, h, w = _pair_on_device(im1, im2)
+        field, vec, status = self._deform_chain(a, b, schedule, iterations, correlator.on_device(self, (h, w), dev),
+                                                _DeformSettings(radius, residual_radius, smooth, eps, threshold))
+        out = torch.cat([field, vec[..., 2:4]], dim=-1)      # dx, dy of the field, peak and ratio of the last correlation
+        if mask is not None and not fill_masked:
+            out = _nan_where_masked_out(out, status)         # piv_mask.fill_masked's other half
         return out.cpu().numpy(), status.cpu().numpy()
 
     # ---- displacement uncertainty from correlation statistics (section 11) -------------------------------------------------
@@ -1109,17 +1090,8 @@ class PhotonLibrary:
         torch device tensors (sigma [n_rows, n_cols, 2] f32 = sigma_x, sigma_y in pixels; flags [n_rows, n_cols] int32; stats
         [n_rows, n_cols, 2, 4] f64 = (C0, C1, S(0), V) per axis, or None), filled asynchronously on `stream`.  The
         definition: include/parallel_ray_tracing.h, section 11 (photon_amd.piv_uncertainty: host model)."""
-        import torch
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        args = ("photon_piv_uncertainty", _vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(reach))
-        self._call(*args, None, None, None, ctypes.byref(rows), ctypes.byref(cols), None)
-        r, c = rows.value, cols.value
-        dev, _ = _device_and_stream()
-        sigma = torch.empty((r, c, 2), dtype=torch.float32, device=dev)
-        flags = torch.empty((r, c), dtype=torch.int32, device=dev)
-        st = torch.empty((r, c, 2, 4), dtype=torch.float64, device=dev) if stats else None
-        self._call(*args, _vp(sigma.data_ptr()), _vp(flags.data_ptr()), _vp(st.data_ptr()) if stats else None, None, None, _vp(stream))
-        return sigma, flags, st
+        head = (_vp(d_im1_ptr), _vp(d_im2_ptr), int(width), int(height), int(win), int(step), int(reach))
+        return self._grid_call("photon_piv_uncertainty", head, (((2,), "float32", True), _FLAGS, ((2, 4), "float64", stats)), stream)
 
     def displacement_uncertainty(self, im1, im2, field, win: int = 32, step: int = 16, reach: int = 2, return_warped: bool = False):
         """Uncertainty (sigma_x, sigma_y) in pixels of every vector of a displacement field on section 5's grid, whatever
@@ -1194,7 +1166,9 @@ class PhotonLibrary:
         of.check_driver_arguments(alpha2, warps, iterations)
         inv_std = 1.0 / torch.std(a, correction=0)
         if predictor is None:
-            predictor = self._correlate_deform_device(a, b, win, step, None, 1, 4, True, 0.1, 2.0, dev, stream)[0]
+            from . import piv_multigrid as pm
+            levels = pm.check_schedule((h, w), ((win, step),), (1,), radius=None, residual_radius=4, method="direct")
+            predictor = self._deform_chain(a, b, *levels, _Correlator((win,)).on_device(self, (h, w), dev))[0]
         pred = _on_device(predictor, torch.float32, dev, "predictor", 3)
         field = torch.empty((2, h, w, 2), dtype=torch.float32, device=dev)      # the current field and the next one
         if of.predictor_shape(pred.shape, (h, w), win, step) == "grid":
@@ -1203,11 +1177,9 @@ class PhotonLibrary:
                                  field[0].data_ptr(), stream)
         else:
             field[0].copy_(pred)
-        coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=dev), torch.empty((2, h, w), dtype=torch.float32, device=dev)
         terms = torch.empty((h, w, 4), dtype=torch.float32, device=dev)
         tmp = torch.empty((h, w, 2), dtype=torch.float32, device=dev) if int(iterations) > self.optflow_iterations_per_launch() else None
-        self.bspline_coefficients(a.data_ptr(), w, h, coef[0].data_ptr(), stream)
-        self.bspline_coefficients(b.data_ptr(), w, h, coef[1].data_ptr(), stream)
+        coef, warped = self._frame_coefficients(a, b, stream)
         gain = float(inv_std)
         cur = 0
         for _ in range(int(warps)):
@@ -1273,25 +1245,15 @@ class PhotonLibrary:
         smoothed field carries the neighbours' median across masked-out nodes; as in the other drivers fill_masked=False
         returns NaN there (set on the device, nothing waits), and a caller who hands the field on as a predictor wants
         fill_masked=True: a node that is not finite reads as (0, 0) in every warp.  weighting: as ``correlate`` takes it."""
-        from . import piv_mask
-        from . import piv_weighting
-        piv_mask.check_method(method, mask)
-        piv_weighting.check_method(method, weighting, mask)
         im1, im2, _ = _checked_pair(im1, im2, mask)
-        weighting = _checked_weighting(weighting)
-        correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter)
-        if weighting is not None:
-            table, = _weight_tables(weighting, (win,), _device_and_stream()[0])
-            correlate, radius, check = self._correlator(method, win, radius, window_sigma, diameter, weighting=table)
-        dev, stream, a, b, h, w = _image_pair(im1, im2)
+        correlator = _Correlator((win,), method, window_sigma=window_sigma, diameter=diameter, mask=mask,
+                                 min_valid_fraction=min_valid_fraction, weighting=weighting)
+        dev, stream, a, b, h, w = _pair_on_device(im1, im2)
+        correlate, radius, check = correlator.on_device(self, (h, w), dev).at(win, radius)
         check((h, w), win, step, radius)
-        if mask is not None:
-            correlate, radius, _ = self._correlator(method, win, radius, window_sigma, diameter, _mask_pair(mask, (h, w), dev), min_valid_fraction)
-        _, _, smoothed, status = self._correlate_validated(correlate, a, b, win, step, radius, eps, threshold, dev, stream)
-        if mask is not None and not fill_masked:
-            import torch
-            smoothed = torch.where(((status & 16) != 0)[..., None], torch.full((), float("nan"), dtype=smoothed.dtype, device=dev), smoothed)
-        return smoothed
+        settings = _DeformSettings(eps=eps, threshold=threshold)
+        _, _, smoothed, status = self._correlate_validated(correlate, a, b, (win, step), radius, settings, stream)
+        return smoothed if mask is None or fill_masked else _nan_where_masked_out(smoothed, status)
 
     def track_dots(self, im1, im2, threshold: float, box_radius: int = 3, sigma_w: float = 1.0, iterations: int = 4,
                    background: float = 0.0, radius: float = 3.0, predictor=None, max_dots: Optional[int] = None, grid=None,

@@ -167,7 +167,7 @@ def validate_model(pred, vectors, flags, eps: float = 0.1, threshold: float = 2.
 
 def model_correlator(method: str, win: int, radius, window_sigma, diameter, mask=None, min_valid_fraction: float = 0.5,
                      weighting=None):
-    """What method= selects in the models of the drivers, as PhotonLibrary._correlator does on the device: (correlate(im1, im2,
+    """What method= selects in the models of the drivers, as library._Correlator does on the device: (correlate(im1, im2,
     win, step, radius) -> (vectors, flags), the radius, check(shape, win, step, radius)).  "direct": piv_correlation's model,
     radius None = win // 2.  "phase": piv_phase.correlate_phase_model in mode 1 (window_sigma None = win / 4; radius None or
     win // 2 = win // 2 - 1).  mask (a plane, or a pair of them for the two frames): piv_mask.correlate_masked_model with

@@ -323,7 +323,8 @@ def test_the_drivers_allocate_device_tensors_through_empty_zeros_and_full_alone(
                 offenders.append(f"{os.path.basename(path)}:{no}: {code.strip()}")
     assert not offenders, "uninitialised device tensors that do not come from torch.empty:\n" + "\n".join(offenders)
     text = open(os.path.join(ROOT, "photon_amd", "library.py"), encoding="utf-8").read()
-    assert len(re.findall(r"\btorch\.empty\(", text)) >= 40        # the patch has something to catch
+    # the patch has something to catch: one site per allocation, the seven grid entry points share _grid_call's (44 sites before that)
+    assert len(re.findall(r"\btorch\.empty\(", text)) >= 20 and "torch.empty(" in text[text.index("def _grid_call("):text.index("def version(")]
     assert not re.search(r"^\s*(from torch import|import torch\.)", text, flags=re.M) and not re.search(r"^import torch", text, flags=re.M), \
         "library.py must look torch.empty up per call (import torch inside the methods): the test patches the attribute"
 

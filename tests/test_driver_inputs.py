@@ -161,8 +161,9 @@ def test_tensors_of_callers_arrays_are_made_in_the_helper_alone():
     unlisted = {k: v for k, v in found.items() if k not in INTERNAL_TENSORS}
     assert not unlisted, f"tensors made outside library._on_device (lines by statement): {unlisted}"
     assert not [k for k in INTERNAL_TENSORS if k not in found], "INTERNAL_TENSORS lists statements that are gone"
-    assert len(found[("library.py", "d_off = torch.from_numpy(offsets).to(dev)")]) == 2          # correlate and correlate_ensemble
+    assert len(found[("library.py", "d_off = torch.from_numpy(offsets).to(dev)")]) == 1          # once, in the shared two-pass helper
     text = open(os.path.join(ROOT, "photon_amd", "library.py"), encoding="utf-8").read()
+    assert "d_off = torch.from_numpy(offsets).to(dev)" in text[text.index("def _two_passes("):text.index("def _replace_masked(")]
     body = text[text.index("def _on_device("):text.index("def _device_and_stream(")]
     assert "torch.from_numpy(c)" in body                                                     # the listed statement is the helper's
     assert len(re.findall(r"\b_on_device\(", text)) >= 20                                   # the lint has something to guard

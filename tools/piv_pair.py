@@ -48,7 +48,7 @@ from conftest import load_fixture_call  # noqa: E402
 from photon_amd import deflections  # noqa: E402
 from photon_amd import piv_correlation as pc  # noqa: E402
 from photon_amd import piv_pairs as pp  # noqa: E402
-from photon_amd.library import PhotonLibrary  # noqa: E402
+from photon_amd.library import PhotonLibrary, _Correlator  # noqa: E402
 from photon_amd.ray_tracing import postprocess_image, write_tiff_u16  # noqa: E402
 
 # the sample frame's particle field (run_simulation_02.py:949-965 with the sample parameters): 1.5 x the field of view
@@ -238,12 +238,13 @@ def multigrid_pair(lib, images, row):
     schedule, iterations = pm.DEFAULT_SCHEDULE, pm.DEFAULT_ITERATIONS
     a, b = (torch.from_numpy(np.ascontiguousarray(im, np.float32)).cuda() for im in images)
     h, w = a.shape
-    dev, stream = a.device, torch.cuda.current_stream().cuda_stream
     win, step = schedule[-1]
-    calls = {f"multigrid_to_level{n - 1}": lambda n=n: lib._correlate_multigrid_device(a, b, schedule[:n], iterations[:n], None, 4, True, 0.1,
-                                                                                          2.0, dev, stream)
-             for n in range(1, len(schedule) + 1)}
-    calls["correlate_deform_3"] = lambda: lib._correlate_deform_device(a, b, win, step, None, 3, 4, True, 0.1, 2.0, dev, stream)
+
+    def chain(schedule, iterations):                        # the drivers' device side with their defaults, nothing copied back
+        levels = pm.check_schedule((h, w), schedule, iterations, radius=None, residual_radius=4, method="direct")
+        return lib._deform_chain(a, b, *levels, _Correlator([win for win, _ in levels[0]]).on_device(lib, (h, w), a.device))
+    calls = {f"multigrid_to_level{n - 1}": lambda n=n: chain(schedule[:n], iterations[:n]) for n in range(1, len(schedule) + 1)}
+    calls["correlate_deform_3"] = lambda: chain(((win, step),), (3,))
     for k, (src, dst) in enumerate(zip(schedule, schedule[1:])):
         r, c = pc.grid_shape((h, w), *src)
         fld = torch.zeros((r, c, 2), device="cuda")
