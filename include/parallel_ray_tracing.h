@@ -1373,6 +1373,116 @@ int photon_piv_correlate_weighted(const float *d_im1, const float *d_im2, const 
                                   int *n_rows, int *n_cols, void *stream);
 int photon_piv_window_weights(int win, int kind, float param, float *weights);
 
+/* ------------------------------------------------------------------------------------
+ * Section 19: stereo PIV -- the frames of two cameras that look at one light sheet from two sides, resampled onto one grid
+ * on the sheet's plane (dewarp), correlated there by any correlator of this header, and the two 2-C fields combined into
+ * three components per node (reconstruct).  Host models, the camera fit and the test generators: photon_amd/piv_stereo.py.
+ * Both entry points take one pointer to a job struct (host memory, read during the call, not kept); the last member is the
+ * stream.  Neither allocates device memory.
+ *
+ * Camera (photon_piv_camera_t): Soloff's polynomial from world (X, Y, Z) to image (x, y) in pixels, x = column, y = row.
+ * With q = ((X, Y, Z) - centre) / scale per component, and the 19 terms T_k(q), cubic in X and Y, quadratic in Z, in this order:
+ *   1, X, Y, Z, X^2, XY, Y^2, XZ, YZ, Z^2, X^3, X^2 Y, X Y^2, Y^3, X^2 Z, XYZ, Y^2 Z, X Z^2, Y Z^2
+ * (products from the left: X^2 Y = (X X) Y, XYZ = (X Y) Z, X Z^2 = X (Z Z)),  x = sum_k cx[k] T_k, y = sum_k cy[k] T_k.
+ * Plane (photon_piv_plane_t): dewarped pixel (row i, column j) is the world point (x0 + j pitch, y0 + i pitch, z), i in
+ * [0, height), j in [0, width); pitch > 0 in world units per dewarped pixel.
+ *
+ * a. photon_piv_dewarp.  Frame f of the source is d_coef + f frame_stride: the cubic B-spline coefficients (section 7a,
+ *    unchanged) of a camera frame, f32[height*width]; frame f of the result is d_out + f out_stride, f32[out_height*out_width]
+ *    (section 14's stride addressing, in floats, on both sides: the two exposures of a camera, or a series, in one launch).
+ *    The camera arrives folded at the plane (piv_stereo.plane_coefficients): with w = (z - centre_z) / scale_z the 10
+ *    coefficients per image coordinate of the bivariate cubic in (u, v) = (q_X, q_Y), in the order 1, u, v, u^2, uv, v^2, u^3,
+ *    u^2 v, u v^2, v^3:
+ *      k0 = (c9 w + c3) w + c0,  k1 = (c17 w + c7) w + c1,  k2 = (c18 w + c8) w + c2,  k3 = c14 w + c4,  k4 = c15 w + c5,
+ *      k5 = c16 w + c6,  k6 = c10,  k7 = c11,  k8 = c12,  k9 = c13       (f64; poly[0] from cx, poly[1] from cy)
+ *    and grid[4] = (u0, du, v0, dv) = ((x0 - centre_X) / scale_X, pitch / scale_X, (y0 - centre_Y) / scale_Y, pitch / scale_Y):
+ *    the kernel divides nothing.  Per output pixel (i, j), one thread, in f64, no fused multiply-add:
+ *      u = u0 + (double)j du,  v = v0 + (double)i dv
+ *      a0 = ((k9 v + k5) v + k2) v + k0,  a1 = (k8 v + k4) v + k1,  a2 = k7 v + k3,  p = ((k6 u + a2) u + a1) u + a0
+ *    for x (poly[0]) and y (poly[1]).  The pixel is inside when 0 <= x <= width - 1 and 0 <= y <= height - 1 (a NaN is
+ *    not).  Inside: fx = floor(x), fy = floor(y), tx = (float)(x - fx), ty = (float)(y - fy) -- the absolute coordinate never
+ *    enters f32 --, the 4 x 4 taps fx - 1 .. fx + 2, fy - 1 .. fy + 2 under section 7's whole-sample mirror, section 7b's
+ *    f32 B-spline weights of tx and ty and section 7b's order of the sums: per row ((w0 c0 + w1 c1) + w2 c2) + w3 c3, the
+ *    rows accumulated from 0 in the order of fy - 1 .. fy + 2.  Coordinate, weights and the 8 mirrored indices are computed
+ *    once and serve all n_frames frames.  Outside: 0.0f in every frame.  d_mask (device u8[out_height*out_width], or
+ *    NULL): 1 outside, 0 inside -- one mask for all frames, it depends on the geometry alone; it is what section 17 takes
+ *    as d_mask1 / d_mask2.  Every pixel of the n_frames output frames and of the mask is written, nothing else (the gaps
+ *    of a stride above out_width out_height are not touched).  With the identity map (x = j, y = i) the result is
+ *    photon_piv_deform's at zero shift bit for bit.  Host model of exactly these f32 / f64 operations:
+ *    piv_stereo.dewarp_model_f32 (equal bit for bit); in f64 throughout: piv_stereo.dewarp_model.
+ *    Refused (1, one stderr line, nothing written, no launch): a null job, d_coef or d_out; d_out == d_coef; a size below 1
+ *    or a side above 2^22 pixels, source or result; n_frames < 1; frame_stride < width height; out_stride < out_width
+ *    out_height; a poly or grid value that is not finite.  Asynchronous on `stream`; two calls return the same bits.
+ *
+ * b. photon_piv_stereo_reconstruct.  d_field1, d_field2: the two cameras' displacement fields on section 5's grid (win,
+ *    step) of the dewarped plane->width x plane->height image, device f32[n][field_stride] with dx, dy first (field_stride
+ *    2: a field of section 7c; 4: section 5's d_vectors), in dewarped pixels; d_flags1, d_flags2: their int[n] flags, or
+ *    NULL (read as 0); d_sigma1, d_sigma2: f32[n][2] = (sigma_x, sigma_y) of section 11 in dewarped pixels, both or neither.
+ *    Per node k = i n_cols + j, one thread, in f64 without fused multiply-add, with the window centre
+ *      P = (x0 + (j step + (win - 1) / 2.0) pitch,  y0 + (i step + (win - 1) / 2.0) pitch,  z):
+ *      1. per camera c the 2 x 3 Jacobian J_c = d(x, y) / d(X, Y, Z) at P: with q as above and the derivatives D_k of the 19
+ *         terms with respect to q_X, q_Y, q_Z (zeros included; 2 X Y = (2 X) Y, 3 X^2 = 3 (X X), 2 X Z = (2 X) Z, the rest as
+ *         the terms), each entry = (sum over k = 0 .. 18 from 0.0 of c[k] D_k) / scale of its world axis.
+ *      2. a_c = pitch (dx_c, dy_c): the apparent in-plane world displacement camera c saw.  Rows 2c, 2c + 1 of A are J_c,
+ *         of b are J_c[:, 0] a_c[0] + J_c[:, 1] a_c[1]: four equations in image pixels for Delta = (dX, dY, dZ).
+ *      3. N = A^T A (each entry summed over the rows 0 .. 3 from the first product), r = A^T b likewise; Cholesky N = L L^T:
+ *         d0 = N00, L10 = N10 / L00, L20 = N20 / L00, d1 = N11 - L10 L10, L21 = (N21 - L20 L10) / L11, d2 = (N22 - L20 L20) -
+ *         L21 L21, L_kk = sqrt(d_k).  Pivot ratio = min d_k / max d_k.  Not (ratio > 1e-12) (a pivot <= 0 or NaN included):
+ *         degenerate, flag 64, all eight outputs NaN.
+ *      4. forward and back substitution for Delta; residual = sqrt(sum over the four rows of ((A Delta)_m - b_m)^2), (A
+ *         Delta)_m = (A_m0 dX + A_m1 dY) + A_m2 dZ: the stereo residual in image pixels, the figure of registration quality.
+ *      5. with sigmas: N^-1 column by column through the same substitutions, M = N^-1 A^T (3 x 4), per camera G_c = M[:,
+ *         2c : 2c + 2] J_c[:, 0 : 2] (3 x 2), var_k = sum over c, then m, from 0.0 of (G_c[k][m] G_c[k][m]) (pitch sigma_cm)^2
+ *         -- the diagonal of (A^T A)^-1 A^T Sigma_b A (A^T A)^-1 with Sigma_b = J_xy diag(pitch^2 sigma^2) J_xy^T per camera --,
+ *         sigma_k = sqrt(var_k).
+ *    d_out f64[n][8] = dX, dY, dZ in world units, the residual, sigma_X, sigma_Y, sigma_Z (NaN without sigmas), the pivot
+ *    ratio.  d_flags int[n] = flags1 | flags2, plus 64 (degenerate geometry) and 128 (a dx or dy of either camera is not
+ *    finite: the first seven outputs NaN, the ratio reported).  Host model: piv_stereo.reconstruct_model (the same
+ *    operations; agreement to 1e-12).
+ *    This is a first-order reconstruction: the Jacobian is taken at the plane, at the window centre, not at the
+ *    half-displaced particle positions, so a displacement sees the camera's curvature (perspective) only to first order;
+ *    and no disparity (self-calibration) correction is applied -- a sheet that is not at plane.z shows up in the residual.
+ *    d_out == NULL: the size query -- *rows_out, *cols_out (where given) receive section 5's grid of the plane, nothing is
+ *    launched, n_rows and n_cols are not read.  Refused (1, one stderr line, nothing written, no launch): a null job;
+ *    section 5's rules for win, step and the plane's size; with d_out: n_rows x n_cols that is not that grid, a null
+ *    d_field1, d_field2 or d_flags, field_stride not 2 or 4, one sigma without the other; a plane or camera value that is
+ *    not finite, pitch <= 0, a camera scale of 0.  Asynchronous on `stream`; two calls return the same bits.
+ *
+ * Driver: PhotonLibrary.dewarp and PhotonLibrary.correlate_stereo.  DESIGN.md section 4.3w. */
+typedef struct photon_piv_camera_t {
+    double centre[3], scale[3], cx[19], cy[19];
+} photon_piv_camera_t;
+typedef struct photon_piv_plane_t {
+    double x0, y0, pitch, z;
+    int width, height;
+} photon_piv_plane_t;
+typedef struct photon_piv_dewarp_t {
+    const float *d_coef;
+    long long frame_stride;
+    int n_frames, width, height;
+    double poly[2][10], grid[4];
+    int out_width, out_height;
+    long long out_stride;
+    float *d_out;
+    unsigned char *d_mask;
+    void *stream;
+} photon_piv_dewarp_t;
+typedef struct photon_piv_stereo_t {
+    const float *d_field1, *d_field2;
+    int field_stride;
+    const int *d_flags1, *d_flags2;
+    const float *d_sigma1, *d_sigma2;
+    int n_rows, n_cols, win, step;
+    photon_piv_plane_t plane;
+    photon_piv_camera_t camera1, camera2;
+    double *d_out;
+    int *d_flags;
+    int *rows_out, *cols_out;
+    void *stream;
+} photon_piv_stereo_t;
+int photon_piv_dewarp(const photon_piv_dewarp_t *job);
+int photon_piv_stereo_reconstruct(const photon_piv_stereo_t *job);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,7 +5,7 @@ Three layers, top to bottom of the file:
     loaded library.  The header is the source of truth; tests/test_abi.py holds the table against its prototypes.
   * ``PhotonLibrary``: one method per entry point -- marshalling only, raw device pointers in, return code checked -- and
     on top of those the pipelines that chain several calls on torch-allocated device buffers on the current stream
-    (``preprocess_series``, ``correlate``, ``correlate_deform``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
+    (``preprocess_series``, ``correlate``, ``correlate_deform``, ``correlate_stereo``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
     ``integrate_gradient``, the tomography solvers).
   * ``Volume``, ``Sources``, ``Flow``, ``Scene``: the library's handles.
 All arithmetic is the HIP library's.  There is no Python or CPU fallback -- if the library is missing or a call fails,
@@ -75,6 +75,30 @@ class photon_march_plan_t(ctypes.Structure):
                 ("seg_begin", ctypes.c_uint * 65), ("groups_per_chunk", ctypes.c_uint), ("grid_blocks", ctypes.c_uint),
                 ("block_threads", ctypes.c_uint), ("persistent", ctypes.c_int), ("save", ctypes.c_int), ("noise", ctypes.c_int),
                 ("segmented", ctypes.c_int), ("generates_rays", ctypes.c_int)]
+
+
+class photon_piv_camera_t(ctypes.Structure):
+    _fields_ = [("centre", ctypes.c_double * 3), ("scale", ctypes.c_double * 3), ("cx", ctypes.c_double * 19), ("cy", ctypes.c_double * 19)]
+
+
+class photon_piv_plane_t(ctypes.Structure):
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("pitch", ctypes.c_double), ("z", ctypes.c_double),
+                ("width", ctypes.c_int), ("height", ctypes.c_int)]
+
+
+class photon_piv_dewarp_t(ctypes.Structure):
+    _fields_ = [("d_coef", ctypes.c_void_p), ("frame_stride", ctypes.c_longlong), ("n_frames", ctypes.c_int), ("width", ctypes.c_int),
+                ("height", ctypes.c_int), ("poly", ctypes.c_double * 10 * 2), ("grid", ctypes.c_double * 4), ("out_width", ctypes.c_int),
+                ("out_height", ctypes.c_int), ("out_stride", ctypes.c_longlong), ("d_out", ctypes.c_void_p), ("d_mask", ctypes.c_void_p),
+                ("stream", ctypes.c_void_p)]
+
+
+class photon_piv_stereo_t(ctypes.Structure):
+    _fields_ = [("d_field1", ctypes.c_void_p), ("d_field2", ctypes.c_void_p), ("field_stride", ctypes.c_int), ("d_flags1", ctypes.c_void_p),
+                ("d_flags2", ctypes.c_void_p), ("d_sigma1", ctypes.c_void_p), ("d_sigma2", ctypes.c_void_p), ("n_rows", ctypes.c_int),
+                ("n_cols", ctypes.c_int), ("win", ctypes.c_int), ("step", ctypes.c_int), ("plane", photon_piv_plane_t),
+                ("camera1", photon_piv_camera_t), ("camera2", photon_piv_camera_t), ("d_out", ctypes.c_void_p), ("d_flags", ctypes.c_void_p),
+                ("rows_out", ctypes.POINTER(ctypes.c_int)), ("cols_out", ctypes.POINTER(ctypes.c_int)), ("stream", ctypes.c_void_p)]
 
 
 def _signatures():
@@ -199,6 +223,9 @@ def _signatures():
         # section 18: direct correlation with a weight per window pixel
         "photon_piv_correlate_weighted": (ci, [vp] * 3 + [ci] * 5 + [vp] * 4 + [P(ci), P(ci), vp]),
         "photon_piv_window_weights": (ci, [ci, ci, cf, vp]),
+        # section 19: stereo PIV (one job struct each; its last member is the stream)
+        "photon_piv_dewarp": (ci, [P(photon_piv_dewarp_t)]),
+        "photon_piv_stereo_reconstruct": (ci, [P(photon_piv_stereo_t)]),
     }
 
 
@@ -239,6 +266,24 @@ def _dims(n):
     """n or (nx, ny, nz) as three ints."""
     nx, ny, nz = (n, n, n) if np.isscalar(n) else n
     return int(nx), int(ny), int(nz)
+
+
+def _stereo_job(cameras, plane, win: int, step: int) -> photon_piv_stereo_t:
+    """Section 19b's job with its host values -- the two cameras and the plane (piv_stereo's dicts), win and step -- and every
+    pointer NULL: as it stands, the size query."""
+    job = photon_piv_stereo_t(win=int(win), step=int(step))
+    job.plane = photon_piv_plane_t(float(plane["x0"]), float(plane["y0"]), float(plane["pitch"]), float(plane["z"]), int(plane["width"]),
+                                   int(plane["height"]))
+    if len(cameras) != 2:
+        raise ValueError("section 19b takes two cameras")
+    for name, cam in zip(("camera1", "camera2"), cameras):
+        c = getattr(job, name)
+        for key, n in (("centre", 3), ("scale", 3), ("cx", 19), ("cy", 19)):
+            v = np.ascontiguousarray(cam[key], np.float64)
+            if v.shape != (n,):
+                raise ValueError(f"a camera's {key} must have {n} values, not shape {v.shape}")
+            ctypes.memmove(getattr(c, key), v.ctypes.data, v.nbytes)
+    return job
 
 
 def _gaussian_args(n, spacing, origin, rho0, amp, centre, sigma):
@@ -1113,13 +1158,168 @@ class PhotonLibrary:
         if fld.dim() != 3 or fld.shape[2] < 2 or tuple(fld.shape[:2]) != (r, c):
             raise ValueError(f"field must be [{r}, {c}, >= 2]: the grid of a {h} x {w} image, win {win}, step {step}")
         fld = (fld if fld.shape[2] in (2, 4) else fld[..., :2]).contiguous()
-        coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=dev), torch.empty((2, h, w), dtype=torch.float32, device=dev)
+        sigma, flags, warped = self._uncertainty_chain(a, b, fld, win, step, reach, stream)
+        out = (sigma.cpu().numpy(), flags.cpu().numpy())
+        return (*out, warped[0], warped[1]) if return_warped else out
+
+    def _uncertainty_chain(self, a, b, fld, win: int, step: int, reach: int, stream: int):
+        """What displacement_uncertainty queues on the device images a, b and the contiguous field fld [n_rows, n_cols, 2 or 4]:
+        the coefficients, the two half-way warps, photon_piv_uncertainty.  Returns (sigma, flags, warped [2, h, w]), device
+        tensors; nothing is copied back."""
+        import torch
+        h, w = a.shape
+        r, c = fld.shape[:2]
+        coef, warped = torch.empty((2, h, w), dtype=torch.float32, device=a.device), torch.empty((2, h, w), dtype=torch.float32, device=a.device)
         for k, (im, scale) in enumerate(((a, -0.5), (b, 0.5))):
             self.bspline_coefficients(im.data_ptr(), w, h, coef[k].data_ptr(), stream)
             self.piv_deform(coef[k].data_ptr(), w, h, fld.data_ptr(), int(fld.shape[2]), r, c, win, step, scale, warped[k].data_ptr(), stream)
         sigma, flags, _ = self.piv_uncertainty(warped[0].data_ptr(), warped[1].data_ptr(), w, h, win, step, reach, stream=stream)
-        out = (sigma.cpu().numpy(), flags.cpu().numpy())
-        return (*out, warped[0], warped[1]) if return_warped else out
+        return sigma, flags, warped
+
+    # ---- stereo PIV: dewarp two cameras, recover three components (section 19) ----------------------------------------------
+    def piv_dewarp(self, d_coef_ptr: int, frame_stride: int, n_frames: int, width: int, height: int, poly, grid, out_width: int,
+                   out_height: int, out_stride: int, d_out_ptr: int, d_mask_ptr: int = 0, stream: int = 0):
+        """photon_piv_dewarp on raw device pointers: n_frames coefficient images f32 [height, width], frame_stride floats apart,
+        resampled through the folded camera (poly [2, 10] and grid [4], host values from piv_stereo.plane_coefficients) into
+        n_frames images f32 [out_height, out_width], out_stride floats apart, and the u8 mask [out_height, out_width] (0 = NULL)
+        of the pixels outside the source; asynchronous on `stream`."""
+        job = photon_piv_dewarp_t(d_coef=int(d_coef_ptr) or None, frame_stride=int(frame_stride), n_frames=int(n_frames), width=int(width),
+                                  height=int(height), out_width=int(out_width), out_height=int(out_height), out_stride=int(out_stride),
+                                  d_out=int(d_out_ptr) or None, d_mask=int(d_mask_ptr) or None, stream=int(stream) or None)
+        folded, pitches = np.ascontiguousarray(poly, np.float64), np.ascontiguousarray(grid, np.float64)
+        if folded.shape != (2, 10) or pitches.shape != (4,):
+            raise ValueError("poly must be [2, 10] and grid [4] (piv_stereo.plane_coefficients)")
+        ctypes.memmove(job.poly, folded.ctypes.data, folded.nbytes)
+        ctypes.memmove(job.grid, pitches.ctypes.data, pitches.nbytes)
+        self._call("photon_piv_dewarp", ctypes.byref(job))
+
+    def piv_stereo_reconstruct(self, d_field1_ptr: int, d_field2_ptr: int, field_stride: int, cameras, plane, win: int, step: int,
+                               d_flags1_ptr: int = 0, d_flags2_ptr: int = 0, d_sigma1_ptr: int = 0, d_sigma2_ptr: int = 0, stream: int = 0):
+        """photon_piv_stereo_reconstruct on raw device pointers: the two cameras' fields f32 [n_rows, n_cols, field_stride] on
+        section 5's grid (win, step) of the plane, their flags and their sigmas f32 [n_rows, n_cols, 2] (0 = NULL), the two
+        cameras and the plane (piv_stereo's dicts).  Returns torch device tensors (out f64 [n_rows, n_cols, 8] = dX, dY, dZ,
+        residual, sigma_X, sigma_Y, sigma_Z, pivot ratio; flags int32 [n_rows, n_cols]), filled asynchronously on `stream`."""
+        import torch
+        job = _stereo_job(cameras, plane, win, step)
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        job.rows_out, job.cols_out = ctypes.pointer(rows), ctypes.pointer(cols)
+        self._call("photon_piv_stereo_reconstruct", ctypes.byref(job))                   # the size query
+        dev = _current_device()
+        out = torch.empty((rows.value, cols.value, 8), dtype=torch.float64, device=dev)
+        flags = torch.empty((rows.value, cols.value), dtype=torch.int32, device=dev)
+        job.d_field1, job.d_field2, job.field_stride = int(d_field1_ptr) or None, int(d_field2_ptr) or None, int(field_stride)
+        job.d_flags1, job.d_flags2 = int(d_flags1_ptr) or None, int(d_flags2_ptr) or None
+        job.d_sigma1, job.d_sigma2 = int(d_sigma1_ptr) or None, int(d_sigma2_ptr) or None
+        job.n_rows, job.n_cols, job.d_out, job.d_flags, job.stream = rows.value, cols.value, out.data_ptr(), flags.data_ptr(), int(stream) or None
+        self._call("photon_piv_stereo_reconstruct", ctypes.byref(job))
+        return out, flags
+
+    def _dewarp_queued(self, stack, camera, plane, stream: int):
+        """The device stack f32 [n, h, w] of one camera's frames onto the plane, queued on `stream`: the coefficients of every
+        frame (section 7a), then one dewarp launch for all of them.  Returns (frames [n, plane height, plane width], mask u8
+        [plane height, plane width], whether any pixel of the plane is outside the source -- decided on the host, from
+        piv_stereo.folded_points, the kernel's own f64 operations, so that nothing waits for the device)."""
+        import torch
+        from . import piv_stereo as ps
+        n, h, w = stack.shape
+        oh, ow = int(plane["height"]), int(plane["width"])
+        poly, grid = ps.plane_coefficients(camera, plane)
+        coef = torch.empty((n, h, w), dtype=torch.float32, device=stack.device)
+        for k in range(n):
+            self.bspline_coefficients(stack[k].data_ptr(), w, h, coef[k].data_ptr(), stream)
+        frames = torch.empty((n, oh, ow), dtype=torch.float32, device=stack.device)
+        outside = torch.empty((oh, ow), dtype=torch.uint8, device=stack.device)
+        self.piv_dewarp(coef.data_ptr(), h * w, n, w, h, poly, grid, ow, oh, oh * ow, frames.data_ptr(), outside.data_ptr(), stream)
+        return frames, outside, bool(ps.outside_mask(poly, grid, (oh, ow), (h, w)).any())
+
+    def dewarp(self, frames_in, camera, plane):
+        """One camera's frames resampled onto the plane's grid (section 19a): frames_in is one frame [height, width] or a
+        stack [n, height, width], taken as the ingest rule of this class takes any image; camera and plane are
+        piv_stereo's dicts (piv_stereo.fit_camera, piv_stereo.plane).  The B-spline coefficients per frame, then one dewarp
+        launch, on the current stream; nothing waits.  Returns device tensors (frames f32 [n, plane height, plane width] or
+        [plane height, plane width]; mask u8 [plane height, plane width], 1 where the plane lies outside the camera's
+        frame), which every correlator driver takes as they are, the mask as its mask=."""
+        import torch
+        x = _checked(frames_in, "frames_in")
+        if x.ndim not in (2, 3):
+            raise ValueError(f"frames_in must be one frame [height, width] or a stack [n, height, width], not shape {tuple(x.shape)}")
+        dev, stream = _device_and_stream()
+        t = _on_device(x, torch.float32, dev, "frames_in")
+        frames, outside, _ = self._dewarp_queued(t.reshape((-1,) + tuple(t.shape[-2:])), camera, plane, stream)
+        return (frames[0] if x.ndim == 2 else frames), outside
+
+    def correlate_stereo(self, cam1_frames, cam2_frames, cameras, plane, evaluate: str = "deform", settings: Optional[dict] = None,
+                         sigma: bool = False):
+        """Three displacement components per node from two cameras on one light sheet (section 19; model:
+        photon_amd.piv_stereo.correlate_stereo_model).  cam1_frames, cam2_frames: the two exposures of each camera, a stack
+        [2, height, width] each, taken as the ingest rule of this class takes any stack (the cameras' sensors may differ);
+        cameras: the two piv_stereo cameras; plane: the piv_stereo plane whose grid both are dewarped to.  On the current
+        stream, in this order: the coefficients and one dewarp launch per camera; per camera the chain that `evaluate` names
+        on the dewarped pair -- "correlate" (one pass of ``correlate``), "deform" (``correlate_deform``) or "multigrid"
+        (``correlate_multigrid``), the same code paths those drivers run -- with the camera's dewarp mask as the chain's mask
+        when a pixel of the plane is outside that camera's frame; with sigma=True ``displacement_uncertainty``'s chain per
+        camera; the reconstruction.  The host waits once, for the result.
+        settings: the chain's options by their names in those drivers -- win (32), step (16), radius, method, window_sigma,
+        diameter, min_valid_fraction, weighting; for "deform" and "multigrid" iterations (3, or one per level), residual_radius,
+        smooth, eps, threshold; for "multigrid" schedule; reach (2) for sigma.  An unknown name is refused.
+        Returns numpy (out f64 [n_rows, n_cols, 8] = dX, dY, dZ in world units, the stereo residual in image pixels,
+        sigma_X, sigma_Y, sigma_Z (NaN without sigma=True), the pivot ratio; status int32 [n_rows, n_cols] = the two cameras'
+        status or-ed, 64 = degenerate geometry, 128 = a camera's vector is not finite (masked out, flat); the two cameras'
+        2-C fields (vectors1, vectors2) [n_rows, n_cols, 4] = dx, dy in dewarped pixels, peak, ratio)."""
+        import torch
+        from . import piv_multigrid as pm
+        from . import piv_uncertainty as pu
+        known = {"win": 32, "step": 16, "radius": None, "method": "direct", "window_sigma": None, "diameter": 2.5, "min_valid_fraction": 0.5,
+                 "weighting": None, "iterations": None, "residual_radius": 4, "smooth": True, "eps": 0.1, "threshold": 2.0, "schedule": None,
+                 "reach": 2}
+        unknown = sorted(set(settings or {}) - set(known))
+        if unknown:
+            raise ValueError(f"correlate_stereo: unknown settings {unknown}; known: {sorted(known)}")
+        s = {**known, **(settings or {})}
+        if evaluate not in ("correlate", "deform", "multigrid"):
+            raise ValueError(f'evaluate must be "correlate", "deform" or "multigrid", not {evaluate!r}')
+        if len(cameras) != 2:
+            raise ValueError("correlate_stereo takes two cameras")
+        stacks = [_checked(x, name, 3) for x, name in ((cam1_frames, "cam1_frames"), (cam2_frames, "cam2_frames"))]
+        for x, name in zip(stacks, ("cam1_frames", "cam2_frames")):
+            if x is None or x.shape[0] != 2:
+                raise ValueError(f"{name} must be the two exposures of a camera, [2, height, width]")
+        shape = (int(plane["height"]), int(plane["width"]))
+        if evaluate == "multigrid":
+            schedule = ((64, 32), (32, 16), (16, 8)) if s["schedule"] is None else s["schedule"]
+            iterations = (1, 1, 2) if s["iterations"] is None else s["iterations"]
+        else:
+            schedule = ((s["win"], s["step"]),)
+            iterations = (0 if evaluate == "correlate" else 3 if s["iterations"] is None else s["iterations"],)
+        schedule, iterations = pm.check_schedule(shape, schedule, iterations, s["radius"], s["residual_radius"], s["method"], s["window_sigma"],
+                                                 s["diameter"])
+        win, step = schedule[-1]
+        if sigma:
+            pu.check_arguments(shape, win, step, s["reach"])
+        chain = _DeformSettings(s["radius"], s["residual_radius"], s["smooth"], s["eps"], s["threshold"])
+        dev, stream = _device_and_stream()
+        fields, statuses, sigmas = [], [], []
+        for x, name, camera in zip(stacks, ("cam1_frames", "cam2_frames"), cameras):
+            frames, outside, any_outside = self._dewarp_queued(_on_device(x, torch.float32, dev, name, 3), camera, plane, stream)
+            correlator = _Correlator([w for w, _ in schedule], s["method"], window_sigma=s["window_sigma"], diameter=s["diameter"],
+                                     mask=outside if any_outside else None, min_valid_fraction=s["min_valid_fraction"],
+                                     weighting=s["weighting"]).on_device(self, shape, dev)
+            if evaluate == "correlate":
+                correlate, radius, check = correlator.at(win, s["radius"])
+                check(shape, win, step, radius)
+                vec, status, _ = correlate(frames[0].data_ptr(), frames[1].data_ptr(), shape[1], shape[0], win, step, radius, stream=stream)
+            else:
+                field, vec, status = self._deform_chain(frames[0], frames[1], schedule, iterations, correlator, chain)
+                vec = torch.cat([field, vec[..., 2:4]], dim=-1)
+            if any_outside:
+                vec = _nan_where_masked_out(vec, status)
+            fields.append(vec.contiguous())
+            statuses.append(status)
+            if sigma:
+                sigmas.append(self._uncertainty_chain(frames[0], frames[1], fields[-1], win, step, s["reach"], stream)[0])
+        out, flags = self.piv_stereo_reconstruct(fields[0].data_ptr(), fields[1].data_ptr(), 4, cameras, plane, win, step,
+                                                 statuses[0].data_ptr(), statuses[1].data_ptr(), *(t.data_ptr() for t in sigmas), stream=stream)
+        return out.cpu().numpy(), flags.cpu().numpy(), (fields[0].cpu().numpy(), fields[1].cpu().numpy())
 
     # ---- dense optical flow on the device (section 12) --------------------------------------------------------------------
     def field_to_pixels(self, d_field_ptr: int, field_stride: int, n_rows: int, n_cols: int, win: int, step: int, width: int, height: int,
