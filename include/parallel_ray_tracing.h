@@ -1376,9 +1376,11 @@ int photon_piv_window_weights(int win, int kind, float param, float *weights);
 /* ------------------------------------------------------------------------------------
  * Section 19: stereo PIV -- the frames of two cameras that look at one light sheet from two sides, resampled onto one grid
  * on the sheet's plane (dewarp), correlated there by any correlator of this header, and the two 2-C fields combined into
- * three components per node (reconstruct).  Host models, the camera fit and the test generators: photon_amd/piv_stereo.py.
- * Both entry points take one pointer to a job struct (host memory, read during the call, not kept); the last member is the
- * stream.  Neither allocates device memory.
+ * three components per node (reconstruct); and the disparity between the two dewarped views of one instant triangulated
+ * into points of the sheet (triangulate), from which the host corrects the cameras for a sheet that is not at the plane.
+ * Host models, the camera fit, the sheet fit and the test generators: photon_amd/piv_stereo.py.
+ * Every entry point takes one pointer to a job struct (host memory, read during the call, not kept); the last member is the
+ * stream.  None allocates device memory.
  *
  * Camera (photon_piv_camera_t): Soloff's polynomial from world (X, Y, Z) to image (x, y) in pixels, x = column, y = row.
  * With q = ((X, Y, Z) - centre) / scale per component, and the 19 terms T_k(q), cubic in X and Y, quadratic in Z, in this order:
@@ -1440,15 +1442,50 @@ int photon_piv_window_weights(int win, int kind, float param, float *weights);
  *    finite: the first seven outputs NaN, the ratio reported).  Host model: piv_stereo.reconstruct_model (the same
  *    operations; agreement to 1e-12).
  *    This is a first-order reconstruction: the Jacobian is taken at the plane, at the window centre, not at the
- *    half-displaced particle positions, so a displacement sees the camera's curvature (perspective) only to first order;
- *    and no disparity (self-calibration) correction is applied -- a sheet that is not at plane.z shows up in the residual.
+ *    half-displaced particle positions, so a displacement sees the camera's curvature (perspective) only to first order.
+ *    The reconstruction itself applies no disparity correction: a sheet that is not at plane.z is found from the disparity
+ *    of the two views (c, below) and repaired in the cameras before this call (PhotonLibrary.self_calibrate_stereo).
  *    d_out == NULL: the size query -- *rows_out, *cols_out (where given) receive section 5's grid of the plane, nothing is
  *    launched, n_rows and n_cols are not read.  Refused (1, one stderr line, nothing written, no launch): a null job;
  *    section 5's rules for win, step and the plane's size; with d_out: n_rows x n_cols that is not that grid, a null
  *    d_field1, d_field2 or d_flags, field_stride not 2 or 4, one sigma without the other; a plane or camera value that is
  *    not finite, pitch <= 0, a camera scale of 0.  Asynchronous on `stream`; two calls return the same bits.
  *
- * Driver: PhotonLibrary.dewarp and PhotonLibrary.correlate_stereo.  DESIGN.md section 4.3w. */
+ * c. photon_piv_stereo_triangulate: the world points of a disparity field (self-calibration after Wieneke 2005).
+ *    d_disparity: device f32[n][field_stride] with dx, dy first (field_stride 2 or 4), in dewarped pixels, on section 5's grid
+ *    (win, step) of the plane: the displacement from camera 1's dewarped frame to camera 2's dewarped frame of the same
+ *    instant -- what photon_piv_correlate_ensemble returns for (dewarped stack of camera 1, dewarped stack of camera 2);
+ *    d_flags_in: its int[n] flags, or NULL (read as 0).  A sheet at plane.z has no disparity; particles off the plane are
+ *    seen by the two cameras at two points of the plane, half the disparity to either side of the window centre.
+ *    Per node k = i n_cols + j, one thread, in f64 without fused multiply-add:
+ *      1. P = the window centre on the plane, b's expression.
+ *      2. h = (pitch / 2.0) (dx, dy);  P1 = (P_X - h_x, P_Y - h_y, z),  P2 = (P_X + h_x, P_Y + h_y, z).
+ *      3. x1 = M1(P1), x2 = M2(P2), M_c the camera: q as above, the 19 terms T_k in the order and with the products above
+ *         (X^3 = (X X) X, X Y^2 = (X Y) Y, Y^3 = (Y Y) Y, X^2 Z = (X X) Z, Y^2 Z = (Y Y) Z), each image coordinate summed
+ *         over k = 0 .. 18 from 0.0 of c[k] T_k.
+ *      4. W = P; `iterations` times (Gauss-Newton):  r = (x1 - M1(W), x2 - M2(W)), four values;  rows 2c, 2c + 1 of A are
+ *         the Jacobian J_c of b.1 at W;  N = A^T A and g = A^T r in b.3's order of sums;  b.3's Cholesky and pivot ratio;
+ *         not (ratio > 1e-12), a pivot <= 0 or NaN included: degenerate, the iterations end;  s = N^-1 g by b.4's
+ *         substitutions;  W = W + s per component.
+ *      5. r once more at the final W.
+ *    d_out f64[n][6] = W_X, W_Y, W_Z in world units; the triangulation error sqrt(sum from 0.0 of r_m r_m) in image
+ *    pixels -- how far the two lines of sight miss each other; the length sqrt((s_X s_X + s_Y s_Y) + s_Z s_Z) of the last
+ *    step in world units, which shows convergence without a second call; the smallest pivot ratio of the iterations (of a
+ *    degenerate iteration: that iteration's own).  d_flags int[n] = flags_in, plus 64 (an iteration was degenerate: the
+ *    first five outputs NaN) and 128 (dx or dy is not finite: the first five outputs NaN, no step taken, the ratio that of
+ *    the start point P).  Every node's six outputs and flag are written, nothing else.  Host model:
+ *    piv_stereo.triangulate_model (the same operations; agreement to 1e-12).
+ *    d_out == NULL: the size query, as b's.  Refused (1, one stderr line, nothing written, no launch): a null job;
+ *    section 5's rules for win, step and the plane's size; with d_out: n_rows x n_cols that is not that grid, a null
+ *    d_disparity or d_flags, field_stride not 2 or 4; iterations outside [1, 16]; a plane or camera value that is not
+ *    finite, pitch <= 0, a camera scale of 0.  Asynchronous on `stream`; allocates nothing; two calls return the same bits.
+ *    What the host does with the points -- the sheet Z = a + b X + c Y by least squares, the frame in which the sheet is
+ *    plane.z, the cameras refitted in that frame, the rounds -- is piv_stereo.fit_sheet, sheet_frame, move_camera and
+ *    self_calibrate_model; the driver is PhotonLibrary.self_calibrate_stereo.  Not done: the sheet's thickness from the
+ *    width of the disparity peak; any correction under a dewarp mask beyond leaving those nodes out.
+ *
+ * Drivers: PhotonLibrary.dewarp, PhotonLibrary.correlate_stereo and PhotonLibrary.self_calibrate_stereo.  DESIGN.md section
+ * 4.3w. */
 typedef struct photon_piv_camera_t {
     double centre[3], scale[3], cx[19], cy[19];
 } photon_piv_camera_t;
@@ -1480,8 +1517,21 @@ typedef struct photon_piv_stereo_t {
     int *rows_out, *cols_out;
     void *stream;
 } photon_piv_stereo_t;
+typedef struct photon_piv_triangulate_t {
+    const float *d_disparity;
+    int field_stride;
+    const int *d_flags_in;
+    int n_rows, n_cols, win, step, iterations;
+    photon_piv_plane_t plane;
+    photon_piv_camera_t camera1, camera2;
+    double *d_out;
+    int *d_flags;
+    int *rows_out, *cols_out;
+    void *stream;
+} photon_piv_triangulate_t;
 int photon_piv_dewarp(const photon_piv_dewarp_t *job);
 int photon_piv_stereo_reconstruct(const photon_piv_stereo_t *job);
+int photon_piv_stereo_triangulate(const photon_piv_triangulate_t *job);
 
 #ifdef __cplusplus
 }

@@ -1,13 +1,16 @@
 // photon_piv_stereo.hip - stereo PIV beside the planar correlators: the frames of a camera resampled onto a grid on the
-// light sheet's plane through the camera's polynomial, and two cameras' 2-C fields on that grid combined into three
-// components per node.  Definition: include/parallel_ray_tracing.h, section 19; host models: photon_amd/piv_stereo.py.
+// light sheet's plane through the camera's polynomial, two cameras' 2-C fields on that grid combined into three
+// components per node, and the disparity between the two dewarped views triangulated into points of the sheet.  Definition: include/parallel_ray_tracing.h, section 19; host models: photon_amd/piv_stereo.py.
 //
 //   dewarp_kernel        one thread per output pixel: two bivariate cubics in f64 (Horner, no division), the fraction taken
 //                        in f64 and rounded once, section 7b's weights and mirrors (piv_warp.hpp) computed once, then per
 //                        frame 16 coefficient taps gathered from global memory and one coalesced store
 //   reconstruct_kernel   one thread per node: two analytic 2 x 3 Jacobians, the 3 x 3 normal equations of four equations,
 //                        Cholesky, the residual and the propagated sigmas, all in f64 in a fixed order
-// Neither kernel needs device scratch or LDS, none writes what another thread reads: two calls return the same bits.
+//   triangulate_kernel   one thread per node of a disparity field between the two cameras' dewarped frames: the two image
+//                        points, then Gauss-Newton steps for the world point both saw -- per step two polynomial
+//                        evaluations, the two Jacobians and the 3 x 3 Cholesky of the reconstruction -- in f64 in a fixed order
+// No kernel needs device scratch or LDS, none writes what another thread reads: two calls return the same bits.
 #include <cmath>
 
 #include "photon_internal.hpp"
@@ -224,6 +227,128 @@ __global__ __launch_bounds__(kNodeThreads) void reconstruct_kernel(const StereoA
     a.flags[k] = flag;
 }
 
+// =============================================================================================
+// c. triangulation of a disparity field
+// =============================================================================================
+constexpr int kMaxTriangulateIterations = 16;
+
+struct TriangulateArgs {
+    const float *disparity;
+    const int *flags_in;
+    int stride, n_rows, n_cols, win, step, iterations;
+    photon_piv_plane_t plane;
+    photon_piv_camera_t cam[2];
+    double *out;
+    int *flags;
+};
+
+// (x, y) of the camera at the world point P: the 19 terms of section 19 in their order, each coordinate summed from 0.0
+__device__ __forceinline__ void image_point(const photon_piv_camera_t &c, const double P[3], double x[2]) {
+    const double X = (P[0] - c.centre[0]) / c.scale[0], Y = (P[1] - c.centre[1]) / c.scale[1], Z = (P[2] - c.centre[2]) / c.scale[2];
+    const double XX = X * X, XY = X * Y, YY = Y * Y, ZZ = Z * Z;
+    const double T[19] = {1.0, X, Y, Z, XX, XY, YY, X * Z, Y * Z, ZZ, XX * X, XX * Y, XY * Y, YY * Y, XX * Z, XY * Z, YY * Z, X * ZZ, Y * ZZ};
+    double sx = 0.0, sy = 0.0;
+#pragma unroll
+    for (int k = 0; k < 19; k++) {
+        sx = sx + c.cx[k] * T[k];
+        sy = sy + c.cy[k] * T[k];
+    }
+    x[0] = sx;
+    x[1] = sy;
+}
+
+// the four residuals (x1 - M1(W), x2 - M2(W)) of section 19c
+__device__ __forceinline__ void residuals(const TriangulateArgs &a, const double x1[2], const double x2[2], const double W[3], double r[4]) {
+    double m[2];
+    image_point(a.cam[0], W, m);
+    r[0] = x1[0] - m[0];
+    r[1] = x1[1] - m[1];
+    image_point(a.cam[1], W, m);
+    r[2] = x2[0] - m[0];
+    r[3] = x2[1] - m[1];
+}
+
+__global__ __launch_bounds__(kNodeThreads) void triangulate_kernel(const TriangulateArgs a) {
+    const int k = blockIdx.x * kNodeThreads + threadIdx.x;
+    if (k >= a.n_rows * a.n_cols) return;
+    const int i = k / a.n_cols, j = k - i * a.n_cols;
+    const double qnan = __builtin_nan(""), pitch = a.plane.pitch, half = (double)(a.win - 1) / 2.0;
+    const double P[3] = {a.plane.x0 + ((double)(j * a.step) + half) * pitch, a.plane.y0 + ((double)(i * a.step) + half) * pitch, a.plane.z};
+    const float *d = a.disparity + (size_t)k * a.stride;
+    const float dx = d[0], dy = d[1];
+    const bool finite = isfinite(dx) && isfinite(dy);
+    int flag = a.flags_in ? a.flags_in[k] : 0;
+
+    const double hx = (pitch / 2.0) * (double)dx, hy = (pitch / 2.0) * (double)dy;
+    const double P1[3] = {P[0] - hx, P[1] - hy, P[2]}, P2[3] = {P[0] + hx, P[1] + hy, P[2]};
+    double x1[2], x2[2];
+    image_point(a.cam[0], P1, x1);
+    image_point(a.cam[1], P2, x2);
+
+    double W[3] = {P[0], P[1], P[2]}, s[3] = {qnan, qnan, qnan}, r[4], lowest = qnan;
+    bool good = true;
+    for (int it = 0; it < a.iterations; it++) {
+        // one camera at a time, in a loop that stays a loop (the camera is read from the kernel arguments at a uniform offset):
+        // the 44 coefficients of one camera fit the scalar registers, those of two do not.  Rows 2c,
+        // 2c + 1 enter N and g in the order of section 19b's sums: (row 0 + row 1), + row 2, + row 3
+        double N[3][3], g[3];
+#pragma unroll 1
+        for (int c = 0; c < 2; c++) {
+            const photon_piv_camera_t &cam = a.cam[c];
+            double m[2], J[2][3];
+            image_point(cam, W, m);
+            const double r0 = (c == 0 ? x1[0] : x2[0]) - m[0], r1 = (c == 0 ? x1[1] : x2[1]) - m[1];
+            jacobian(cam, W, J);
+#pragma unroll
+            for (int p = 0; p < 3; p++) {
+#pragma unroll
+                for (int q = 0; q < 3; q++) {
+                    const double u = J[0][p] * J[0][q], v = J[1][p] * J[1][q];
+                    N[p][q] = c == 0 ? u + v : (N[p][q] + u) + v;
+                }
+                const double u = J[0][p] * r0, v = J[1][p] * r1;
+                g[p] = c == 0 ? u + v : (g[p] + u) + v;
+            }
+        }
+        Cholesky3 L;
+        const double d0 = N[0][0];
+        L.l00 = sqrt(d0);
+        L.l10 = N[1][0] / L.l00;
+        L.l20 = N[2][0] / L.l00;
+        const double d1 = N[1][1] - L.l10 * L.l10;
+        L.l11 = sqrt(d1);
+        L.l21 = (N[2][1] - L.l20 * L.l10) / L.l11;
+        const double d2 = (N[2][2] - L.l20 * L.l20) - L.l21 * L.l21;
+        L.l22 = sqrt(d2);
+        const double ratio = fmin(fmin(d0, d1), d2) / fmax(fmax(d0, d1), d2);
+        const bool ok = ratio > kMinPivotRatio && d0 > 0.0 && d1 > 0.0 && d2 > 0.0;
+        lowest = (ok && it > 0) ? (ratio < lowest ? ratio : lowest) : ratio;
+        if (!ok) good = false;
+        if (!ok || !finite) break;          // a vector that is not finite: the start point's ratio, no step
+        L.solve(g, s);
+        W[0] = W[0] + s[0];
+        W[1] = W[1] + s[1];
+        W[2] = W[2] + s[2];
+    }
+    double out[6] = {qnan, qnan, qnan, qnan, qnan, lowest};
+    if (good && finite) {
+        residuals(a, x1, x2, W, r);
+        double ss = 0.0;
+#pragma unroll
+        for (int m = 0; m < 4; m++) ss = ss + r[m] * r[m];
+        out[0] = W[0];
+        out[1] = W[1];
+        out[2] = W[2];
+        out[3] = sqrt(ss);
+        out[4] = sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]);
+    }
+    if (!good) flag |= 64;
+    if (!finite) flag |= 128;
+#pragma unroll
+    for (int m = 0; m < 6; m++) a.out[6 * (size_t)k + m] = out[m];
+    a.flags[k] = flag;
+}
+
 bool all_finite(const double *v, int n) {
     for (int i = 0; i < n; i++)
         if (!std::isfinite(v[i])) return false;
@@ -303,6 +428,43 @@ extern "C" int photon_piv_stereo_reconstruct(const photon_piv_stereo_t *job) {
     a.out = job->d_out, a.flags = job->d_flags;
     const unsigned blocks = (unsigned)(((long long)rows * cols + kNodeThreads - 1) / kNodeThreads);
     hipLaunchKernelGGL(reconstruct_kernel, dim3(blocks), dim3(kNodeThreads), 0, (hipStream_t)job->stream, a);
+    PH_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int photon_piv_stereo_triangulate(const photon_piv_triangulate_t *job) {
+    if (!job) {
+        fprintf(stderr, "photon: photon_piv_stereo_triangulate: null job\n");
+        return 1;
+    }
+    const photon_piv_plane_t &pl = job->plane;
+    const char *bad = piv_grid::grid_error(pl.width, pl.height, job->win, job->step);
+    if (!bad && job->d_out) bad = piv_grid::grid_error(pl.width, pl.height, job->win, job->step, job->n_rows, job->n_cols);
+    if (!bad && job->d_out) {
+        if (!job->d_disparity || !job->d_flags) bad = "null d_disparity or d_flags";
+        else if (job->field_stride != 2 && job->field_stride != 4) bad = "field_stride must be 2 or 4";
+    }
+    if (!bad) {
+        if (job->iterations < 1 || job->iterations > kMaxTriangulateIterations) bad = "iterations must be within [1, 16]";
+        else if (!(std::isfinite(pl.x0) && std::isfinite(pl.y0) && std::isfinite(pl.z) && std::isfinite(pl.pitch))) bad = "a plane value is not finite";
+        else if (!(pl.pitch > 0.0)) bad = "pitch must be > 0";
+        else if (!camera_ok(job->camera1) || !camera_ok(job->camera2)) bad = "a camera value is not finite, or a scale is 0";
+    }
+    if (bad) {
+        fprintf(stderr, "photon: photon_piv_stereo_triangulate: %s (win %d, step %d, %d x %d plane, %d x %d grid, stride %d, %d iterations)\n", bad,
+                job->win, job->step, pl.width, pl.height, job->n_rows, job->n_cols, job->field_stride, job->iterations);
+        return 1;
+    }
+    int rows, cols;
+    PH_TRY(piv_grid::grid_size("photon_piv_stereo_triangulate", pl.width, pl.height, job->win, job->step, rows, cols, job->rows_out, job->cols_out));
+    if (!job->d_out) return 0;                  // the size query
+    TriangulateArgs a;
+    a.disparity = job->d_disparity, a.flags_in = job->d_flags_in;
+    a.stride = job->field_stride, a.n_rows = rows, a.n_cols = cols, a.win = job->win, a.step = job->step, a.iterations = job->iterations;
+    a.plane = pl, a.cam[0] = job->camera1, a.cam[1] = job->camera2;
+    a.out = job->d_out, a.flags = job->d_flags;
+    const unsigned blocks = (unsigned)(((long long)rows * cols + kNodeThreads - 1) / kNodeThreads);
+    hipLaunchKernelGGL(triangulate_kernel, dim3(blocks), dim3(kNodeThreads), 0, (hipStream_t)job->stream, a);
     PH_CHECK(hipGetLastError());
     return 0;
 }

@@ -5,7 +5,7 @@ Three layers, top to bottom of the file:
     loaded library.  The header is the source of truth; tests/test_abi.py holds the table against its prototypes.
   * ``PhotonLibrary``: one method per entry point -- marshalling only, raw device pointers in, return code checked -- and
     on top of those the pipelines that chain several calls on torch-allocated device buffers on the current stream
-    (``preprocess_series``, ``correlate``, ``correlate_deform``, ``correlate_stereo``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
+    (``preprocess_series``, ``correlate``, ``correlate_deform``, ``correlate_stereo``, ``self_calibrate_stereo``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
     ``integrate_gradient``, the tomography solvers).
   * ``Volume``, ``Sources``, ``Flow``, ``Scene``: the library's handles.
 All arithmetic is the HIP library's.  There is no Python or CPU fallback -- if the library is missing or a call fails,
@@ -99,6 +99,14 @@ class photon_piv_stereo_t(ctypes.Structure):
                 ("n_cols", ctypes.c_int), ("win", ctypes.c_int), ("step", ctypes.c_int), ("plane", photon_piv_plane_t),
                 ("camera1", photon_piv_camera_t), ("camera2", photon_piv_camera_t), ("d_out", ctypes.c_void_p), ("d_flags", ctypes.c_void_p),
                 ("rows_out", ctypes.POINTER(ctypes.c_int)), ("cols_out", ctypes.POINTER(ctypes.c_int)), ("stream", ctypes.c_void_p)]
+
+
+class photon_piv_triangulate_t(ctypes.Structure):
+    _fields_ = [("d_disparity", ctypes.c_void_p), ("field_stride", ctypes.c_int), ("d_flags_in", ctypes.c_void_p), ("n_rows", ctypes.c_int),
+                ("n_cols", ctypes.c_int), ("win", ctypes.c_int), ("step", ctypes.c_int), ("iterations", ctypes.c_int),
+                ("plane", photon_piv_plane_t), ("camera1", photon_piv_camera_t), ("camera2", photon_piv_camera_t), ("d_out", ctypes.c_void_p),
+                ("d_flags", ctypes.c_void_p), ("rows_out", ctypes.POINTER(ctypes.c_int)), ("cols_out", ctypes.POINTER(ctypes.c_int)),
+                ("stream", ctypes.c_void_p)]
 
 
 def _signatures():
@@ -226,6 +234,7 @@ def _signatures():
         # section 19: stereo PIV (one job struct each; its last member is the stream)
         "photon_piv_dewarp": (ci, [P(photon_piv_dewarp_t)]),
         "photon_piv_stereo_reconstruct": (ci, [P(photon_piv_stereo_t)]),
+        "photon_piv_stereo_triangulate": (ci, [P(photon_piv_triangulate_t)]),
     }
 
 
@@ -268,14 +277,14 @@ def _dims(n):
     return int(nx), int(ny), int(nz)
 
 
-def _stereo_job(cameras, plane, win: int, step: int) -> photon_piv_stereo_t:
-    """Section 19b's job with its host values -- the two cameras and the plane (piv_stereo's dicts), win and step -- and every
-    pointer NULL: as it stands, the size query."""
-    job = photon_piv_stereo_t(win=int(win), step=int(step))
+def _stereo_job(cameras, plane, win: int, step: int, kind=photon_piv_stereo_t):
+    """Section 19b's job (kind photon_piv_triangulate_t: 19c's) with its host values -- the two cameras and the plane
+    (piv_stereo's dicts), win and step -- and every pointer NULL: as it stands, the size query."""
+    job = kind(win=int(win), step=int(step))
     job.plane = photon_piv_plane_t(float(plane["x0"]), float(plane["y0"]), float(plane["pitch"]), float(plane["z"]), int(plane["width"]),
                                    int(plane["height"]))
     if len(cameras) != 2:
-        raise ValueError("section 19b takes two cameras")
+        raise ValueError("section 19 takes two cameras")
     for name, cam in zip(("camera1", "camera2"), cameras):
         c = getattr(job, name)
         for key, n in (("centre", 3), ("scale", 3), ("cx", 19), ("cy", 19)):
@@ -1214,6 +1223,27 @@ class PhotonLibrary:
         self._call("photon_piv_stereo_reconstruct", ctypes.byref(job))
         return out, flags
 
+    def piv_stereo_triangulate(self, d_disparity_ptr: int, field_stride: int, cameras, plane, win: int, step: int, iterations: int = 4,
+                               d_flags_in_ptr: int = 0, stream: int = 0):
+        """photon_piv_stereo_triangulate on raw device pointers: the disparity field f32 [n_rows, n_cols, field_stride] between
+        the two cameras' dewarped frames on section 5's grid (win, step) of the plane and its flags (0 = NULL), the two
+        cameras and the plane (piv_stereo's dicts).  Returns torch device tensors (out f64 [n_rows, n_cols, 6] = X, Y, Z, the
+        triangulation error, the last step's length, the smallest pivot ratio; flags int32 [n_rows, n_cols]), filled
+        asynchronously on `stream`."""
+        import torch
+        job = _stereo_job(cameras, plane, win, step, photon_piv_triangulate_t)
+        job.iterations = int(iterations)
+        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
+        job.rows_out, job.cols_out = ctypes.pointer(rows), ctypes.pointer(cols)
+        self._call("photon_piv_stereo_triangulate", ctypes.byref(job))                   # the size query
+        dev = _current_device()
+        out = torch.empty((rows.value, cols.value, 6), dtype=torch.float64, device=dev)
+        flags = torch.empty((rows.value, cols.value), dtype=torch.int32, device=dev)
+        job.d_disparity, job.field_stride, job.d_flags_in = int(d_disparity_ptr) or None, int(field_stride), int(d_flags_in_ptr) or None
+        job.n_rows, job.n_cols, job.d_out, job.d_flags, job.stream = rows.value, cols.value, out.data_ptr(), flags.data_ptr(), int(stream) or None
+        self._call("photon_piv_stereo_triangulate", ctypes.byref(job))
+        return out, flags
+
     def _dewarp_queued(self, stack, camera, plane, stream: int):
         """The device stack f32 [n, h, w] of one camera's frames onto the plane, queued on `stream`: the coefficients of every
         frame (section 7a), then one dewarp launch for all of them.  Returns (frames [n, plane height, plane width], mask u8
@@ -1320,6 +1350,69 @@ class PhotonLibrary:
         out, flags = self.piv_stereo_reconstruct(fields[0].data_ptr(), fields[1].data_ptr(), 4, cameras, plane, win, step,
                                                  statuses[0].data_ptr(), statuses[1].data_ptr(), *(t.data_ptr() for t in sigmas), stream=stream)
         return out.cpu().numpy(), flags.cpu().numpy(), (fields[0].cpu().numpy(), fields[1].cpu().numpy())
+
+    def self_calibrate_stereo(self, cam1_frames, cam2_frames, cameras, plane, win: int = 64, step: int = 32, radius: Optional[int] = None,
+                              passes: int = 1, rounds: int = 3, iterations: int = 4, tolerance: float = 0.05, timings: Optional[list] = None):
+        """The two cameras corrected for a light sheet that is not where the calibration target stood (section 19c; model:
+        photon_amd.piv_stereo.self_calibrate_model).  cam1_frames, cam2_frames: stacks [N, height, width], frame k of both
+        cameras the same instant, taken as the ingest rule of this class takes any stack; cameras, plane: piv_stereo's
+        dicts.  Per round, with the current cameras, on the current stream: the coefficients and one dewarp launch per camera;
+        the ensemble correlation of the two dewarped stacks (``piv_correlate_ensemble``, what ``correlate_ensemble`` runs;
+        passes=2, for disparities beyond the radius, adds its host step and second pass); the triangulation; one host wait;
+        then on the host piv_stereo.selfcal_round -- the nodes under a dewarp mask left out, fit_sheet, sheet_frame,
+        move_camera on both cameras.  The rounds end early once the rms disparity is below `tolerance` px.
+        Returns (cameras, report) as the model does; hand the cameras to ``correlate_stereo``, which is unchanged.
+        timings: a list that receives per round a dict of device milliseconds (dewarp, correlate, triangulate) measured with
+        events; the waits this needs are extra, so leave it None outside a tool."""
+        import torch
+        from . import piv_correlation as pc
+        from . import piv_stereo as ps
+        passes = _checked_passes(passes)
+        radius = int(win) // 2 if radius is None else int(radius)
+        if len(cameras) != 2:
+            raise ValueError("self_calibrate_stereo takes two cameras")
+        if int(rounds) < 1:
+            raise ValueError("rounds must be >= 1")
+        if not 1 <= int(iterations) <= ps.MAX_TRIANGULATE_ITERATIONS:
+            raise ValueError(f"iterations must be within [1, {ps.MAX_TRIANGULATE_ITERATIONS}]")
+        names = ("cam1_frames", "cam2_frames")
+        stacks = [_checked(x, name, 3) for x, name in zip((cam1_frames, cam2_frames), names)]
+        if stacks[0] is None or stacks[1] is None or stacks[0].shape[0] != stacks[1].shape[0] or stacks[0].shape[0] < 1:
+            raise ValueError("cam1_frames and cam2_frames must be two stacks [N, height, width] of the same N >= 1 instants")
+        oh, ow = int(plane["height"]), int(plane["width"])
+        pc.check_arguments((oh, ow), win, step, radius)
+        dev, stream = _device_and_stream()
+        device_stacks = [_on_device(x, torch.float32, dev, name, 3) for x, name in zip(stacks, names)]
+        n = int(device_stacks[0].shape[0])
+
+        def mark():
+            if timings is None:
+                return None
+            event = torch.cuda.Event(enable_timing=True)
+            event.record()
+            return event
+        cameras, frame, entries = tuple(cameras), ps.identity_frame(plane), []
+        for _ in range(int(rounds)):
+            t0 = mark()
+            dewarped = [self._dewarp_queued(x, camera, plane, stream) for x, camera in zip(device_stacks, cameras)]
+            t1 = mark()
+            correlate = lambda off: self.piv_correlate_ensemble(dewarped[0][0].data_ptr(), dewarped[1][0].data_ptr(), oh * ow, n, ow, oh, win,      # noqa: E731
+                                                                step, radius, off, stream=stream)
+            found = correlate(0) if passes == 1 else _two_passes(correlate, passes, dev)[2]
+            t2 = mark()
+            points, flags = self.piv_stereo_triangulate(found[0].data_ptr(), 4, cameras, plane, win, step, iterations, found[1].data_ptr(), stream)
+            t3 = mark()
+            points, flags, vectors = points.cpu().numpy(), flags.cpu().numpy(), found[0].cpu().numpy()      # the host waits here
+            outside = [ps.outside_mask(*ps.plane_coefficients(camera, plane), (oh, ow), tuple(x.shape[1:]))
+                       for x, camera in zip(device_stacks, cameras)]
+            cameras, moved, entry = ps.selfcal_round(points, flags, vectors, outside, cameras, plane, win, step)
+            frame = ps.compose_frames(frame, moved)
+            entries.append(entry)
+            if timings is not None:
+                timings.append(dict(dewarp=t0.elapsed_time(t1), correlate=t1.elapsed_time(t2), triangulate=t2.elapsed_time(t3)))
+            if entry["disparity_rms"] < tolerance:
+                break
+        return cameras, ps.selfcal_report(entries, frame)
 
     # ---- dense optical flow on the device (section 12) --------------------------------------------------------------------
     def field_to_pixels(self, d_field_ptr: int, field_stride: int, n_rows: int, n_cols: int, win: int, step: int, width: int, height: int,

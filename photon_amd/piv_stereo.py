@@ -18,8 +18,19 @@ The device forms are photon_piv_dewarp and photon_piv_stereo_reconstruct (includ
 A camera is a dict centre[3], scale[3], cx[19], cy[19] (f64); a plane a dict x0, y0, pitch, z, width, height: dewarped
 pixel (row i, column j) is the world point (x0 + j pitch, y0 + i pitch, z).
 
+Self-calibration (Wieneke 2005; section 19c): a sheet that is not where the calibration target stood shows as a disparity
+between the two cameras' dewarped frames of one instant.  ``triangulate_model`` (the model of
+photon_piv_stereo_triangulate) turns that disparity field into world points, ``fit_sheet`` fits Z = a + b X + c Y to them,
+``sheet_frame`` and ``move_camera`` re-express both cameras in coordinates in which the sheet is the plane's z, and
+``self_calibrate_model`` runs the rounds (the model of ``PhotonLibrary.self_calibrate_stereo``).  ``sheet_frames`` and
+``sheet_pair`` render particles in a displaced sheet; ``SELFCAL_CASE`` and ``selfcal_figures`` are the case the tests and
+the tool measure.
+
 The reconstruction is first order: the Jacobian is taken at the plane, at the window centre, not at the half-displaced
-particle positions; and nothing corrects a sheet that is not where the calibration says (no disparity correction).
+particle positions.  A sheet that is not where the calibration says is found and corrected by the self-calibration above,
+before ``correlate_stereo`` and by the caller: the reconstruction itself applies no correction.  What does not exist: an
+estimate of the sheet's thickness from the width of the disparity peak, and any correction under a dewarp mask beyond
+leaving those nodes out of the sheet fit.
 """
 from __future__ import annotations
 
@@ -329,6 +340,233 @@ def correlate_stereo_model(cam1_frames, cam2_frames, cameras, pl, win: int = 32,
     return out, flags, tuple(vectors)
 
 
+# ---- self-calibration: the sheet from the disparity of the two views (section 19c) ---------------------------------------------
+UNUSABLE = pc.FLAG_EDGE_PEAK | pc.FLAG_FLAT | 16 | FLAG_DEGENERATE | FLAG_NOT_FINITE       # 16: masked out; bit 4 (outside) stays in
+MAX_TRIANGULATE_ITERATIONS = 16
+
+
+def _image(cam, P):
+    """(x, y) of the world points P [..., 3] in section 19c's order: each coordinate summed from 0.0 over the 19 terms."""
+    t = _terms(_normalised(cam, P))
+    x = y = np.zeros(t.shape[:-1])
+    for k in range(N_TERMS):
+        x = x + cam["cx"][k] * t[..., k]
+        y = y + cam["cy"][k] * t[..., k]
+    return x, y
+
+
+def triangulate_model(disparity, cameras, pl, win: int, step: int, iterations: int, flags=None):
+    """Host model of photon_piv_stereo_triangulate, operation by operation (section 19c).  disparity [n_rows, n_cols, >= 2]
+    (dx, dy first: the displacement from camera 1's dewarped frame to camera 2's of the same instant, in dewarped pixels;
+    taken as given -- the device reads f32) on section 5's grid of the plane; flags int [n_rows, n_cols] or None.  Returns
+    (out f64 [n_rows, n_cols, 6] = X, Y, Z of the world point both cameras saw, the triangulation error in image pixels, the
+    length of the last Gauss-Newton step in world units, the smallest pivot ratio of the iterations; flags int32 with 64 = an
+    iteration was degenerate and 128 = dx or dy not finite, the first five outputs NaN for either)."""
+    grid = pc.grid_shape((pl["height"], pl["width"]), win, step)
+    d = np.asarray(disparity, np.float64)[..., :2]
+    if d.shape != grid + (2,):
+        raise ValueError(f"the disparity must be [{grid[0]}, {grid[1]}, >= 2]: the grid of the plane, win {win}, step {step}")
+    if not 1 <= int(iterations) <= MAX_TRIANGULATE_ITERATIONS:
+        raise ValueError(f"iterations must be within [1, {MAX_TRIANGULATE_ITERATIONS}]")
+    if len(cameras) != 2:
+        raise ValueError("the triangulation takes two cameras")
+    P, pitch = window_centres(pl, win, step), pl["pitch"]
+    finite = np.isfinite(d).all(axis=-1)
+    with np.errstate(all="ignore"):
+        hx, hy = (pitch / 2.0) * d[..., 0], (pitch / 2.0) * d[..., 1]
+        P1, P2 = P.copy(), P.copy()
+        P1[..., 0], P1[..., 1] = P[..., 0] - hx, P[..., 1] - hy
+        P2[..., 0], P2[..., 1] = P[..., 0] + hx, P[..., 1] + hy
+        x = (*_image(cameras[0], P1), *_image(cameras[1], P2))                      # x1, y1, x2, y2
+
+        def residual(W):
+            m = (*_image(cameras[0], W), *_image(cameras[1], W))
+            return [x[k] - m[k] for k in range(4)]
+
+        W = P.copy()
+        alive, good = finite.copy(), np.ones(grid, bool)         # alive: still iterating; a node that is not keeps what it has
+        lowest = np.full(grid, np.nan)
+        s = [np.full(grid, np.nan) for _ in range(3)]
+        for it in range(int(iterations)):
+            todo = alive | ((it == 0) & ~finite)                                    # a vector that is not finite: the start point's ratio
+            r = residual(W)
+            J = [jacobian(cam, W) for cam in cameras]
+            A = [J[c][..., q, :] for c in range(2) for q in range(2)]
+            N = [[((A[0][..., p] * A[0][..., q] + A[1][..., p] * A[1][..., q]) + A[2][..., p] * A[2][..., q]) + A[3][..., p] * A[3][..., q]
+                  for q in range(3)] for p in range(3)]
+            g = [((A[0][..., p] * r[0] + A[1][..., p] * r[1]) + A[2][..., p] * r[2]) + A[3][..., p] * r[3] for p in range(3)]
+            d0 = N[0][0]
+            l00 = np.sqrt(d0)
+            l10, l20 = N[1][0] / l00, N[2][0] / l00
+            d1 = N[1][1] - l10 * l10
+            l11 = np.sqrt(d1)
+            l21 = (N[2][1] - l20 * l10) / l11
+            d2 = (N[2][2] - l20 * l20) - l21 * l21
+            ratio = np.minimum(np.minimum(d0, d1), d2) / np.maximum(np.maximum(d0, d1), d2)
+            ok = (ratio > MIN_PIVOT_RATIO) & (d0 > 0.0) & (d1 > 0.0) & (d2 > 0.0)
+            lowest = np.where(todo, np.where(ok & (it > 0), np.where(ratio < lowest, ratio, lowest), ratio), lowest)
+            good &= ~(todo & ~ok)
+            alive &= ok
+            ds = _solve((l00, l10, l20, l11, l21, np.sqrt(d2)), g)
+            for p in range(3):
+                s[p] = np.where(alive, ds[p], s[p])
+                W[..., p] = np.where(alive, W[..., p] + ds[p], W[..., p])
+        r = residual(W)
+        ss = np.zeros(grid)
+        for m in range(4):
+            ss = ss + r[m] * r[m]
+        out = np.full(grid + (6,), np.nan)
+        out[..., :3], out[..., 3], out[..., 4], out[..., 5] = W, np.sqrt(ss), np.sqrt((s[0] * s[0] + s[1] * s[1]) + s[2] * s[2]), lowest
+    out[~(finite & good), :5] = np.nan
+    result = np.zeros(grid, np.int32) if flags is None else np.array(flags, np.int32)
+    result |= np.where(good, 0, FLAG_DEGENERATE).astype(np.int32) | np.where(finite, 0, FLAG_NOT_FINITE).astype(np.int32)
+    return out, result
+
+
+def usable_nodes(flags) -> np.ndarray:
+    """bool: the nodes the sheet fit may use -- none of the bits 1 (edge peak), 2 (flat), 16 (masked out), 64, 128."""
+    return (np.asarray(flags) & UNUSABLE) == 0
+
+
+def fit_sheet(points, flags, error=None):
+    """Z = a + b X + c Y by least squares over the usable nodes (usable_nodes; finite X, Y, Z) of points [..., >= 3] with
+    flags [...]: three fixed rounds of rejection, each dropping the nodes whose residual lies more than 3 x 1.4826 x MAD
+    from the residuals' median (differences at rounding level, 1e-12 of the coordinates, never count), then the final fit.  error [...] (the triangulation error, optional): a node whose error
+    is not finite is left out from the start.
+    Returns ((a, b, c), rms residual, nodes used); raises ValueError when fewer than 6 nodes remain or X or Y has no spread."""
+    pts = np.asarray(points, np.float64)
+    pts = pts.reshape(-1, pts.shape[-1])[:, :3]
+    keep = usable_nodes(flags).reshape(-1) & np.isfinite(pts).all(axis=-1)
+    if keep.shape[0] != pts.shape[0]:
+        raise ValueError("points and flags must describe the same nodes")
+    if error is not None:
+        keep &= np.isfinite(np.asarray(error, np.float64).reshape(-1))
+
+    def fit(sel):
+        if sel.sum() < 6:
+            raise ValueError(f"the sheet fit needs at least 6 usable nodes, {int(sel.sum())} remain")
+        X, Y, Z = pts[sel].T
+        if np.ptp(X) == 0.0 or np.ptp(Y) == 0.0:
+            raise ValueError("the usable nodes have no spread in X or in Y: no sheet can be fitted")
+        mx, my = X.mean(), Y.mean()
+        sol = np.linalg.lstsq(np.stack([np.ones_like(X), X - mx, Y - my], axis=-1), Z, rcond=None)[0]
+        abc = np.array([sol[0] - sol[1] * mx - sol[2] * my, sol[1], sol[2]])
+        return abc, pts[:, 2] - (abc[0] + abc[1] * pts[:, 0] + abc[2] * pts[:, 1])
+
+    floor = 1e-12 * (1.0 + float(np.abs(pts[keep]).max())) if keep.any() else 0.0          # rounding is no outlier: exact points have MAD 0
+    for _ in range(3):
+        abc, res = fit(keep)
+        med = np.median(res[keep])
+        keep = keep & (np.abs(res - med) <= max(3.0 * 1.4826 * np.median(np.abs(res[keep] - med)), floor))
+    abc, res = fit(keep)
+    return (float(abc[0]), float(abc[1]), float(abc[2])), float(np.sqrt(np.mean(res[keep] ** 2))), int(keep.sum())
+
+
+def sheet_frame(sheet, pl):
+    """(R, O, C) of coordinates in which the sheet Z = a + b X + c Y is the plane's own z: e3 = (-b, -c, 1) normalised, e1 =
+    the world X axis minus its part along e3, normalised, e2 = e3 x e1, R = [e1 e2 e3] as columns; C = the plane's centre (x_c,
+    y_c, z), O = (x_c, y_c, a + b x_c + c y_c).  A point W' of the new coordinates is the old world point O + R (W' - C)."""
+    a, b, c = (float(v) for v in sheet)
+    e3 = np.array([-b, -c, 1.0])
+    e3 /= np.linalg.norm(e3)
+    e1 = np.array([1.0, 0.0, 0.0]) - e3[0] * e3
+    e1 /= np.linalg.norm(e1)
+    R = np.stack([e1, np.cross(e3, e1), e3], axis=1)
+    xc, yc = pl["x0"] + (pl["width"] - 1) / 2.0 * pl["pitch"], pl["y0"] + (pl["height"] - 1) / 2.0 * pl["pitch"]
+    return R, np.array([xc, yc, a + b * xc + c * yc]), np.array([xc, yc, pl["z"]])
+
+
+def to_world(frame, P) -> np.ndarray:
+    """The old world points O + R (P - C) of the points P [..., 3] given in a frame (R, O, C)."""
+    R, O, C = frame
+    return O + (np.asarray(P, np.float64) - C) @ np.asarray(R).T
+
+
+def compose_frames(outer, inner):
+    """The frame that takes `inner`'s coordinates to `outer`'s world: O1 + R1 (O2 + R2 (W - C) - C) = (O1 + R1 (O2 - C)) + R1 R2 (W - C)."""
+    (R1, O1, C), (R2, O2, _) = outer, inner
+    return R1 @ R2, O1 + R1 @ (O2 - C), C
+
+
+def frame_sheet(frame):
+    """(a, b, c) of the plane Z' = z of a frame (R, O, C), in the world the frame maps to."""
+    R, O, _ = frame
+    b, c = -R[0, 2] / R[2, 2], -R[1, 2] / R[2, 2]
+    return float(O[2] - b * O[0] - c * O[1]), float(b), float(c)
+
+
+def move_camera(cam, R, O, C, pl):
+    """The camera in the coordinates of the frame (R, O, C): fit_camera on calibration_target(pl, 9, (-1, 0, 1)) against the
+    camera's images of the old world points O + R (target - C).  Returns (camera, rms, max) as fit_camera does: the refit's
+    residual says whether the moved camera is still within the 19-term family."""
+    target = calibration_target(pl, 9, (-1.0, 0.0, 1.0))
+    return fit_camera(target, map_points(cam, to_world((R, O, C), target)))
+
+
+def windows_touching(mask, win: int, step: int) -> np.ndarray:
+    """bool [n_rows, n_cols]: the windows of section 5's grid that hold a nonzero pixel of mask [height, width]."""
+    mask = np.asarray(mask) != 0
+    n_rows, n_cols = pc.grid_shape(mask.shape, win, step)
+    return np.array([[mask[i * step:i * step + win, j * step:j * step + win].any() for j in range(n_cols)] for i in range(n_rows)])
+
+
+def selfcal_round(points, flags, disparity, outside, cameras, pl, win: int, step: int):
+    """The host half of one self-calibration round, shared by the model and the device driver: the nodes whose window
+    touches a pixel that is outside either camera (outside: the two dewarp masks) leave with flag 16; fit_sheet on the rest;
+    sheet_frame; move_camera on both cameras.  Returns (cameras, frame (R, O, C), the round's report entry)."""
+    flags = np.array(flags, np.int32)
+    for mask in outside:
+        flags[windows_touching(mask, win, step)] |= 16
+    points, d = np.asarray(points, np.float64), np.asarray(disparity, np.float64)[..., :2]
+    ok = usable_nodes(flags) & np.isfinite(points[..., :5]).all(axis=-1)
+    if not ok.any():
+        raise ValueError("self-calibration: no usable disparity vector")
+    sheet, rms, used = fit_sheet(points, flags, points[..., 3])
+    frame = sheet_frame(sheet, pl)
+    moved = [move_camera(cam, *frame, pl) for cam in cameras]
+    entry = dict(disparity_rms=float(np.sqrt(np.mean(d[ok] ** 2))), sheet=sheet, sheet_rms=rms, nodes=used,
+                 error_median=float(np.median(points[..., 3][ok])), step_max=float(points[..., 4][ok].max()),
+                 refit=tuple((m[1], m[2]) for m in moved))
+    return tuple(m[0] for m in moved), frame, entry
+
+
+def selfcal_report(entries, frame) -> dict:
+    """What self-calibration returns beside the cameras: the rounds' entries, the accumulated frame (R, O, C) from the final
+    coordinates to the original calibration's world, and the sheet that frame describes in that world."""
+    return dict(rounds=list(entries), R=frame[0], O=frame[1], C=frame[2], sheet=frame_sheet(frame))
+
+
+def identity_frame(pl):
+    return sheet_frame((pl["z"], 0.0, 0.0), pl)
+
+
+def self_calibrate_model(cam1_frames, cam2_frames, cameras, pl, win: int = 64, step: int = 32, radius=None, rounds: int = 3,
+                         iterations: int = 4, tolerance: float = 0.05):
+    """Host model of PhotonLibrary.self_calibrate_stereo in f64.  cam1_frames, cam2_frames [N, height, width]: frame k of both
+    is the same instant.  Per round, with the current cameras: dewarp_model per camera, piv_ensemble.correlate_ensemble_model
+    of the two dewarped stacks (the disparity field), triangulate_model, selfcal_round; the rounds end early once the rms
+    disparity of the usable nodes is below `tolerance` px (that round's correction is still applied).  Returns (cameras,
+    report): report["rounds"][k] = disparity_rms, sheet (a, b, c) in that round's coordinates, sheet_rms, nodes,
+    error_median, step_max, refit ((rms, max) per camera); report["R"], ["O"], ["C"] the accumulated frame and
+    report["sheet"] the sheet in the original calibration's world."""
+    from . import piv_ensemble as pe
+    radius = int(win) // 2 if radius is None else int(radius)
+    if int(rounds) < 1:
+        raise ValueError("rounds must be >= 1")
+    shape = (pl["height"], pl["width"])
+    cameras, frame, entries = tuple(cameras), identity_frame(pl), []
+    for _ in range(int(rounds)):
+        dewarped = [dewarp_model(f, *plane_coefficients(cam, pl), shape) for cam, f in zip(cameras, (cam1_frames, cam2_frames))]
+        vectors, status, _ = pe.correlate_ensemble_model(dewarped[0][0], dewarped[1][0], win, step, radius)
+        points, flags = triangulate_model(vectors, cameras, pl, win, step, iterations, status)
+        cameras, moved, entry = selfcal_round(points, flags, vectors, (dewarped[0][1], dewarped[1][1]), cameras, pl, win, step)
+        frame = compose_frames(frame, moved)
+        entries.append(entry)
+        if entry["disparity_rms"] < tolerance:
+            break
+    return cameras, selfcal_report(entries, frame)
+
+
 # ---- generators ----------------------------------------------------------------------------------------------------------------
 class Pinhole:
     """A perspective camera to calibrate against: it sits `distance` from the world origin, rotated by theta about the Y
@@ -408,6 +646,54 @@ def particle_pair(cameras, flow, pl, seed: int, shape=(224, 256), density: float
     return tuple(out)
 
 
+def _sheet_particles(rng, pl, sheet, density, sheet_sigma, margin):
+    """Particles scattered uniformly over the plane's extent (`margin` beyond its sides) within 2.5 sheet_sigma of the sheet
+    Z = a + b X + c Y, `density` per dewarped pixel: (P [n, 3], brightness [n])."""
+    a, b, c = sheet
+    lo = np.array([pl["x0"] - margin, pl["y0"] - margin])
+    hi = np.array([pl["x0"] + (pl["width"] - 1) * pl["pitch"] + margin, pl["y0"] + (pl["height"] - 1) * pl["pitch"] + margin])
+    n = int(round(density * (hi[0] - lo[0]) * (hi[1] - lo[1]) / pl["pitch"] ** 2))
+    XY = rng.uniform(lo, hi, (n, 2))
+    Z = a + b * XY[:, 0] + c * XY[:, 1] + rng.uniform(-2.5 * sheet_sigma, 2.5 * sheet_sigma, n)
+    return np.concatenate([XY, Z[:, None]], axis=1), rng.uniform(0.5, 1.0, n)
+
+
+def _sheet_light(Q, sheet, sheet_sigma):
+    a, b, c = sheet
+    return np.exp(-((Q[:, 2] - (a + b * Q[:, 0] + c * Q[:, 1])) ** 2) / (2.0 * sheet_sigma ** 2))
+
+
+def sheet_frames(cameras, pl, sheet, n_frames: int, seed: int, shape=(224, 256), density: float = 0.035, diameter: float = 2.5,
+                 sheet_sigma: float = 0.3, margin: float = 4.0):
+    """n_frames simultaneous single exposures per camera of particles in a Gaussian sheet around Z = a + b X + c Y (sheet =
+    (a, b, c), in the cameras' world): every instant has its own particles, lit by exp(-(Z - sheet(X, Y))^2 / (2
+    sheet_sigma^2)) and imaged as particle_pair images them.  What self-calibration takes: frame k of both cameras shows the
+    same particles.  Returns one f32 stack [n_frames, height, width] per camera."""
+    rng = np.random.default_rng(seed)
+    out = [[] for _ in cameras]
+    for _ in range(int(n_frames)):
+        P, brightness = _sheet_particles(rng, pl, sheet, density, sheet_sigma, margin)
+        lit = brightness * _sheet_light(P, sheet, sheet_sigma)
+        for frames, cam in zip(out, cameras):
+            frames.append(_render(_project(cam, P), lit, shape, diameter))
+    return tuple(np.stack(frames).astype(np.float32) for frames in out)
+
+
+def sheet_pair(cameras, flow, pl, sheet, seed: int, shape=(224, 256), density: float = 0.035, diameter: float = 2.5,
+               sheet_sigma: float = 0.3, margin: float = 4.0):
+    """particle_pair on a sheet that is not the plane: two exposures per camera of particles around Z = a + b X + c Y that
+    move with `flow`, particle k at P_k - flow(P_k) / 2 and P_k + flow(P_k) / 2, lit by the sheet's profile at its position
+    in each exposure.  Returns one f32 stack [2, height, width] per camera."""
+    rng = np.random.default_rng(seed)
+    P, brightness = _sheet_particles(rng, pl, sheet, density, sheet_sigma, margin)
+    half = 0.5 * np.asarray(flow(P), np.float64)
+    out = []
+    for cam in cameras:
+        frames = [_render(_project(cam, Q), brightness * _sheet_light(Q, sheet, sheet_sigma), shape, diameter) for Q in (P - half, P + half)]
+        out.append(np.stack(frames).astype(np.float32))
+    return tuple(out)
+
+
 # ---- the synthetic stereo pairs of the tests and of tools/piv_stereo.py ---------------------------------------------------------
 CASE_PLANE = centred_plane(192, 160, 0.2)       # 38.4 x 32 mm at 0.2 mm per dewarped pixel
 CASE_SENSOR = (224, 256)
@@ -456,3 +742,40 @@ def case_figures(name: str, out, vectors1):
     alone = (np.asarray(vectors1, np.float64)[..., 0] - truth[..., 0] / CASE_PLANE["pitch"])[inner]
     res = np.asarray(out)[..., 3][inner]
     return np.sqrt(np.mean(err ** 2, axis=(0, 1))), float(np.sqrt(np.mean(alone ** 2))), float(np.median(res)), float(res.max())
+
+
+# ---- the self-calibration case of the tests and of tools/piv_stereo.py --self-calibrate ----------------------------------------
+def selfcal_flow(P):
+    P = np.asarray(P, np.float64)
+    return np.stack([0.3 + 0.05 * P[..., 0], -0.2 + 0.01 * P[..., 1], np.full(P.shape[:-1], 0.2)], axis=-1)
+
+
+SELFCAL_CASE = dict(plane=CASE_PLANE, kind="symmetric", sheet_sigma=0.3, sheet=(0.8, 0.02, -0.015), flow=selfcal_flow, n_frames=8, density=0.12,
+                    seed=3, pair_seed=42, disparity=dict(win=64, step=32, radius=16), evaluation=dict(CASE_GRID, iterations=2))
+
+
+def selfcal_inputs():
+    """Of SELFCAL_CASE: (the calibrated views as calibrated_pair returns them; the two stacks of simultaneous frames that
+    self-calibration takes; the two-exposure pair of the flow on the displaced sheet; the same flow on the aligned sheet)."""
+    case = SELFCAL_CASE
+    views = calibrated_pair(case["kind"])
+    pinholes, pl = [v[0] for v in views], case["plane"]
+    common = dict(shape=CASE_SENSOR, sheet_sigma=case["sheet_sigma"])
+    frames = sheet_frames(pinholes, pl, case["sheet"], case["n_frames"], case["seed"], density=case["density"], **common)
+    pair = sheet_pair(pinholes, case["flow"], pl, case["sheet"], case["pair_seed"], **common)
+    aligned = sheet_pair(pinholes, case["flow"], pl, (pl["z"], 0.0, 0.0), case["pair_seed"], **common)
+    return views, frames, pair, aligned
+
+
+def selfcal_figures(out, frame=None):
+    """Of a stereo result on SELFCAL_CASE's evaluation grid (out [9, 11, 8]) computed with cameras that live in `frame` (R, O,
+    C; None: the original calibration's world), over the interior nodes, in dewarped pixels: (rms error of dX, dY, dZ; the
+    median stereo residual).  The truth at a node is the flow at the node's world point, in the frame's components:
+    flow(O + R (node - C)) . R."""
+    case = SELFCAL_CASE
+    pl, grid = case["plane"], case["evaluation"]
+    R, O, C = identity_frame(pl) if frame is None else frame
+    truth = case["flow"](to_world((R, O, C), window_centres(pl, grid["win"], grid["step"]))) @ np.asarray(R)
+    inner = (slice(1, -1), slice(1, -1))
+    err = (np.asarray(out)[..., :3] - truth)[inner] / pl["pitch"]
+    return np.sqrt(np.mean(err ** 2, axis=(0, 1))), float(np.median(np.asarray(out)[..., 3][inner]))

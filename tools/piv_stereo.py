@@ -3,6 +3,11 @@
 chain and the model chain, and the kernels' static resources -- the figures of DESIGN.md section 4.3w.
 
     python tools/piv_stereo.py [--size 1024] [--reps 20] [--no-model]
+    python tools/piv_stereo.py --self-calibrate [--no-model]
+
+--self-calibrate: the self-calibration of photon_amd.piv_stereo.SELFCAL_CASE instead (section 19c) -- the table of the rounds
+with the device times of the two dewarps, the ensemble correlation and the triangulation per round, the accuracy of the three
+components before and after on the case's pair, and the triangulation's time against the reconstruction's on 512 x 512 nodes.
 
 Times are device events around `reps` back-to-back calls (one wait at the end), after a warm-up; the driver is timed on the
 host around whole calls.  The accuracy pairs are photon_amd.piv_stereo.CASES (192 x 160 plane at 0.2 mm/px, sensors 224 x 256,
@@ -33,8 +38,70 @@ def device_us(run, reps):
     return start.elapsed_time(stop) * 1e3 / reps
 
 
+def self_calibrate(lib, with_model):
+    import torch
+    from photon_amd import piv_stereo as ps
+    case = ps.SELFCAL_CASE
+    pl, grid, settings = case["plane"], case["disparity"], dict(case["evaluation"])
+    views, frames, pair, aligned = ps.selfcal_inputs()
+    cams = tuple(v[1] for v in views)
+    true = ps.sheet_frame(case["sheet"], pl)
+    target = ps.calibration_target(pl, 9, (-0.5, 0.0, 0.5))
+
+    def off_by(cameras):
+        return max(float(np.linalg.norm(ps.map_points(c, target) - v[0].project(ps.to_world(true, target)), axis=-1).max()) for c, v in zip(cameras, views))
+    d = [torch.from_numpy(f).cuda() for f in frames]
+    lib.self_calibrate_stereo(d[0], d[1], cams, pl, **grid)                                 # warm-up
+    timings = []
+    t0 = time.perf_counter()
+    corrected, report = lib.self_calibrate_stereo(d[0], d[1], cams, pl, timings=timings, **grid)
+    ms = (time.perf_counter() - t0) * 1e3
+    chains = [("device", corrected, report)]
+    if with_model:
+        chains.append(("model", *ps.self_calibrate_model(frames[0], frames[1], cams, pl, **grid)))
+    print(f"sheet {case['sheet']}, {case['n_frames']} frames per camera, win {grid['win']} step {grid['step']} radius {grid['radius']}; cameras off by "
+          f"{off_by(cams):.2f} px before")
+    print("chain  round  disparity rms [px]  sheet a [mm]      b         c      sheet rms [mm]  nodes  error median [px]  refit max [px]"
+          "   dewarps  correlation  triangulation [ms]")
+    for chain, _, rep in chains:
+        for k, e in enumerate(rep["rounds"]):
+            took = f"{timings[k]['dewarp']:8.3f}  {timings[k]['correlate']:8.3f}  {timings[k]['triangulate']:8.3f}" if chain == "device" else ""
+            print(f"{chain:6s} {k + 1:3d}    {e['disparity_rms']:10.4f}        {e['sheet'][0]:9.5f} {e['sheet'][1]:9.6f} {e['sheet'][2]:9.6f}    "
+                  f"{e['sheet_rms']:8.5f}     {e['nodes']:4d}     {e['error_median']:8.4f}         {max(r[1] for r in e['refit']):8.1e}     {took}")
+    for chain, cameras, rep in chains:
+        print(f"{chain}: sheet in the calibration's world {np.round(rep['sheet'], 5)}, cameras off by {off_by(cameras):.4f} px after"
+              + (f"; the driver took {ms:.1f} ms with the timing waits" if chain == "device" else ""))
+    print("chain   cameras       sheet      rms dX     dY     dZ [px]   residual median [px]")
+    rows = [("device", "original", "displaced", lambda: lib.correlate_stereo(*pair, cams, pl, settings=settings)[0], None),
+            ("device", "corrected", "displaced", lambda: lib.correlate_stereo(*pair, corrected, pl, settings=settings)[0], report),
+            ("device", "original", "aligned", lambda: lib.correlate_stereo(*aligned, cams, pl, settings=settings)[0], None)]
+    if with_model:
+        args = tuple(settings[k] for k in ("win", "step", "radius", "iterations"))
+        rows += [("model", "original", "displaced", lambda: ps.correlate_stereo_model(*pair, cams, pl, *args)[0], None),
+                 ("model", "corrected", "displaced", lambda: ps.correlate_stereo_model(*pair, chains[1][1], pl, *args)[0], chains[1][2]),
+                 ("model", "original", "aligned", lambda: ps.correlate_stereo_model(*aligned, cams, pl, *args)[0], None)]
+    for chain, which, sheet, run, rep in rows:
+        rms, median = ps.selfcal_figures(run(), None if rep is None else (rep["R"], rep["O"], rep["C"]))
+        print(f"{chain:7s} {which:13s} {sheet:10s} {rms[0]:6.4f} {rms[1]:6.4f} {rms[2]:6.4f}       {median:6.4f}")
+
+    n, win, step = 512, 32, 16
+    side = (n - 1) * step + win
+    big = ps.centred_plane(side, side, 30.0 / side)
+    rng = np.random.default_rng(5)
+    f = [torch.from_numpy(rng.uniform(-0.5, 0.5, (n, n, 4)).astype(np.float32) / np.float32(big["pitch"])).cuda() for _ in range(2)]
+    s = [torch.from_numpy(rng.uniform(0.02, 0.2, (n, n, 2)).astype(np.float32)).cuda() for _ in range(2)]
+    t_rec = device_us(lambda: lib.piv_stereo_reconstruct(f[0].data_ptr(), f[1].data_ptr(), 4, cams, big, win, step, 0, 0, s[0].data_ptr(),
+                                                         s[1].data_ptr()), 20)
+    line = f"{n} x {n} nodes (size query and allocation included): photon_piv_stereo_reconstruct with sigmas {t_rec:.1f} us; photon_piv_stereo_triangulate"
+    for iterations in (1, 4, 16):
+        t_tri = device_us(lambda: lib.piv_stereo_triangulate(f[0].data_ptr(), 4, cams, big, win, step, iterations), 20)
+        line += f", {iterations} iterations {t_tri:.1f} us"
+    print(line)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--self-calibrate", action="store_true", help="the self-calibration of SELFCAL_CASE instead of the stereo tables")
     ap.add_argument("--size", type=int, default=1024, help="side of the frames the dewarp and the warp are timed on")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--no-model", action="store_true", help="skip the host model chain (the accuracy table's second half)")
@@ -43,6 +110,9 @@ def main():
     from photon_amd import piv_stereo as ps
     from photon_amd.library import PhotonLibrary
     lib = PhotonLibrary()
+    if args.self_calibrate:
+        self_calibrate(lib, not args.no_model)
+        return
     n, rng = args.size, np.random.default_rng(1)
 
     # ---- kernels
