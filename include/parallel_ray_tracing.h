@@ -1533,6 +1533,102 @@ int photon_piv_dewarp(const photon_piv_dewarp_t *job);
 int photon_piv_stereo_reconstruct(const photon_piv_stereo_t *job);
 int photon_piv_stereo_triangulate(const photon_piv_triangulate_t *job);
 
+/* ------------------------------------------------------------------------------------
+ * Section 20: tomographic PIV -- three components in a volume from three or more cameras: the cameras' frames combined by
+ * line of sight into a particle volume (volume_los), and two such volumes correlated with three-dimensional windows and a
+ * three-dimensional search region (correlate_volume).  Host models and the test generators: photon_amd/piv_tomo.py.
+ * Both entry points take one pointer to a job struct (host memory, read during the call, not kept) whose last member is the
+ * stream, as section 19's do; both are asynchronous on that stream, allocate no device memory, write every element they own
+ * and nothing else, and return the same bits from two calls.
+ *
+ * Volume (photon_piv_volume_t): voxel (k, i, j) is the world point (x0 + j pitch, y0 + i pitch, z0 + k pitch), k in [0, nz),
+ * i in [0, ny), j in [0, nx); of frame f it is stored at d_out + f out_stride + (k ny + i) nx + j, out_stride >= nx ny nz.
+ *
+ * a. photon_piv_volume_los.  n_cameras in [2, 8] cameras; of camera c: d_coef[c], the section 7a coefficients of its n_frames
+ *    frames, frame_stride[c] floats apart, f32[height[c]*width[c]] each (the sensors may differ), and grid[c][4], section 19a's
+ *    grid of that camera on the volume's (x0, y0, pitch).  d_poly: device f64[n_cameras][nz][2][10], camera c folded at slice
+ *    k's z = z0 + k pitch by section 19a's formulas (piv_tomo.los_coefficients): the host computes it, the kernel divides
+ *    nothing; it is on the device and is not inspected.  Per voxel (k, i, j), one thread: let s_c be the value photon_piv_dewarp
+ *    gives at pixel (i, j) with poly = d_poly[c][k], grid[c] and the output size nx x ny -- the same f64 Horner, the same
+ *    inside test, the same f32 weights and the same order of sums.  If any camera is outside, the voxel is 0.0f in every
+ *    frame and the mask is 1.  Otherwise, with v_c = s_c > 0 ? s_c : 0:  mode 0 (MinLOS): the minimum over c, in camera
+ *    order;  mode 1 (multiplicative LOS): the product ((v_0 v_1) v_2) ..., in f32, nothing fused.  The N-th root of the
+ *    product is deliberately absent: photon_det_math.h has no bit-reproducible log or pow; the root belongs with the
+ *    intensity normalisation of an iterative reconstruction.  Coordinate, weights and mirrored indices are computed once per
+ *    camera and voxel and serve the frames four at a time: a pair of exposures costs one coordinate evaluation (a longer
+ *    series one per four frames; the bits do not depend on it).  d_mask: device u8[nz ny nx], or NULL: 1 where a camera
+ *    does not see the voxel.  The gaps of an out_stride above nx ny nz are not touched.  Host model of exactly these
+ *    operations: piv_tomo.los_model_f32 (equal bit for bit); in f64: piv_tomo.los_model.
+ *    Refused (1, one stderr line, nothing written, no launch): a null job, d_poly, d_out or d_coef[c]; n_cameras outside [2,
+ *    8]; a mode that is not 0 or 1; n_frames < 1; a size below 1 or a side above 2^22, sensor or volume; nx ny nz above
+ *    INT_MAX; a frame_stride[c] below width[c] height[c]; out_stride below nx ny nz; d_out's frames overlapping a camera's; a
+ *    grid value that is not finite.
+ *
+ * b. photon_piv_correlate_volume.  d_vol1, d_vol2: device f32[nz][ny][nx], contiguous.  In the plane win, step and radius are
+ *    section 5's, under section 5's rules; along z win_z in [1, 64] (<= nz), step_z >= 1, radius_z in [0, min(16, win_z / 2)].
+ *    Grid: n_slabs = (nz - win_z) / step_z + 1, n_rows and n_cols as in section 5; node w = (l n_rows + i) n_cols + j has its
+ *    centre where section 5 has it in the plane and at l step_z + (win_z - 1) / 2 in z.  d_offset: device int[n][3] = (ox, oy,
+ *    oz) per node, or NULL; in a volume of one slice oz is not read and counts as 0.  With R = radius, Rz = radius_z and the
+ *    shifts s = (sz, sy, sx) in [-Rz, Rz] x [-R, R]^2, section 5's definition with one more axis:
+ *      C(s) = sum_p (a(p) - mean a)(b(p + o + s) - mean b) over the win_z win^2 voxels p of the window;  mean a over the
+ *      window;  mean b over the in-volume voxels of the offset window at zero shift (0 where there are none);  voxels of vol2
+ *      outside the volume read as mean b (contribute 0);  Cn = C / sqrt(ea eb),  ea = sum (a - mean a)^2,  eb = sum (b - mean
+ *      b)^2 at zero shift.
+ *    Flat (flag 2, every output of the window NaN): all voxels of a equal; the in-volume voxels of b at zero shift all
+ *    equal, or none; an f32 energy not above 0 -- decided from the voxels, as in section 5.  Flag 4: a voxel of vol2 the
+ *    window needs (offset, any shift) lies outside the volume.  Flag 1: the integer peak lies on the edge of the search
+ *    region in a searched axis; z is searched when radius_z >= 1: with radius_z = 0, dz = oz and z raises no flag.
+ *    The peak is the argmax, ties to the first shift in (sz, sy, sx) order; per axis section 5's three-point fit in f64 through
+ *    the peak's two neighbours along that axis; the ratio is taken against the largest value at Chebyshev distance >= 2 of
+ *    the peak (the largest of the three axes' distances), +inf where that is not positive.
+ *    d_vectors f32[n][5] = dx, dy, dz, peak, ratio;  d_flags int[n];  d_planes f32[n][(2Rz+1)(2R+1)^2], in (sz, sy, sx)
+ *    order: required together with d_vectors and d_flags -- it is the kernel's workspace for the raw planes, so that the
+ *    call needs no second buffer and allocates nothing, and holds Cn on return.  d_vectors == NULL: the size query into
+ *    *n_slabs, *n_rows, *n_cols (where given), nothing launched.
+ *    One workgroup per window under section 5's plan; the means and the exact flatness counts from a first pass over the
+ *    window's planes; then per z-shift (the zero shift first) the win_z plane pairs (pz, pz + oz + sz), each staged as section
+ *    5 stages a pair (a plane of vol2 outside [0, nz) is all zeros) and added into the running plane as section 14 adds a
+ *    pair; the energies summed in plane order; f32 sums in a fixed order.  A volume of one slice with win_z = 1, step_z =
+ *    1, radius_z = 0 returns photon_piv_correlate's dx, dy, peak, ratio, flags and plane bit for bit.
+ *    Host model: piv_tomo.correlate_volume_model (f64, planes included).
+ *    Refused (1, one stderr line, nothing written, no launch): a null job; section 5's rules for win, radius, step and the
+ *    slice's size; a side above 2^22 or nx ny nz above INT_MAX; win_z, step_z or radius_z outside the ranges above; nz <
+ *    win_z; a null volume; d_vectors without d_flags or d_planes; more than INT_MAX windows; a (win, radius) whose LDS the
+ *    device does not have.
+ *
+ * Drivers: PhotonLibrary.reconstruct_volume and PhotonLibrary.correlate_tomo.  Not here: iterative reconstruction (MART /
+ * SMART), 3-D validation and multi-pass refinement, volumetric self-calibration.  DESIGN.md section 4.3x. */
+typedef struct photon_piv_volume_t {
+    double x0, y0, z0, pitch;
+    int nx, ny, nz;
+} photon_piv_volume_t;
+typedef struct photon_piv_volume_los_t {
+    int n_cameras, n_frames, mode;
+    const float *d_coef[8];
+    long long frame_stride[8];
+    int width[8], height[8];
+    double grid[8][4];
+    const double *d_poly;
+    photon_piv_volume_t volume;
+    long long out_stride;
+    float *d_out;
+    unsigned char *d_mask;
+    void *stream;
+} photon_piv_volume_los_t;
+typedef struct photon_piv_correlate_volume_t {
+    const float *d_vol1, *d_vol2;
+    int nx, ny, nz;
+    int win, step, radius, win_z, step_z, radius_z;
+    const int *d_offset;
+    float *d_vectors;
+    int *d_flags;
+    float *d_planes;
+    int *n_slabs, *n_rows, *n_cols;
+    void *stream;
+} photon_piv_correlate_volume_t;
+int photon_piv_volume_los(const photon_piv_volume_los_t *job);
+int photon_piv_correlate_volume(const photon_piv_correlate_volume_t *job);
+
 #ifdef __cplusplus
 }
 #endif

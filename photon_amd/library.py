@@ -5,7 +5,7 @@ Three layers, top to bottom of the file:
     loaded library.  The header is the source of truth; tests/test_abi.py holds the table against its prototypes.
   * ``PhotonLibrary``: one method per entry point -- marshalling only, raw device pointers in, return code checked -- and
     on top of those the pipelines that chain several calls on torch-allocated device buffers on the current stream
-    (``preprocess_series``, ``correlate``, ``correlate_deform``, ``correlate_stereo``, ``self_calibrate_stereo``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
+    (``preprocess_series``, ``correlate``, ``correlate_deform``, ``correlate_stereo``, ``self_calibrate_stereo``, ``reconstruct_volume``, ``correlate_tomo``, ``optical_flow``, ``displacement_uncertainty``, ``correlation_predictor``, ``track_dots``,
     ``integrate_gradient``, the tomography solvers).
   * ``Volume``, ``Sources``, ``Flow``, ``Scene``: the library's handles.
 All arithmetic is the HIP library's.  There is no Python or CPU fallback -- if the library is missing or a call fails,
@@ -107,6 +107,26 @@ class photon_piv_triangulate_t(ctypes.Structure):
                 ("plane", photon_piv_plane_t), ("camera1", photon_piv_camera_t), ("camera2", photon_piv_camera_t), ("d_out", ctypes.c_void_p),
                 ("d_flags", ctypes.c_void_p), ("rows_out", ctypes.POINTER(ctypes.c_int)), ("cols_out", ctypes.POINTER(ctypes.c_int)),
                 ("stream", ctypes.c_void_p)]
+
+
+class photon_piv_volume_t(ctypes.Structure):
+    _fields_ = [("x0", ctypes.c_double), ("y0", ctypes.c_double), ("z0", ctypes.c_double), ("pitch", ctypes.c_double),
+                ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nz", ctypes.c_int)]
+
+
+class photon_piv_volume_los_t(ctypes.Structure):
+    _fields_ = [("n_cameras", ctypes.c_int), ("n_frames", ctypes.c_int), ("mode", ctypes.c_int), ("d_coef", ctypes.c_void_p * 8),
+                ("frame_stride", ctypes.c_longlong * 8), ("width", ctypes.c_int * 8), ("height", ctypes.c_int * 8),
+                ("grid", ctypes.c_double * 4 * 8), ("d_poly", ctypes.c_void_p), ("volume", photon_piv_volume_t),
+                ("out_stride", ctypes.c_longlong), ("d_out", ctypes.c_void_p), ("d_mask", ctypes.c_void_p), ("stream", ctypes.c_void_p)]
+
+
+class photon_piv_correlate_volume_t(ctypes.Structure):
+    _fields_ = [("d_vol1", ctypes.c_void_p), ("d_vol2", ctypes.c_void_p), ("nx", ctypes.c_int), ("ny", ctypes.c_int), ("nz", ctypes.c_int),
+                ("win", ctypes.c_int), ("step", ctypes.c_int), ("radius", ctypes.c_int), ("win_z", ctypes.c_int), ("step_z", ctypes.c_int),
+                ("radius_z", ctypes.c_int), ("d_offset", ctypes.c_void_p), ("d_vectors", ctypes.c_void_p), ("d_flags", ctypes.c_void_p),
+                ("d_planes", ctypes.c_void_p), ("n_slabs", ctypes.POINTER(ctypes.c_int)), ("n_rows", ctypes.POINTER(ctypes.c_int)),
+                ("n_cols", ctypes.POINTER(ctypes.c_int)), ("stream", ctypes.c_void_p)]
 
 
 def _signatures():
@@ -235,6 +255,9 @@ def _signatures():
         "photon_piv_dewarp": (ci, [P(photon_piv_dewarp_t)]),
         "photon_piv_stereo_reconstruct": (ci, [P(photon_piv_stereo_t)]),
         "photon_piv_stereo_triangulate": (ci, [P(photon_piv_triangulate_t)]),
+        # section 20: tomographic PIV (job structs as section 19's)
+        "photon_piv_volume_los": (ci, [P(photon_piv_volume_los_t)]),
+        "photon_piv_correlate_volume": (ci, [P(photon_piv_correlate_volume_t)]),
     }
 
 
@@ -1413,6 +1436,132 @@ class PhotonLibrary:
             if entry["disparity_rms"] < tolerance:
                 break
         return cameras, ps.selfcal_report(entries, frame)
+
+    # ---- tomographic PIV: line-of-sight volumes, 3-D correlation (section 20) -------------------------------------------------
+    def piv_volume_los(self, d_coef_ptrs, frame_strides, n_frames: int, sensor_shapes, grids, d_poly_ptr: int, vol, out_stride: int,
+                       d_out_ptr: int, d_mask_ptr: int = 0, mode: int = 0, stream: int = 0):
+        """photon_piv_volume_los on raw device pointers: per camera the pointer of its n_frames coefficient images, their
+        stride in floats, the sensor's (height, width) and its grid [4]; d_poly_ptr the device table f64 [N, nz, 2, 10] and
+        grids the host table [N, 4] of piv_tomo.los_coefficients; vol a piv_tomo volume.  Writes n_frames volumes f32 [nz, ny,
+        nx], out_stride floats apart, and the u8 mask [nz, ny, nx] (0 = NULL); mode 0 the minimum, 1 the product;
+        asynchronous on `stream`."""
+        n = len(d_coef_ptrs)
+        if not (len(frame_strides) == len(sensor_shapes) == n and 0 < n <= 8):
+            raise ValueError("piv_volume_los takes 2 to 8 cameras: one pointer, stride and sensor shape each")
+        pitches = np.ascontiguousarray(grids, np.float64)
+        if pitches.shape != (n, 4):
+            raise ValueError(f"grids must be [{n}, 4] (piv_tomo.los_coefficients)")
+        job = photon_piv_volume_los_t(n_cameras=n, n_frames=int(n_frames), mode=int(mode), d_poly=int(d_poly_ptr) or None,
+                                      out_stride=int(out_stride), d_out=int(d_out_ptr) or None, d_mask=int(d_mask_ptr) or None,
+                                      stream=int(stream) or None)
+        job.volume = photon_piv_volume_t(float(vol["x0"]), float(vol["y0"]), float(vol["z0"]), float(vol["pitch"]), int(vol["nx"]), int(vol["ny"]),
+                                         int(vol["nz"]))
+        for c in range(n):
+            job.d_coef[c], job.frame_stride[c] = int(d_coef_ptrs[c]) or None, int(frame_strides[c])
+            job.height[c], job.width[c] = int(sensor_shapes[c][0]), int(sensor_shapes[c][1])
+        ctypes.memmove(job.grid, pitches.ctypes.data, pitches.nbytes)
+        self._call("photon_piv_volume_los", ctypes.byref(job))
+
+    def piv_correlate_volume(self, d_vol1_ptr: int, d_vol2_ptr: int, nx: int, ny: int, nz: int, win: int, step: int, radius: int, win_z: int,
+                             step_z: int, radius_z: int, d_offset_ptr: int = 0, stream: int = 0):
+        """photon_piv_correlate_volume on raw device pointers: two volumes f32 [nz, ny, nx], the int32 offsets [n, 3] (0 =
+        NULL).  The size query first, then the launch.  Returns torch device tensors (vectors f32 [n_slabs, n_rows, n_cols, 5] =
+        dx, dy, dz, peak, ratio; flags int32 [n_slabs, n_rows, n_cols]; planes f32 [n_slabs, n_rows, n_cols, 2Rz+1, 2R+1,
+        2R+1], the call's workspace and on return the normalised planes), filled asynchronously on `stream`."""
+        import torch
+        slabs, rows, cols = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
+        job = photon_piv_correlate_volume_t(d_vol1=int(d_vol1_ptr) or None, d_vol2=int(d_vol2_ptr) or None, nx=int(nx), ny=int(ny), nz=int(nz),
+                                            win=int(win), step=int(step), radius=int(radius), win_z=int(win_z), step_z=int(step_z),
+                                            radius_z=int(radius_z), n_slabs=ctypes.pointer(slabs), n_rows=ctypes.pointer(rows),
+                                            n_cols=ctypes.pointer(cols))
+        self._call("photon_piv_correlate_volume", ctypes.byref(job))                     # the size query
+        dev, grid = _current_device(), (slabs.value, rows.value, cols.value)
+        nS, nSz = 2 * int(radius) + 1, 2 * int(radius_z) + 1
+        vectors = torch.empty(grid + (5,), dtype=torch.float32, device=dev)
+        flags = torch.empty(grid, dtype=torch.int32, device=dev)
+        planes = torch.empty(grid + (nSz, nS, nS), dtype=torch.float32, device=dev)
+        job.d_offset, job.d_vectors, job.d_flags, job.d_planes = int(d_offset_ptr) or None, vectors.data_ptr(), flags.data_ptr(), planes.data_ptr()
+        job.stream = int(stream) or None
+        self._call("photon_piv_correlate_volume", ctypes.byref(job))
+        return vectors, flags, planes
+
+    def _los_queued(self, camera_frames, cameras, vol, mode: str, stream: int, dev):
+        """reconstruct_volume's work, queued on `stream`: (volumes f32 [n, nz, ny, nx], mask u8 [nz, ny, nx], whether
+        camera_frames held single frames)."""
+        import torch
+        from . import piv_tomo as pt
+        if mode not in pt.MODES:
+            raise ValueError(f'mode must be one of {sorted(pt.MODES)}, not {mode!r}')
+        if not 2 <= len(cameras) <= 8 or len(camera_frames) != len(cameras):
+            raise ValueError("a line-of-sight volume takes 2 to 8 cameras and one frame or stack of frames per camera")
+        checked = [_checked(x, f"camera_frames[{c}]") for c, x in enumerate(camera_frames)]
+        if any(x is None or x.ndim not in (2, 3) or x.ndim != checked[0].ndim for x in checked):
+            raise ValueError("camera_frames must hold one frame [height, width] or one stack [n, height, width] per camera, all alike")
+        stacks = [_on_device(x, torch.float32, dev, f"camera_frames[{c}]") for c, x in enumerate(checked)]
+        stacks = [t.reshape((-1,) + tuple(t.shape[-2:])) for t in stacks]
+        n = int(stacks[0].shape[0])
+        if any(int(t.shape[0]) != n for t in stacks):
+            raise ValueError("every camera must bring the same number of frames")
+        poly, grids = pt.los_coefficients(cameras, vol)
+        d_poly = _on_device(poly, torch.float64, dev, "poly")
+        coefs = []
+        for t in stacks:
+            coef = torch.empty(tuple(t.shape), dtype=torch.float32, device=dev)
+            for k in range(n):
+                self.bspline_coefficients(t[k].data_ptr(), int(t.shape[2]), int(t.shape[1]), coef[k].data_ptr(), stream)
+            coefs.append(coef)
+        nz, ny, nx = int(vol["nz"]), int(vol["ny"]), int(vol["nx"])
+        out = torch.empty((n, nz, ny, nx), dtype=torch.float32, device=dev)
+        unseen = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
+        self.piv_volume_los([c.data_ptr() for c in coefs], [int(c.shape[1] * c.shape[2]) for c in coefs], n, [tuple(c.shape[1:]) for c in coefs],
+                            grids, d_poly.data_ptr(), vol, nz * ny * nx, out.data_ptr(), unseen.data_ptr(), pt.MODES[mode], stream)
+        return out, unseen, checked[0].ndim == 2
+
+    def reconstruct_volume(self, camera_frames, cameras, vol, mode: str = "min"):
+        """A particle volume from N cameras by line of sight (section 20a; models: photon_amd.piv_tomo.los_model_f32, bit for
+        bit, and los_model).  camera_frames: a list with one frame [height, width] or one stack [n, height, width] per
+        camera, taken as the ingest rule of this class takes any image (the sensors may differ); cameras: 2 to 8 piv_stereo
+        cameras; vol: a piv_tomo volume; mode "min" (MinLOS) or "product" (multiplicative LOS, without the N-th root).  On
+        the current stream: the B-spline coefficients per frame, the cameras folded at every slice on the host and uploaded
+        (a copy on the current stream), one line-of-sight launch for all frames; nothing waits for the result.  Returns device tensors (volumes f32 [n, nz, ny, nx], or [nz,
+        ny, nx] for single frames; mask u8 [nz, ny, nx], 1 where a camera does not see the voxel)."""
+        dev, stream = _device_and_stream()
+        out, unseen, single = self._los_queued(camera_frames, cameras, vol, mode, stream, dev)
+        return (out[0] if single else out), unseen
+
+    def correlate_tomo(self, camera_frames, cameras, vol, win: int = 32, step: int = 16, radius: int = 4, win_z: Optional[int] = None,
+                       step_z: Optional[int] = None, radius_z: Optional[int] = None, mode: str = "min", offsets=None):
+        """Three displacement components on a 3-D grid from N cameras (section 20; model:
+        photon_amd.piv_tomo.correlate_tomo_model).  camera_frames: a list with the two exposures of each camera, a stack [2,
+        height, width], taken as the ingest rule of this class takes any stack; cameras, vol, mode as reconstruct_volume
+        takes them.  win_z defaults to win, capped at 64 and nz; step_z to max(1, win_z / 2); radius_z to min(radius, 16,
+        win_z / 2).  offsets: integer (ox, oy, oz) per node [n_slabs, n_rows, n_cols, 3] in voxels, or None.  On the current
+        stream: both exposures through one line-of-sight launch, then the 3-D correlation; the host waits once.
+        Returns numpy (displacements f64 [n_slabs, n_rows, n_cols, 3] = pitch (dx, dy, dz) in world units; vectors f32
+        [n_slabs, n_rows, n_cols, 5] = dx, dy, dz in voxels, peak, ratio; flags int32 [n_slabs, n_rows, n_cols]; partial bool
+        [n_slabs, n_rows, n_cols], true where the window holds a voxel some camera does not see)."""
+        import torch
+        from . import piv_tomo as pt
+        win_z, step_z, radius_z = pt.z_defaults(vol, win, radius, win_z, step_z, radius_z)
+        pt.check_arguments((int(vol["nz"]), int(vol["ny"]), int(vol["nx"])), win, step, radius, win_z, step_z, radius_z)
+        dev, stream = _device_and_stream()
+        d_off = None
+        if offsets is not None:
+            grid = pt.grid_shape((int(vol["nz"]), int(vol["ny"]), int(vol["nx"])), win, step, win_z, step_z)
+            table = _checked(offsets, "offsets")
+            if tuple(table.shape) != grid + (3,):
+                raise ValueError(f"offsets must be {grid + (3,)}: (ox, oy, oz) per node, not {tuple(table.shape)}")
+            d_off = _on_device(table, torch.float64, dev, "offsets").to(torch.int32).contiguous()      # whole numbers: exact in f64
+        volumes, unseen, _ = self._los_queued(camera_frames, cameras, vol, mode, stream, dev)
+        if volumes.shape[0] != 2:
+            raise ValueError("correlate_tomo takes the two exposures of each camera, [2, height, width]")
+        nz, ny, nx = (int(v) for v in volumes.shape[1:])
+        vectors, flags, _ = self.piv_correlate_volume(volumes[0].data_ptr(), volumes[1].data_ptr(), nx, ny, nz, win, step, radius, win_z, step_z,
+                                                      radius_z, 0 if d_off is None else d_off.data_ptr(), stream)
+        # a window holds an unseen voxel where the mask's maximum over the window is 1
+        pooled = torch.nn.functional.max_pool3d(unseen[None, None].to(torch.float32), (win_z, win, win), (step_z, step, step))[0, 0]
+        vectors, flags, partial = vectors.cpu().numpy(), flags.cpu().numpy(), (pooled > 0).cpu().numpy()       # the host waits here
+        return float(vol["pitch"]) * vectors[..., :3].astype(np.float64), vectors, flags, partial
 
     # ---- dense optical flow on the device (section 12) --------------------------------------------------------------------
     def field_to_pixels(self, d_field_ptr: int, field_stride: int, n_rows: int, n_cols: int, win: int, step: int, width: int, height: int,
