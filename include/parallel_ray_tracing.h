@@ -1596,8 +1596,9 @@ int photon_piv_stereo_triangulate(const photon_piv_triangulate_t *job);
  *    win_z; a null volume; d_vectors without d_flags or d_planes; more than INT_MAX windows; a (win, radius) whose LDS the
  *    device does not have.
  *
- * Drivers: PhotonLibrary.reconstruct_volume and PhotonLibrary.correlate_tomo.  Not here: iterative reconstruction (MART /
- * SMART), 3-D validation and multi-pass refinement, volumetric self-calibration.  DESIGN.md section 4.3x. */
+ * Drivers: PhotonLibrary.reconstruct_volume and PhotonLibrary.correlate_tomo.  Iterative reconstruction (MART) from the
+ * line-of-sight volume: section 21.  Not here: SMART and MLEM, 3-D validation and multi-pass refinement, volumetric
+ * self-calibration.  DESIGN.md section 4.3x. */
 typedef struct photon_piv_volume_t {
     double x0, y0, z0, pitch;
     int nx, ny, nz;
@@ -1628,6 +1629,94 @@ typedef struct photon_piv_correlate_volume_t {
 } photon_piv_correlate_volume_t;
 int photon_piv_volume_los(const photon_piv_volume_los_t *job);
 int photon_piv_correlate_volume(const photon_piv_correlate_volume_t *job);
+
+/* ------------------------------------------------------------------------------------
+ * Section 21: MART particle volumes for tomographic PIV -- the exact re-projection of a volume onto its cameras
+ * (volume_project) and the multiplicative, camera-sequential update that starts from section 20a's line-of-sight volume
+ * (volume_mart: MLOS-MART).  Host models: photon_amd/piv_mart.py.  Both entry points take one job struct whose last member
+ * is the stream, as section 20's do; both are asynchronous on that stream, allocate no device memory and return the same
+ * bits from two calls.  Cameras (n_cameras in [2, 8], width[c], height[c], grid[c], d_poly) and the volume are section 20a's.
+ *
+ * Footprint.  Voxel (k, i, j) lands on camera c at (x, y) by section 20a's pipeline: d_poly[c][k], grid[c], the same f64 Horner,
+ * the same inside test (a NaN is outside: the camera does not see the voxel).  x0 = floor(x), fx = (float)(x - x0); the x
+ * taps are x0 and min(x0 + 1, width - 1) with the weights 1.0f - fx and fx; the same in y.  The four tap weights are w = wy wx
+ * in f32, nothing fused, in the order (y0, x0), (y0, x1), (y1, x0), (y1, x1): a bilinear footprint.  The projection scatters
+ * with these weights and the update gathers with them: a matched pair.
+ *
+ * a. photon_piv_volume_project.  d_vol: device f32, n_frames volumes [nz][ny][nx], vol_stride floats apart (read only).
+ *    d_acc[c]: device int64, n_frames accumulators [height[c] width[c]], acc_stride[c] apart.  With s = scale_log2:
+ *      every accumulator starts at 0 (zeroed by the call on its stream);  every voxel with E > 0 that camera c sees adds,
+ *      to each of its four taps,  q = llrint(min((double)(w E) 2^s, 2^31)),  the product w E taken in f32; a product that is
+ *      not above 0 adds 0 (w = 0, and the NaN of an infinite E under a zero weight).  Voxels with !(E > 0) -- zeros,
+ *      negatives, NaN -- add nothing.
+ *    This is the definition; the order of the additions is free: integer addition is associative, so atomics in any
+ *    order return these integers, and so does piv_mart.project_model (np.add.at on int64).  Bound: two taps of one voxel
+ *    share a pixel only where a tap is clamped at the sensor's edge, and the clamped tap's weight is 0; so a voxel adds at
+ *    most 2^31 to a pixel, and with nx ny nz <= INT_MAX every sum stays below 2^62 for any input.
+ *    d_image[c]: device f32, n_frames images acc_stride[c] floats apart, or NULL:  image = (float)((double)acc 2^-s).
+ *    One launch reads every voxel once and scatters it to all cameras; the gaps of a longer acc_stride are not touched.
+ *    Refused (1, one stderr line, nothing written, no launch): a null job, d_poly, d_vol or d_acc[c]; n_cameras outside [2,
+ *    8]; n_frames < 1; scale_log2 outside [-126, 62]; a size below 1 or a side above 2^22, sensor or volume; nx ny nz above
+ *    INT_MAX; vol_stride below nx ny nz; an acc_stride[c] below width[c] height[c]; a grid value that is not finite;
+ *    accumulators or images that overlap each other or the volume.
+ *
+ * b. photon_piv_volume_mart.  d_frame[c]: device f32, the n_frames raw frames of camera c themselves (not section 7a's
+ *    coefficients), frame_stride[c] floats apart.  d_vol: device f32, n_frames volumes vol_stride apart, the first guess on
+ *    entry, updated in place.  d_mask: device u8[nz ny nx] as section 20a writes it, or NULL: 1 marks a voxel that stays 0.
+ *    iterations >= 1; mu_roots in [0, 3]: the relaxation mu = 2^-mu_roots; threshold >= 0, finite.  d_acc: the caller's
+ *    workspace, device int64[2][n_frames][max_c height[c] width[c]]: its content on entry does not matter.
+ *    For it = 0 .. iterations - 1, for c = 0 .. n_cameras - 1, in this order, per frame:
+ *      1. P_c = 21a's accumulators of the current volume for camera c alone;  P_t = (float)((double)acc_t 2^-s) at pixel t.
+ *      2. For every voxel with E > 0:  E = 0.0f if camera c does not see the voxel or the mask is 1.  Otherwise, at the
+ *         voxel's four taps,  I_bar = ((w0 I0+ + w1 I1+) + w2 I2+) + w3 I3+  with I+ = I > 0 ? I : 0 of the frame, and
+ *         P_bar the same expression on P; everything in f32, nothing fused.  If P_bar > 0:  r = I_bar / P_bar, mu_roots
+ *         times r = sqrtf(r), E = E r (division and roots correctly rounded).  Then E < threshold gives 0.0f.
+ *      3. Voxels with !(E > 0) are not read further and not written: zeros stay zero, before any coordinate is computed.
+ *    The ratio is raised to mu alone -- the interpolation weight sits in the footprint, not in the exponent -- so the power
+ *    is 0 to 3 square roots and photon_det_math.h needs no log or pow.  One thread per voxel in section 20a's launch shape;
+ *    a footprint serves the frames four at a time.  Camera c's update and camera c + 1's projection (camera 0's of the next
+ *    iteration behind the last camera) are one launch: a voxel's new value is final when the voxel scatters it, and the
+ *    integer sums do not depend on the order; the two halves of d_acc alternate, the half written next is zeroed on the
+ *    stream.  One projection launch first; iterations x n_cameras launches in all behind it.  Host models:
+ *    piv_mart.mart_model_f32 (equal bit for bit) and piv_mart.mart_model (f64, unquantised).
+ *    Refused (1, one stderr line, nothing written, no launch): a null job, d_poly, d_vol, d_acc or d_frame[c]; 21a's rules
+ *    for the cameras, the frames' count, scale_log2, the sizes, vol_stride and the grids; a frame_stride[c] below width[c]
+ *    height[c]; iterations < 1; mu_roots outside [0, 3]; a threshold that is negative or not finite; d_vol, d_acc and d_mask
+ *    overlapping one another, or d_vol or d_acc overlapping a camera's frames.
+ *
+ * Drivers: PhotonLibrary.reproject, reconstruct_volume(method="mart") and correlate_tomo(reconstruction="mart").  Not here:
+ * SMART and MLEM, 3-D validation and multi-pass refinement, volumetric self-calibration (re-projection is the operator it
+ * will need), masks and weights in 3-D.  DESIGN.md section 4.3y. */
+typedef struct photon_piv_volume_project_t {
+    int n_cameras, n_frames, scale_log2;
+    int width[8], height[8];
+    double grid[8][4];
+    const double *d_poly;
+    photon_piv_volume_t volume;
+    const float *d_vol;
+    long long vol_stride;
+    long long *d_acc[8];
+    long long acc_stride[8];
+    float *d_image[8];
+    void *stream;
+} photon_piv_volume_project_t;
+typedef struct photon_piv_volume_mart_t {
+    int n_cameras, n_frames, iterations, mu_roots, scale_log2;
+    float threshold;
+    const float *d_frame[8];
+    long long frame_stride[8];
+    int width[8], height[8];
+    double grid[8][4];
+    const double *d_poly;
+    photon_piv_volume_t volume;
+    long long vol_stride;
+    float *d_vol;
+    const unsigned char *d_mask;
+    long long *d_acc;
+    void *stream;
+} photon_piv_volume_mart_t;
+int photon_piv_volume_project(const photon_piv_volume_project_t *job);
+int photon_piv_volume_mart(const photon_piv_volume_mart_t *job);
 
 #ifdef __cplusplus
 }

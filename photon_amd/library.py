@@ -129,6 +129,22 @@ class photon_piv_correlate_volume_t(ctypes.Structure):
                 ("n_cols", ctypes.POINTER(ctypes.c_int)), ("stream", ctypes.c_void_p)]
 
 
+class photon_piv_volume_project_t(ctypes.Structure):
+    _fields_ = [("n_cameras", ctypes.c_int), ("n_frames", ctypes.c_int), ("scale_log2", ctypes.c_int), ("width", ctypes.c_int * 8),
+                ("height", ctypes.c_int * 8), ("grid", ctypes.c_double * 4 * 8), ("d_poly", ctypes.c_void_p), ("volume", photon_piv_volume_t),
+                ("d_vol", ctypes.c_void_p), ("vol_stride", ctypes.c_longlong), ("d_acc", ctypes.c_void_p * 8),
+                ("acc_stride", ctypes.c_longlong * 8), ("d_image", ctypes.c_void_p * 8), ("stream", ctypes.c_void_p)]
+
+
+class photon_piv_volume_mart_t(ctypes.Structure):
+    _fields_ = [("n_cameras", ctypes.c_int), ("n_frames", ctypes.c_int), ("iterations", ctypes.c_int), ("mu_roots", ctypes.c_int),
+                ("scale_log2", ctypes.c_int), ("threshold", ctypes.c_float), ("d_frame", ctypes.c_void_p * 8),
+                ("frame_stride", ctypes.c_longlong * 8), ("width", ctypes.c_int * 8), ("height", ctypes.c_int * 8),
+                ("grid", ctypes.c_double * 4 * 8), ("d_poly", ctypes.c_void_p), ("volume", photon_piv_volume_t),
+                ("vol_stride", ctypes.c_longlong), ("d_vol", ctypes.c_void_p), ("d_mask", ctypes.c_void_p), ("d_acc", ctypes.c_void_p),
+                ("stream", ctypes.c_void_p)]
+
+
 def _signatures():
     """(restype, argtypes) of every symbol include/parallel_ray_tracing.h declares, in the header's order.  Device and host
     arrays, handles and streams are c_void_p; a struct or a scalar the call writes through is a POINTER."""
@@ -258,6 +274,9 @@ def _signatures():
         # section 20: tomographic PIV (job structs as section 19's)
         "photon_piv_volume_los": (ci, [P(photon_piv_volume_los_t)]),
         "photon_piv_correlate_volume": (ci, [P(photon_piv_correlate_volume_t)]),
+        # section 21: MART particle volumes (job structs as section 20's)
+        "photon_piv_volume_project": (ci, [P(photon_piv_volume_project_t)]),
+        "photon_piv_volume_mart": (ci, [P(photon_piv_volume_mart_t)]),
     }
 
 
@@ -1485,9 +1504,58 @@ class PhotonLibrary:
         self._call("photon_piv_correlate_volume", ctypes.byref(job))
         return vectors, flags, planes
 
-    def _los_queued(self, camera_frames, cameras, vol, mode: str, stream: int, dev):
+    @staticmethod
+    def _volume_cameras(job, sensor_shapes, grids, vol, d_poly_ptr: int):
+        """The members sections 21a and 21b share: the sensors, the grids [N, 4], the table's pointer and the volume."""
+        n = len(sensor_shapes)
+        table = np.ascontiguousarray(grids, np.float64)
+        if not 0 < n <= 8 or table.shape != (n, 4):
+            raise ValueError(f"section 21 takes 2 to 8 cameras: one sensor shape each and grids [{n}, 4] (piv_tomo.los_coefficients)")
+        job.n_cameras, job.d_poly = n, int(d_poly_ptr) or None
+        job.volume = photon_piv_volume_t(float(vol["x0"]), float(vol["y0"]), float(vol["z0"]), float(vol["pitch"]), int(vol["nx"]), int(vol["ny"]),
+                                         int(vol["nz"]))
+        for c in range(n):
+            job.height[c], job.width[c] = int(sensor_shapes[c][0]), int(sensor_shapes[c][1])
+        ctypes.memmove(job.grid, table.ctypes.data, table.nbytes)
+        return n
+
+    def piv_volume_project(self, d_vol_ptr: int, vol_stride: int, n_frames: int, sensor_shapes, grids, d_poly_ptr: int, vol, d_acc_ptrs,
+                           acc_strides, scale_log2: int, d_image_ptrs=None, stream: int = 0):
+        """photon_piv_volume_project on raw device pointers: n_frames volumes f32 [nz, ny, nx], vol_stride floats apart; per
+        camera the sensor's (height, width), its grid [4], the pointer of its int64 accumulators [n_frames, height width] and
+        their stride; d_image_ptrs: per camera the pointer of the f32 images (the accumulators' stride), 0 = none.  Zeroes the
+        accumulators and adds every voxel above 0 in fixed point with 2^scale_log2; asynchronous on `stream`."""
+        job = photon_piv_volume_project_t(n_frames=int(n_frames), scale_log2=int(scale_log2), d_vol=int(d_vol_ptr) or None, vol_stride=int(vol_stride),
+                                          stream=int(stream) or None)
+        n = self._volume_cameras(job, sensor_shapes, grids, vol, d_poly_ptr)
+        images = [0] * n if d_image_ptrs is None else list(d_image_ptrs)
+        if not len(d_acc_ptrs) == len(acc_strides) == len(images) == n:
+            raise ValueError("piv_volume_project takes one accumulator pointer, stride and image pointer per camera")
+        for c in range(n):
+            job.d_acc[c], job.acc_stride[c], job.d_image[c] = int(d_acc_ptrs[c]) or None, int(acc_strides[c]), int(images[c]) or None
+        self._call("photon_piv_volume_project", ctypes.byref(job))
+
+    def piv_volume_mart(self, d_frame_ptrs, frame_strides, n_frames: int, sensor_shapes, grids, d_poly_ptr: int, vol, vol_stride: int,
+                        d_vol_ptr: int, d_acc_ptr: int, iterations: int, mu_roots: int, threshold: float, scale_log2: int, d_mask_ptr: int = 0,
+                        stream: int = 0):
+        """photon_piv_volume_mart on raw device pointers: per camera the pointer of its n_frames raw frames f32, their stride
+        and the sensor's (height, width); the n_frames volumes f32 at d_vol_ptr, vol_stride apart, are the first guess and
+        are updated in place; d_acc_ptr: the workspace int64 [2, n_frames, max height width]; d_mask_ptr: u8 [nz, ny, nx], 1 =
+        the voxel stays 0 (0 = NULL).  `iterations` MART iterations with the relaxation 2^-mu_roots; asynchronous on
+        `stream`."""
+        job = photon_piv_volume_mart_t(n_frames=int(n_frames), iterations=int(iterations), mu_roots=int(mu_roots), scale_log2=int(scale_log2),
+                                       threshold=float(threshold), vol_stride=int(vol_stride), d_vol=int(d_vol_ptr) or None,
+                                       d_mask=int(d_mask_ptr) or None, d_acc=int(d_acc_ptr) or None, stream=int(stream) or None)
+        n = self._volume_cameras(job, sensor_shapes, grids, vol, d_poly_ptr)
+        if not len(d_frame_ptrs) == len(frame_strides) == n:
+            raise ValueError("piv_volume_mart takes one frame pointer and stride per camera")
+        for c in range(n):
+            job.d_frame[c], job.frame_stride[c] = int(d_frame_ptrs[c]) or None, int(frame_strides[c])
+        self._call("photon_piv_volume_mart", ctypes.byref(job))
+
+    def _los_queued(self, camera_frames, cameras, vol, mode: str, stream: int, dev, mart=None):
         """reconstruct_volume's work, queued on `stream`: (volumes f32 [n, nz, ny, nx], mask u8 [nz, ny, nx], whether
-        camera_frames held single frames)."""
+        camera_frames held single frames).  mart: None, or _mart_settings' tuple."""
         import torch
         from . import piv_tomo as pt
         if mode not in pt.MODES:
@@ -1515,28 +1583,98 @@ class PhotonLibrary:
         unseen = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)
         self.piv_volume_los([c.data_ptr() for c in coefs], [int(c.shape[1] * c.shape[2]) for c in coefs], n, [tuple(c.shape[1:]) for c in coefs],
                             grids, d_poly.data_ptr(), vol, nz * ny * nx, out.data_ptr(), unseen.data_ptr(), pt.MODES[mode], stream)
+        if mart is not None:            # the iterations on the frames themselves, behind the first guess on the same stream
+            iterations, roots, threshold, scale_log2 = mart
+            acc = torch.empty((2, n, max(int(t.shape[1] * t.shape[2]) for t in stacks)), dtype=torch.int64, device=dev)
+            self.piv_volume_mart([t.data_ptr() for t in stacks], [int(t.shape[1] * t.shape[2]) for t in stacks], n, [tuple(t.shape[1:]) for t in stacks],
+                                 grids, d_poly.data_ptr(), vol, nz * ny * nx, out.data_ptr(), acc.data_ptr(), iterations, roots, threshold, scale_log2,
+                                 unseen.data_ptr(), stream)
         return out, unseen, checked[0].ndim == 2
 
-    def reconstruct_volume(self, camera_frames, cameras, vol, mode: str = "min"):
+    @staticmethod
+    def _mart_settings(method: str, mode: str, camera_frames, iterations, relaxation, threshold, scale_log2):
+        """The drivers' method= / reconstruction= on the host: None for "los"; for "mart" (iterations, mu_roots, threshold,
+        scale_log2), the last two chosen from the frames' maximum where the caller gives None (piv_mart.default_threshold,
+        scale_log2_for: read on the host; frames that are device tensors are read back first, one more wait)."""
+        from . import piv_mart as pm
+        if method not in ("los", "mart"):
+            raise ValueError(f'the reconstruction must be "los" or "mart", not {method!r}')
+        if method == "los":
+            return None
+        if mode != "min":
+            raise ValueError('MART starts from the line-of-sight volume in mode "min"')
+        roots = pm.mu_roots_of(relaxation)
+        if threshold is None or scale_log2 is None:
+            host = [x.detach().cpu().numpy() if hasattr(x, "detach") else np.asarray(x) for x in camera_frames]
+            threshold = pm.default_threshold(host) if threshold is None else threshold
+            scale_log2 = pm.scale_log2_for(host) if scale_log2 is None else scale_log2
+        pm.check_arguments(iterations, roots, threshold, scale_log2)
+        return int(iterations), roots, float(threshold), int(scale_log2)
+
+    def reconstruct_volume(self, camera_frames, cameras, vol, mode: str = "min", method: str = "los", iterations: int = 5,
+                           relaxation: float = 0.5, threshold: Optional[float] = None, scale_log2: Optional[int] = None):
         """A particle volume from N cameras by line of sight (section 20a; models: photon_amd.piv_tomo.los_model_f32, bit for
         bit, and los_model).  camera_frames: a list with one frame [height, width] or one stack [n, height, width] per
         camera, taken as the ingest rule of this class takes any image (the sensors may differ); cameras: 2 to 8 piv_stereo
         cameras; vol: a piv_tomo volume; mode "min" (MinLOS) or "product" (multiplicative LOS, without the N-th root).  On
         the current stream: the B-spline coefficients per frame, the cameras folded at every slice on the host and uploaded
         (a copy on the current stream), one line-of-sight launch for all frames; nothing waits for the result.  Returns device tensors (volumes f32 [n, nz, ny, nx], or [nz,
-        ny, nx] for single frames; mask u8 [nz, ny, nx], 1 where a camera does not see the voxel)."""
+        ny, nx] for single frames; mask u8 [nz, ny, nx], 1 where a camera does not see the voxel).
+        method "mart": the line-of-sight volume in mode "min" is the first guess of `iterations` MART iterations on the
+        frames themselves (section 21b; models: photon_amd.piv_mart.mart_model_f32 of los_model_f32, bit for bit, and
+        reconstruct_model), on the same stream, nothing waits.  relaxation: 1, 0.5, 0.25 or 0.125; threshold: voxels below it
+        become 0 (None: 1e-4 of the frames' maximum); scale_log2: section 21a's fixed-point scale (None: the largest s with 4
+        max(frames) 2^s <= 2^31)."""
         dev, stream = _device_and_stream()
-        out, unseen, single = self._los_queued(camera_frames, cameras, vol, mode, stream, dev)
+        mart = self._mart_settings(method, mode, camera_frames, iterations, relaxation, threshold, scale_log2)
+        out, unseen, single = self._los_queued(camera_frames, cameras, vol, mode, stream, dev, mart)
         return (out[0] if single else out), unseen
 
+    def reproject(self, volumes, cameras, vol, sensor_shapes, scale_log2: Optional[int] = None):
+        """The images the cameras would see of a particle volume (section 21a; model: photon_amd.piv_mart.project_model, integer
+        for integer).  volumes: one volume [nz, ny, nx] or a stack [n, nz, ny, nx], taken as the ingest rule of this class
+        takes any array; cameras: 2 to 8 piv_stereo cameras; vol: a piv_tomo volume; sensor_shapes: (height, width) per camera.
+        scale_log2: the fixed-point scale (None: the largest s with max(volumes) 2^s <= 2^31, read on the host: a volume on
+        the device is waited for).  On the current stream; nothing waits for the result.  Returns two lists of device
+        tensors, one entry per camera: (images f32 [n, height, width], accumulators int64 [n, height, width]), [height,
+        width] for one volume."""
+        import torch
+        from . import piv_mart as pm
+        from . import piv_tomo as pt
+        dev, stream = _device_and_stream()
+        checked = _checked(volumes, "volumes")
+        if checked is None or checked.ndim not in (3, 4) or tuple(checked.shape[-3:]) != (int(vol["nz"]), int(vol["ny"]), int(vol["nx"])):
+            raise ValueError("volumes must be [nz, ny, nx] or [n, nz, ny, nx] of the volume's size")
+        if not 2 <= len(cameras) <= 8 or len(sensor_shapes) != len(cameras):
+            raise ValueError("a re-projection takes 2 to 8 cameras and one sensor shape per camera")
+        d_vol = _on_device(checked, torch.float32, dev, "volumes")
+        d_vol = d_vol.reshape((-1,) + tuple(d_vol.shape[-3:]))
+        if scale_log2 is None:
+            scale_log2 = min(pm.scale_log2_for([d_vol.cpu().numpy()]) + 2, pm.SCALE_LOG2_RANGE[1])
+        pm.check_scale(scale_log2)
+        poly, grids = pt.los_coefficients(cameras, vol)
+        d_poly = _on_device(poly, torch.float64, dev, "poly")
+        n, shapes = int(d_vol.shape[0]), [(int(h), int(w)) for h, w in sensor_shapes]
+        acc = [torch.empty((n, h, w), dtype=torch.int64, device=dev) for h, w in shapes]
+        images = [torch.empty((n, h, w), dtype=torch.float32, device=dev) for h, w in shapes]
+        self.piv_volume_project(d_vol.data_ptr(), int(d_vol.shape[1] * d_vol.shape[2] * d_vol.shape[3]), n, shapes, grids, d_poly.data_ptr(), vol,
+                                [a.data_ptr() for a in acc], [h * w for h, w in shapes], int(scale_log2), [i.data_ptr() for i in images], stream)
+        if checked.ndim == 3:
+            return [i[0] for i in images], [a[0] for a in acc]
+        return images, acc
+
     def correlate_tomo(self, camera_frames, cameras, vol, win: int = 32, step: int = 16, radius: int = 4, win_z: Optional[int] = None,
-                       step_z: Optional[int] = None, radius_z: Optional[int] = None, mode: str = "min", offsets=None):
+                       step_z: Optional[int] = None, radius_z: Optional[int] = None, mode: str = "min", offsets=None,
+                       reconstruction: str = "los", iterations: int = 5, relaxation: float = 0.5, threshold: Optional[float] = None,
+                       scale_log2: Optional[int] = None):
         """Three displacement components on a 3-D grid from N cameras (section 20; model:
         photon_amd.piv_tomo.correlate_tomo_model).  camera_frames: a list with the two exposures of each camera, a stack [2,
         height, width], taken as the ingest rule of this class takes any stack; cameras, vol, mode as reconstruct_volume
         takes them.  win_z defaults to win, capped at 64 and nz; step_z to max(1, win_z / 2); radius_z to min(radius, 16,
         win_z / 2).  offsets: integer (ox, oy, oz) per node [n_slabs, n_rows, n_cols, 3] in voxels, or None.  On the current
         stream: both exposures through one line-of-sight launch, then the 3-D correlation; the host waits once.
+        reconstruction "mart" with iterations, relaxation, threshold and scale_log2 as reconstruct_volume(method="mart")
+        takes them: the MART iterations between the two, on the same stream (model: photon_amd.piv_mart.mart_tomo_model).
         Returns numpy (displacements f64 [n_slabs, n_rows, n_cols, 3] = pitch (dx, dy, dz) in world units; vectors f32
         [n_slabs, n_rows, n_cols, 5] = dx, dy, dz in voxels, peak, ratio; flags int32 [n_slabs, n_rows, n_cols]; partial bool
         [n_slabs, n_rows, n_cols], true where the window holds a voxel some camera does not see)."""
@@ -1544,6 +1682,7 @@ class PhotonLibrary:
         from . import piv_tomo as pt
         win_z, step_z, radius_z = pt.z_defaults(vol, win, radius, win_z, step_z, radius_z)
         pt.check_arguments((int(vol["nz"]), int(vol["ny"]), int(vol["nx"])), win, step, radius, win_z, step_z, radius_z)
+        mart = self._mart_settings(reconstruction, mode, camera_frames, iterations, relaxation, threshold, scale_log2)
         dev, stream = _device_and_stream()
         d_off = None
         if offsets is not None:
@@ -1552,7 +1691,7 @@ class PhotonLibrary:
             if tuple(table.shape) != grid + (3,):
                 raise ValueError(f"offsets must be {grid + (3,)}: (ox, oy, oz) per node, not {tuple(table.shape)}")
             d_off = _on_device(table, torch.float64, dev, "offsets").to(torch.int32).contiguous()      # whole numbers: exact in f64
-        volumes, unseen, _ = self._los_queued(camera_frames, cameras, vol, mode, stream, dev)
+        volumes, unseen, _ = self._los_queued(camera_frames, cameras, vol, mode, stream, dev, mart)
         if volumes.shape[0] != 2:
             raise ValueError("correlate_tomo takes the two exposures of each camera, [2, height, width]")
         nz, ny, nx = (int(v) for v in volumes.shape[1:])

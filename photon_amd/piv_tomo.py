@@ -16,9 +16,9 @@ The device forms are photon_piv_volume_los and photon_piv_correlate_volume (incl
   reconstruction with the true particle field), and the synthetic cases the tests and tools/piv_tomo.py measure (``CASES``,
   ``case_inputs``, ``case_figures``).
 
-Reconstruction is by line of sight alone (MinLOS, multiplicative LOS without the N-th root).  What does not exist:
-iterative reconstruction (MART / SMART), 3-D vector validation, multi-pass refinement and volume deformation, volumetric
-self-calibration, masks and window weights in 3-D, sum-of-correlation over volume pairs.
+Reconstruction here is by line of sight (MinLOS, multiplicative LOS without the N-th root); MART from that first guess is
+photon_amd/piv_mart.py (section 21).  What does not exist: SMART and MLEM, 3-D vector validation, multi-pass refinement and
+volume deformation, volumetric self-calibration, masks and window weights in 3-D, sum-of-correlation over volume pairs.
 """
 from __future__ import annotations
 

@@ -4,6 +4,7 @@ the accuracy table of the synthetic cases for the device chain and the model cha
 figures of DESIGN.md section 4.3x.
 
     python tools/piv_tomo.py [--reps 10] [--no-model]
+    python tools/piv_tomo.py --mart [--reps 10] [--no-model]      MART (section 21): the figures of DESIGN.md section 4.3y
 
 Times are device events around `reps` back-to-back calls (one wait at the end), after a warm-up; the driver is timed on the
 host around whole calls.  The accuracy cases are photon_amd.piv_tomo.CASES (volume 64 x 64 x 24 voxels at 0.1 mm, sensors 96 x
@@ -36,15 +37,75 @@ def device_us(run, reps):
     return start.elapsed_time(stop) * 1e3 / reps
 
 
+def mart(lib, args):
+    """--mart: the figures of DESIGN.md section 4.3y.  Times on section 4.3x's line-of-sight shape from the MinLOS volume of a
+    rendered pair: the whole call with 1 and with 2 iterations (each behind a copy that restores the first guess; the copy
+    alone is subtracted), so that one fused camera step is a quarter of their difference.  Then per case of
+    photon_amd.piv_mart.CASES at seed 0: Q of the first exposure on the whole volume and on the interior for MinLOS and after
+    every iteration, and the vector rms of the MART chain next to MinLOS's."""
+    import torch
+    from photon_amd import piv_mart as pm
+    from photon_amd import piv_tomo as pt
+    vol = pt.centred_volume(256, 256, 32, 0.1)
+    views = pt.calibrated_views(pt.CASES["uniform"]["angles"], vol, shape=(512, 512), px_per_mm=15.0)
+    cams = [v[1] for v in views]
+    frames, _ = pt.particle_volume_pair([v[0] for v in views], pt.uniform_flow, vol, 7, shape=(512, 512), ppp=0.05)
+    poly, grids = pt.los_coefficients(cams, vol)
+    first, unseen = lib.reconstruct_volume(list(frames), cams, vol)
+    d_frames = [torch.from_numpy(f).cuda() for f in frames]
+    d_poly = torch.from_numpy(poly).cuda()
+    d_vol = first.clone()
+    acc = torch.empty((2, 2, 512 * 512), dtype=torch.int64, device="cuda")
+    s, thr = pm.scale_log2_for(list(frames)), pm.default_threshold(list(frames))
+
+    def run(iterations):
+        d_vol.copy_(first)
+        if iterations:
+            lib.piv_volume_mart([f.data_ptr() for f in d_frames], [512 * 512] * 4, 2, [(512, 512)] * 4, grids, d_poly.data_ptr(), vol, 32 * 256 * 256,
+                                d_vol.data_ptr(), acc.data_ptr(), iterations, 1, thr, s, unseen.data_ptr())
+    t0, t1, t2, t5 = (device_us(lambda k=k: run(k), args.reps) for k in (0, 1, 2, 5))
+    live = [float((first > 0).float().mean().item())]
+    run(5)
+    live.append(float((d_vol > 0).float().mean().item()))
+    print(f"{lib.version()}")
+    print(f"MART, 4 cameras 512^2, volume 256 x 256 x 32, 2 frames, live voxels {live[0]:.3f} of the first guess, {live[1]:.3f} after 5 iterations:")
+    print(f"  1 iteration {t1 - t0:.0f} us, 2 iterations {t2 - t0:.0f} us, 5 iterations {t5 - t0:.0f} us; one camera step {(t2 - t1) / 4:.1f} us "
+          f"(the copy that restores the first guess, subtracted: {t0:.0f} us)")
+
+    print("case            Q MinLOS (interior)   Q after iteration 1 .. 5, whole volume / interior                 chain    rms dX     dY     dZ [voxels]")
+    for name in pm.CASES:
+        frames, cameras, vol, (P, brightness, half) = pm.case_inputs(name, 0)
+        truth = pt.true_volume(vol, P - half, brightness)
+        los = lib.reconstruct_volume(list(frames), cameras, vol)[0][0].cpu().numpy()
+        qs = []
+        for k in range(1, 6):
+            E = lib.reconstruct_volume(list(frames), cameras, vol, method="mart", iterations=k)[0][0].cpu().numpy()
+            qs.append(f"{pt.quality(E, truth):.3f}/{pm.interior_quality(E, truth):.3f}")
+        chains = [("MinLOS", lib.correlate_tomo(list(frames), cameras, vol, **pt.CASE_GRID)),
+                  ("MART", lib.correlate_tomo(list(frames), cameras, vol, reconstruction="mart", **pt.CASE_GRID))]
+        if not args.no_model:
+            chains.append(("model", pm.mart_tomo_model(frames, cameras, vol, **pt.CASE_GRID)))
+        for chain, res in chains:
+            rms, _ = pm.case_figures(name, res[0])
+            head = f"{name:15s} {pt.quality(los, truth):.3f} ({pm.interior_quality(los, truth):.3f})         {' '.join(qs)}" if chain == "MinLOS" else " " * 96
+            print(f"{head:96s}   {chain:7s} {rms[0]:6.4f} {rms[1]:6.4f} {rms[2]:6.4f}")
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "kernel_report.py"), "--unit", "photon_piv_mart", "--match", "kernel"],
+                       capture_output=True, text=True)
+    print(r.stdout.strip() or r.stderr.strip()[-500:])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--no-model", action="store_true", help="skip the host model chain (the accuracy table's second half)")
+    ap.add_argument("--mart", action="store_true", help="the MART figures (section 21, DESIGN.md section 4.3y) instead of section 20's")
     args = ap.parse_args()
     import torch
     from photon_amd import library
     from photon_amd import piv_tomo as pt
     lib = library.PhotonLibrary()
+    if args.mart:
+        return mart(lib, args)
     p = lambda t: ctypes.c_void_p(t.data_ptr())     # noqa: E731
 
     # ---- the 3-D correlator against the ensemble correlator on as many plane pairs
