@@ -22,7 +22,7 @@ UNITS = ("photon_pool", "photon_volume", "photon_scene", "photon_cull", "photon_
          "photon_sensor", "photon_moments", "photon_trace", "photon_post", "photon_piv", "photon_piv_masked", "photon_piv_weighted", "photon_piv_ensemble", "photon_piv_deform", "photon_piv_uncertainty", "photon_piv_phase", "photon_piv_preprocess", "photon_piv_stereo", "photon_piv_tomo", "photon_piv_mart", "photon_optflow", "photon_dots", "photon_density", "photon_tomo", "photon_abi", "photon_sort", "photon_flow", "photon_version")
 SOURCES = [os.path.join(CSRC, u + ".hip") for u in UNITS]
 HEADERS = [os.path.join(CSRC, h) for h in ("block_reduce.hpp", "device_vec.hpp", "device_volume.hpp", "device_volume_coop.hpp", "device_volume_extra.hpp", "device_optics.hpp",
-                                            "fixed_sum.hpp", "march_args.hpp", "march_kernel.hpp", "photon_internal.hpp", "photon_pool.hpp", "photon_sort.hpp", "piv_direct.hpp", "piv_field.hpp", "piv_footprint.hpp", "piv_grid.hpp", "piv_peak.hpp", "piv_warp.hpp")] + [
+                                            "fixed_sum.hpp", "march_args.hpp", "march_kernel.hpp", "photon_internal.hpp", "photon_pool.hpp", "photon_sort.hpp", "piv_camera.hpp", "piv_direct.hpp", "piv_field.hpp", "piv_grid.hpp", "piv_peak.hpp", "piv_warp.hpp")] + [
     os.path.join(ROOT, "include", "parallel_ray_tracing.h"),
     os.path.join(ROOT, "include", "photon_det_math.h"),
     os.path.join(ROOT, "include", "photon_philox.h"),

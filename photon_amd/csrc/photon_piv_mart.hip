@@ -2,9 +2,9 @@
 // the multiplicative, camera-sequential update that starts from a line-of-sight volume.  Definition:
 // include/parallel_ray_tracing.h, section 21; host models: photon_amd/piv_mart.py.
 //
-//   mart_kernel<UPDATE>   one thread per voxel in los_kernel's shape (a 64 x 4 block over (j, i), the slice in the block
-//                         index: a wave's voxels land on neighbouring pixels).  Voxels that are not above 0 leave before any
-//                         coordinate is computed: that skip is the algorithm's sparsity.  UPDATE: the voxel's footprint on
+//   mart_kernel<UPDATE>   one thread per voxel in los_kernel's shape (piv_camera.hpp, VoxelGrid: a 64 x 4 block over (j, i),
+//                         the slice in the block index: a wave's voxels land on neighbouring pixels).  Voxels that are not
+//                         above 0 leave before any coordinate is computed: the algorithm's sparsity.  UPDATE: the footprint on
 //                         the update's camera, the frame and the re-projection gathered there, the ratio, its roots, the
 //                         threshold, the store.  Then, for each camera of the projection list, the footprint there and four
 //                         64-bit integer atomic adds of the voxel's new value: camera c's update and camera c + 1's
@@ -13,12 +13,12 @@
 //   image_kernel          the accumulators as f32 images (section 21a's optional output).
 // The accumulators are 64-bit integers: integer addition is associative, so any arrival order of the atomics returns the same
 // integers, two calls return the same bits, and the fused pass equals the two-step definition bit for bit.
-// Neither entry point allocates: the accumulators are the caller's.
+// Neither entry point allocates: the accumulators are the caller's.  Footprint, voxel shape, shared rules: piv_camera.hpp.
 #include <climits>
 #include <cmath>
 
 #include "photon_internal.hpp"
-#include "piv_footprint.hpp"
+#include "piv_camera.hpp"
 #include "piv_grid.hpp"
 #include "piv_warp.hpp"
 
@@ -26,13 +26,10 @@ using namespace photon;
 
 namespace {
 
-using piv_footprint::Footprint;
-using piv_footprint::footprint;
+using namespace piv_camera;
 using piv_warp::kWarpX;
 using piv_warp::kWarpY;
 
-constexpr int kMaxCameras = 8;
-constexpr int kFrameChunk = 4;      // frames that share one footprint per camera and voxel
 constexpr int kMaxRoots = 3;
 constexpr int kScaleMin = -126, kScaleMax = 62;
 #ifdef PHOTON_MART_UNFUSED
@@ -53,7 +50,8 @@ struct MartArgs {
     long long vol_stride;
     const unsigned char *mask;
     const double *poly;             // [n_cameras][nz][2][10]
-    int n_frames, nx, ny, nz, col_blocks, row_blocks;
+    int n_frames;
+    VoxelGrid vox;
     double scale, inv_scale;        // 2^s, 2^-s
     View upd;                       // UPDATE: the camera of the update; acc holds its re-projection
     const float *frames;            // its raw frames, frame_stride apart
@@ -72,11 +70,9 @@ __device__ __forceinline__ unsigned long long quantise(float p, double scale) {
 
 template <bool UPDATE>
 __global__ __launch_bounds__(kWarpX *kWarpY) void mart_kernel(const MartArgs a) {
-    const int cb = blockIdx.x % a.col_blocks, rest = blockIdx.x / a.col_blocks;
-    const int rb = rest % a.row_blocks, k = rest / a.row_blocks;
-    const int j = cb * kWarpX + threadIdx.x, i = rb * kWarpY + threadIdx.y;
-    if (j >= a.nx || i >= a.ny) return;
-    const size_t o = ((size_t)k * a.ny + i) * a.nx + j;
+    int i, j, k;
+    size_t o;
+    if (!a.vox.voxel(i, j, k, o)) return;
     for (int f0 = 0; f0 < a.n_frames; f0 += kFrameChunk) {
         const int nf = min(kFrameChunk, a.n_frames - f0);
         float E[kFrameChunk] = {0.f, 0.f, 0.f, 0.f};
@@ -91,7 +87,7 @@ __global__ __launch_bounds__(kWarpX *kWarpY) void mart_kernel(const MartArgs a) 
         Footprint fp;
         if (UPDATE) {
             const View &u = a.upd;
-            const bool seen = !(a.mask && a.mask[o]) && footprint(a.poly + ((size_t)u.camera * a.nz + k) * 20, u.grid, i, j, u.W, u.H, fp);
+            const bool seen = !(a.mask && a.mask[o]) && footprint(a.poly + ((size_t)u.camera * a.vox.nz + k) * 20, u.grid, i, j, u.W, u.H, fp);
 #pragma unroll
             for (int f = 0; f < kFrameChunk; f++) {
                 if (f >= nf || !(E[f] > 0.f)) continue;
@@ -124,7 +120,7 @@ __global__ __launch_bounds__(kWarpX *kWarpY) void mart_kernel(const MartArgs a) 
 #pragma unroll 1
         for (int c = 0; c < a.n_proj; c++) {
             const View &v = a.proj[c];
-            if (!footprint(a.poly + ((size_t)v.camera * a.nz + k) * 20, v.grid, i, j, v.W, v.H, fp)) continue;
+            if (!footprint(a.poly + ((size_t)v.camera * a.vox.nz + k) * 20, v.grid, i, j, v.W, v.H, fp)) continue;
 #pragma unroll
             for (int f = 0; f < kFrameChunk; f++) {
                 if (f >= nf || !(E[f] > 0.f)) continue;
@@ -148,49 +144,29 @@ __global__ __launch_bounds__(256) void image_kernel(const long long *acc, float 
 
 template <bool UPDATE>
 int launch(const MartArgs &a, hipStream_t stream) {
-    const long long blocks = (long long)a.col_blocks * a.row_blocks * a.nz;          // below 2^31: nx ny nz <= INT_MAX, sides <= 2^22
-    hipLaunchKernelGGL(mart_kernel<UPDATE>, dim3((unsigned)blocks), dim3(kWarpX, kWarpY), 0, stream, a);
+    hipLaunchKernelGGL(mart_kernel<UPDATE>, dim3(a.vox.blocks()), dim3(kWarpX, kWarpY), 0, stream, a);
     PH_CHECK(hipGetLastError());
     return 0;
 }
 
-bool all_finite(const double *v, int n) {
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-struct Range {
-    const char *lo;
-    size_t bytes;
-};
-Range range_of(const void *p, size_t element, long long stride, int n) { return {reinterpret_cast<const char *>(p), element * (size_t)stride * (size_t)n}; }
-bool overlap(const Range &a, const Range &b) { return a.lo < b.lo + b.bytes && b.lo < a.lo + a.bytes; }
-
-// what sections 21a and 21b share of section 20a's rules: the counts, the volume, the sensors, the grids
+// what sections 21a and 21b share of section 20a's rules (piv_camera.hpp): counts, scale, volume, sensors, grids, in this order
 const char *common_error(int n_cameras, int n_frames, int scale_log2, const photon_piv_volume_t &vol, long long vol_stride, const int *width,
                          const int *height, const double (*grid)[4]) {
-    if (n_cameras < 2 || n_cameras > kMaxCameras) return "n_cameras must be within [2, 8]";
-    if (n_frames < 1) return "n_frames must be >= 1";
-    if (scale_log2 < kScaleMin || scale_log2 > kScaleMax) return "scale_log2 must be within [-126, 62]";
-    const char *bad = piv_grid::side_error(vol.nx, vol.ny);
-    if (!bad) bad = piv_grid::side_error(vol.nz, vol.nz);
-    if (bad) return bad;
-    if ((long long)vol.nx * vol.ny * vol.nz > INT_MAX) return "nx ny nz is above INT_MAX";
-    if (vol_stride < (long long)vol.nx * vol.ny * vol.nz) return "vol_stride is below nx ny nz";
-    for (int c = 0; c < n_cameras; c++) {
+    const char *bad = cameras_error(n_cameras);
+    if (!bad) bad = frames_error(n_frames);
+    if (!bad && (scale_log2 < kScaleMin || scale_log2 > kScaleMax)) bad = "scale_log2 must be within [-126, 62]";
+    if (!bad) bad = volume_error(vol, vol_stride, "vol_stride is below nx ny nz");
+    for (int c = 0; !bad && c < n_cameras; c++) {
         bad = piv_grid::side_error(width[c], height[c]);
-        if (bad) return bad;
-        if (!all_finite(grid[c], 4)) return "a grid value is not finite";
+        if (!bad) bad = grid_values_error(grid[c]);
     }
-    return nullptr;
+    return bad;
 }
 
 void fill_common(MartArgs &a, const photon_piv_volume_t &vol, const float *d_vol, long long vol_stride, const double *d_poly, int n_frames, int scale_log2) {
     a.vol = const_cast<float *>(d_vol), a.vol_stride = vol_stride;
     a.mask = nullptr, a.poly = d_poly;
-    a.n_frames = n_frames, a.nx = vol.nx, a.ny = vol.ny, a.nz = vol.nz;
-    a.col_blocks = (vol.nx + kWarpX - 1) / kWarpX, a.row_blocks = (vol.ny + kWarpY - 1) / kWarpY;
+    a.n_frames = n_frames, a.vox = VoxelGrid::make(vol);
     a.scale = std::ldexp(1.0, scale_log2), a.inv_scale = std::ldexp(1.0, -scale_log2);
     a.upd = View{}, a.frames = nullptr, a.frame_stride = 0, a.roots = 0, a.threshold = 0.f, a.n_proj = 0;
     for (int c = 0; c < kMaxCameras; c++) a.proj[c] = View{};

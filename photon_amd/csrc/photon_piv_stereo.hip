@@ -2,22 +2,25 @@
 // light sheet's plane through the camera's polynomial, two cameras' 2-C fields on that grid combined into three
 // components per node, and the disparity between the two dewarped views triangulated into points of the sheet.  Definition: include/parallel_ray_tracing.h, section 19; host models: photon_amd/piv_stereo.py.
 //
-//   dewarp_kernel        one thread per output pixel: two bivariate cubics in f64 (Horner, no division), the fraction taken
-//                        in f64 and rounded once, section 7b's weights and mirrors (piv_warp.hpp) computed once, then per
-//                        frame 16 coefficient taps gathered from global memory and one coalesced store
+//   dewarp_kernel        one thread per output pixel: where the pixel lands on the sensor (piv_camera.hpp, sensor_point: two
+//                        bivariate cubics in f64, the fraction taken in f64 and rounded once), section 7b's weights and
+//                        mirrors (piv_warp.hpp, BsplineTaps) computed once, then per frame 16 coefficient taps gathered
+//                        from global memory and one coalesced store
 //   reconstruct_kernel   one thread per node: two analytic 2 x 3 Jacobians, the 3 x 3 normal equations of four equations,
 //                        Cholesky, the residual and the propagated sigmas, all in f64 in a fixed order
 //   triangulate_kernel   one thread per node of a disparity field between the two cameras' dewarped frames: the two image
 //                        points, then Gauss-Newton steps for the world point both saw -- per step two polynomial
 //                        evaluations, the two Jacobians and the 3 x 3 Cholesky of the reconstruction -- in f64 in a fixed order
-// No kernel needs device scratch or LDS, none writes what another thread reads: two calls return the same bits.
+// Host rules: piv_camera.hpp.  No kernel needs device scratch or LDS, none writes what another thread reads: two calls return the same bits.
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_camera.hpp"
 #include "piv_grid.hpp"
 #include "piv_warp.hpp"
 
 using namespace photon;
+using namespace photon::piv_camera;
 using namespace photon::piv_warp;
 
 namespace {
@@ -29,55 +32,24 @@ struct DewarpArgs {
     const float *coef;
     long long in_stride, out_stride;
     int n_frames, W, H, OW, OH;
-    double kx[10], ky[10], u0, du, v0, dv;
+    double poly[2][10], grid[4];
     float *out;
     unsigned char *mask;
 };
 
-// the bivariate cubic of section 19a in its fixed Horner order; k: 1, u, v, u^2, uv, v^2, u^3, u^2 v, u v^2, v^3
-__device__ __forceinline__ double cubic(const double k[10], double u, double v) {
-    const double a0 = ((k[9] * v + k[5]) * v + k[2]) * v + k[0];
-    const double a1 = (k[8] * v + k[4]) * v + k[1];
-    const double a2 = k[7] * v + k[3];
-    return ((k[6] * u + a2) * u + a1) * u + a0;
-}
-
 __global__ __launch_bounds__(kWarpX *kWarpY) void dewarp_kernel(const DewarpArgs a) {
     const int j = blockIdx.x * kWarpX + threadIdx.x, i = blockIdx.y * kWarpY + threadIdx.y;
     if (j >= a.OW || i >= a.OH) return;
-    const double u = a.u0 + (double)j * a.du, v = a.v0 + (double)i * a.dv;
-    const double x = cubic(a.kx, u, v), y = cubic(a.ky, u, v);
     const size_t o = (size_t)i * a.OW + j;
-    const bool inside = x >= 0.0 && x <= (double)(a.W - 1) && y >= 0.0 && y <= (double)(a.H - 1);      // false for a NaN
+    SensorPoint p;
+    const bool inside = sensor_point(&a.poly[0][0], a.grid, i, j, a.W, a.H, p);
     if (a.mask) a.mask[o] = inside ? 0 : 1;
     if (!inside) {
         for (int f = 0; f < a.n_frames; f++) a.out[(size_t)f * a.out_stride + o] = 0.f;
         return;
     }
-    // the absolute coordinate never enters a float: the fraction is taken in f64 and rounded once
-    const double fx = floor(x), fy = floor(y);
-    float wxs[4], wys[4];
-    bspline_weights((float)(x - fx), wxs);
-    bspline_weights((float)(y - fy), wys);
-    const int bx0 = (int)fx - 1, by0 = (int)fy - 1;
-    int xi[4];
-    size_t yo[4];
-#pragma unroll
-    for (int t = 0; t < 4; t++) {
-        xi[t] = mirror(bx0 + t, a.W);
-        yo[t] = (size_t)mirror(by0 + t, a.H) * a.W;
-    }
-    for (int f = 0; f < a.n_frames; f++) {
-        const float *coef = a.coef + (size_t)f * a.in_stride;
-        float acc = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; t++) {
-            const float *row = coef + yo[t];
-            const float s = ((wxs[0] * row[xi[0]] + wxs[1] * row[xi[1]]) + wxs[2] * row[xi[2]]) + wxs[3] * row[xi[3]];
-            acc = acc + wys[t] * s;
-        }
-        a.out[(size_t)f * a.out_stride + o] = acc;
-    }
+    const BsplineTaps taps(p.ix, p.iy, p.fx, p.fy, a.W, a.H);
+    for (int f = 0; f < a.n_frames; f++) a.out[(size_t)f * a.out_stride + o] = taps.sample(a.coef + (size_t)f * a.in_stride);
 }
 
 // =============================================================================================
@@ -116,8 +88,31 @@ __device__ __forceinline__ void jacobian(const photon_piv_camera_t &c, const dou
     }
 }
 
+// the node's point on the plane: the centre of window (i, j) of section 5's grid
+__device__ __forceinline__ void node_point(const photon_piv_plane_t &plane, int win, int step, int i, int j, double P[3]) {
+    const double half = (double)(win - 1) / 2.0;
+    P[0] = plane.x0 + ((double)(j * step) + half) * plane.pitch;
+    P[1] = plane.y0 + ((double)(i * step) + half) * plane.pitch;
+    P[2] = plane.z;
+}
+
 struct Cholesky3 {
     double l00, l10, l20, l11, l21, l22;
+    // N = L L^T.  Returns the smallest pivot over the largest; ok: that is above kMinPivotRatio and every pivot above 0 (no NaN)
+    __device__ __forceinline__ double factor(const double N[3][3], bool &ok) {
+        const double d0 = N[0][0];
+        l00 = sqrt(d0);
+        l10 = N[1][0] / l00;
+        l20 = N[2][0] / l00;
+        const double d1 = N[1][1] - l10 * l10;
+        l11 = sqrt(d1);
+        l21 = (N[2][1] - l20 * l10) / l11;
+        const double d2 = (N[2][2] - l20 * l20) - l21 * l21;
+        l22 = sqrt(d2);
+        const double ratio = fmin(fmin(d0, d1), d2) / fmax(fmax(d0, d1), d2);
+        ok = ratio > kMinPivotRatio && d0 > 0.0 && d1 > 0.0 && d2 > 0.0;
+        return ratio;
+    }
     __device__ __forceinline__ void solve(const double r[3], double z[3]) const {
         const double y0 = r[0] / l00;
         const double y1 = (r[1] - l10 * y0) / l11;
@@ -132,8 +127,9 @@ __global__ __launch_bounds__(kNodeThreads) void reconstruct_kernel(const StereoA
     const int k = blockIdx.x * kNodeThreads + threadIdx.x;
     if (k >= a.n_rows * a.n_cols) return;
     const int i = k / a.n_cols, j = k - i * a.n_cols;
-    const double qnan = __builtin_nan(""), pitch = a.plane.pitch, half = (double)(a.win - 1) / 2.0;
-    const double P[3] = {a.plane.x0 + ((double)(j * a.step) + half) * pitch, a.plane.y0 + ((double)(i * a.step) + half) * pitch, a.plane.z};
+    const double qnan = __builtin_nan(""), pitch = a.plane.pitch;
+    double P[3];
+    node_point(a.plane, a.win, a.step, i, j, P);
     const float *f[2] = {a.field1 + (size_t)k * a.stride, a.field2 + (size_t)k * a.stride};
     const float *sg[2] = {a.sigma1 ? a.sigma1 + 2 * (size_t)k : nullptr, a.sigma2 ? a.sigma2 + 2 * (size_t)k : nullptr};
     int flag = (a.flags1 ? a.flags1[k] : 0) | (a.flags2 ? a.flags2[k] : 0);
@@ -161,19 +157,11 @@ __global__ __launch_bounds__(kNodeThreads) void reconstruct_kernel(const StereoA
         r[p] = ((A[0][p] * b[0] + A[1][p] * b[1]) + A[2][p] * b[2]) + A[3][p] * b[3];
     }
     Cholesky3 L;
-    const double d0 = N[0][0];
-    L.l00 = sqrt(d0);
-    L.l10 = N[1][0] / L.l00;
-    L.l20 = N[2][0] / L.l00;
-    const double d1 = N[1][1] - L.l10 * L.l10;
-    L.l11 = sqrt(d1);
-    L.l21 = (N[2][1] - L.l20 * L.l10) / L.l11;
-    const double d2 = (N[2][2] - L.l20 * L.l20) - L.l21 * L.l21;
-    L.l22 = sqrt(d2);
-    const double ratio = fmin(fmin(d0, d1), d2) / fmax(fmax(d0, d1), d2);
+    bool ok;
+    const double ratio = L.factor(N, ok);
 
     double out[8] = {qnan, qnan, qnan, qnan, qnan, qnan, qnan, qnan};
-    if (!(ratio > kMinPivotRatio) || !(d0 > 0.0 && d1 > 0.0 && d2 > 0.0)) flag |= 64;
+    if (!ok) flag |= 64;
     else {
         out[7] = ratio;
         if (finite) {
@@ -272,8 +260,9 @@ __global__ __launch_bounds__(kNodeThreads) void triangulate_kernel(const Triangu
     const int k = blockIdx.x * kNodeThreads + threadIdx.x;
     if (k >= a.n_rows * a.n_cols) return;
     const int i = k / a.n_cols, j = k - i * a.n_cols;
-    const double qnan = __builtin_nan(""), pitch = a.plane.pitch, half = (double)(a.win - 1) / 2.0;
-    const double P[3] = {a.plane.x0 + ((double)(j * a.step) + half) * pitch, a.plane.y0 + ((double)(i * a.step) + half) * pitch, a.plane.z};
+    const double qnan = __builtin_nan(""), pitch = a.plane.pitch;
+    double P[3];
+    node_point(a.plane, a.win, a.step, i, j, P);
     const float *d = a.disparity + (size_t)k * a.stride;
     const float dx = d[0], dy = d[1];
     const bool finite = isfinite(dx) && isfinite(dy);
@@ -311,17 +300,8 @@ __global__ __launch_bounds__(kNodeThreads) void triangulate_kernel(const Triangu
             }
         }
         Cholesky3 L;
-        const double d0 = N[0][0];
-        L.l00 = sqrt(d0);
-        L.l10 = N[1][0] / L.l00;
-        L.l20 = N[2][0] / L.l00;
-        const double d1 = N[1][1] - L.l10 * L.l10;
-        L.l11 = sqrt(d1);
-        L.l21 = (N[2][1] - L.l20 * L.l10) / L.l11;
-        const double d2 = (N[2][2] - L.l20 * L.l20) - L.l21 * L.l21;
-        L.l22 = sqrt(d2);
-        const double ratio = fmin(fmin(d0, d1), d2) / fmax(fmax(d0, d1), d2);
-        const bool ok = ratio > kMinPivotRatio && d0 > 0.0 && d1 > 0.0 && d2 > 0.0;
+        bool ok;
+        const double ratio = L.factor(N, ok);
         lowest = (ok && it > 0) ? (ratio < lowest ? ratio : lowest) : ratio;
         if (!ok) good = false;
         if (!ok || !finite) break;          // a vector that is not finite: the start point's ratio, no step
@@ -347,17 +327,6 @@ __global__ __launch_bounds__(kNodeThreads) void triangulate_kernel(const Triangu
 #pragma unroll
     for (int m = 0; m < 6; m++) a.out[6 * (size_t)k + m] = out[m];
     a.flags[k] = flag;
-}
-
-bool all_finite(const double *v, int n) {
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
-bool camera_ok(const photon_piv_camera_t &c) {
-    return all_finite(c.centre, 3) && all_finite(c.scale, 3) && all_finite(c.cx, 19) && all_finite(c.cy, 19) && c.scale[0] != 0.0 &&
-           c.scale[1] != 0.0 && c.scale[2] != 0.0;
 }
 
 }  // namespace
@@ -386,8 +355,8 @@ extern "C" int photon_piv_dewarp(const photon_piv_dewarp_t *job) {
     a.coef = job->d_coef;
     a.in_stride = job->frame_stride, a.out_stride = job->out_stride;
     a.n_frames = job->n_frames, a.W = job->width, a.H = job->height, a.OW = job->out_width, a.OH = job->out_height;
-    for (int k = 0; k < 10; k++) a.kx[k] = job->poly[0][k], a.ky[k] = job->poly[1][k];
-    a.u0 = job->grid[0], a.du = job->grid[1], a.v0 = job->grid[2], a.dv = job->grid[3];
+    for (int k = 0; k < 10; k++) a.poly[0][k] = job->poly[0][k], a.poly[1][k] = job->poly[1][k];
+    for (int k = 0; k < 4; k++) a.grid[k] = job->grid[k];
     a.out = job->d_out, a.mask = job->d_mask;
     hipLaunchKernelGGL(dewarp_kernel, warp_grid(a.OW, a.OH), dim3(kWarpX, kWarpY), 0, (hipStream_t)job->stream, a);
     PH_CHECK(hipGetLastError());
@@ -407,11 +376,7 @@ extern "C" int photon_piv_stereo_reconstruct(const photon_piv_stereo_t *job) {
         else if (job->field_stride != 2 && job->field_stride != 4) bad = "field_stride must be 2 or 4";
         else if (!job->d_sigma1 != !job->d_sigma2) bad = "d_sigma1 and d_sigma2 come together or not at all";
     }
-    if (!bad) {
-        if (!(std::isfinite(pl.x0) && std::isfinite(pl.y0) && std::isfinite(pl.z) && std::isfinite(pl.pitch))) bad = "a plane value is not finite";
-        else if (!(pl.pitch > 0.0)) bad = "pitch must be > 0";
-        else if (!camera_ok(job->camera1) || !camera_ok(job->camera2)) bad = "a camera value is not finite, or a scale is 0";
-    }
+    if (!bad) bad = plane_cameras_error(pl, job->camera1, job->camera2);
     if (bad) {
         fprintf(stderr, "photon: photon_piv_stereo_reconstruct: %s (win %d, step %d, %d x %d plane, %d x %d grid, stride %d)\n", bad, job->win,
                 job->step, pl.width, pl.height, job->n_rows, job->n_cols, job->field_stride);
@@ -444,12 +409,8 @@ extern "C" int photon_piv_stereo_triangulate(const photon_piv_triangulate_t *job
         if (!job->d_disparity || !job->d_flags) bad = "null d_disparity or d_flags";
         else if (job->field_stride != 2 && job->field_stride != 4) bad = "field_stride must be 2 or 4";
     }
-    if (!bad) {
-        if (job->iterations < 1 || job->iterations > kMaxTriangulateIterations) bad = "iterations must be within [1, 16]";
-        else if (!(std::isfinite(pl.x0) && std::isfinite(pl.y0) && std::isfinite(pl.z) && std::isfinite(pl.pitch))) bad = "a plane value is not finite";
-        else if (!(pl.pitch > 0.0)) bad = "pitch must be > 0";
-        else if (!camera_ok(job->camera1) || !camera_ok(job->camera2)) bad = "a camera value is not finite, or a scale is 0";
-    }
+    if (!bad && (job->iterations < 1 || job->iterations > kMaxTriangulateIterations)) bad = "iterations must be within [1, 16]";
+    if (!bad) bad = plane_cameras_error(pl, job->camera1, job->camera2);
     if (bad) {
         fprintf(stderr, "photon: photon_piv_stereo_triangulate: %s (win %d, step %d, %d x %d plane, %d x %d grid, stride %d, %d iterations)\n", bad,
                 job->win, job->step, pl.width, pl.height, job->n_rows, job->n_cols, job->field_stride, job->iterations);

@@ -2,10 +2,10 @@
 // N cameras by line of sight, and the windowed direct correlation of two volumes with three-dimensional windows and a
 // three-dimensional search region.  Definition: include/parallel_ray_tracing.h, section 20; host models: photon_amd/piv_tomo.py.
 //
-//   los_kernel                one thread per voxel: per camera the dewarp of section 19a at the voxel's slice (the same f64
-//                             Horner, inside test, f32 weights and order of sums as photon_piv_stereo.hip's dewarp_kernel),
-//                             the samples clamped at 0 and combined over the cameras in camera order (minimum or product);
-//                             coordinate, weights and mirrored indices of a camera serve up to kFrameChunk frames at once
+//   los_kernel                one thread per voxel (piv_camera.hpp, VoxelGrid): per camera the dewarp of section 19a at the
+//                             voxel's slice -- dewarp_kernel's own sensor_point (piv_camera.hpp) and BsplineTaps
+//                             (piv_warp.hpp) --, the samples clamped at 0 and combined over the cameras in camera order
+//                             (minimum or product); a camera's taps serve up to kFrameChunk frames at once
 //   correlate_volume_kernel   one workgroup per window under section 5's plan (piv_direct.hpp).  A 3-D correlation at one
 //                             z-shift is the ensemble correlation of the window's z-planes taken with whole-window means:
 //                             per z-shift the win_z plane pairs are staged as photon_piv.hip stages a pair, correlate_tiles
@@ -17,6 +17,7 @@
 #include <cmath>
 
 #include "photon_internal.hpp"
+#include "piv_camera.hpp"
 #include "piv_direct.hpp"
 #include "piv_grid.hpp"
 #include "piv_peak.hpp"
@@ -26,79 +27,47 @@ using namespace photon;
 
 namespace {
 
+using namespace piv_camera;
 using namespace piv_direct;
 using namespace piv_warp;
 
 // =============================================================================================
 // a. line-of-sight volume
 // =============================================================================================
-constexpr int kMaxCameras = 8;
-constexpr int kFrameChunk = 4;      // frames that share one coordinate evaluation per camera and voxel
-
 struct LosArgs {
     const float *coef[kMaxCameras];
     long long in_stride[kMaxCameras];
     int W[kMaxCameras], H[kMaxCameras];
     double grid[kMaxCameras][4];
     const double *poly;             // [n_cameras][nz][2][10]
-    int n_cameras, n_frames, mode, nx, ny, nz, col_blocks, row_blocks;
+    int n_cameras, n_frames, mode;
+    VoxelGrid vox;
     long long out_stride;
     float *out;
     unsigned char *mask;
 };
 
-// section 19a's bivariate cubic in its fixed Horner order (photon_piv_stereo.hip's)
-__device__ __forceinline__ double cubic(const double *k, double u, double v) {
-    const double a0 = ((k[9] * v + k[5]) * v + k[2]) * v + k[0];
-    const double a1 = (k[8] * v + k[4]) * v + k[1];
-    const double a2 = k[7] * v + k[3];
-    return ((k[6] * u + a2) * u + a1) * u + a0;
-}
-
 __global__ __launch_bounds__(kWarpX *kWarpY) void los_kernel(const LosArgs a) {
-    const int cb = blockIdx.x % a.col_blocks, rest = blockIdx.x / a.col_blocks;
-    const int rb = rest % a.row_blocks, k = rest / a.row_blocks;
-    const int j = cb * kWarpX + threadIdx.x, i = rb * kWarpY + threadIdx.y;
-    if (j >= a.nx || i >= a.ny) return;
-    const size_t o = ((size_t)k * a.ny + i) * a.nx + j;
+    int i, j, k;
+    size_t o;
+    if (!a.vox.voxel(i, j, k, o)) return;
     for (int f0 = 0; f0 < a.n_frames; f0 += kFrameChunk) {
         const int nf = min(kFrameChunk, a.n_frames - f0);
         float acc[kFrameChunk] = {0.f, 0.f, 0.f, 0.f};
         bool inside = true;
 #pragma unroll 1
         for (int c = 0; c < a.n_cameras; c++) {
-            const double *kx = a.poly + ((size_t)c * a.nz + k) * 20, *ky = kx + 10;
-            const double u = a.grid[c][0] + (double)j * a.grid[c][1], v = a.grid[c][2] + (double)i * a.grid[c][3];
-            const double x = cubic(kx, u, v), y = cubic(ky, u, v);
             const int W = a.W[c], H = a.H[c];
-            if (!(x >= 0.0 && x <= (double)(W - 1) && y >= 0.0 && y <= (double)(H - 1))) {      // a NaN is outside
+            SensorPoint p;
+            if (!sensor_point(a.poly + ((size_t)c * a.vox.nz + k) * 20, a.grid[c], i, j, W, H, p)) {
                 inside = false;
                 break;
             }
-            // the absolute coordinate never enters a float: the fraction is taken in f64 and rounded once
-            const double fx = floor(x), fy = floor(y);
-            float wxs[4], wys[4];
-            bspline_weights((float)(x - fx), wxs);
-            bspline_weights((float)(y - fy), wys);
-            const int bx0 = (int)fx - 1, by0 = (int)fy - 1;
-            int xi[4];
-            size_t yo[4];
-#pragma unroll
-            for (int t = 0; t < 4; t++) {
-                xi[t] = mirror(bx0 + t, W);
-                yo[t] = (size_t)mirror(by0 + t, H) * W;
-            }
+            const BsplineTaps taps(p.ix, p.iy, p.fx, p.fy, W, H);
 #pragma unroll
             for (int f = 0; f < kFrameChunk; f++) {
                 if (f >= nf) break;
-                const float *coef = a.coef[c] + (size_t)(f0 + f) * a.in_stride[c];
-                float s_c = 0.f;
-#pragma unroll
-                for (int t = 0; t < 4; t++) {
-                    const float *row = coef + yo[t];
-                    const float s = ((wxs[0] * row[xi[0]] + wxs[1] * row[xi[1]]) + wxs[2] * row[xi[2]]) + wxs[3] * row[xi[3]];
-                    s_c = s_c + wys[t] * s;
-                }
+                const float s_c = taps.sample(a.coef[c] + (size_t)(f0 + f) * a.in_stride[c]);
                 const float val = s_c > 0.f ? s_c : 0.f;
                 acc[f] = c == 0 ? val : a.mode == 0 ? (val < acc[f] ? val : acc[f]) : acc[f] * val;
             }
@@ -316,12 +285,6 @@ int launch(const CorrelateArgs &args, long long n_windows, hipStream_t stream) {
     return 0;
 }
 
-bool all_finite(const double *v, int n) {
-    for (int i = 0; i < n; i++)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
 }  // namespace
 
 extern "C" int photon_piv_volume_los(const photon_piv_volume_los_t *job) {
@@ -330,24 +293,19 @@ extern "C" int photon_piv_volume_los(const photon_piv_volume_los_t *job) {
         return 1;
     }
     const photon_piv_volume_t &vol = job->volume;
-    const char *bad = nullptr;
-    if (job->n_cameras < 2 || job->n_cameras > kMaxCameras) bad = "n_cameras must be within [2, 8]";
-    else if (job->mode != 0 && job->mode != 1) bad = "mode must be 0 (minimum) or 1 (product)";
-    else if (job->n_frames < 1) bad = "n_frames must be >= 1";
-    else if (!job->d_poly || !job->d_out) bad = "null d_poly or d_out";
-    if (!bad) bad = piv_grid::side_error(vol.nx, vol.ny);
-    if (!bad) bad = piv_grid::side_error(vol.nz, vol.nz);
-    if (!bad && (long long)vol.nx * vol.ny * vol.nz > INT_MAX) bad = "nx ny nz is above INT_MAX";
-    if (!bad && job->out_stride < (long long)vol.nx * vol.ny * vol.nz) bad = "out_stride is below nx ny nz";
+    const char *bad = cameras_error(job->n_cameras);
+    if (!bad && job->mode != 0 && job->mode != 1) bad = "mode must be 0 (minimum) or 1 (product)";
+    if (!bad) bad = frames_error(job->n_frames);
+    if (!bad && (!job->d_poly || !job->d_out)) bad = "null d_poly or d_out";
+    if (!bad) bad = volume_error(vol, job->out_stride, "out_stride is below nx ny nz");
     for (int c = 0; !bad && c < job->n_cameras; c++) {
         bad = piv_grid::side_error(job->width[c], job->height[c]);
         if (bad) break;
-        const char *out_lo = reinterpret_cast<const char *>(job->d_out), *src_lo = reinterpret_cast<const char *>(job->d_coef[c]);
         if (!job->d_coef[c]) bad = "a null d_coef";
         else if (job->frame_stride[c] < (long long)job->width[c] * job->height[c]) bad = "a frame_stride is below width height";
-        else if (out_lo < src_lo + 4 * (size_t)job->frame_stride[c] * job->n_frames && src_lo < out_lo + 4 * (size_t)job->out_stride * job->n_frames)
+        else if (overlap(range_of(job->d_out, 4, job->out_stride, job->n_frames), range_of(job->d_coef[c], 4, job->frame_stride[c], job->n_frames)))
             bad = "d_out must not overlap a d_coef";
-        else if (!all_finite(job->grid[c], 4)) bad = "a grid value is not finite";
+        else bad = grid_values_error(job->grid[c]);
     }
     if (bad) {
         fprintf(stderr, "photon: photon_piv_volume_los: %s (%d cameras, %d frames, mode %d, volume %d x %d x %d, stride %lld)\n", bad, job->n_cameras,
@@ -364,11 +322,9 @@ extern "C" int photon_piv_volume_los(const photon_piv_volume_los_t *job) {
     }
     a.poly = job->d_poly;
     a.n_cameras = job->n_cameras, a.n_frames = job->n_frames, a.mode = job->mode;
-    a.nx = vol.nx, a.ny = vol.ny, a.nz = vol.nz;
-    a.col_blocks = (vol.nx + kWarpX - 1) / kWarpX, a.row_blocks = (vol.ny + kWarpY - 1) / kWarpY;
+    a.vox = VoxelGrid::make(vol);
     a.out_stride = job->out_stride, a.out = job->d_out, a.mask = job->d_mask;
-    const long long blocks = (long long)a.col_blocks * a.row_blocks * vol.nz;        // below 2^31: nx ny nz <= INT_MAX, sides <= 2^22
-    hipLaunchKernelGGL(los_kernel, dim3((unsigned)blocks), dim3(kWarpX, kWarpY), 0, (hipStream_t)job->stream, a);
+    hipLaunchKernelGGL(los_kernel, dim3(a.vox.blocks()), dim3(kWarpX, kWarpY), 0, (hipStream_t)job->stream, a);
     PH_CHECK(hipGetLastError());
     return 0;
 }

@@ -2,6 +2,7 @@
 // interpolated from the window grid) and photon_optflow.hip (the displacement read per pixel).  One kernel template over
 // where the displacement D of a pixel comes from; everything after D -- the clamp, the taps, the weights, the order of
 // the sums -- is the same code, so both forms return the same bits for the same D.
+// BsplineTaps, the same taps as a struct, samples for piv_camera.hpp's users (dewarp, line of sight), which reuse them per frame.
 #pragma once
 #include <cmath>
 
@@ -126,6 +127,32 @@ static __device__ __forceinline__ void bspline_weights(float t, float w[4]) {
     w[3] = t2 * t * (1.f / 6.f);
 }
 
+// the 16 taps of a cubic B-spline sample around the base pixel (ix, iy): weights and mirrored indices, good for every W x H image
+struct BsplineTaps {
+    float wx[4], wy[4];
+    int xi[4];          // mirrored columns ix - 1 .. ix + 2
+    size_t yo[4];       // mirrored rows iy - 1 .. iy + 2, times W
+    __device__ __forceinline__ BsplineTaps(int ix, int iy, float fx, float fy, int W, int H) {
+        bspline_weights(fx, wx);
+        bspline_weights(fy, wy);
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            xi[t] = mirror(ix - 1 + t, W);
+            yo[t] = (size_t)mirror(iy - 1 + t, H) * W;
+        }
+    }
+    __device__ __forceinline__ float sample(const float *coef) const {
+        float acc = 0.f;
+#pragma unroll
+        for (int t = 0; t < 4; t++) {
+            const float *row = coef + yo[t];
+            const float s = ((wx[0] * row[xi[0]] + wx[1] * row[xi[1]]) + wx[2] * row[xi[2]]) + wx[3] * row[xi[3]];
+            acc = acc + wy[t] * s;
+        }
+        return acc;
+    }
+};
+
 // one thread per output pixel: D, 16 coefficient taps gathered from global memory, one coalesced store
 template <typename Field>
 __global__ __launch_bounds__(kWarpX *kWarpY) void deform_kernel(const float *__restrict__ coef, int W, int H, Field D, float scale,
@@ -138,6 +165,7 @@ __global__ __launch_bounds__(kWarpX *kWarpY) void deform_kernel(const float *__r
     const float sy = fminf(fmaxf(scale * dy, -kMaxShift), kMaxShift);
     // the pixel index never enters a float: the fraction comes from the shift alone
     const float fx = floorf(sx), fy = floorf(sy);
+    // BsplineTaps' operations in this kernel's own schedule, a row's mirror between the rows' loads: measured 1 to 2 % faster here
     float wxs[4], wys[4];
     bspline_weights(sx - fx, wxs);
     bspline_weights(sy - fy, wys);

@@ -1071,6 +1071,15 @@ class PhotonLibrary:
                           eps=settings.eps, threshold=settings.threshold, stream=stream)
         return vec, field, smoothed, status
 
+    def _coefficients_of(self, stack, stream: int):
+        """The B-spline coefficients (section 7a) of every frame of the device stack f32 [n, h, w], queued on `stream`."""
+        import torch
+        n, h, w = (int(v) for v in stack.shape)
+        coef = torch.empty((n, h, w), dtype=torch.float32, device=stack.device)
+        for k in range(n):
+            self.bspline_coefficients(stack[k].data_ptr(), w, h, coef[k].data_ptr(), stream)
+        return coef
+
     def _frame_coefficients(self, a, b, stream: int):
         """(coef, warped), two device tensors [2, h, w]: the B-spline coefficients of the frames a and b, queued on `stream`, and
         the scratch their warps go to."""
@@ -1250,20 +1259,12 @@ class PhotonLibrary:
         section 5's grid (win, step) of the plane, their flags and their sigmas f32 [n_rows, n_cols, 2] (0 = NULL), the two
         cameras and the plane (piv_stereo's dicts).  Returns torch device tensors (out f64 [n_rows, n_cols, 8] = dX, dY, dZ,
         residual, sigma_X, sigma_Y, sigma_Z, pivot ratio; flags int32 [n_rows, n_cols]), filled asynchronously on `stream`."""
-        import torch
-        job = _stereo_job(cameras, plane, win, step)
-        rows, cols = ctypes.c_int(0), ctypes.c_int(0)
-        job.rows_out, job.cols_out = ctypes.pointer(rows), ctypes.pointer(cols)
-        self._call("photon_piv_stereo_reconstruct", ctypes.byref(job))                   # the size query
-        dev = _current_device()
-        out = torch.empty((rows.value, cols.value, 8), dtype=torch.float64, device=dev)
-        flags = torch.empty((rows.value, cols.value), dtype=torch.int32, device=dev)
-        job.d_field1, job.d_field2, job.field_stride = int(d_field1_ptr) or None, int(d_field2_ptr) or None, int(field_stride)
-        job.d_flags1, job.d_flags2 = int(d_flags1_ptr) or None, int(d_flags2_ptr) or None
-        job.d_sigma1, job.d_sigma2 = int(d_sigma1_ptr) or None, int(d_sigma2_ptr) or None
-        job.n_rows, job.n_cols, job.d_out, job.d_flags, job.stream = rows.value, cols.value, out.data_ptr(), flags.data_ptr(), int(stream) or None
-        self._call("photon_piv_stereo_reconstruct", ctypes.byref(job))
-        return out, flags
+
+        def fill(job):
+            job.d_field1, job.d_field2, job.field_stride = int(d_field1_ptr) or None, int(d_field2_ptr) or None, int(field_stride)
+            job.d_flags1, job.d_flags2 = int(d_flags1_ptr) or None, int(d_flags2_ptr) or None
+            job.d_sigma1, job.d_sigma2 = int(d_sigma1_ptr) or None, int(d_sigma2_ptr) or None
+        return self._stereo_node_call("photon_piv_stereo_reconstruct", _stereo_job(cameras, plane, win, step), 8, fill, stream)
 
     def piv_stereo_triangulate(self, d_disparity_ptr: int, field_stride: int, cameras, plane, win: int, step: int, iterations: int = 4,
                                d_flags_in_ptr: int = 0, stream: int = 0):
@@ -1272,18 +1273,26 @@ class PhotonLibrary:
         cameras and the plane (piv_stereo's dicts).  Returns torch device tensors (out f64 [n_rows, n_cols, 6] = X, Y, Z, the
         triangulation error, the last step's length, the smallest pivot ratio; flags int32 [n_rows, n_cols]), filled
         asynchronously on `stream`."""
-        import torch
         job = _stereo_job(cameras, plane, win, step, photon_piv_triangulate_t)
         job.iterations = int(iterations)
+
+        def fill(job):
+            job.d_disparity, job.field_stride, job.d_flags_in = int(d_disparity_ptr) or None, int(field_stride), int(d_flags_in_ptr) or None
+        return self._stereo_node_call("photon_piv_stereo_triangulate", job, 6, fill, stream)
+
+    def _stereo_node_call(self, entry: str, job, width: int, fill, stream: int):
+        """The two calls of a stereo node entry point: the size query on `job` (plane, cameras, win, step in it), then out f64
+        [n_rows, n_cols, width] and flags int32 [n_rows, n_cols], fill(job) for the entry's own members, and the launch."""
+        import torch
         rows, cols = ctypes.c_int(0), ctypes.c_int(0)
         job.rows_out, job.cols_out = ctypes.pointer(rows), ctypes.pointer(cols)
-        self._call("photon_piv_stereo_triangulate", ctypes.byref(job))                   # the size query
+        self._call(entry, ctypes.byref(job))                                             # the size query
         dev = _current_device()
-        out = torch.empty((rows.value, cols.value, 6), dtype=torch.float64, device=dev)
+        out = torch.empty((rows.value, cols.value, width), dtype=torch.float64, device=dev)
         flags = torch.empty((rows.value, cols.value), dtype=torch.int32, device=dev)
-        job.d_disparity, job.field_stride, job.d_flags_in = int(d_disparity_ptr) or None, int(field_stride), int(d_flags_in_ptr) or None
+        fill(job)
         job.n_rows, job.n_cols, job.d_out, job.d_flags, job.stream = rows.value, cols.value, out.data_ptr(), flags.data_ptr(), int(stream) or None
-        self._call("photon_piv_stereo_triangulate", ctypes.byref(job))
+        self._call(entry, ctypes.byref(job))
         return out, flags
 
     def _dewarp_queued(self, stack, camera, plane, stream: int):
@@ -1296,9 +1305,7 @@ class PhotonLibrary:
         n, h, w = stack.shape
         oh, ow = int(plane["height"]), int(plane["width"])
         poly, grid = ps.plane_coefficients(camera, plane)
-        coef = torch.empty((n, h, w), dtype=torch.float32, device=stack.device)
-        for k in range(n):
-            self.bspline_coefficients(stack[k].data_ptr(), w, h, coef[k].data_ptr(), stream)
+        coef = self._coefficients_of(stack, stream)
         frames = torch.empty((n, oh, ow), dtype=torch.float32, device=stack.device)
         outside = torch.empty((oh, ow), dtype=torch.uint8, device=stack.device)
         self.piv_dewarp(coef.data_ptr(), h * w, n, w, h, poly, grid, ow, oh, oh * ow, frames.data_ptr(), outside.data_ptr(), stream)
@@ -1464,21 +1471,16 @@ class PhotonLibrary:
         grids the host table [N, 4] of piv_tomo.los_coefficients; vol a piv_tomo volume.  Writes n_frames volumes f32 [nz, ny,
         nx], out_stride floats apart, and the u8 mask [nz, ny, nx] (0 = NULL); mode 0 the minimum, 1 the product;
         asynchronous on `stream`."""
+        job = photon_piv_volume_los_t(n_frames=int(n_frames), mode=int(mode), out_stride=int(out_stride), d_out=int(d_out_ptr) or None,
+                                      d_mask=int(d_mask_ptr) or None, stream=int(stream) or None)
         n = len(d_coef_ptrs)
         if not (len(frame_strides) == len(sensor_shapes) == n and 0 < n <= 8):
             raise ValueError("piv_volume_los takes 2 to 8 cameras: one pointer, stride and sensor shape each")
-        pitches = np.ascontiguousarray(grids, np.float64)
-        if pitches.shape != (n, 4):
+        if np.asarray(grids, np.float64).shape != (n, 4):
             raise ValueError(f"grids must be [{n}, 4] (piv_tomo.los_coefficients)")
-        job = photon_piv_volume_los_t(n_cameras=n, n_frames=int(n_frames), mode=int(mode), d_poly=int(d_poly_ptr) or None,
-                                      out_stride=int(out_stride), d_out=int(d_out_ptr) or None, d_mask=int(d_mask_ptr) or None,
-                                      stream=int(stream) or None)
-        job.volume = photon_piv_volume_t(float(vol["x0"]), float(vol["y0"]), float(vol["z0"]), float(vol["pitch"]), int(vol["nx"]), int(vol["ny"]),
-                                         int(vol["nz"]))
+        self._volume_cameras(job, sensor_shapes, grids, vol, d_poly_ptr)
         for c in range(n):
             job.d_coef[c], job.frame_stride[c] = int(d_coef_ptrs[c]) or None, int(frame_strides[c])
-            job.height[c], job.width[c] = int(sensor_shapes[c][0]), int(sensor_shapes[c][1])
-        ctypes.memmove(job.grid, pitches.ctypes.data, pitches.nbytes)
         self._call("photon_piv_volume_los", ctypes.byref(job))
 
     def piv_correlate_volume(self, d_vol1_ptr: int, d_vol2_ptr: int, nx: int, ny: int, nz: int, win: int, step: int, radius: int, win_z: int,
@@ -1506,7 +1508,7 @@ class PhotonLibrary:
 
     @staticmethod
     def _volume_cameras(job, sensor_shapes, grids, vol, d_poly_ptr: int):
-        """The members sections 21a and 21b share: the sensors, the grids [N, 4], the table's pointer and the volume."""
+        """The members sections 20a, 21a and 21b share: the sensors, the grids [N, 4], the table's pointer and the volume."""
         n = len(sensor_shapes)
         table = np.ascontiguousarray(grids, np.float64)
         if not 0 < n <= 8 or table.shape != (n, 4):
@@ -1572,12 +1574,7 @@ class PhotonLibrary:
             raise ValueError("every camera must bring the same number of frames")
         poly, grids = pt.los_coefficients(cameras, vol)
         d_poly = _on_device(poly, torch.float64, dev, "poly")
-        coefs = []
-        for t in stacks:
-            coef = torch.empty(tuple(t.shape), dtype=torch.float32, device=dev)
-            for k in range(n):
-                self.bspline_coefficients(t[k].data_ptr(), int(t.shape[2]), int(t.shape[1]), coef[k].data_ptr(), stream)
-            coefs.append(coef)
+        coefs = [self._coefficients_of(t, stream) for t in stacks]
         nz, ny, nx = int(vol["nz"]), int(vol["ny"]), int(vol["nx"])
         out = torch.empty((n, nz, ny, nx), dtype=torch.float32, device=dev)
         unseen = torch.empty((nz, ny, nx), dtype=torch.uint8, device=dev)

@@ -40,20 +40,16 @@ DEFAULT_THRESHOLD = 1e-4                    # of the frames' maximum
 # ---- the footprint -----------------------------------------------------------------------------------------------------------------
 def footprint(poly_k, grid, out_shape, sensor_shape, dtype=np.float32):
     """Where the voxels of one slice land on a camera.  poly_k f64 [2, 10] and grid f64 [4]: the camera folded at the slice
-    (piv_tomo.los_coefficients); out_shape (ny, nx); sensor_shape (height, width).  The coordinate (x, y) and the inside test
-    are piv_stereo's (a NaN is outside); x0 = floor(x), fx = dtype(x - x0), the x taps x0 and min(x0 + 1, width - 1) with the
+    (piv_tomo.los_coefficients); out_shape (ny, nx); sensor_shape (height, width).  The inside test (a NaN is outside), x0 =
+    floor(x) and x - x0 are piv_stereo.sensor_points'; fx = dtype(x - x0), the x taps x0 and min(x0 + 1, width - 1) with the
     weights 1 - fx and fx; the same in y; the four weights wy wx in `dtype`, in the order (y0, x0), (y0, x1), (y1, x0), (y1,
     x1).  Returns (inside bool [ny, nx], pixel index int64 [4, ny, nx] = y width + x, weights dtype [4, ny, nx]); outside
     voxels hold index 0 and what the coordinate (0, 0) gives."""
     h, w = (int(v) for v in sensor_shape)
-    x, y = ps.folded_points(poly_k, grid, out_shape)
-    inside = ~ps.outside_mask(poly_k, grid, out_shape, (h, w))
-    x, y = np.where(inside, x, 0.0), np.where(inside, y, 0.0)
-    x0, y0 = np.floor(x), np.floor(y)
+    inside, ix0, iy0, tx, ty = ps.sensor_points(poly_k, grid, out_shape, (h, w))
     one = dtype(1)
-    fx, fy = (x - x0).astype(dtype), (y - y0).astype(dtype)
+    fx, fy = tx.astype(dtype), ty.astype(dtype)
     wx, wy = (one - fx, fx), (one - fy, fy)
-    ix0, iy0 = x0.astype(np.int64), y0.astype(np.int64)
     ix, iy = (ix0, np.minimum(ix0 + 1, w - 1)), (iy0, np.minimum(iy0 + 1, h - 1))
     index = np.stack([iy[a] * w + ix[b] for a in (0, 1) for b in (0, 1)])
     weights = np.stack([wy[a] * wx[b] for a in (0, 1) for b in (0, 1)])

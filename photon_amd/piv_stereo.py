@@ -8,7 +8,7 @@ The device forms are photon_piv_dewarp and photon_piv_stereo_reconstruct (includ
   (least squares on a calibration target), ``map_points``, ``jacobian`` (analytic, in section 19b's operation order) and
   ``plane_coefficients`` (the camera folded at a plane into what the dewarp kernel takes);
 * ``dewarp_model_f32`` (the kernel's operations in numpy f64 and f32: the device equals it bit for bit) and ``dewarp_model``
-  (f64 throughout, from piv_deformation.bspline_coefficients_model);
+  (f64 throughout, from piv_deformation.bspline_coefficients_model); ``sensor_points``, ``bspline_sample``: their shared parts;
 * ``reconstruct_model``: section 19b in numpy, operation by operation;
 * ``correlate_stereo_model``: the model of the driver's "deform" chain;
 * generators for the tests and tools: ``pinhole`` (a perspective camera to calibrate against), ``calibration_target``,
@@ -207,15 +207,30 @@ def _stack(a, dtype):
     return a.reshape((-1,) + a.shape[-2:]), a.ndim == 2
 
 
-def _taps(poly, grid, out_shape, shape):
-    h, w = shape
+def sensor_points(poly, grid, out_shape, shape):
+    """Where every output pixel lands on a source of `shape` (height, width), as piv_camera.hpp's sensor_point decides it:
+    (inside bool, ix, iy int64 = floor(x), floor(y), tx, ty f64 = x - floor(x), y - floor(y)), each [out_height, out_width]; a
+    pixel outside (NaN included) holds what (0, 0) gives.  The dewarp's taps and piv_mart's footprint both start here."""
     x, y = folded_points(poly, grid, out_shape)
     inside = ~outside_mask(poly, grid, out_shape, shape)
     x, y = np.where(inside, x, 0.0), np.where(inside, y, 0.0)
     fx, fy = np.floor(x), np.floor(y)
-    xi = [pd.mirror_index(fx.astype(np.int64) - 1 + t, w) for t in range(4)]
-    yi = [pd.mirror_index(fy.astype(np.int64) - 1 + t, h) for t in range(4)]
-    return inside, x - fx, y - fy, xi, yi
+    return inside, fx.astype(np.int64), fy.astype(np.int64), x - fx, y - fy
+
+
+def _taps(poly, grid, out_shape, shape):
+    h, w = shape
+    inside, ix, iy, tx, ty = sensor_points(poly, grid, out_shape, shape)
+    return inside, tx, ty, [pd.mirror_index(ix - 1 + t, w) for t in range(4)], [pd.mirror_index(iy - 1 + t, h) for t in range(4)]
+
+
+def bspline_sample(c, tx, ty, xi, yi):
+    """The 16-tap sum in f64 at _taps' fractions and indices, rows in order, each summed left to right: c [..., height, width]."""
+    wx, wy = pd._bspline_weights(tx), pd._bspline_weights(ty)
+    acc = np.zeros(c.shape[:-2] + tx.shape)
+    for t in range(4):
+        acc = acc + wy[t] * (((wx[0] * c[..., yi[t], xi[0]] + wx[1] * c[..., yi[t], xi[1]]) + wx[2] * c[..., yi[t], xi[2]]) + wx[3] * c[..., yi[t], xi[3]])
+    return acc
 
 
 def dewarp_model_f32(coef, poly, grid, out_shape):
@@ -241,14 +256,9 @@ def dewarp_model(frames, poly, grid, out_shape):
     piv_deformation.bspline_coefficients_model: (frames f64, mask u8) shaped as dewarp_model_f32's."""
     a, single = _stack(frames, np.float64)
     inside, tx, ty, xi, yi = _taps(poly, grid, out_shape, a.shape[-2:])
-    wx, wy = pd._bspline_weights(tx), pd._bspline_weights(ty)
     out = np.zeros((a.shape[0],) + tuple(inside.shape))
     for f in range(a.shape[0]):
-        c = pd.bspline_coefficients_model(a[f])
-        acc = np.zeros(inside.shape)
-        for t in range(4):
-            acc = acc + wy[t] * (((wx[0] * c[yi[t], xi[0]] + wx[1] * c[yi[t], xi[1]]) + wx[2] * c[yi[t], xi[2]]) + wx[3] * c[yi[t], xi[3]])
-        out[f] = np.where(inside, acc, 0.0)
+        out[f] = np.where(inside, bspline_sample(pd.bspline_coefficients_model(a[f]), tx, ty, xi, yi), 0.0)
     return (out[0] if single else out), (~inside).astype(np.uint8)
 
 

@@ -112,11 +112,7 @@ def los_samples(camera_frames, poly, grids, shape):
         c = np.stack([pd.bspline_coefficients_model(f) for f in s])
         for k in range(nz):
             inside, tx, ty, xi, yi = ps._taps(poly[i][k], grids[i], (ny, nx), c.shape[-2:])
-            wx, wy = pd._bspline_weights(tx), pd._bspline_weights(ty)
-            acc = np.zeros((c.shape[0], ny, nx))
-            for t in range(4):
-                acc = acc + wy[t] * (((wx[0] * c[:, yi[t], xi[0]] + wx[1] * c[:, yi[t], xi[1]]) + wx[2] * c[:, yi[t], xi[2]]) + wx[3] * c[:, yi[t], xi[3]])
-            samples[i, :, k], outside[i, k] = np.where(inside, acc, 0.0), ~inside
+            samples[i, :, k], outside[i, k] = np.where(inside, ps.bspline_sample(c, tx, ty, xi, yi), 0.0), ~inside
     return samples, outside
 
 
